@@ -104,7 +104,14 @@ def parse(argv=None):
     ap.add_argument("--cold", action="store_true", help="--iterate: every timed call is the FIRST call of a fresh handle (lx_create, the sequence "
                     "sets, lx_reserve with hints, then the one call a search makes): what `lambda3 searchn` pays, not the tenth call")
     ap.add_argument("--dry-run", action="store_true", help="launch + rendezvous (gloo) + sharding only; no GPU, value = null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step returned to its "
+                    "caller (rank 0's share, a fixed seeded sample of its extensions) as DIR/<name>.npy in float32 / float64, at most 64 MB "
+                    "in all: the device-resident step only (see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.dry_run or args.host_path or args.ragged or args.iterate):
+        ap.error("--dump-outputs: only the device-resident step (no --dry-run, --host-path, --ragged or --iterate)")
     # (--iterate without --config keeps timing the read set of configs[2]; `--iterate --config 1` is the metric's own program: the protein list)
     args.config_given = any(a == "--config" or a.startswith("--config=") for a in (sys.argv[1:] if argv is None else argv))
     return args
@@ -690,6 +697,74 @@ def host_cpu_baseline(args, w, q, s, ext):
                       f"OpenMP with {cores} threads ({note}), best of 2, {best:.3f} s"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 19       # extensions of the sample (all of them when the share has no more)
+DUMP_OPS_SURVIVORS = 4096   # survivors of the sample whose ops are written
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, batches, pass1_only: bool) -> dict:
+    """What the last timed step of the device-resident path handed its caller, for comparing two builds output for output.
+    The extensions of the rank's batches are numbered in batch order; a fixed seeded sample of DUMP_SAMPLE of them is kept.
+        ext_index.npy   (float64) the sample's extension numbers, ascending
+        score.npy       (float32) d_out_score of the sample
+        survivors.npy   (float64) d_out_count[1] of every batch
+        hsp_<field>.npy (float32) every lx_hsp field (capi.HSP_DTYPE) of the sample; a filtered-out row carries only its score
+                        and n_ops = 0 (include/lambda_ext.h), so its other fields are written as 0
+        ops.npy         (float32) the op bytes ('M', 'D', 'I') of the first DUMP_OPS_SURVIVORS survivors of the sample, concatenated
+        ops_ext_index.npy (float64) those survivors' extension numbers (their lengths: hsp_n_ops)
+    Without pass 2 (--pass1-only) only ext_index, score and survivors are written.  Returns {name: bytes}."""
+    import torch
+
+    from lambda_amd import capi
+
+    n_all = sum(b.n for b in batches)
+    if n_all > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_all, DUMP_SAMPLE, replace=False))
+    else:
+        pick = np.arange(n_all)
+    fields = capi.HSP_DTYPE.names
+    score, hsp, ops, ops_ext = [], [], [], []
+    at = 0
+    for b in batches:
+        sel = pick[(pick >= at) & (pick < at + b.n)]
+        loc = torch.from_numpy(sel - at).to(b.d_score.device)
+        score.append(b.d_score[loc].cpu().numpy())
+        if not pass1_only:
+            rows = b.d_hsp.view(torch.int32).view(b.n, len(fields))[loc].cpu().numpy().copy()
+            n_ops = rows[:, fields.index("n_ops")]
+            undefined = [k for k, f in enumerate(fields) if f not in ("score", "n_ops")]
+            rows[np.ix_(n_ops == 0, undefined)] = 0
+            hsp.append(rows)
+            room = DUMP_OPS_SURVIVORS - sum(len(e) for e in ops_ext)
+            surv = np.nonzero(n_ops > 0)[0][:max(room, 0)]
+            if len(surv):
+                off = b.d_off[loc[torch.from_numpy(surv).to(loc.device)]].cpu().numpy()
+                start = off + rows[surv, fields.index("ops_shift")]
+                lens = n_ops[surv].astype(np.int64)
+                byte_at = np.repeat(start - np.cumsum(lens) + lens, lens) + np.arange(int(lens.sum()))
+                if byte_at.min() < 0 or byte_at.max() >= b.d_ops.numel():
+                    raise SystemExit("bench.py --dump-outputs: a record's ops lie outside the ops buffer")
+                ops.append(b.d_ops[torch.from_numpy(byte_at).to(b.d_ops.device)].cpu().numpy())
+                ops_ext.append(sel[surv])
+        at += b.n
+    arrays = {"ext_index": pick.astype(np.float64), "score": np.concatenate(score).astype(np.float32),
+              "survivors": np.array([float(b.d_count.cpu()[1]) for b in batches], dtype=np.float64)}
+    if not pass1_only:
+        hsp = np.concatenate(hsp)
+        arrays.update({f"hsp_{f}": hsp[:, k].astype(np.float32) for k, f in enumerate(fields)})
+        arrays["ops"] = (np.concatenate(ops) if ops else np.zeros(0, np.uint8)).astype(np.float32)
+        arrays["ops_ext_index"] = (np.concatenate(ops_ext) if ops_ext else np.zeros(0, np.int64)).astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: int(a.nbytes) for name, a in arrays.items()}
+
+
 class DevBatch:
     """One device call's inputs and outputs, resident in HBM."""
 
@@ -982,6 +1057,8 @@ def main():
             # ~84 Gcells of CPU work per repetition at most (a second or so on the box's 16 granted CPUs), three repetitions
             default_sample = max(1, min(pl.n_queries, int(84.5e9 / (w.windows * lq * ls))))
             out["cpu_baseline"] = cpu_baseline(w, min(args.cpu_sample_queries or default_sample, pl.n_queries), cores, note)
+        if args.dump_outputs:
+            out["dumped_outputs"] = {"dir": str(args.dump_outputs), "bytes": dump_outputs(args.dump_outputs, batches, args.pass1_only)}
         print(json.dumps(out), flush=True)
     h.close()
     if use_dist:

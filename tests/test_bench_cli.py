@@ -168,3 +168,106 @@ def test_newest_pmc_profiles_were_made_from_the_kernels_in_the_tree():
     doc["kernel_sources"][k] = "0" * 40
     assert "STALE" in bench.profile_sources_note(doc) and k in bench.stale_profile_sources(doc)
 
+
+
+def _fake_dev_batch(rng, n):
+    """A DevBatch's output buffers as the device-resident step leaves them, on the CPU: filtered-out rows carry a stale q_begin."""
+    import types
+
+    import numpy as np
+    import torch
+
+    from lambda_amd import capi
+
+    sizes = rng.integers(5, 20, n) + rng.integers(5, 20, n)
+    off = np.zeros(n, np.int64)
+    off[1:] = np.cumsum(sizes)[:-1]
+    hsp = np.zeros(n, capi.HSP_DTYPE)
+    hsp["score"] = rng.integers(0, 100, n)
+    hsp["n_ops"] = np.where(hsp["score"] >= 50, rng.integers(1, 5, n), 0)
+    hsp["q_begin"] = 7
+    hsp["ops_shift"] = sizes - hsp["n_ops"]
+    ops = rng.integers(65, 90, int(sizes.sum()) + 16).astype(np.uint8)
+    b = types.SimpleNamespace(n=n, d_score=torch.from_numpy(hsp["score"].copy()), d_hsp=torch.from_numpy(hsp.view(np.uint8).copy()),
+                              d_off=torch.from_numpy(off), d_ops=torch.from_numpy(ops),
+                              d_count=torch.tensor([0, int((hsp["n_ops"] > 0).sum())]))
+    return b, hsp, ops, off
+
+
+def test_dump_outputs_writes_a_seeded_sample_of_what_the_step_returned(tmp_path):
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(1)
+    parts = [_fake_dev_batch(rng, 300_000), _fake_dev_batch(rng, 400_000)]
+    sizes = bench.dump_outputs(tmp_path / "a", [p[0] for p in parts], pass1_only=False)
+    assert sum(sizes.values()) <= 64 << 20
+    d = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in sizes}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    idx = d["ext_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and (np.diff(idx) > 0).all()
+    hsp = np.concatenate([p[1] for p in parts])
+    assert (d["score"] == hsp["score"][idx]).all() and (d["hsp_n_ops"] == hsp["n_ops"][idx]).all()
+    surv = d["hsp_n_ops"] > 0
+    assert (d["hsp_q_begin"][surv] == 7).all() and (d["hsp_q_begin"][~surv] == 0).all()  # undefined fields of filtered rows: 0
+    assert list(d["survivors"]) == [float(p[0].d_count[1]) for p in parts]
+    want = []
+    for e in d["ops_ext_index"].astype(np.int64):
+        _, h, ops, off = parts[0] if e < 300_000 else parts[1]
+        e = e if e < 300_000 else e - 300_000
+        want.append(ops[off[e] + h["ops_shift"][e]: off[e] + h["ops_shift"][e] + h["n_ops"][e]])
+    assert len(want) == bench.DUMP_OPS_SURVIVORS and (d["ops"] == np.concatenate(want)).all()
+    # the same buffers give the same files
+    bench.dump_outputs(tmp_path / "b", [p[0] for p in parts], pass1_only=False)
+    assert all((np.load(tmp_path / "b" / f"{k}.npy") == d[k]).all() for k in sizes)
+    assert set(bench.dump_outputs(tmp_path / "c", [p[0] for p in parts], pass1_only=True)) == {"ext_index", "score", "survivors"}
+
+
+def test_dump_outputs_is_refused_where_it_does_not_apply():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--dry-run", "--dump-outputs", "x"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--dry-run", "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_outputs_of_its_last_step(tmp_path, oracle):
+    """`--dump-outputs`: two runs with the same arguments write the same files, `--steps` is the number of timed steps, and the
+    dumped scores, records and ops are the oracle's on the same synthetic batch."""
+    import numpy as np
+
+    from lambda_amd import capi
+    from tests import oracle_lib
+
+    argv = ["--steps", "3", "--warmup", "1", "--queries", "2048", "--no-cpu-baseline"]
+    runs = [run_bench(*argv, "--dump-outputs", str(tmp_path / k)) for k in ("a", "b")]
+    for r in runs:
+        assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["config"]["job_queries"] == 2048
+    names = sorted(runs[0]["dumped_outputs"]["bytes"])
+    d = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all((np.load(tmp_path / "b" / f"{k}.npy") == d[k]).all() for k in names)
+
+    w = workloads.WORKLOADS[1]
+    b = workloads.plan(w, 1, 0, None, 2048, None).batches[0]
+    d_q, d_s, _, ext = synth.make_batch_torch(b.n_queries, w.lq, w.windows, b.seed, "cuda:0", alphabet=workloads.alphabet_array(w),
+                                              sub_rate=w.sub_rate, indel_rate=w.indel_rate, n_rate=w.n_rate, n_rank=w.n_rank,
+                                              convert=b.direction.convert, convert_rate=w.convert_rate, homolog_frac=0.5)
+    q, s = d_q.cpu().numpy(), d_s.cpu().numpy()
+    m, ma, mi, go, ge = w.directions[0].scoring
+    osc = oracle_lib.scoring_from(capi.builtin_scoring(m, match=ma, mismatch=mi, gap_open=go, gap_extend=ge))
+    idx = d["ext_index"].astype(np.int64)
+    assert len(idx) == len(ext) == 2048 * w.windows  # a share this small is dumped whole
+    want = oracle.score_batch(q, s, ext, osc, threads=4)
+    assert (d["score"] == want).all() and (d["hsp_score"] == want).all()
+    surv = np.nonzero(d["hsp_n_ops"] > 0)[0]
+    assert d["survivors"][0] == len(surv) > 0
+    traced = d["ops_ext_index"].astype(np.int64)
+    assert len(traced) == min(len(surv), 4096) and (traced == surv[:len(traced)]).all()
+    at = 0
+    for i, (oh, oops) in zip(traced, oracle.align_batch(q, s, ext[traced], osc)):
+        got = tuple(int(d[f"hsp_{f}"][i]) for f in ("score", "q_begin", "q_end", "s_begin", "s_end", "n_ops"))
+        assert got == (oh.score, oh.q_begin, oh.q_end, oh.s_begin, oh.s_end, oh.n_ops), i
+        assert bytes(d["ops"][at: at + oh.n_ops].astype(np.uint8)) == oops, i
+        at += oh.n_ops
+    assert at == len(d["ops"])
