@@ -574,7 +574,8 @@ enum
 {
     LX_OUT_BLAST_TAB          = 0, /* -m8: 12 standard columns (src/search_options.hpp:716-760 default)         */
     LX_OUT_BLAST_TAB_COMMENTS = 1, /* -m9                                                                        */
-    LX_OUT_SAM                = 2  /* SAM, default tags "AS NM ae ai qf" (src/search_options.hpp:351)            */
+    LX_OUT_SAM                = 2, /* SAM, default tags "AS NM ae ai qf" (src/search_options.hpp:351)            */
+    LX_OUT_BAM                = 3  /* BAM: lx_render_records / lx_write_records_bgzf only (binary, BGZF-compressed) */
 };
 /* Appends header (if write_header) and records to `path` (myWriteHeader / myWriteRecord,
  * src/search_output.hpp:305-461, :463-733).  `ops` is the ops buffer the matches' ops_off index into; `program` is
@@ -634,6 +635,41 @@ int lx_check_output_options(int format, lx_output_options const * opt);
 int lx_write_footer(char const * path, int format, uint64_t n_records);
 char const * lx_last_output_error(void);
 
+/* ---- rendered output and BGZF compression ------------------------------------------------------ */
+/* An opaque byte buffer handed out by lx_render_records. */
+typedef struct lx_bytes lx_bytes;
+uint8_t const * lx_bytes_data(lx_bytes const * b);
+uint64_t        lx_bytes_size(lx_bytes const * b);
+void            lx_bytes_free(lx_bytes * b);
+/* The bytes a writer produces, in memory (host only).  Same arguments as lx_write_records_ex, plus footer_records: >= 0 appends
+ * what lx_write_footer(format, footer_records) would, < 0 no footer.  For LX_OUT_BLAST_TAB, LX_OUT_BLAST_TAB_COMMENTS and LX_OUT_SAM
+ * exactly what lx_write_records_ex + lx_write_footer put in a file.  For LX_OUT_BAM the uncompressed BAM stream (SAM/BAM
+ * specification 4.2): magic, the SAM header text with one @SQ line per subject (BAM always carries the references, as seqan's
+ * writeHeader does), the reference list, then the SAM writer's records in binary (refID = n_sid, MAPQ 255, bin by reg2bin over the
+ * CIGAR's reference span, no mate, QUAL 0xFF; tag types ae f, AS ap S, ar ai C, qf sf c, lt NM IH I, st ls qs OC Z,
+ * src/search_output.hpp:601-717).  LX_EINVAL as lx_write_records_ex; *out is released with lx_bytes_free. */
+int lx_render_records(int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+                      lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                      lx_output_options const * opt, int64_t footer_records, lx_bytes ** out);
+enum
+{
+    LX_BGZF_EOF = 1 /* lx_bgzf_compress: append the 28-byte empty member that ends a BGZF file */
+};
+/* Bytes lx_bgzf_compress may write for n input bytes (EOF member included). */
+uint64_t lx_bgzf_bound(uint64_t n);
+/* BGZF (blocked gzip, SAM/BAM specification 4.1) on the handle's device: the input cut into blocks of at most 65 280 bytes, each a
+ * gzip member with the BC subfield (dynamic Huffman DEFLATE, or stored where that is not larger), the members one after another.
+ * Every member is a complete gzip member, so the output is also a valid .gz file.  Deterministic: the same input gives the same
+ * bytes on every call and handle.  Large inputs stream through the device in chunks.  cap must be >= lx_bgzf_bound(n); *out_n =
+ * bytes written.  lx_last_phase_ms(h, 4, ...) = device time of the encoder's kernels in the last call.  LX_EINVAL for NULL
+ * buffers, a short cap or unknown flags, before any device work. */
+int lx_bgzf_compress(lx_handle * h, uint8_t const * in, uint64_t n, uint8_t * out, uint64_t cap, uint64_t * out_n, int32_t flags);
+/* lx_render_records (header, records, footer when footer_records >= 0) compressed by lx_bgzf_compress with the EOF member, written
+ * to `path` (created or truncated).  LX_OUT_BAM gives a .bam file, the text formats their .gz form. */
+int lx_write_records_bgzf(lx_handle * h, char const * path, int format, char const * program, lx_blast_match const * m, uint64_t n,
+                          uint8_t const * ops, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                          lx_output_options const * opt, int64_t footer_records);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Blocks until everything queued on the handle's stream has finished. */
 int lx_synchronize(lx_handle * h);
@@ -645,7 +681,8 @@ int lx_last_kernel_ms(lx_handle * h, float * ms);
 char const * lx_last_kernel_name(lx_handle const * h);
 char const * lx_last_trace_kernel_name(lx_handle const * h);
 /* Device time (HIP events on the launch stream) the most recent call spent in one phase, summed over its launches:
- * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel. */
+ * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
+ * 4 = BGZF encoder (lx_bgzf_compress). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

@@ -31,7 +31,8 @@ EXPORTED_SYMBOLS = [
     "lx_iterate_result_free", "lx_karlin_params", "lx_length_adjustment", "lx_evalue", "lx_bitscore",
     "lx_widen_and_preprocess", "lx_postprocess_records", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
-    "lx_plan_step",
+    "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
+    "lx_write_records_bgzf",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -89,7 +90,8 @@ class SeqNames(C.Structure):
                 ("s_lens", C.c_void_p), ("n_q", C.c_uint64), ("n_s", C.c_uint64)]
 
 
-LX_OUT_BLAST_TAB, LX_OUT_BLAST_TAB_COMMENTS, LX_OUT_SAM = 0, 1, 2
+LX_OUT_BLAST_TAB, LX_OUT_BLAST_TAB_COMMENTS, LX_OUT_SAM, LX_OUT_BAM = 0, 1, 2, 3
+LX_BGZF_EOF = 1
 
 
 class Scoring(C.Structure):
@@ -225,6 +227,18 @@ def load():
     lib.lx_output_options_default.restype = None
     lib.lx_last_output_error.restype = C.c_char_p
     lib.lx_compute_lca.argtypes = [vp, u64, C.POINTER(TaxTree), vp, vp, C.POINTER(u64)]
+    lib.lx_render_records.argtypes = [i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions), C.c_int64, C.POINTER(vp)]
+    lib.lx_bytes_data.argtypes = [vp]
+    lib.lx_bytes_data.restype = vp
+    lib.lx_bytes_size.argtypes = [vp]
+    lib.lx_bytes_size.restype = u64
+    lib.lx_bytes_free.argtypes = [vp]
+    lib.lx_bytes_free.restype = None
+    lib.lx_bgzf_bound.argtypes = [u64]
+    lib.lx_bgzf_bound.restype = u64
+    lib.lx_bgzf_compress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
+    lib.lx_write_records_bgzf.argtypes = [vp, C.c_char_p, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
+                                          C.c_int64]
     _lib = lib
     return lib
 
@@ -282,6 +296,42 @@ def write_footer(path, fmt: int, n_records: int):
     rc = load().lx_write_footer(str(path).encode(), fmt, C.c_uint64(n_records))
     if rc != LX_OK:
         raise LambdaExtError(rc, "lx_write_footer")
+
+
+def _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options):
+    """The arguments the writers share (the arrays are returned too: they must outlive the call)."""
+    m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE)
+    qa = (C.c_char_p * len(q_ids))(*[x.encode() for x in q_ids])
+    sa = (C.c_char_p * len(s_ids))(*[x.encode() for x in s_ids])
+    ql = np.ascontiguousarray(q_lens, dtype=np.uint64)
+    sl = np.ascontiguousarray(s_lens, dtype=np.uint64)
+    names = SeqNames(qa, ql.ctypes.data, sa, sl.ctypes.data, len(q_ids), len(s_ids))
+    o = np.frombuffer(ops + b"\0", dtype=np.uint8)
+    qasc = np.frombuffer(q_ascii, dtype=np.uint8) if q_ascii else None
+    qoff = np.ascontiguousarray(q_ascii_off, dtype=np.uint64) if q_ascii_off is not None else None
+    args = (_ptr(m), len(m), _ptr(o), C.byref(names), _ptr(qasc) if qasc is not None else None, _ptr(qoff) if qoff is not None else None,
+            C.byref(options) if options is not None else None)
+    return args, (m, qa, sa, ql, sl, names, o, qasc, qoff)
+
+
+def render_records(fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", write_header=True,
+                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1) -> bytes:
+    """lx_render_records: the bytes of a text format (what write_records + write_footer put in a file), or the uncompressed BAM
+    stream (LX_OUT_BAM).  footer_records < 0: no footer."""
+    args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+    lib = load()
+    out = C.c_void_p()
+    rc = lib.lx_render_records(fmt, 1 if write_header else 0, program.encode(), *args, footer_records, C.byref(out))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, "lx_render_records: " + last_output_error())
+    try:
+        return C.string_at(lib.lx_bytes_data(out), lib.lx_bytes_size(out)) if lib.lx_bytes_size(out) else b""
+    finally:
+        lib.lx_bytes_free(out)
+
+
+def bgzf_bound(n: int) -> int:
+    return int(load().lx_bgzf_bound(n))
 
 
 def write_records(path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",
@@ -655,6 +705,20 @@ class Handle:
 
     def synchronize(self):
         self._check(self.lib.lx_synchronize(self.h))
+
+    def bgzf_compress(self, data: bytes, eof: bool = False) -> bytes:
+        """lx_bgzf_compress: BGZF members of `data` made on this handle's device (+ the EOF member if asked)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+        out = np.empty(bgzf_bound(len(data)), dtype=np.uint8)
+        got = C.c_uint64(0)
+        self._check(self.lib.lx_bgzf_compress(self.h, _ptr(buf), len(data), _ptr(out), len(out), C.byref(got), LX_BGZF_EOF if eof else 0))
+        return out[: got.value].tobytes()
+
+    def write_records_bgzf(self, path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",
+                           q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1):
+        """lx_write_records_bgzf: header, records and footer (footer_records >= 0) of `fmt`, BGZF-compressed into `path`."""
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        self._check(self.lib.lx_write_records_bgzf(self.h, str(path).encode(), fmt, program.encode(), *args, footer_records))
 
     def last_kernel_name(self) -> str:
         return self.lib.lx_last_kernel_name(self.h).decode()

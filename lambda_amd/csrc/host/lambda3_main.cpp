@@ -273,11 +273,13 @@ bool looksLikeDna(std::string const & path)
     return all > 0 && nuc * 10 >= all * 9;
 }
 
+static int outputFormat(std::string const & path, bool & gz);
+
 Options parse(int argc, char ** argv)
 {
     Options o;
     if (argc < 2)
-        throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.fasta (-i DB.lba | -d DB.fasta) -o OUT.{m8,m9,sam} [-e EVALUE] [-n N] "
+        throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.fasta (-i DB.lba | -d DB.fasta) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
                                  "[--devices 0,1,...] [-t THREADS]\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.fasta [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
@@ -523,11 +525,8 @@ Options parse(int argc, char ** argv)
     {
         // the output format and what the writers are asked for, before anything is read or searched (:684-816: the reference fails
         // while it parses its options)
-        auto ends = [&](char const * suf)
-        { return o.output.size() >= std::strlen(suf) && o.output.compare(o.output.size() - std::strlen(suf), std::string::npos, suf) == 0; };
-        int const fmt = ends(".m9") ? LX_OUT_BLAST_TAB_COMMENTS : ends(".sam") ? LX_OUT_SAM : ends(".m8") ? LX_OUT_BLAST_TAB : -1;
-        if (fmt < 0)
-            throw std::runtime_error("output format is chosen by the extension: .m8, .m9 or .sam"); // :684-710
+        bool      gz  = false;
+        int const fmt = outputFormat(o.output, gz);
         lx_output_options oo;
         lx_output_options_default(&oo);
         oo.columns  = o.outputColumns.c_str();
@@ -536,6 +535,27 @@ Options parse(int argc, char ** argv)
             throw std::runtime_error(lx_last_output_error());
     }
     return o;
+}
+
+// The output format from the file name (src/search_options.hpp:684-710): .m8, .m9, .sam or .bam; the text formats also BGZF-
+// compressed (.gz).  .m0 (the pairwise report), .bz2 and .bam.gz are refused.
+static char const * const kFormatMessage =
+    "output format is chosen by the extension: .m8, .m9, .sam or .bam, the first three optionally with .gz (.m0, .bz2 and .bam.gz are not supported)";
+static int outputFormat(std::string const & path, bool & gz)
+{
+    auto ends = [&](std::string const & p, char const * suf)
+    { return p.size() >= std::strlen(suf) && p.compare(p.size() - std::strlen(suf), std::string::npos, suf) == 0; };
+    gz                 = ends(path, ".gz");
+    std::string const base = gz ? path.substr(0, path.size() - 3) : path;
+    if (ends(base, ".m9"))
+        return LX_OUT_BLAST_TAB_COMMENTS;
+    if (ends(base, ".sam"))
+        return LX_OUT_SAM;
+    if (ends(base, ".m8"))
+        return LX_OUT_BLAST_TAB;
+    if (ends(base, ".bam") && !gz)
+        return LX_OUT_BAM;
+    throw std::runtime_error(kFormatMessage);
 }
 
 // ---- the index file of `lambda3 mkindex*`.  It holds what the reference's index_file holds (src/shared_definitions.hpp:343-379:
@@ -938,7 +958,9 @@ int main(int argc, char ** argv)
         sp.s_frame_mode     = bs ? LX_FRAMES_BISULFITE : sTrans ? LX_FRAMES_TRANSLATED : LX_FRAMES_NONE;
         sp.karlin           = ka;
         // only the SAM writer reads alignment columns (its CIGAR); the tables are made from the counts
-        bool const wantOps  = opt.output.size() >= 4 && opt.output.compare(opt.output.size() - 4, std::string::npos, ".sam") == 0;
+        bool       outGz    = false;
+        int const  outFmt   = outputFormat(opt.output, outGz);
+        bool const wantOps  = outFmt == LX_OUT_SAM || outFmt == LX_OUT_BAM;
         sp.flags            = wantOps ? 0 : LX_ITERATE_NO_OPS;
 
         lambda_amd::SeedParams const so1{opt.seedLength, opt.seedOffset, opt.seedDelta}, so0{opt.seedLength0, opt.seedOffset0, opt.seedDelta0};
@@ -1158,15 +1180,8 @@ int main(int argc, char ** argv)
         for (auto const & s : db.ids)
             sid.push_back(s.c_str());
         lx_seq_names names{qid.data(), qs.orig_len.data(), sid.data(), db.orig_len.data(), qid.size(), sid.size()};
-        int          fmt = LX_OUT_BLAST_TAB;
-        auto         ends = [&](char const * suf)
-        { return opt.output.size() >= std::strlen(suf) && opt.output.compare(opt.output.size() - std::strlen(suf), std::string::npos, suf) == 0; };
-        if (ends(".m9"))
-            fmt = LX_OUT_BLAST_TAB_COMMENTS;
-        else if (ends(".sam"))
-            fmt = LX_OUT_SAM;
-        else if (!ends(".m8"))
-            throw std::runtime_error("output format is chosen by the extension: .m8, .m9 or .sam"); // :684-710
+        int const    fmt = outFmt;
+        double       msCompress = 0; // (.bam, *.gz: BGZF on the first handle's device)
         {
             lx_output_options oo;
             lx_output_options_default(&oo);
@@ -1180,12 +1195,39 @@ int main(int argc, char ** argv)
             oo.command_line        = opt.commandLine.c_str();
             oo.db_name             = opt.db.c_str(); // the index path there (src/search_algo.hpp:320)
             oo.genetic_code        = geneticCodeQry;
-            int const rcw = lx_write_records_ex(opt.output.c_str(), fmt, 1, program, bms.data(), nOut, ops.data(), &names,
-                                                reinterpret_cast<uint8_t const *>(qs.ascii.data()), qs.ascii_off.data(), &oo);
-            if (rcw != LX_OK)
-                throw std::runtime_error(*lx_last_output_error() ? lx_last_output_error() : ("cannot write " + opt.output).c_str());
-            if (lx_write_footer(opt.output.c_str(), fmt, rst.qrys_with_hit) != LX_OK) // myWriteFooter, src/search.cpp
-                throw std::runtime_error("cannot write " + opt.output);
+            if (fmt == LX_OUT_BAM || outGz)
+            {
+                // records, footer and header rendered on the host threads, compressed on the device, written at once
+                lx_bytes * raw = nullptr;
+                if (lx_render_records(fmt, 1, program, bms.data(), nOut, ops.data(), &names, reinterpret_cast<uint8_t const *>(qs.ascii.data()),
+                                      qs.ascii_off.data(), &oo, (int64_t)rst.qrys_with_hit, &raw) != LX_OK)
+                    throw std::runtime_error(*lx_last_output_error() ? lx_last_output_error() : ("cannot write " + opt.output).c_str());
+                std::unique_ptr<lx_bytes, void (*)(lx_bytes *)> keep(raw, lx_bytes_free);
+                auto const           tZip = std::chrono::steady_clock::now();
+                lx_handle *          zh   = nullptr;
+                if (lx_create(devices[0], &zh) != LX_OK)
+                    throw std::runtime_error(lx_last_error(nullptr));
+                std::unique_ptr<lx_handle, void (*)(lx_handle *)> keepH(zh, lx_destroy);
+                std::vector<uint8_t> packed(lx_bgzf_bound(lx_bytes_size(raw)));
+                uint64_t             got = 0;
+                if (lx_bgzf_compress(zh, lx_bytes_data(raw), lx_bytes_size(raw), packed.data(), packed.size(), &got, LX_BGZF_EOF) != LX_OK)
+                    throw std::runtime_error(std::string("BGZF compression: ") + lx_last_error(zh));
+                msCompress     = msSince(tZip);
+                std::FILE * of = std::fopen(opt.output.c_str(), "wb");
+                bool        ok = of && std::fwrite(packed.data(), 1, got, of) == got;
+                ok             = of && (std::fclose(of) == 0) && ok;
+                if (!ok)
+                    throw std::runtime_error("cannot write " + opt.output);
+            }
+            else
+            {
+                int const rcw = lx_write_records_ex(opt.output.c_str(), fmt, 1, program, bms.data(), nOut, ops.data(), &names,
+                                                    reinterpret_cast<uint8_t const *>(qs.ascii.data()), qs.ascii_off.data(), &oo);
+                if (rcw != LX_OK)
+                    throw std::runtime_error(*lx_last_output_error() ? lx_last_output_error() : ("cannot write " + opt.output).c_str());
+                if (lx_write_footer(opt.output.c_str(), fmt, rst.qrys_with_hit) != LX_OK) // myWriteFooter, src/search.cpp
+                    throw std::runtime_error("cannot write " + opt.output);
+            }
         }
 
         std::fprintf(stderr,
@@ -1197,9 +1239,10 @@ int main(int argc, char ** argv)
         // where the wall clock went (the reference prints its own at verbosity 2, src/search.cpp): per worker the slowest counts
         std::fprintf(stderr,
                      "lambda3 times [ms]: read %.0f, reduce + word table %s%.0f, search %.0f (seeding on the %s %.0f [%zu read(s) and %zu launch(es) left to "
-                     "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records + output %.0f, total %.0f\n",
+                     "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records + output %.0f%s, total %.0f\n",
                      msRead, fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
-                     nPassesOnHost, msExtendMax, msSince(tOut), msSince(tStart));
+                     nPassesOnHost, msExtendMax, msSince(tOut) - msCompress,
+                     (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str() : "", msSince(tStart));
         return 0;
     }
     catch (std::exception const & e)

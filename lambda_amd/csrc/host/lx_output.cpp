@@ -7,12 +7,14 @@
 //   blastMatchOneCigar    src/search_output.hpp:115-194                  (hard or soft clips, frame clips always hard)
 //   blastMatchTwoCigar    src/search_output.hpp:197-298                  (the protein-space cigar of tag OC)
 //   the output options    src/search_options.hpp:224-379, :716-816       (lx_output_options: columns, SAM tags, sequence, clipping)
-// Scope: every program in the tabular formats and in SAM; not BAM and not the pairwise .m0 report (seqan's writers, absent).  The
+// Scope: every program in the tabular formats, in SAM and in BAM (the SAM records in binary, SAM/BAM specification 4.2; compressed
+// by lx_bgzf.hip); not the pairwise .m0 report (seqan's writer, absent).  The
 // number formats of the tabular columns are SeqAn2's (source absent): [UPSTREAM-RECALL] pident %.2f, evalue %.1e, bitscore %.1f,
 // 1-based inclusive positions.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <set>
@@ -267,7 +269,138 @@ void reverseComplementAscii(std::string & seq)
         }
 }
 
+// Where the writers put their bytes: a file (lx_write_records_ex) or memory (lx_render_records)
+struct Sink
+{
+    std::FILE *   f = nullptr;
+    std::string * s = nullptr;
+    bool          ok = true;
+    void          write(void const * p, size_t k)
+    {
+        if (f)
+            ok = std::fwrite(p, 1, k, f) == k && ok;
+        else
+            s->append(static_cast<char const *>(p), k);
+    }
+    void put(char c) { write(&c, 1); }
+    __attribute__((format(printf, 2, 3))) void print(char const * fmt, ...)
+    {
+        va_list ap;
+        va_start(ap, fmt);
+        if (f)
+            ok = std::vfprintf(f, fmt, ap) >= 0 && ok;
+        else
+        {
+            char    buf[512];
+            va_list aq;
+            va_copy(aq, ap);
+            int const k = std::vsnprintf(buf, sizeof(buf), fmt, aq);
+            va_end(aq);
+            if (k >= 0 && (size_t)k < sizeof(buf))
+                s->append(buf, (size_t)k);
+            else if (k >= 0)
+            {
+                std::string big((size_t)k + 1, '\0');
+                std::vsnprintf(&big[0], big.size(), fmt, ap);
+                s->append(big.data(), (size_t)k);
+            }
+        }
+        va_end(ap);
+    }
+};
+
+// ---- BAM (SAM/BAM specification section 4.2): little-endian fields
+template <class T>
+void putLe(std::string & o, T v)
+{
+    for (size_t i = 0; i < sizeof(T); ++i)
+        o.push_back((char)(uint8_t)((uint64_t)v >> (8 * i)));
+}
+
+// the specification's reg2bin over [beg, end)
+int reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14)
+        return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17)
+        return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20)
+        return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23)
+        return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26)
+        return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+// one BAM alignment record from the fields the SAM line carries (MAPQ 255, no mate, QUAL absent = 0xFF per base)
+void bamRecord(std::string & o, int32_t refId, int64_t pos0, std::string const & qname, int flag, std::string const & cigar,
+               std::string const & seq, std::string const & tags)
+{
+    std::vector<uint32_t> ops;
+    int64_t               span = 0;
+    if (cigar != "*")
+    {
+        uint64_t len = 0;
+        for (char c : cigar)
+        {
+            if (c >= '0' && c <= '9')
+            {
+                len = len * 10 + (uint64_t)(c - '0');
+                continue;
+            }
+            char const * const kOps = "MIDNSHP=X";
+            uint32_t const     op   = (uint32_t)(std::strchr(kOps, c) - kOps);
+            ops.push_back((uint32_t)len << 4 | op);
+            if (c == 'M' || c == 'D' || c == 'N' || c == '=' || c == 'X')
+                span += (int64_t)len;
+            len = 0;
+        }
+    }
+    size_t const lseq = seq == "*" ? 0 : seq.size();
+    size_t const at   = o.size();
+    putLe<int32_t>(o, 0); // block_size, filled in below
+    putLe<int32_t>(o, refId);
+    putLe<int32_t>(o, (int32_t)pos0);
+    putLe<uint8_t>(o, (uint8_t)(qname.size() + 1));
+    putLe<uint8_t>(o, 255);
+    putLe<uint16_t>(o, (uint16_t)reg2bin(pos0, pos0 + (span > 0 ? span : 1)));
+    putLe<uint16_t>(o, (uint16_t)ops.size());
+    putLe<uint16_t>(o, (uint16_t)flag);
+    putLe<int32_t>(o, (int32_t)lseq);
+    putLe<int32_t>(o, -1); // next refID
+    putLe<int32_t>(o, -1); // next pos
+    putLe<int32_t>(o, 0);  // tlen
+    o.append(qname.c_str(), qname.size() + 1);
+    for (uint32_t x : ops)
+        putLe<uint32_t>(o, x);
+    static char const kNt16[] = "=ACMGRSVTWYHKDBN";
+    for (size_t i = 0; i < lseq; i += 2)
+    {
+        auto code = [&](size_t k) -> uint8_t
+        {
+            if (k >= lseq)
+                return 0;
+            char const * p = std::strchr(kNt16, std::toupper((unsigned char)seq[k]));
+            return p && *p ? (uint8_t)(p - kNt16) : (uint8_t)15;
+        };
+        o.push_back((char)(code(i) << 4 | code(i + 1)));
+    }
+    o.append(lseq, (char)0xff);
+    o += tags;
+    uint32_t const bs = (uint32_t)(o.size() - at - 4);
+    for (int i = 0; i < 4; ++i)
+        o[at + i] = (char)(uint8_t)(bs >> (8 * i));
+}
+
 } // namespace
+
+// the bytes lx_render_records hands out
+struct lx_bytes
+{
+    std::string b;
+};
 
 extern "C" {
 
@@ -444,7 +577,7 @@ int lx_write_footer(char const * path, int format, uint64_t n_records)
 int lx_check_output_options(int format, lx_output_options const * opt_in)
 {
     g_output_error.clear();
-    if (format != LX_OUT_BLAST_TAB && format != LX_OUT_BLAST_TAB_COMMENTS && format != LX_OUT_SAM)
+    if (format != LX_OUT_BLAST_TAB && format != LX_OUT_BLAST_TAB_COMMENTS && format != LX_OUT_SAM && format != LX_OUT_BAM)
     {
         g_output_error = "unknown output format";
         return LX_EINVAL;
@@ -455,7 +588,7 @@ int lx_check_output_options(int format, lx_output_options const * opt_in)
         opt = *opt_in;
     std::vector<int> cols;
     bool             tags[kNumSamTags] = {};
-    if (format == LX_OUT_SAM)
+    if (format == LX_OUT_SAM || format == LX_OUT_BAM)
         return resolveTags(opt.sam_tags, tags) ? LX_OK : LX_EINVAL;
     return resolveColumns(opt.columns, cols) ? LX_OK : LX_EINVAL;
 }
@@ -467,12 +600,16 @@ int lx_write_records(char const * path, int format, int write_header, char const
     return lx_write_records_ex(path, format, write_header, program, m, n, ops, names, q_res_ascii, q_ascii_off, nullptr);
 }
 
-int lx_write_records_ex(char const * path, int format, int write_header, char const * program, lx_blast_match const * m,
-                        uint64_t n, uint8_t const * ops, lx_seq_names const * names, uint8_t const * q_res_ascii,
-                        uint64_t const * q_ascii_off, lx_output_options const * opt_in)
+} // extern "C"
+
+// The writers of myWriteHeader / myWriteRecord into a sink: the text formats, or BAM (format LX_OUT_BAM: the SAM records in
+// binary, the SAM header with its @SQ lines and the reference list in front).  `f` == nullptr: only the arguments are checked.
+static int renderRecords(Sink * f, int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n,
+                         uint8_t const * ops, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                         lx_output_options const * opt_in)
 {
     g_output_error.clear();
-    if (!path || !names || (!m && n) || !program)
+    if (!names || (!m && n) || !program)
         return LX_EINVAL;
     lx_output_options opt;
     lx_output_options_default(&opt);
@@ -484,21 +621,18 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
     if (!isN && !qTrans && !sTrans && std::strcmp(program, "blastp") != 0)
         return LX_EINVAL;
     // what the caller asked for is resolved before the file is touched (the reference fails while parsing its options)
+    bool const       bam = format == LX_OUT_BAM;
     std::vector<int> cols;
     bool             tags[kNumSamTags] = {};
-    if (format == LX_OUT_SAM)
+    if (format == LX_OUT_SAM || bam)
     {
         if (!resolveTags(opt.sam_tags, tags))
             return LX_EINVAL;
     }
     else if (!resolveColumns(opt.columns, cols))
         return LX_EINVAL;
-    std::FILE * f = std::fopen(path, write_header ? "w" : "a");
     if (!f)
-    {
-        g_output_error = std::string("cannot open ") + path;
-        return LX_EINVAL;
-    }
+        return LX_OK;
     bool        io_ok = true;
     std::string upper(program);
     for (char & c : upper)
@@ -559,28 +693,51 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
         return protFrames[b.q_frame > 0 ? b.q_frame - 1 : 2 - b.q_frame];
     };
 
-    if (format == LX_OUT_SAM)
+    if (format == LX_OUT_SAM || bam)
     {
+        // BAM always carries the reference sequences (seqan's writeHeader, src/search_output.hpp:440-456): its header text is what
+        // --sam-with-refheader writes
+        std::string headerText;
+        Sink        textSink{nullptr, &headerText};
+        Sink &      hs = bam ? textSink : *f;
+        if (bam)
+            opt.sam_with_ref_header = 1;
         if (write_header) // src/search_output.hpp:347-460
         {
-            std::fprintf(f, "@HD\tVN:1.4\tGO:query\n");
+            hs.print("@HD\tVN:1.4\tGO:query\n");
             // --sam-with-refheader: seqan's writeHeader adds one @SQ per subject from the context ([UPSTREAM-RECALL] behind @HD)
             if (opt.sam_with_ref_header)
                 for (uint64_t i = 0; i < names->n_s; ++i)
-                    std::fprintf(f, "@SQ\tSN:%s\tLN:%llu\n", firstWord(names->s_ids[i]).c_str(), (unsigned long long)names->s_lens[i]);
+                    hs.print("@SQ\tSN:%s\tLN:%llu\n", firstWord(names->s_ids[i]).c_str(), (unsigned long long)names->s_lens[i]);
             if (opt.version_to_output) // :391-399
-                std::fprintf(f, "@PG\tID:lambda\tPN:lambda\tVN:%s\tCL:%s\n", opt.version ? opt.version : "", opt.command_line ? opt.command_line : "");
-            std::fprintf(f, "@CO\tLambda is a high performance BLAST compatible local aligner, please see http://seqan.de/lambda "
+                hs.print("@PG\tID:lambda\tPN:lambda\tVN:%s\tCL:%s\n", opt.version ? opt.version : "", opt.command_line ? opt.command_line : "");
+            hs.print("@CO\tLambda is a high performance BLAST compatible local aligner, please see http://seqan.de/lambda "
                             "for more information.\n");
-            std::fprintf(f, "@CO\tSAM/BAM dialect documentation is available here: https://github.com/seqan/lambda/wiki/Output-Formats\n");
-            std::fprintf(f, "@CO\tIf you use any results found by Lambda, please cite Hauswedell et al. (2014) doi: "
+            hs.print("@CO\tSAM/BAM dialect documentation is available here: https://github.com/seqan/lambda/wiki/Output-Formats\n");
+            hs.print("@CO\tIf you use any results found by Lambda, please cite Hauswedell et al. (2014) doi: "
                             "10.1093/bioinformatics/btu439\n");
             std::string tagLine = "Optional tags as follow"; // :424-437
             for (int t = 0; t < kNumSamTags; ++t)
                 if (tags[t])
                     tagLine += std::string("\t") + kSamTags[t].key + ":" + kSamTags[t].desc;
-            std::fprintf(f, "@CO\t%s\n", tagLine.c_str());
+            hs.print("@CO\t%s\n", tagLine.c_str());
+            if (bam)
+            {
+                std::string h = "BAM\1";
+                putLe<int32_t>(h, (int32_t)headerText.size());
+                h += headerText;
+                putLe<int32_t>(h, (int32_t)names->n_s);
+                for (uint64_t i = 0; i < names->n_s; ++i)
+                {
+                    std::string const sn = firstWord(names->s_ids[i]);
+                    putLe<int32_t>(h, (int32_t)(sn.size() + 1));
+                    h.append(sn.c_str(), sn.size() + 1);
+                    putLe<int32_t>(h, (int32_t)names->s_lens[i]);
+                }
+                f->write(h.data(), h.size());
+            }
         }
+        std::string rec, tagBytes; // (BAM: one record, its optional fields)
         for (uint64_t lo = 0; lo < n;)
         {
             uint64_t hi = lo + 1;
@@ -591,10 +748,7 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
             {
                 lx_blast_match const & b = m[k];
                 if (b.n_qid >= names->n_q || b.n_sid >= names->n_s)
-                {
-                    std::fclose(f);
                     return LX_EINVAL;
-                }
                 int const         flag = ((k == lo) ? 0 : 256) | (b.q_frame < 0 ? 16 : 0); // secondary (:505, :723), RC (:506-507)
                 std::string const qn = firstWord(names->q_ids[b.n_qid]), sn = firstWord(names->s_ids[b.n_sid]);
                 bool const        hard = opt.sam_hard_clip != 0;
@@ -648,43 +802,92 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
                     if (b.s_frame < 0)
                         pos = qLen - pos;
                 }
-                std::fprintf(f, "%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t*", qn.c_str(), flag, sn.c_str(),
-                             (unsigned long long)(pos + 1), cigar.c_str(), seq.c_str());
-                // tags in the order myWriteRecord appends them (:601-719), with the widths it casts to
+                if (!bam)
+                    f->print("%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t*", qn.c_str(), flag, sn.c_str(), (unsigned long long)(pos + 1),
+                             cigar.c_str(), seq.c_str());
+                // tags in the order myWriteRecord appends them (:601-719), with the widths it casts to; in BAM with the types it
+                // passes (f, S, C, c, I, Z)
+                tagBytes.clear();
+                auto tagNum = [&](char const * key, char type, int64_t v)
+                {
+                    if (!bam)
+                    {
+                        f->print("\t%s:i:%lld", key, (long long)v);
+                        return;
+                    }
+                    tagBytes.append(key, 2);
+                    tagBytes.push_back(type);
+                    switch (type)
+                    {
+                        case 'c': putLe<int8_t>(tagBytes, (int8_t)v); break;
+                        case 'C': putLe<uint8_t>(tagBytes, (uint8_t)v); break;
+                        case 'S': putLe<uint16_t>(tagBytes, (uint16_t)v); break;
+                        default: putLe<uint32_t>(tagBytes, (uint32_t)v); break;
+                    }
+                };
+                auto tagStr = [&](char const * key, std::string const & v)
+                {
+                    if (!bam)
+                    {
+                        f->print("\t%s:Z:%s", key, v.c_str());
+                        return;
+                    }
+                    tagBytes.append(key, 2);
+                    tagBytes.push_back('Z');
+                    tagBytes.append(v.c_str(), v.size() + 1);
+                };
                 if (tags[kTagEValue])
-                    std::fprintf(f, "\tae:f:%g", (double)(float)b.e_value);
+                {
+                    float const e = (float)b.e_value;
+                    if (!bam)
+                        f->print("\tae:f:%g", (double)e);
+                    else
+                    {
+                        uint32_t bits;
+                        std::memcpy(&bits, &e, 4);
+                        tagBytes += "aef";
+                        putLe<uint32_t>(tagBytes, bits);
+                    }
+                }
                 if (tags[kTagBitScore])
-                    std::fprintf(f, "\tAS:i:%u", (unsigned)(uint16_t)b.bit_score);
+                    tagNum("AS", 'S', (uint16_t)b.bit_score);
                 if (tags[kTagScore])
-                    std::fprintf(f, "\tar:i:%u", (unsigned)(uint8_t)b.score); // (uint8_t in the reference, :612-616: scores beyond 255 wrap)
+                    tagNum("ar", 'C', (uint8_t)b.score); // (uint8_t in the reference, :612-616: scores beyond 255 wrap)
                 if (tags[kTagPIdent])
-                    std::fprintf(f, "\tai:i:%u", (unsigned)(uint8_t)b.identity);
+                    tagNum("ai", 'C', (uint8_t)b.identity);
                 if (tags[kTagPPos])
-                    std::fprintf(f, "\tap:i:%u", (unsigned)(uint16_t)(b.alignment_length ? 100.0 * b.num_positives / b.alignment_length : 0.0));
+                    tagNum("ap", 'S', (uint16_t)(b.alignment_length ? 100.0 * b.num_positives / b.alignment_length : 0.0));
                 if (tags[kTagQFrame])
-                    std::fprintf(f, "\tqf:i:%d", (int)(int8_t)b.q_frame);
+                    tagNum("qf", 'c', (int8_t)b.q_frame);
                 if (tags[kTagSFrame])
-                    std::fprintf(f, "\tsf:i:%d", (int)(int8_t)b.s_frame);
+                    tagNum("sf", 'c', (int8_t)b.s_frame);
                 if (tags[kTagSTaxIds])
-                    std::fprintf(f, "\tst:Z:%s", taxIdsOf(b.n_sid).c_str());
+                    tagStr("st", taxIdsOf(b.n_sid));
                 if (tags[kTagLcaId])
-                    std::fprintf(f, "\tls:Z:%s", (opt.tax_names && opt.tax && lca < opt.tax->n_taxa && opt.tax_names[lca]) ? opt.tax_names[lca] : "*");
+                    tagStr("ls", (opt.tax_names && opt.tax && lca < opt.tax->n_taxa && opt.tax_names[lca]) ? opt.tax_names[lca] : "*");
                 if (tags[kTagLcaTaxId])
-                    std::fprintf(f, "\tlt:i:%u", lca);
+                    tagNum("lt", 'I', lca);
                 if (tags[kTagProtSeq]) // :669-689
                 {
                     std::string prot = (isN || !writeSeq) ? std::string() : frameProtein(b);
                     if (!prot.empty() && hard)
                         prot = b.q_end <= prot.size() && b.q_start <= b.q_end ? prot.substr(b.q_start, b.q_end - b.q_start) : std::string();
-                    std::fprintf(f, "\tqs:Z:%s", prot.empty() ? "*" : prot.c_str());
+                    tagStr("qs", prot.empty() ? "*" : prot);
                 }
                 if (tags[kTagProtCigar])
-                    std::fprintf(f, "\tOC:Z:%s", protCigar.c_str());
+                    tagStr("OC", protCigar);
                 if (tags[kTagEditDistance])
-                    std::fprintf(f, "\tNM:i:%u", (unsigned)(b.alignment_length - b.num_matches));
+                    tagNum("NM", 'I', (uint32_t)(b.alignment_length - b.num_matches));
                 if (tags[kTagMatchCount])
-                    std::fprintf(f, "\tIH:i:%u", (unsigned)(hi - lo));
-                std::fputc('\n', f);
+                    tagNum("IH", 'I', (uint32_t)(hi - lo));
+                if (bam)
+                {
+                    rec.clear();
+                    bamRecord(rec, (int32_t)b.n_sid, (int64_t)pos, qn, flag, cigar, seq, tagBytes);
+                    f->write(rec.data(), rec.size());
+                }
+                else
+                    f->put('\n');
             }
             lo = hi;
         }
@@ -702,10 +905,7 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
             fields += (fields.empty() ? "" : ", ") + std::string(kColumns[c].desc);
         for (uint64_t k = 0; k < n; ++k)
             if (m[k].n_qid >= names->n_q || m[k].n_sid >= names->n_s)
-            {
-                std::fclose(f);
                 return LX_EINVAL;
-            }
         for (uint64_t lo = 0; lo < n;)
         {
             uint64_t hi = lo + 1;
@@ -713,9 +913,9 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
                 ++hi;
             if (comments)
             {
-                std::fprintf(f, "# %s\n", versionLine.c_str());
-                std::fprintf(f, "# Query: %s\n# Database: %s\n", names->q_ids[m[lo].n_qid], opt.db_name ? opt.db_name : "lambda_ext");
-                std::fprintf(f, "# Fields: %s\n# %llu hits found\n", fields.c_str(), (unsigned long long)(hi - lo));
+                f->print("# %s\n", versionLine.c_str());
+                f->print("# Query: %s\n# Database: %s\n", names->q_ids[m[lo].n_qid], opt.db_name ? opt.db_name : "lambda_ext");
+                f->print("# Fields: %s\n# %llu hits found\n", fields.c_str(), (unsigned long long)(hi - lo));
             }
             uint32_t lca = 0;
             for (int c : cols)
@@ -825,11 +1025,10 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
                 {
                     if (failed[t])
                     {
-                        std::fclose(f);
                         g_output_error = "out of memory while formatting the records";
                         return LX_ENOMEM;
                     }
-                    io_ok = (std::fwrite(piece[t].data(), 1, piece[t].size(), f) == piece[t].size()) && io_ok;
+                    f->write(piece[t].data(), piece[t].size());
                 }
                 break;
             }
@@ -838,20 +1037,95 @@ int lx_write_records_ex(char const * path, int format, int write_header, char co
             {
                 line.clear();
                 formatRecord(m[k], lca, line);
-                io_ok = (std::fwrite(line.data(), 1, line.size(), f) == line.size()) && io_ok;
+                f->write(line.data(), line.size());
             }
             lo = hi;
         }
     }
+    return io_ok ? LX_OK : LX_EINVAL;
+}
+
+extern "C" {
+
+int lx_write_records_ex(char const * path, int format, int write_header, char const * program, lx_blast_match const * m,
+                        uint64_t n, uint8_t const * ops, lx_seq_names const * names, uint8_t const * q_res_ascii,
+                        uint64_t const * q_ascii_off, lx_output_options const * opt_in)
+{
+    g_output_error.clear();
+    if (!path || format == LX_OUT_BAM) // (BAM is binary and BGZF-compressed: lx_write_records_bgzf)
+        return LX_EINVAL;
+    // what the caller asked for is resolved before the file is touched
+    int rc = renderRecords(nullptr, format, write_header, program, m, n, ops, names, q_res_ascii, q_ascii_off, opt_in);
+    if (rc != LX_OK)
+        return rc;
+    std::FILE * file = std::fopen(path, write_header ? "w" : "a");
+    if (!file)
+    {
+        g_output_error = std::string("cannot open ") + path;
+        return LX_EINVAL;
+    }
+    Sink f{file, nullptr};
+    rc = renderRecords(&f, format, write_header, program, m, n, ops, names, q_res_ascii, q_ascii_off, opt_in);
     // (the fprintf paths set the stream's error indicator: one look at the end covers them)
-    io_ok = !std::ferror(f) && io_ok;
-    io_ok = (std::fclose(f) == 0) && io_ok;
+    bool io_ok = f.ok && !std::ferror(file);
+    io_ok      = (std::fclose(file) == 0) && io_ok;
+    if (rc != LX_OK)
+        return rc;
     if (!io_ok)
     {
         g_output_error = std::string("error while writing ") + path + " (disk full?)";
         return LX_EINVAL;
     }
     return LX_OK;
+}
+
+int lx_render_records(int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+                      lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                      lx_output_options const * opt, int64_t footer_records, lx_bytes ** out)
+{
+    g_output_error.clear();
+    if (!out || format < LX_OUT_BLAST_TAB || format > LX_OUT_BAM)
+        return LX_EINVAL;
+    *out = nullptr;
+    int rc = renderRecords(nullptr, format, write_header, program, m, n, ops, names, q_res_ascii, q_ascii_off, opt);
+    if (rc != LX_OK)
+        return rc;
+    lx_bytes * r = nullptr;
+    try
+    {
+        r = new lx_bytes();
+        Sink s{nullptr, &r->b};
+        rc = renderRecords(&s, format, write_header, program, m, n, ops, names, q_res_ascii, q_ascii_off, opt);
+        if (rc == LX_OK && footer_records >= 0 && format == LX_OUT_BLAST_TAB_COMMENTS) // lx_write_footer
+            s.print("# BLAST processed %llu queries\n", (unsigned long long)footer_records);
+    }
+    catch (std::bad_alloc const &)
+    {
+        g_output_error = "out of memory while formatting the records";
+        rc             = LX_ENOMEM;
+    }
+    if (rc != LX_OK)
+    {
+        delete r;
+        return rc;
+    }
+    *out = r;
+    return LX_OK;
+}
+
+uint8_t const * lx_bytes_data(lx_bytes const * b)
+{
+    return b ? reinterpret_cast<uint8_t const *>(b->b.data()) : nullptr;
+}
+
+uint64_t lx_bytes_size(lx_bytes const * b)
+{
+    return b ? b->b.size() : 0;
+}
+
+void lx_bytes_free(lx_bytes * b)
+{
+    delete b;
 }
 
 } // extern "C"

@@ -1167,6 +1167,12 @@ void lx_destroy(lx_handle * h)
             if (ev)
                 (void)hipEventDestroy(ev);
     }
+    for (DevBuf * b : {&h->bgzf.d_in, &h->bgzf.d_slots, &h->bgzf.d_dist, &h->bgzf.d_sym, &h->bgzf.d_sizes, &h->bgzf.d_out, &h->bgzf.d_total})
+        if (b->ptr)
+            (void)hipFree(b->ptr);
+    for (lx_handle::Pinned * b : {&h->bgzf.p_in[0], &h->bgzf.p_in[1], &h->bgzf.p_out, &h->bgzf.p_total})
+        if (b->ptr)
+            (void)hipHostFree(b->ptr);
     for (lx_handle::Pinned * b : {&h->p_all, &h->p_score_all})
         if (b->ptr)
             (void)hipHostFree(b->ptr);

@@ -239,6 +239,12 @@ struct lx_handle
         double                exp_lambda = 0;         // the scheme d_exp was made for
         uint32_t              exp_n      = 0;
     } l2;
+    // lx_bgzf_compress (lx_bgzf_host.cpp): one chunk's device buffers, its input in two pinned lanes, its members on the way out
+    struct Bgzf
+    {
+        DevBuf d_in, d_slots, d_dist, d_sym, d_sizes, d_out, d_total;
+        Pinned p_in[2], p_out, p_total;
+    } bgzf;
     bool     keep_phase_events = false; // lx_extend_batch: the phase events of every chunk of the call stay (lx_last_phase_ms sums them)
     bool     in_fused      = false; // lx_extend_batch_dev is driving the sub-steps (it owns ev0/ev1 and the phase list)
 };
