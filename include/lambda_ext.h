@@ -636,7 +636,7 @@ int lx_write_footer(char const * path, int format, uint64_t n_records);
 char const * lx_last_output_error(void);
 
 /* ---- rendered output and BGZF compression ------------------------------------------------------ */
-/* An opaque byte buffer handed out by lx_render_records. */
+/* An opaque byte buffer handed out by lx_render_records and lx_gunzip. */
 typedef struct lx_bytes lx_bytes;
 uint8_t const * lx_bytes_data(lx_bytes const * b);
 uint64_t        lx_bytes_size(lx_bytes const * b);
@@ -670,6 +670,16 @@ int lx_write_records_bgzf(lx_handle * h, char const * path, int format, char con
                           uint8_t const * ops, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
                           lx_output_options const * opt, int64_t footer_records);
 
+/* Decompresses a gzip stream of one or more members (RFC 1952): BGZF members on h's device, other members on the calling
+ * thread; h may be NULL (every member on the host).  *out is released with lx_bytes_free.  Malformed input: LX_EINVAL.
+ * A member with the BGZF subfield (BC, BSIZE) whose DEFLATE bytes and ISIZE are at most 64 KiB is decoded on the device, one
+ * workgroup per member; a member without it (what gzip, pigz and most downloads make) is decoded on the host, as is every member
+ * when h is NULL.  Every member's CRC32, ISIZE and final block are checked; a malformed one (invalid code, distance before the
+ * start of the output, output past ISIZE, truncation, BSIZE past the end of the data, bytes that are no gzip member) fails the
+ * call with a message that names the member and its byte offset: lx_last_error(h), or lx_last_output_error() when h is NULL.
+ * lx_last_phase_ms(h, 5, ...) = device time of the decoder's kernel in the last call. */
+int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Blocks until everything queued on the handle's stream has finished. */
 int lx_synchronize(lx_handle * h);
@@ -682,7 +692,7 @@ char const * lx_last_kernel_name(lx_handle const * h);
 char const * lx_last_trace_kernel_name(lx_handle const * h);
 /* Device time (HIP events on the launch stream) the most recent call spent in one phase, summed over its launches:
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
- * 4 = BGZF encoder (lx_bgzf_compress). */
+ * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

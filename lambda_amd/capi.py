@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "lx_widen_and_preprocess", "lx_postprocess_records", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
-    "lx_write_records_bgzf",
+    "lx_write_records_bgzf", "lx_gunzip",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -237,6 +237,7 @@ def load():
     lib.lx_bgzf_bound.argtypes = [u64]
     lib.lx_bgzf_bound.restype = u64
     lib.lx_bgzf_compress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
+    lib.lx_gunzip.argtypes = [vp, vp, u64, C.POINTER(vp)]
     lib.lx_write_records_bgzf.argtypes = [vp, C.c_char_p, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
                                           C.c_int64]
     _lib = lib
@@ -332,6 +333,23 @@ def render_records(fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, 
 
 def bgzf_bound(n: int) -> int:
     return int(load().lx_bgzf_bound(n))
+
+
+def gunzip(handle: "Handle | None", data: bytes) -> bytes:
+    """lx_gunzip: the bytes of a gzip stream of one or more members.  BGZF members are decoded on the handle's device, every other
+    member on this thread; handle None = every member on the host.  Malformed input raises LambdaExtError(LX_EINVAL) with the
+    library's message, which names the member and its byte offset."""
+    lib = load()
+    buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+    out = C.c_void_p()
+    h = handle.h if handle is not None else None
+    rc = lib.lx_gunzip(h, _ptr(buf), len(data), C.byref(out))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, lib.lx_last_error(h).decode() if h is not None else last_output_error())
+    try:
+        return C.string_at(lib.lx_bytes_data(out), lib.lx_bytes_size(out)) if lib.lx_bytes_size(out) else b""
+    finally:
+        lib.lx_bytes_free(out)
 
 
 def write_records(path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",

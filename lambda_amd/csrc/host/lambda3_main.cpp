@@ -4,6 +4,12 @@
 //   lambda3 searchp -q queries.fasta -d db.fasta -o out.m8 [-e 1e-2] [-n 25] [--seed-length 10] [--seed-offset 5]
 //                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--seeding gpu|host]
 //
+// Inputs (-q, -d of search* and mkindex*) are FASTA or FASTQ, plain or gzip-compressed, as the reference's (fa, fq, fasta, fastq,
+// fna, faa, each optionally .gz: src/search_options.hpp:157-167, src/mkindex_options.hpp:96-105); the format comes from the bytes
+// (gzip magic, then ">" or "@"), not the name.  lx_gunzip decompresses: BGZF members on the first device of --devices for search*
+// (mkindex*: on the host unless --table gpu), other members on the reading thread.  FASTQ qualities are read and dropped
+// (src/search_algo.hpp:342); bzip2 is refused.
+//
 // What it mirrors from the reference, and what it does not:
 //   * subcommand split and the search command line (src/lambda.cpp:30-118; src/search_options.hpp:143-816): -q, -o (format from
 //     the extension, :684-710), -e, --bit-score, --percent-identity, -n, the seeding options (--seed-length/-offset/-delta[0],
@@ -107,16 +113,145 @@ uint8_t dnaRankSeqan(char c) // SeqAn Dna5 rank A,C,G,T,N: the bisulfite schemes
     return table[(unsigned char)c];
 }
 
+// ---- input files: FASTA or FASTQ, plain or gzip-compressed (BGZF or not), told apart by their bytes, not their names
+// (the reference reads fa, fq, fasta, fastq, fna, faa, each optionally .gz: src/search_options.hpp:157-167, src/mkindex_options.hpp:96-105)
+struct InputText
+{
+    std::string text;
+    double      msGunzip = 0; // decompression time (0: the file was not compressed)
+    bool        onDevice = false;
+};
+
+// the file's bytes, decompressed by lx_gunzip when they start with the gzip magic: BGZF members on `device` (< 0: every member on the
+// host), other members on this thread.  One handle per call, so that the two reader threads never share one.
+InputText readInput(std::string const & path, int device)
+{
+    std::FILE * f = std::fopen(path.c_str(), "rb");
+    if (!f)
+        throw std::runtime_error("cannot open " + path);
+    InputText r;
+    std::string raw;
+    char        buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof(buf), f)) > 0;)
+        raw.append(buf, got);
+    bool const err = std::ferror(f) != 0;
+    std::fclose(f);
+    if (err)
+        throw std::runtime_error("error while reading " + path);
+    if (raw.size() >= 3 && raw.compare(0, 3, "BZh") == 0)
+        throw std::runtime_error(path + ": bzip2-compressed input is not supported (decompress it, or recompress it with gzip or bgzip)");
+    if (raw.size() < 2 || (uint8_t)raw[0] != 0x1f || (uint8_t)raw[1] != 0x8b)
+    {
+        r.text.swap(raw);
+        return r;
+    }
+    auto const  t0 = std::chrono::steady_clock::now();
+    lx_handle * h  = nullptr;
+    if (device >= 0 && lx_create(device, &h) != LX_OK)
+        throw std::runtime_error(lx_last_error(nullptr));
+    std::unique_ptr<lx_handle, void (*)(lx_handle *)> keepH(h, lx_destroy);
+    lx_bytes *                                        out = nullptr;
+    if (lx_gunzip(h, reinterpret_cast<uint8_t const *>(raw.data()), raw.size(), &out) != LX_OK)
+        throw std::runtime_error(path + ": " + (h ? lx_last_error(h) : lx_last_output_error()));
+    std::unique_ptr<lx_bytes, void (*)(lx_bytes *)> keep(out, lx_bytes_free);
+    r.text.assign(reinterpret_cast<char const *>(lx_bytes_data(out)), lx_bytes_size(out));
+    r.msGunzip = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    r.onDevice = h != nullptr;
+    return r;
+}
+
+// calls f(id, letters) per record of a FASTA (">") or FASTQ ("@") text, until f returns false.  FASTQ: the "@" line, sequence
+// lines up to a line starting with "+", then quality lines until there are as many quality characters as letters; the qualities
+// are dropped, as the reference drops them (src/search_algo.hpp:342).
+template <class F>
+void forEachRecord(std::string const & text, std::string const & path, F && f)
+{
+    size_t       p = 0;
+    size_t const n = text.size();
+    auto         nextLine = [&](char const *& a, size_t & len) -> bool
+    {
+        if (p >= n)
+            return false;
+        size_t e = text.find('\n', p);
+        if (e == std::string::npos)
+            e = n;
+        a   = text.data() + p;
+        len = e - p;
+        p   = e + 1;
+        if (len && a[len - 1] == '\r')
+            --len;
+        return true;
+    };
+    auto append = [](std::string & cur, char const * a, size_t len)
+    {
+        for (size_t i = 0; i < len; ++i)
+            if (!std::isspace((unsigned char)a[i]))
+                cur.push_back(a[i]);
+    };
+    size_t const first = text.find_first_not_of(" \t\r\n");
+    char const * a     = nullptr;
+    size_t       len   = 0;
+    std::string  id, cur;
+    if (first != std::string::npos && text[first] == '@')
+    {
+        while (nextLine(a, len))
+        {
+            if (len == 0)
+                continue;
+            if (a[0] != '@')
+                throw std::runtime_error(path + ": FASTQ record expected, found a line starting with '" + std::string(1, a[0]) + "'");
+            id.assign(a + 1, len - 1);
+            cur.clear();
+            bool plus = false;
+            while (nextLine(a, len))
+            {
+                if (len && a[0] == '+')
+                {
+                    plus = true;
+                    break;
+                }
+                append(cur, a, len);
+            }
+            if (!plus)
+                throw std::runtime_error(path + ": FASTQ record '" + id + "' has no '+' line");
+            size_t quals = 0;
+            while (quals < cur.size() && nextLine(a, len))
+                quals += len;
+            if (quals != cur.size())
+                throw std::runtime_error(path + ": FASTQ record '" + id + "' has " + std::to_string(quals) + " quality characters for " +
+                                         std::to_string(cur.size()) + " letters");
+            if (!f(id, cur))
+                return;
+        }
+        return;
+    }
+    bool have = false;
+    while (nextLine(a, len))
+    {
+        if (len == 0)
+            continue;
+        if (a[0] == '>')
+        {
+            if (have && !f(id, cur))
+                return;
+            id.assign(a + 1, len - 1);
+            cur.clear();
+            have = true;
+        }
+        else if (have)
+            append(cur, a, len);
+    }
+    if (have)
+        f(id, cur);
+}
+
 // translate = six protein frames per nucleotide sequence (BLASTX queries: qryNumFrames = 6, translate_join)
 // bsFrames: 0 = none; 1 = bisulfite subjects (every sequence twice: views::duplicate, src/shared_definitions.hpp:249-250);
 // 2 = bisulfite queries (strand, strand, reverse complement, reverse complement: add_reverse_complement | duplicate, :260-261)
-void readFasta(std::string const & path, bool protein, bool addRevComp, SeqSet & out, bool translate = false, int geneticCode = 1,
-               int bsFrames = 0)
+void readFasta(std::string const & text, std::string const & path, bool protein, bool addRevComp, SeqSet & out, bool translate = false,
+               int geneticCode = 1, int bsFrames = 0)
 {
-    std::ifstream in(path);
-    if (!in)
-        throw std::runtime_error("cannot open " + path);
-    std::string line, cur;
+    std::string cur;
     auto flush = [&]()
     {
         if (out.ids.size() == out.orig_len.size())
@@ -192,25 +327,14 @@ void readFasta(std::string const & path, bool protein, bool addRevComp, SeqSet &
         }
         cur.clear();
     };
-    while (std::getline(in, line))
-    {
-        if (!line.empty() && line.back() == '\r')
-            line.pop_back();
-        if (line.empty())
-            continue;
-        if (line[0] == '>')
-        {
-            flush();
-            out.ids.push_back(line.substr(1));
-        }
-        else if (line.find_first_of(" \t\v\f") == std::string::npos)
-            cur += line;
-        else
-            for (char c : line)
-                if (!std::isspace((unsigned char)c))
-                    cur.push_back(c);
-    }
-    flush();
+    forEachRecord(text, path,
+                  [&](std::string const & id, std::string & letters)
+                  {
+                      out.ids.push_back(id);
+                      cur.swap(letters);
+                      flush();
+                      return true;
+                  });
 }
 
 struct Options
@@ -253,23 +377,17 @@ struct Options
 
 // the reference lets BioC++ detect the query alphabet (src/search_options.hpp); here: nucleotide if >= 90 % of the
 // letters of the first sequences are ACGTUN
-bool looksLikeDna(std::string const & path)
+bool looksLikeDna(std::string const & text, std::string const & path)
 {
-    std::ifstream in(path);
-    std::string   line;
-    uint64_t      nuc = 0, all = 0;
-    while (std::getline(in, line) && all < 100000)
-    {
-        if (line.empty() || line[0] == '>')
-            continue;
-        for (char c : line)
-        {
-            if (std::isspace((unsigned char)c))
-                continue;
-            ++all;
-            nuc += std::strchr("ACGTUNacgtun", c) != nullptr;
-        }
-    }
+    uint64_t nuc = 0, all = 0;
+    forEachRecord(text, path,
+                  [&](std::string const &, std::string const & letters)
+                  {
+                      for (char c : letters)
+                          nuc += std::strchr("ACGTUNacgtun", c) != nullptr;
+                      all += letters.size();
+                      return all < 100000;
+                  });
     return all > 0 && nuc * 10 >= all * 9;
 }
 
@@ -279,8 +397,8 @@ Options parse(int argc, char ** argv)
 {
     Options o;
     if (argc < 2)
-        throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.fasta (-i DB.lba | -d DB.fasta) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
-                                 "[--devices 0,1,...] [-t THREADS]\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.fasta [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]");
+        throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.{fa,fq,fasta,fastq,fna,faa}[.gz] (-i DB.lba | -d DB.fasta[.gz]) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
+                                 "[--devices 0,1,...] [-t THREADS]\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
     if (o.cmd != "searchp" && o.cmd != "searchn" && o.cmd != "searchbs" && !mk)
@@ -739,12 +857,50 @@ int main(int argc, char ** argv)
                     throw std::runtime_error("Attempting to use nucleotid index for bisulfite search.");
             }
         }
+        // the input files' bytes, decompressed (two files, two threads and a handle each; -t 1 keeps it to one): search* decodes BGZF
+        // members on the first device of --devices, mkindex* on the host unless --table gpu already asks for a device
+        int const   gunzipDevice = (!mk || opt.table == "gpu") ? (opt.devices.empty() ? 0 : opt.devices[0]) : -1;
+        InputText   qIn, dIn;
+        std::string loadError;
+        {
+            std::thread qLoader;
+            auto        loadQueries = [&]()
+            {
+                try
+                {
+                    qIn = readInput(opt.query, gunzipDevice);
+                }
+                catch (std::exception const & e)
+                {
+                    loadError = e.what();
+                }
+            };
+            struct LoadJoiner
+            {
+                std::thread & t;
+                ~LoadJoiner()
+                {
+                    if (t.joinable())
+                        t.join();
+                }
+            } loadJoiner{qLoader};
+            if (!mk && opt.threads != 1)
+                qLoader = std::thread(loadQueries);
+            else if (!mk)
+                loadQueries();
+            if (!fromIndex)
+                dIn = readInput(opt.db, gunzipDevice);
+        }
+        if (!loadError.empty())
+            throw std::runtime_error(loadError);
+        double const msGunzip = std::max(qIn.msGunzip, dIn.msGunzip);
+        bool const   gunzipOnDevice = qIn.onDevice || dIn.onDevice;
         std::string const reduction = !fromIndex ? opt.reduction : ifo.redAlph == kAlphLi10 ? "li10" : ifo.redAlph == kAlphMurphy10 ? "murphy10" : "none";
         // searchp with nucleotide queries is BLASTX: six translated frames per query against the protein database
-        bool const    blastx = !mk && prot && (opt.qryAlphabet == "dna5" || (opt.qryAlphabet == "auto" && looksLikeDna(opt.query)));
+        bool const    blastx = !mk && prot && (opt.qryAlphabet == "dna5" || (opt.qryAlphabet == "auto" && looksLikeDna(qIn.text, opt.query)));
         // searchp against a nucleotide database translates the subjects instead (TBLASTN), or both sides (TBLASTX)
         bool const    sTrans  = fromIndex ? (prot && ifo.origAlph != ifo.transAlph)
-                                          : prot && (opt.dbAlphabet == "dna5" || (opt.dbAlphabet == "auto" && looksLikeDna(opt.db)));
+                                          : prot && (opt.dbAlphabet == "dna5" || (opt.dbAlphabet == "auto" && looksLikeDna(dIn.text, opt.db)));
         // genetic code: the subjects' is the index's; the queries' is -g, else the index's (src/search.cpp:157-178)
         int const geneticCodeDb  = fromIndex ? (int)ifo.geneticCode : opt.geneticCode;
         int const geneticCodeQry = (opt.geneticCodeGiven || !fromIndex || !sTrans) ? opt.geneticCode : (int)ifo.geneticCode;
@@ -764,7 +920,7 @@ int main(int argc, char ** argv)
         {
             try
             {
-                readFasta(opt.query, prot, !prot, qs, blastx, geneticCodeQry, bs ? 2 : 0);
+                readFasta(qIn.text, opt.query, prot, !prot, qs, blastx, geneticCodeQry, bs ? 2 : 0);
             }
             catch (std::exception const & e)
             {
@@ -786,14 +942,11 @@ int main(int argc, char ** argv)
             readQueries();
         if (!fromIndex)
         {
-            std::ifstream probe(opt.db, std::ios::binary);
-            char          c = 0;
-            while (probe.get(c) && std::isspace((unsigned char)c))
-                ;
-            if (probe && c != '>')
-                throw std::runtime_error(opt.db + " is neither a FASTA file nor an index of this front end (an index written by the reference -- a cereal "
+            size_t const first = dIn.text.find_first_not_of(" \t\r\n\v\f");
+            if (first != std::string::npos && dIn.text[first] != '>' && dIn.text[first] != '@')
+                throw std::runtime_error(opt.db + " is neither a FASTA file nor an index of this front end (nor FASTQ, plain or gzip-compressed; an index written by the reference -- a cereal "
                                          "archive of an fmindex-collection FM-index -- cannot be read here: run lambda3 mkindexp|mkindexn|mkindexbs on the FASTA file)");
-            readFasta(opt.db, prot, false, db, sTrans, geneticCodeDb, bs ? 1 : 0);
+            readFasta(dIn.text, opt.db, prot, false, db, sTrans, geneticCodeDb, bs ? 1 : 0);
         }
         if (qryReader.joinable())
             qryReader.join();
@@ -806,7 +959,10 @@ int main(int argc, char ** argv)
         if (mk && opt.truncateIds) // src/mkindex_algo.hpp:123
             for (std::string & id : db.ids)
                 id.resize(std::min(id.size(), id.find_first_of(" \t")));
-        double const msRead = msSince(tStart);
+        double const      msRead = msSince(tStart);
+        std::string const gunzipNote = msGunzip > 0 ? " (gzip decompression " + std::string(gunzipOnDevice ? "of BGZF on the GPU " : "on the host ") +
+                                                          std::to_string((long)(msGunzip + 0.5)) + ")"
+                                                    : std::string();
         unsigned const nThreads = opt.threads > 0 ? (unsigned)opt.threads : grantedThreads();
 
         // ---- the reduced alphabet of the seeding stage and the word table over the reduced database (the FM-index's place)
@@ -894,9 +1050,9 @@ int main(int argc, char ** argv)
                 residues += l;
             std::fprintf(stderr,
                          "lambda3 %s: %zu sequences (%llu residues in %d frame(s); original alphabet %s, translated %s, reduced %s, genetic code %d) -> %s\n"
-                         "lambda3 times [ms]: read %.0f, reduce + word table %.0f (%s), write %.0f, total %.0f\n",
+                         "lambda3 times [ms]: read %.0f%s, reduce + word table %.0f (%s), write %.0f, total %.0f\n",
                          opt.cmd.c_str(), db.ids.size(), (unsigned long long)residues, sFrames, alphName(out.origAlph), alphName(out.transAlph),
-                         alphName(out.redAlph), (int)out.geneticCode, opt.index.c_str(), msRead, msIndex, tableOnGpu ? "on the GPU" : (std::to_string(nThreads) + " host thread(s)").c_str(),
+                         alphName(out.redAlph), (int)out.geneticCode, opt.index.c_str(), msRead, gunzipNote.c_str(), msIndex, tableOnGpu ? "on the GPU" : (std::to_string(nThreads) + " host thread(s)").c_str(),
                          msSince(tWrite), msSince(tStart));
             return 0;
         }
@@ -1238,9 +1394,9 @@ int main(int argc, char ** argv)
                      (unsigned long long)nHsp, (unsigned long long)nOut, (unsigned long long)rst.qrys_with_hit);
         // where the wall clock went (the reference prints its own at verbosity 2, src/search.cpp): per worker the slowest counts
         std::fprintf(stderr,
-                     "lambda3 times [ms]: read %.0f, reduce + word table %s%.0f, search %.0f (seeding on the %s %.0f [%zu read(s) and %zu launch(es) left to "
+                     "lambda3 times [ms]: read %.0f%s, reduce + word table %s%.0f, search %.0f (seeding on the %s %.0f [%zu read(s) and %zu launch(es) left to "
                      "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records + output %.0f%s, total %.0f\n",
-                     msRead, fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
+                     msRead, gunzipNote.c_str(), fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
                      nPassesOnHost, msExtendMax, msSince(tOut) - msCompress,
                      (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str() : "", msSince(tStart));
         return 0;

@@ -396,11 +396,26 @@ void bamRecord(std::string & o, int32_t refId, int64_t pos0, std::string const &
 
 } // namespace
 
-// the bytes lx_render_records hands out
+// the bytes lx_render_records and lx_gunzip hand out
 struct lx_bytes
 {
     std::string b;
 };
+
+namespace lxi
+{
+lx_bytes * bytes_adopt(std::string && s)
+{
+    lx_bytes * r = new lx_bytes();
+    r->b.swap(s);
+    return r;
+}
+
+void set_output_error(std::string const & msg)
+{
+    g_output_error = msg;
+}
+} // namespace lxi
 
 extern "C" {
 

@@ -1173,6 +1173,13 @@ void lx_destroy(lx_handle * h)
     for (lx_handle::Pinned * b : {&h->bgzf.p_in[0], &h->bgzf.p_in[1], &h->bgzf.p_out, &h->bgzf.p_total})
         if (b->ptr)
             (void)hipHostFree(b->ptr);
+    for (DevBuf * b : {&h->gunzip.d_in, &h->gunzip.d_mem, &h->gunzip.d_status, &h->gunzip.d_out})
+        if (b->ptr)
+            (void)hipFree(b->ptr);
+    for (lx_handle::Pinned * b : {&h->gunzip.p_in[0], &h->gunzip.p_in[1], &h->gunzip.p_mem[0], &h->gunzip.p_mem[1], &h->gunzip.p_status[0],
+                                  &h->gunzip.p_status[1]})
+        if (b->ptr)
+            (void)hipHostFree(b->ptr);
     for (lx_handle::Pinned * b : {&h->p_all, &h->p_score_all})
         if (b->ptr)
             (void)hipHostFree(b->ptr);

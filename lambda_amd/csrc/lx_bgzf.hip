@@ -2,8 +2,8 @@
 //
 // The input is cut into blocks of at most kBgzfBlock = 65 280 bytes (htslib's cut: a stored block never exceeds 64 KiB).  One
 // workgroup encodes one block into one gzip member in a slot of kBgzfSlot bytes:
-//   1. the block goes to LDS; CRC32 by per-lane slices, combined by multiplication with x^(8k) mod P (the GF(2) algebra of
-//      zlib's crc32_combine) and an atomic XOR -- the order of the lanes does not matter;
+//   1. the block goes to LDS; CRC32 by per-lane slices, combined by multiplication with x^(8k) mod P (lx_crc32.h) and an atomic
+//      XOR -- the order of the lanes does not matter;
 //   2. LZ77 with one candidate per position: positions are taken 256 at a time; each lane looks up the last earlier position
 //      with the same 4-byte hash BEFORE the chunk's inserts, then inserts with atomicMax (the largest position wins whatever
 //      the timing), then measures the match (up to 258 bytes, distance up to 32 768);
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lx_bgzf.h"
+#include "lx_crc32.h"
 
 namespace lx
 {
@@ -30,43 +31,9 @@ constexpr uint32_t kDataLds  = 65536;                  // the block (65 280 byte
 constexpr uint32_t kLenLds   = kBgzfBlock;             // match length - 3 per position, 0 = none
 constexpr uint32_t kAuxLds   = 4u << kHashBits;        // the hash heads; after the matching the code tables
 constexpr uint32_t kLdsBytes = kDataLds + kLenLds + kAuxLds;
-constexpr uint32_t kCrcPoly  = 0xedb88320u;
 
 static_assert(kLdsBytes <= 160 * 1024 - 256, "the encoder's LDS exceeds what gfx950 gives a workgroup");
 static_assert((kDataLds + kLenLds) % 16 == 0, "the hash heads must be aligned");
-
-// ---- CRC32 algebra (reflected; x^0 = bit 31)
-__device__ uint32_t mul_mod_p(uint32_t a, uint32_t b)
-{
-    uint32_t m = 1u << 31, p = 0;
-    for (;;)
-    {
-        if (a & m)
-        {
-            p ^= b;
-            if ((a & (m - 1)) == 0)
-                break;
-        }
-        m >>= 1;
-        b = (b & 1) ? (b >> 1) ^ kCrcPoly : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 n) mod P
-__device__ uint32_t x_pow_8n(uint32_t n)
-{
-    uint32_t p = 1u << 31, t = 1u << 23; // t = x^8
-    while (n)
-    {
-        if (n & 1)
-            p = mul_mod_p(t, p);
-        n >>= 1;
-        if (n)
-            t = mul_mod_p(t, t);
-    }
-    return p;
-}
 
 // ---- DEFLATE symbols (RFC 1951 3.2.5)
 __device__ __forceinline__ void length_symbol(uint32_t len, uint32_t & sym, uint32_t & nextra, uint32_t & extra)

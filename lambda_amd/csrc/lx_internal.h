@@ -245,6 +245,12 @@ struct lx_handle
         DevBuf d_in, d_slots, d_dist, d_sym, d_sizes, d_out, d_total;
         Pinned p_in[2], p_out, p_total;
     } bgzf;
+    // lx_gunzip (lx_gunzip_host.cpp): one chunk of BGZF members on the device; its bytes, member table and status words in two pinned lanes
+    struct Gunzip
+    {
+        DevBuf d_in, d_mem, d_status, d_out;
+        Pinned p_in[2], p_mem[2], p_status[2];
+    } gunzip;
     bool     keep_phase_events = false; // lx_extend_batch: the phase events of every chunk of the call stay (lx_last_phase_ms sums them)
     bool     in_fused      = false; // lx_extend_batch_dev is driving the sub-steps (it owns ev0/ev1 and the phase list)
 };
@@ -322,6 +328,9 @@ struct PhaseTimer
 
 int    ensure(lx_handle * h, DevBuf & b, size_t bytes);
 int    bind(lx_handle * h);
+// (host/lx_output.cpp) an lx_bytes that takes over s; the message lx_last_output_error() returns
+lx_bytes * bytes_adopt(std::string && s);
+void       set_output_error(std::string const & msg);
 size_t pair_lds_limit();
 int    pick_cfg(uint32_t qlen, bool shared);
 int    ckpt_cfg_for(uint64_t max_q, bool packed16 = false);
