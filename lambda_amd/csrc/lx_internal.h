@@ -26,6 +26,7 @@
 #include "host/scoring_tables.hpp"
 #include "lx_aids.h"
 #include "lx_device.h"
+#include "lx_host_plan.h"
 #include "lx_host_pool.h"
 
 
@@ -87,15 +88,10 @@ struct lx_handle
     bool        timed = false;
     std::string error;
     // lx_extend_batch: host staging that keeps its pages between calls
-    std::vector<uint32_t>     xb_idx, xb_src, xb_sel, xb_pos;
-    std::vector<uint32_t>     xb_pool_pan, xb_pool_maxs, xb_pool_place, xb_pool_order, xb_pool_key, xb_pool_tmp; // the pool's wavefronts before they are put in launch order
-    std::vector<uint8_t>      xb_newrun;
+    lxi::HostPlan             plan; // lx_extend_batch*'s host plan (lx_host_plan.cpp)
+    std::vector<uint32_t>     xb_src, xb_pos;
     uint64_t                  xb_stats[4] = {0, 0, 0, 0}; // lx_extend_batch: extensions, slots, cells, cells executed (padding included)
-    std::vector<uint64_t>     xb_grp, xb_off, xb_starts;
-    std::vector<uint32_t>     xb_sbfirst, xb_sbkey, xb_sborder, xb_sbtmp; // multi-query plan: the pool's sub-blocks of 4 windows
-    std::vector<uint8_t>      xb_sbcnt;
-    std::vector<uint32_t>     xb_runkey, xb_runorder, xb_runtmp;          // ... the streamed runs in packing order
-    std::vector<uint32_t>     xb_slot, xb_wfpan, xb_wfmaxs;               // ... the plan: caller index per slot, panels / longest window per wavefront
+    std::vector<uint64_t>     xb_grp, xb_off;
     std::vector<lx_extension> xb_ext;
     std::vector<int32_t>      xb_min, xb_score;
     std::vector<uint8_t> ext_ops; // band mode: the ops of the last lx_extend_batch call (handed out by pointer)
