@@ -680,6 +680,71 @@ int lx_write_records_bgzf(lx_handle * h, char const * path, int format, char con
  * lx_last_phase_ms(h, 5, ...) = device time of the decoder's kernel in the last call. */
 int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out);
 
+/* ---- taxonomy of an index (mkindex -m / -x: src/mkindex_algo.hpp:68-107, :277-598, src/mkindex_misc.hpp:69-144) ----------- */
+/* Every non-overlapping match of the reference's accession regex in text[0, n) (UniProt, NCBI nucleotide / protein / WGS / MGA,
+ * RefSeq, UniParc; ECMAScript's leftmost-first alternation, greedy counts), left to right: the first min(cap, *n_found) of them
+ * into out_begin / out_len; *n_found = their number.  No handle, no device. */
+int lx_find_accessions(uint8_t const * text, uint64_t n, uint64_t * out_begin, uint32_t * out_len, uint64_t cap, uint64_t * n_found);
+
+enum
+{
+    LX_TAXMAP_NCBI    = 0, /* *.accession2taxid: first line "accession\taccession.version\ttaxid\tgi"; field 0 = accession, 2 = taxon */
+    LX_TAXMAP_UNIPROT = 1  /* *.dat (idmapping.dat): lines with field 1 == "NCBI_TaxID"; field 0 = accession, 2 = taxon          */
+};
+typedef struct lx_taxmap lx_taxmap;
+/* The accession table of n_s subjects: ids[id_off[s] .. id_off[s + 1]) is subject s's id (after --truncate-ids); each accession
+ * in it maps to s, the later subject winning an accession two share.  h: the join runs on h's device (the table is uploaded
+ * here, once), NULL: on the library's host threads (n_threads parts; 0 = LX_OPT_HOST_THREADS' width).  chunk_bytes: the map is
+ * joined in chunks of whole lines of at most this many bytes (0 = 256 MiB; a line longer than a chunk is refused).  Errors go to
+ * lx_last_error(h), or lx_last_output_error() when h is NULL, for this call and the lx_taxmap_* calls on *out. */
+int lx_taxmap_create(lx_handle * h, int format, uint8_t const * ids, uint64_t const * id_off, uint64_t n_s, uint64_t chunk_bytes,
+                     uint32_t n_threads, lx_taxmap ** out);
+/* The next n bytes of the map, cut anywhere (a line may span calls).  LX_EINVAL with the reference's text and the 1-based line
+ * number: "Unexpected first line in NCBI taxid file." (NCBI format), "Error: Expected taxonomical ID, but got something I couldn't
+ * read: X" (a line whose accession is in the table and whose taxon field is no number; on other lines it is not read).  Both
+ * paths name the first such line of the file.  After an error every later call returns it again. */
+int lx_taxmap_feed(lx_taxmap * tm, uint8_t const * bytes, uint64_t n);
+typedef struct lx_taxmap_result
+{
+    uint64_t const * s_tax_off;     /* n_s + 1: subject s's taxa are s_tax_ids[s_tax_off[s] .. s_tax_off[s + 1]), in file order,
+                                       duplicates kept */
+    uint32_t const * s_tax_ids;
+    uint64_t         n_s;
+    uint32_t const * present;       /* the taxa that occur, ascending, taxon 1 (the root) always among them */
+    uint64_t         n_present;
+    uint64_t         no_acc, multi_acc; /* subjects whose id holds no / more than one accession                  */
+    uint64_t         no_tax, multi_tax; /* subjects with no / more than one taxon                                  */
+    uint64_t         lines, matched;    /* lines of the map (the NCBI header included), lines that gave a pair  */
+} lx_taxmap_result;
+/* The end of the map (an unterminated last line is a line) and the result, valid until lx_taxmap_destroy.
+ * lx_last_phase_ms(h, 6, ...) = device time of the join kernels since lx_taxmap_create. */
+int  lx_taxmap_finish(lx_taxmap * tm, lx_taxmap_result * out);
+void lx_taxmap_destroy(lx_taxmap * tm);
+
+/* The reference's tree (parseAndStoreTaxTree): nodes.dmp (field 0 = taxon, field 2 = parent) and names.dmp (field 6 ==
+ * "scientific name": field 2 names field 0) as text, present = the taxa of the subjects (lx_taxmap_result.present).  Present
+ * taxa and their ancestors are kept, every other parent becomes 0; parents of in-degree 1 that are not present themselves are
+ * skipped and disconnected; heights count the steps to a parent of at most 1; name 0 is "invalid", a kept taxon without a name
+ * "n/a" (one warning each, and one more when over 10 % of the taxa have none).  The arrays cover every node and every present
+ * taxon: a present taxon without a node has parent 0 (the reference reads past its arrays there).  No handle; errors (unreadable
+ * ids, "Error: taxonomical ID is N, but no such taxon in tree.") go to lx_last_output_error(). */
+typedef struct lx_taxonomy lx_taxonomy;
+int lx_taxonomy_build(char const * nodes, uint64_t nodes_n, char const * names, uint64_t names_n, uint32_t const * present, uint64_t n_present,
+                      lx_taxonomy ** out);
+typedef struct lx_taxonomy_info
+{
+    uint32_t const *     parents;  /* n_taxa */
+    uint32_t const *     heights;  /* n_taxa */
+    char const * const * names;    /* n_taxa, "" for the taxa that are not kept */
+    uint64_t             n_taxa;
+    uint64_t             n_nodes;  /* taxa with a parent after the thinning */
+    uint32_t             max_height;
+    uint32_t             unnamed;  /* kept taxa named "n/a" */
+    char const *         warnings; /* the warnings, one per line ("" = none) */
+} lx_taxonomy_info;
+int  lx_taxonomy_get(lx_taxonomy const * t, lx_taxonomy_info * out);
+void lx_taxonomy_free(lx_taxonomy * t);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Blocks until everything queued on the handle's stream has finished. */
 int lx_synchronize(lx_handle * h);
@@ -692,7 +757,7 @@ char const * lx_last_kernel_name(lx_handle const * h);
 char const * lx_last_trace_kernel_name(lx_handle const * h);
 /* Device time (HIP events on the launch stream) the most recent call spent in one phase, summed over its launches:
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
- * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip). */
+ * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

@@ -32,7 +32,8 @@ EXPORTED_SYMBOLS = [
     "lx_widen_and_preprocess", "lx_postprocess_records", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
-    "lx_write_records_bgzf", "lx_gunzip",
+    "lx_write_records_bgzf", "lx_gunzip", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
+    "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -83,6 +84,19 @@ class RecordStats(C.Structure):
 class TaxTree(C.Structure):
     _fields_ = [("parents", C.c_void_p), ("heights", C.c_void_p), ("n_taxa", C.c_uint64), ("s_tax_off", C.c_void_p),
                 ("s_tax_ids", C.c_void_p), ("n_s", C.c_uint64)]
+
+
+class TaxmapResult(C.Structure):
+    _fields_ = [("s_tax_off", C.c_void_p), ("s_tax_ids", C.c_void_p), ("n_s", C.c_uint64), ("present", C.c_void_p), ("n_present", C.c_uint64)] + [
+        (n, C.c_uint64) for n in ("no_acc", "multi_acc", "no_tax", "multi_tax", "lines", "matched")]
+
+
+class TaxonomyInfo(C.Structure):
+    _fields_ = [("parents", C.c_void_p), ("heights", C.c_void_p), ("names", C.POINTER(C.c_char_p)), ("n_taxa", C.c_uint64),
+                ("n_nodes", C.c_uint64), ("max_height", C.c_uint32), ("unnamed", C.c_uint32), ("warnings", C.c_char_p)]
+
+
+LX_TAXMAP_NCBI, LX_TAXMAP_UNIPROT = 0, 1
 
 
 class SeqNames(C.Structure):
@@ -238,6 +252,16 @@ def load():
     lib.lx_bgzf_bound.restype = u64
     lib.lx_bgzf_compress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
     lib.lx_gunzip.argtypes = [vp, vp, u64, C.POINTER(vp)]
+    lib.lx_find_accessions.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
+    lib.lx_taxmap_create.argtypes = [vp, i32, vp, vp, u64, u64, C.c_uint32, C.POINTER(vp)]
+    lib.lx_taxmap_feed.argtypes = [vp, vp, u64]
+    lib.lx_taxmap_finish.argtypes = [vp, C.POINTER(TaxmapResult)]
+    lib.lx_taxmap_destroy.argtypes = [vp]
+    lib.lx_taxmap_destroy.restype = None
+    lib.lx_taxonomy_build.argtypes = [C.c_char_p, u64, C.c_char_p, u64, vp, u64, C.POINTER(vp)]
+    lib.lx_taxonomy_get.argtypes = [vp, C.POINTER(TaxonomyInfo)]
+    lib.lx_taxonomy_free.argtypes = [vp]
+    lib.lx_taxonomy_free.restype = None
     lib.lx_write_records_bgzf.argtypes = [vp, C.c_char_p, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
                                           C.c_int64]
     _lib = lib
@@ -350,6 +374,93 @@ def gunzip(handle: "Handle | None", data: bytes) -> bytes:
         return C.string_at(lib.lx_bytes_data(out), lib.lx_bytes_size(out)) if lib.lx_bytes_size(out) else b""
     finally:
         lib.lx_bytes_free(out)
+
+
+def find_accessions(text: bytes):
+    """lx_find_accessions: every non-overlapping match of the reference's accession regex in `text`, as (start, length) pairs."""
+    lib = load()
+    buf = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
+    cnt = C.c_uint64()
+    if lib.lx_find_accessions(_ptr(buf), len(text), None, None, 0, C.byref(cnt)) != LX_OK:
+        raise LambdaExtError(LX_EINVAL, "lx_find_accessions")
+    beg = np.zeros(max(cnt.value, 1), np.uint64)
+    ln = np.zeros(max(cnt.value, 1), np.uint32)
+    if lib.lx_find_accessions(_ptr(buf), len(text), _ptr(beg), _ptr(ln), cnt.value, C.byref(cnt)) != LX_OK:
+        raise LambdaExtError(LX_EINVAL, "lx_find_accessions")
+    return [(int(b), int(l)) for b, l in zip(beg[: cnt.value], ln[: cnt.value])]
+
+
+class TaxMap:
+    """lx_taxmap_*: the accession table of the subject ids joined with an accession-to-taxon map fed in pieces.  handle None = the
+    library's host threads (`threads` parts, 0 = its default); chunk_bytes 0 = 256 MiB.  finish() returns a dict: s_tax_off,
+    s_tax_ids, present (numpy arrays) and the counts.  Errors raise LambdaExtError with the library's message."""
+
+    def __init__(self, handle: "Handle | None", fmt: int, ids, chunk_bytes: int = 0, threads: int = 0):
+        self.lib = load()
+        self.hh = handle.h if handle is not None else None
+        raw = [x.encode() if isinstance(x, str) else bytes(x) for x in ids]
+        off = np.zeros(len(raw) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in raw]) if raw else []
+        blob = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+        tm = C.c_void_p()
+        rc = self.lib.lx_taxmap_create(self.hh, fmt, _ptr(blob), _ptr(off), len(raw), chunk_bytes, threads, C.byref(tm))
+        self._check(rc)
+        self.tm = tm
+
+    def _check(self, rc):
+        if rc != LX_OK:
+            raise LambdaExtError(rc, self.lib.lx_last_error(self.hh).decode() if self.hh is not None else last_output_error())
+
+    def feed(self, data: bytes):
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+        self._check(self.lib.lx_taxmap_feed(self.tm, _ptr(buf), len(data)))
+
+    def finish(self):
+        r = TaxmapResult()
+        self._check(self.lib.lx_taxmap_finish(self.tm, C.byref(r)))
+        off = np.ctypeslib.as_array(C.cast(r.s_tax_off, C.POINTER(C.c_uint64)), (r.n_s + 1,)).copy()
+        nids = int(off[-1])
+        ids = np.ctypeslib.as_array(C.cast(r.s_tax_ids, C.POINTER(C.c_uint32)), (nids,)).copy() if nids else np.zeros(0, np.uint32)
+        present = np.ctypeslib.as_array(C.cast(r.present, C.POINTER(C.c_uint32)), (r.n_present,)).copy()
+        out = {"s_tax_off": off, "s_tax_ids": ids, "present": present}
+        out.update({n: int(getattr(r, n)) for n in ("no_acc", "multi_acc", "no_tax", "multi_tax", "lines", "matched")})
+        return out
+
+    def close(self):
+        if getattr(self, "tm", None):
+            self.lib.lx_taxmap_destroy(self.tm)
+            self.tm = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def taxonomy_build(nodes: bytes, names: bytes, present):
+    """lx_taxonomy_build: the reference's thinned and flattened tree.  A dict: parents, heights (numpy), names (list of str; "" for
+    taxa that are not kept), n_nodes, max_height, unnamed, warnings."""
+    lib = load()
+    pres = np.ascontiguousarray(present, dtype=np.uint32)
+    t = C.c_void_p()
+    rc = lib.lx_taxonomy_build(nodes, len(nodes), names, len(names), _ptr(pres) if len(pres) else None, len(pres), C.byref(t))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, last_output_error())
+    try:
+        info = TaxonomyInfo()
+        lib.lx_taxonomy_get(t, C.byref(info))
+        n = int(info.n_taxa)
+        par = np.ctypeslib.as_array(C.cast(info.parents, C.POINTER(C.c_uint32)), (n,)).copy()
+        hgt = np.ctypeslib.as_array(C.cast(info.heights, C.POINTER(C.c_uint32)), (n,)).copy()
+        nm = [info.names[i].decode() for i in range(n)]
+        return {"parents": par, "heights": hgt, "names": nm, "n_nodes": int(info.n_nodes), "max_height": int(info.max_height),
+                "unnamed": int(info.unnamed), "warnings": (info.warnings or b"").decode()}
+    finally:
+        lib.lx_taxonomy_free(t)
 
 
 def write_records(path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",

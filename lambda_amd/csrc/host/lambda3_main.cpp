@@ -28,7 +28,10 @@
 //     writeRecords, with the three middle stages on the GPU through the C ABI;
 //   * mkindexp | mkindexn | mkindexbs (src/lambda.cpp:86-88, src/mkindex_options.hpp:96-262: -d, -i with the .lba / .lta name and the
 //     refusal to overwrite, -r, -g, --input-alphabet, --truncate-ids, --db-index-type, -t) and `search* -i INDEX`: the index file
-//     holds what the reference's holds (the options that fix the types, ids, sequences in the translated alphabet; no taxonomy)
+//     holds what the reference's holds (the options that fix the types, ids, sequences in the translated alphabet; with -m / -x the
+//     subjects' taxa and the taxonomic tree, :107-128, src/mkindex_algo.hpp:277-598: accessions of the ids joined with a plain or
+//     .gz NCBI *.accession2taxid or UniProt *.dat map -- on the device under --table gpu, else on the -t host threads --, the tree
+//     from nodes.dmp / names.dmp)
 //     with this front end's word table in the FM-index's place -- its own format, not the reference's cereal archive; the
 //     searches take the domain, the reduction and the subjects' genetic code from it and refuse an index of another domain
 //     with the reference's messages (src/search.cpp:157-207);
@@ -371,6 +374,7 @@ struct Options
     std::string dbIndexType = "fm";   // --db-index-type fm | bifm (:157-165; recorded, the word table answers both)
     bool        truncateIds = false;  // --truncate-ids (:167-173)
     bool        geneticCodeGiven = false;
+    std::string accTaxMap, taxDumpDir; // -m / -x of mkindex* (:107-128)
     std::string qryAlphabet = "auto"; // searchp: "aminoacid" = BLASTP, "dna5" = BLASTX, "auto" = decide from the letters
     std::string dbAlphabet  = "auto"; // searchp: "dna5" = six-frame translated subjects (TBLASTN / TBLASTX)
 };
@@ -398,7 +402,7 @@ Options parse(int argc, char ** argv)
     Options o;
     if (argc < 2)
         throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.{fa,fq,fasta,fastq,fna,faa}[.gz] (-i DB.lba | -d DB.fasta[.gz]) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
-                                 "[--devices 0,1,...] [-t THREADS]\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]");
+                                 "[--devices 0,1,...] [-t THREADS]\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
     if (o.cmd != "searchp" && o.cmd != "searchn" && o.cmd != "searchbs" && !mk)
@@ -453,8 +457,10 @@ Options parse(int argc, char ** argv)
         }
         else if (mk && a == "--truncate-ids")
             o.truncateIds = true;
-        else if (mk && (a == "-m" || a == "--acc-tax-map" || a == "-x" || a == "--tax-dump-dir"))
-            throw std::runtime_error(a + ": the taxonomy part of the index (src/mkindex_options.hpp:113-128) is not built by this front end");
+        else if (mk && (a == "-m" || a == "--acc-tax-map"))
+            o.accTaxMap = val();
+        else if (mk && (a == "-x" || a == "--tax-dump-dir"))
+            o.taxDumpDir = val();
         else if (a == "-d" || a == "--database" || a == "-i" || a == "--index")
             o.db = val();
         else if (a == "-o" || a == "--output")
@@ -605,6 +611,17 @@ Options parse(int argc, char ** argv)
         { return o.index.size() >= std::strlen(suf) && o.index.compare(o.index.size() - std::strlen(suf), std::string::npos, suf) == 0; };
         if (!ends(".lba") && !ends(".lta")) // :133, :145
             throw std::runtime_error("the index file name must end in .lba or .lta");
+        if (!o.taxDumpDir.empty() && o.accTaxMap.empty()) // :256-264
+            throw std::runtime_error("There is no point in including a taxonomic tree in the index, if you don't also include taxonomic IDs for your sequences.");
+        if (!o.accTaxMap.empty())
+        {
+            auto mapEnds = [&](char const * suf)
+            { return o.accTaxMap.size() >= std::strlen(suf) && o.accTaxMap.compare(o.accTaxMap.size() - std::strlen(suf), std::string::npos, suf) == 0; };
+            if (mapEnds(".accession2taxid.bz2") || mapEnds(".dat.bz2"))
+                throw std::runtime_error(o.accTaxMap + ": bzip2-compressed input is not supported (decompress it, or recompress it with gzip or bgzip)");
+            if (!mapEnds(".accession2taxid") && !mapEnds(".accession2taxid.gz") && !mapEnds(".dat") && !mapEnds(".dat.gz"))
+                throw std::runtime_error("-m " + o.accTaxMap + ": the accession-to-taxonomy map must be named *.accession2taxid or *.dat, optionally .gz");
+        }
         if (std::ifstream(o.index).good()) // :252-256
             throw std::runtime_error("ERROR: An output file already exists at " + o.index + "\n       Remove it, or choose a different location.");
         return o;
@@ -677,7 +694,7 @@ static int outputFormat(std::string const & path, bool & gz)
 }
 
 // ---- the index file of `lambda3 mkindex*`.  It holds what the reference's index_file holds (src/shared_definitions.hpp:343-379:
-// the options that fix the types, the ids, the sequences in the translated alphabet) except the taxonomy, and this front end's
+// the options that fix the types, the ids, the sequences in the translated alphabet, the taxonomy when -m was given), and this front end's
 // word table in place of the FM-index.  NOT the reference's on-disk format: that is a cereal archive of fmindex-collection
 // objects, neither of which is available here; a file of the reference is recognised by the missing magic and refused.
 constexpr char kIndexMagic[8] = {'L', 'X', 'I', 'N', 'D', 'E', 'X', '1'};
@@ -701,7 +718,27 @@ bool isIndexFile(std::string const & path)
     return f.read(m, 8) && std::memcmp(m, kIndexMagic, 8) == 0;
 }
 
-void writeIndexFile(std::string const & path, IndexFileOptions const & io, SeqSet const & db, lambda_amd::ReducedIndex const & ix)
+// The taxonomy of an index (mkindex* -m / -x; the reference's indexFile.sTaxIds, taxonParentIDs, taxonHeights, taxonNames).
+struct IndexTaxonomy
+{
+    bool                     has = false;     // the index holds subject taxa
+    std::vector<uint64_t>    off;             // n_s + 1
+    std::vector<uint32_t>    ids;
+    bool                     hasTree = false; // ... and the tree
+    std::vector<uint32_t>    parents, heights;
+    std::vector<std::string> names;
+};
+constexpr char kTaxonMagic[8] = {'L', 'X', 'T', 'A', 'X', 'O', 'N', '1'};
+
+// The file, in this order (integers little-endian, as the machine writes them):
+//   "LXINDEX1"; IndexFileOptions (16 bytes); u64 n ids, then per id u64 length + bytes; u64 n frames, u64 off[n], u64 len[n];
+//   u64 n, u64 orig_len[n]; u64 n residues + the residues; the word table (ReducedIndex::save).
+//   Optional, only in an index built with -m -- an index without it ends with the word table, as before the section existed:
+//   "LXTAXON1"; u64 n_s; u64 s_tax_off[n_s + 1]; u32 s_tax_ids[s_tax_off[n_s]] (subject s's taxa, in the map's order);
+//   u64 has_tree (0 or 1); if 1: u64 n_taxa, u32 parents[n_taxa], u32 heights[n_taxa], u32 name_len[n_taxa], then the names'
+//   bytes one after another (no terminators; "" for the taxa the tree does not keep).
+void writeIndexFile(std::string const & path, IndexFileOptions const & io, SeqSet const & db, lambda_amd::ReducedIndex const & ix,
+                    IndexTaxonomy const & tax)
 {
     FILE * f = std::fopen(path.c_str(), "wb");
     if (!f)
@@ -725,6 +762,26 @@ void writeIndexFile(std::string const & path, IndexFileOptions const & io, SeqSe
     u64(db.res.size());
     write(db.res.data(), db.res.size());
     ix.save(write);
+    if (tax.has)
+    {
+        write(kTaxonMagic, 8);
+        u64(tax.off.size() - 1);
+        write(tax.off.data(), tax.off.size() * sizeof(uint64_t));
+        write(tax.ids.data(), tax.ids.size() * sizeof(uint32_t));
+        u64(tax.hasTree ? 1 : 0);
+        if (tax.hasTree)
+        {
+            u64(tax.parents.size());
+            write(tax.parents.data(), tax.parents.size() * sizeof(uint32_t));
+            write(tax.heights.data(), tax.heights.size() * sizeof(uint32_t));
+            std::vector<uint32_t> lens;
+            for (std::string const & n : tax.names)
+                lens.push_back((uint32_t)n.size());
+            write(lens.data(), lens.size() * sizeof(uint32_t));
+            for (std::string const & n : tax.names)
+                write(n.data(), n.size());
+        }
+    }
     ok = (std::fclose(f) == 0) && ok;
     if (!ok)
     {
@@ -797,6 +854,152 @@ void readIndexHead(std::string const & path, IndexFileOptions & io, SeqSet & db,
             throw bad("residues outside the index's alphabet");
     }
     *fp = f;
+}
+
+// the optional taxonomy section after the word table (writeIndexFile); f stands right behind the word table
+void readIndexTaxonomy(std::string const & path, FILE * f, uint64_t nSubjects, IndexTaxonomy & tax)
+{
+    auto read = [&](void * p, size_t bytes) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; };
+    auto bad  = [&](char const * what) { return std::runtime_error("index file " + path + ": taxonomy section: " + what); };
+    char m[8];
+    size_t const got = std::fread(m, 1, 8, f);
+    if (got == 0)
+        return; // (no section: an index built without -m)
+    if (got != 8 || std::memcmp(m, kTaxonMagic, 8) != 0)
+        throw bad("unknown data after the word table");
+    auto count = [&](uint64_t limit) -> uint64_t
+    {
+        uint64_t v = 0;
+        if (!read(&v, sizeof(v)) || v > limit)
+            throw bad("truncated or corrupt");
+        return v;
+    };
+    if (count(1ull << 40) != nSubjects)
+        throw bad("its subject count differs from the index's");
+    tax.off.resize(nSubjects + 1);
+    if (!read(tax.off.data(), tax.off.size() * sizeof(uint64_t)))
+        throw bad("truncated");
+    for (uint64_t s = 0; s < nSubjects; ++s)
+        if (tax.off[s + 1] < tax.off[s] || tax.off[0] != 0)
+            throw bad("corrupt subject lists");
+    if (tax.off.back() > (1ull << 40))
+        throw bad("corrupt subject lists");
+    tax.ids.resize(tax.off.back());
+    if (!read(tax.ids.data(), tax.ids.size() * sizeof(uint32_t)))
+        throw bad("truncated");
+    tax.has     = true;
+    tax.hasTree = count(1) == 1;
+    if (!tax.hasTree)
+        return;
+    uint64_t const n = count(1ull << 33);
+    tax.parents.resize(n);
+    tax.heights.resize(n);
+    std::vector<uint32_t> lens(n);
+    if (!read(tax.parents.data(), n * sizeof(uint32_t)) || !read(tax.heights.data(), n * sizeof(uint32_t)) || !read(lens.data(), n * sizeof(uint32_t)))
+        throw bad("truncated");
+    tax.names.resize(n);
+    for (uint64_t t = 0; t < n; ++t)
+    {
+        tax.names[t].resize(lens[t]);
+        if (!read(tax.names[t].data(), lens[t]))
+            throw bad("truncated");
+    }
+}
+
+// The taxonomy of mkindex -m [-x]: the ids' accessions joined with the map (lx_taxmap_*: on the device of `h`, else on `threads` host
+// threads), then the tree from the taxdump (lx_taxonomy_build).  Progress and the reference's counts go to stderr.
+void buildIndexTaxonomy(std::string const & map, std::string const & dumpDir, std::vector<std::string> const & ids, lx_handle * h,
+                        unsigned threads, IndexTaxonomy & tax, double & msJoin, float & msKernel)
+{
+    auto const t0 = std::chrono::steady_clock::now();
+    auto ends = [&](char const * suf) { return map.size() >= std::strlen(suf) && map.compare(map.size() - std::strlen(suf), std::string::npos, suf) == 0; };
+    bool const ncbi = ends(".accession2taxid") || ends(".accession2taxid.gz"); // (else *.dat[.gz]: parse() admits nothing else)
+    std::string blob;
+    std::vector<uint64_t> off{0};
+    for (std::string const & id : ids)
+    {
+        blob += id;
+        off.push_back(blob.size());
+    }
+    lx_taxmap * tm = nullptr;
+    if (lx_taxmap_create(h, ncbi ? LX_TAXMAP_NCBI : LX_TAXMAP_UNIPROT, reinterpret_cast<uint8_t const *>(blob.data()), off.data(), ids.size(), 0,
+                         threads, &tm) != LX_OK)
+        throw std::runtime_error(h ? lx_last_error(h) : lx_last_output_error());
+    std::unique_ptr<lx_taxmap, void (*)(lx_taxmap *)> keep(tm, lx_taxmap_destroy);
+    auto check = [&](int rc)
+    {
+        if (rc != LX_OK)
+            throw std::runtime_error("-m " + map + ": " + (h ? lx_last_error(h) : lx_last_output_error()));
+    };
+    std::FILE * f = std::fopen(map.c_str(), "rb");
+    if (!f)
+        throw std::runtime_error("cannot open " + map);
+    std::unique_ptr<std::FILE, int (*)(std::FILE *)> keepF(f, std::fclose);
+    std::vector<char> buf(64u << 20);
+    size_t got = std::fread(buf.data(), 1, buf.size(), f);
+    if (got >= 2 && (uint8_t)buf[0] == 0x1f && (uint8_t)buf[1] == 0x8b)
+    {
+        // a .gz map is decompressed whole (as -d is), then fed in pieces
+        std::string raw(buf.data(), got);
+        for (size_t k; (k = std::fread(buf.data(), 1, buf.size(), f)) > 0;)
+            raw.append(buf.data(), k);
+        lx_bytes * text = nullptr;
+        if (lx_gunzip(h, reinterpret_cast<uint8_t const *>(raw.data()), raw.size(), &text) != LX_OK)
+            throw std::runtime_error(map + ": " + (h ? lx_last_error(h) : lx_last_output_error()));
+        std::unique_ptr<lx_bytes, void (*)(lx_bytes *)> keepT(text, lx_bytes_free);
+        std::string().swap(raw);
+        uint8_t const * p = lx_bytes_data(text);
+        for (uint64_t at = 0, n = lx_bytes_size(text); at < n; at += buf.size())
+            check(lx_taxmap_feed(tm, p + at, std::min<uint64_t>(buf.size(), n - at)));
+    }
+    else
+    {
+        // a plain map is read and fed in pieces, never whole
+        for (; got > 0; got = std::fread(buf.data(), 1, buf.size(), f))
+            check(lx_taxmap_feed(tm, reinterpret_cast<uint8_t const *>(buf.data()), got));
+    }
+    if (std::ferror(f))
+        throw std::runtime_error("error while reading " + map);
+    lx_taxmap_result r;
+    check(lx_taxmap_finish(tm, &r));
+    msJoin = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    msKernel = 0;
+    if (h)
+        (void)lx_last_phase_ms(h, 6, &msKernel, nullptr);
+    tax.has = true;
+    tax.off.assign(r.s_tax_off, r.s_tax_off + r.n_s + 1);
+    tax.ids.assign(r.s_tax_ids, r.s_tax_ids + r.s_tax_off[r.n_s]);
+    uint64_t const n = ids.size();
+    std::fprintf(stderr,
+                 "lambda3 taxonomy: %llu map lines, %llu matched; subjects without accession: %llu/%llu, with more than one accession: %llu/%llu\n"
+                 "Subjects without tax IDs:             %llu/%llu\nSubjects with more than one tax ID:   %llu/%llu\n",
+                 (unsigned long long)r.lines, (unsigned long long)r.matched, (unsigned long long)r.no_acc, (unsigned long long)n,
+                 (unsigned long long)r.multi_acc, (unsigned long long)n, (unsigned long long)r.no_tax, (unsigned long long)n,
+                 (unsigned long long)r.multi_tax, (unsigned long long)n);
+    if (r.no_tax > 0 && n / r.no_tax < 5) // src/mkindex_algo.hpp:343-349
+        std::fprintf(stderr, "WARNING: %g%% of subjects have no taxID.\n         Maybe you specified the wrong map file?\n", double(r.no_tax) * 100 / n);
+    if (dumpDir.empty())
+        return;
+    auto slurp = [](std::string const & path)
+    {
+        std::ifstream in(path, std::ios::binary);
+        if (!in)
+            throw std::runtime_error("cannot open " + path);
+        return std::string(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+    };
+    std::string const nodes = slurp(dumpDir + "/nodes.dmp"), names = slurp(dumpDir + "/names.dmp");
+    lx_taxonomy *     tree  = nullptr;
+    if (lx_taxonomy_build(nodes.data(), nodes.size(), names.data(), names.size(), r.present, r.n_present, &tree) != LX_OK)
+        throw std::runtime_error("-x " + dumpDir + ": " + lx_last_output_error());
+    std::unique_ptr<lx_taxonomy, void (*)(lx_taxonomy *)> keepTree(tree, lx_taxonomy_free);
+    lx_taxonomy_info info;
+    (void)lx_taxonomy_get(tree, &info);
+    std::fputs(info.warnings, stderr);
+    tax.hasTree = true;
+    tax.parents.assign(info.parents, info.parents + info.n_taxa);
+    tax.heights.assign(info.heights, info.heights + info.n_taxa);
+    tax.names.assign(info.names, info.names + info.n_taxa);
+    std::fprintf(stderr, "Number of nodes in tree: %llu\nMaximum Tree Height: %u\n", (unsigned long long)info.n_nodes, info.max_height);
 }
 
 // host threads this process may use: the hardware's, capped by the affinity mask and the cgroup's CPU quota
@@ -996,6 +1199,23 @@ int main(int argc, char ** argv)
                 if (d < 0 || d >= lx_device_count())
                     throw std::runtime_error("device_id " + std::to_string(d) + " out of range [0," + std::to_string(lx_device_count()) + ")");
         auto const                 tIndex = std::chrono::steady_clock::now();
+        // taxonomy columns (src/search_options.hpp:736-820): lcataxid, lt or ls ask for the LCA
+        IndexTaxonomy indexTax;
+        auto          hasWord = [](std::string const & list, char const * w)
+        {
+            for (size_t at = 0; at < list.size();)
+            {
+                size_t const b = list.find_first_not_of(" \t", at);
+                if (b == std::string::npos)
+                    break;
+                size_t const e = std::min(list.find_first_of(" \t", b), list.size());
+                if (list.compare(b, e - b, w) == 0)
+                    return true;
+                at = e;
+            }
+            return false;
+        };
+        bool const wantLca = !mk && (hasWord(opt.outputColumns, "lcataxid") || hasWord(opt.samTags, "lt") || hasWord(opt.samTags, "ls"));
         std::vector<uint8_t> const dbRed = reduce(db);
         lambda_amd::ReducedIndex   ix;
         bool                       tableOnGpu = false;
@@ -1004,9 +1224,13 @@ int main(int argc, char ** argv)
         {
             bool const ok = ix.load([&](void * p, size_t bytes) { return bytes == 0 || std::fread(p, 1, bytes, indexFile) == bytes; }, dbRed, db.off, db.len) &&
                             ix.alphabet() == alph;
-            indexFileOwner.reset();
             if (!ok)
                 throw std::runtime_error("index file " + opt.db + ": the word table is truncated or does not fit the sequences");
+            readIndexTaxonomy(opt.db, indexFile, db.ids.size(), indexTax);
+            indexFileOwner.reset();
+            // an LCA needs the tree (src/search_algo.hpp:309-313); an index without any taxonomy keeps printing "*" and 0
+            if (wantLca && indexTax.has && !indexTax.hasTree)
+                throw std::runtime_error("You requested taxonomic binning, but the index does not contain a taxonomic tree. Recreate it and provide --tax-dump-dir .");
         }
         else
         {
@@ -1043,8 +1267,22 @@ int main(int argc, char ** argv)
             out.transAlph   = prot ? kAlphAminoAcid : kAlphDna5;
             out.redAlph     = bs ? kAlphDna3Bs : !prot ? kAlphDna4 : reduction == "li10" ? kAlphLi10 : reduction == "murphy10" ? kAlphMurphy10 : kAlphAminoAcid;
             out.geneticCode = (uint8_t)geneticCodeDb;
+            IndexTaxonomy tax;
+            double        msTax = 0;
+            float         msTaxKernel = 0;
+            if (!opt.accTaxMap.empty())
+            {
+                // the join on the device under --table gpu, else on the -t host threads (the same bytes either way)
+                lx_handle * th = nullptr;
+                if (opt.table == "gpu" && lx_create(opt.devices.empty() ? 0 : opt.devices[0], &th) != LX_OK)
+                    throw std::runtime_error(lx_last_error(nullptr));
+                std::unique_ptr<lx_handle, void (*)(lx_handle *)> keepH(th, lx_destroy);
+                buildIndexTaxonomy(opt.accTaxMap, opt.taxDumpDir, db.ids, th, nThreads, tax, msTax, msTaxKernel);
+                std::fprintf(stderr, "lambda3 times [ms]: taxonomy %.0f (%s)\n", msTax,
+                             th ? ("join on the GPU, kernels " + std::to_string((long)(msTaxKernel + 0.5))).c_str() : (std::to_string(nThreads) + " host thread(s)").c_str());
+            }
             auto const tWrite = std::chrono::steady_clock::now();
-            writeIndexFile(opt.index, out, db, ix);
+            writeIndexFile(opt.index, out, db, ix, tax);
             uint64_t residues = 0;
             for (auto l : db.len)
                 residues += l;
@@ -1351,6 +1589,36 @@ int main(int argc, char ** argv)
             oo.command_line        = opt.commandLine.c_str();
             oo.db_name             = opt.db.c_str(); // the index path there (src/search_algo.hpp:320)
             oo.genetic_code        = geneticCodeQry;
+            // the index's taxonomy (the reference's _writeRecord, src/search_algo.hpp:884-908): the LCA per query, over the records
+            // of every worker together
+            lx_tax_tree               tree{};
+            std::vector<uint64_t>     lcaQid;
+            std::vector<uint32_t>     lcaTax;
+            std::vector<char const *> taxNames;
+            if (indexTax.has)
+            {
+                tree.parents   = indexTax.parents.data();
+                tree.heights   = indexTax.heights.data();
+                tree.n_taxa    = indexTax.parents.size();
+                tree.s_tax_off = indexTax.off.data();
+                tree.s_tax_ids = indexTax.ids.data();
+                tree.n_s       = indexTax.off.size() - 1;
+                oo.tax         = &tree;
+                if (wantLca && indexTax.hasTree)
+                {
+                    lcaQid.resize(std::max<uint64_t>(nOut, 1));
+                    lcaTax.resize(std::max<uint64_t>(nOut, 1));
+                    uint64_t nLca = 0;
+                    if (lx_compute_lca(bms.data(), nOut, &tree, lcaQid.data(), lcaTax.data(), &nLca) != LX_OK)
+                        throw std::runtime_error("LCA-computation error: One of the paths didn't lead to root.");
+                    oo.lca_qid = lcaQid.data();
+                    oo.lca_tax = lcaTax.data();
+                    oo.n_lca   = nLca;
+                    for (std::string const & n : indexTax.names)
+                        taxNames.push_back(n.c_str());
+                    oo.tax_names = taxNames.data();
+                }
+            }
             if (fmt == LX_OUT_BAM || outGz)
             {
                 // records, footer and header rendered on the host threads, compressed on the device, written at once
