@@ -226,7 +226,7 @@ int check_async_error(lx_handle * h)
 // (or need the multi-panel path when wider).
 
 int launch_score_list(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n,
-                      void * d_out, int cfg, bool multi, bool shared, hipStream_t stream, int pair_cfg, int pair_share)
+                      void * d_out, int cfg, bool multi, bool shared, hipStream_t stream, int32_t const * band_diag, int pair_cfg, int pair_share)
 {
     lx::ScoreParams p{};
     p.q_res          = static_cast<uint8_t const *>(d_q);
@@ -240,7 +240,7 @@ int launch_score_list(lx_handle * h, int slot, void const * d_q, void const * d_
     p.ws_cap         = (uint32_t)std::min<uint64_t>(h->d_ws.cap / 8, 0xffffffffu);
     p.err            = reinterpret_cast<int32_t *>(h->d_ws_top + 1);
     p.shared_profile = shared ? 1 : 0;
-    p.nrows          = ((h->sc_host[slot].alphabet_size + 1 + 3) / 4) * 4;
+    p.nrows          = h->facts[slot].nrows();
     p.fixup          = 0;
     p.pair_share     = pair_share;
     char buf[128];
@@ -248,7 +248,7 @@ int launch_score_list(lx_handle * h, int slot, void const * d_q, void const * d_
     {
         // band mode: the int32 kernel of the generic geometry, any query width (the packed kernels carry no band code)
         p.band           = (int32_t)h->opt_band;
-        p.band_diag      = h->band_dev;
+        p.band_diag      = band_diag;
         // query runs of a multiple of 8 whose queries fit 152 columns: (8,19), one LDS profile per wavefront
         bool const narrow = shared && cfg == 6 && !multi;
         p.shared_profile  = narrow ? 1 : 0;
@@ -328,17 +328,83 @@ int lxi::resolve_subjects(lx_handle * h, uint8_t const * s_res, uint64_t s_bytes
 }
 
 
+// the device entry points' limits: the handle's options
+static ListLimits option_limits(lx_handle const * h)
+{
+    return ListLimits{h->opt_max_qlen, h->opt_max_slen, h->opt_query_run, h->band_dev, h->opt_bs_rule};
+}
+
+
+// ---- pass 1 ------------------------------------------------------------------------------------------
+
+// geometry from the caller's hints; any geometry is correct for any query length (multi-panel path)
+static int score_geometry(ListLimits const & lim, bool & multi)
+{
+    bool const want_shared = lim.query_run != 0 && lim.query_run % 8 == 0;
+    int const  cfg         = lim.max_qlen ? pick_cfg((uint32_t)std::min<uint64_t>(lim.max_qlen, 0xffffffffu), want_shared) : 0;
+    multi                  = lim.max_qlen == 0 || lim.max_qlen > (uint64_t)lx::score_cfg_panel(cfg);
+    return cfg;
+}
+
+uint64_t lxi::score_ws_pairs(lx_handle const * h, ListLimits const & lim, uint64_t n)
+{
+    bool multi;
+    (void)score_geometry(lim, multi);
+    // (the packed 16-bit kernel sweeps wide queries in (8,19) panels even where the int32 geometry is a single one)
+    bool const wide16 = h->opt_f16 && lim.query_run % 16 == 0 && lim.query_run != 0 && lim.max_qlen > (uint64_t)lx::trace_cfg_panel(2);
+    return (multi || wide16 || (h->opt_band && (lim.max_qlen == 0 || lim.max_qlen > 160))) ? n * ((lim.max_slen + 3) & ~3ull) : 0;
+}
+
+int lxi::score_dev_impl(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out,
+                        hipStream_t stream, ListLimits const & lim)
+{
+    bool       multi;
+    int const  cfg    = score_geometry(lim, multi);
+    bool const shared = lim.query_run != 0 && (lim.query_run % (uint64_t)lx::score_cfg_groups(cfg)) == 0;
+    // packed-half path: the extensions of a wavefront (or, where two LDS profiles fit, of each half of it) must
+    // share their query and the query must fit one panel
+    int pair_cfg = -1, pair_share = 0;
+    if (h->opt_f16 && shared && lim.max_qlen != 0)
+    {
+        int const pc = lx::score_pair_cfg_for((uint32_t)std::min<uint64_t>(lim.max_qlen, 0xffffffffu));
+        if (pc >= 0)
+        {
+            int const      groups   = 64 / lx::score_pair_cfg_group(pc);
+            uint64_t const per_wave = 2ull * groups;
+            if (lim.query_run % per_wave == 0)
+                pair_cfg = pc;
+            else if (groups >= 2 && lim.query_run % (per_wave / 2) == 0 && 2 * lx::score_pair_profile_bytes(pc, h->facts[slot].nrows()) <= pair_lds_limit())
+            {
+                pair_cfg   = pc;
+                pair_share = groups / 2;
+            }
+            else if (lim.query_run % 8 == 0) // two profiles do not fit: a 16-lane geometry holds 8 extensions per wavefront
+                pair_cfg = lx::score_pair_cfg_for_runs_of_8((uint32_t)std::min<uint64_t>(lim.max_qlen, 0xffffffffu));
+        }
+        else if (lim.query_run % 16 == 0 && lim.max_slen != 0) // wider than any packed-half geometry
+            pair_cfg = kPair16;
+    }
+    PhaseTimer pt(h, stream, 0);
+    int const  rc = launch_score_list(h, slot, d_q, d_s, d_ext, n, d_out, cfg, multi, shared, stream, lim.band_diag, pair_cfg, pair_share);
+    if (rc)
+        return rc;
+    pt.close();
+    return LX_OK;
+}
+
+
 // ---- pass 2 ------------------------------------------------------------------------------------------
 
 // Runs pass 2 over a device-resident list of `n` extension slots, in chunks sized to the trace budget.
 // src / d_count are set by the fused path (slots compacted by launch_select): results are then written to
 // out_hsp[src[slot]] / ops_off[src[slot]] and slots beyond *d_count are skipped on the device.
 int lxi::align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * d_s, lx::Extension const * d_ext,
-                          uint64_t n, lx::Hsp * d_hsp, uint8_t * d_ops, uint64_t const * d_ops_off, hipStream_t stream,
-                          uint64_t max_q, uint64_t max_s, int share_slots, uint32_t const * d_src,
-                        uint64_t const * d_count, int32_t const * d_score_in, bool by_pos, uint64_t ops_stride)
+                        uint64_t n, lx::Hsp * d_hsp, uint8_t * d_ops, uint64_t const * d_ops_off, hipStream_t stream,
+                        ListLimits const & lim, int share_slots, uint32_t const * d_src, uint64_t const * d_count,
+                        int32_t const * d_score_in, bool by_pos, uint64_t ops_stride)
 {
-    if (!h->trace_ok[slot])
+    uint64_t const max_q = lim.max_qlen, max_s = lim.max_slen;
+    if (!h->facts[slot].trace_ok)
         return fail(h, LX_EINVAL, "pass 2 needs every (matrix entry - gap_extend) in [-31, 31]");
     if ((reinterpret_cast<uintptr_t>(d_q) | reinterpret_cast<uintptr_t>(d_s)) & 15)
         return fail(h, LX_EINVAL, "pass 2 reads residues in aligned 16-byte groups: the residue buffers must be 16-byte aligned");
@@ -346,10 +412,7 @@ int lxi::align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * 
         return fail(h, LX_EINVAL, "pass 2 supports subject windows up to %d residues (got %llu)", lx::kMaxTraceRows, (unsigned long long)max_s);
     // share_slots = every aligned block of that many slots holds one query (0: no such guarantee).  The 8-lane
     // geometry puts 8 extensions in a wavefront and needs blocks of >= 4 (two LDS profiles per wavefront).
-    int smax_entry = 0;
-    for (int a = 0; a < h->sc_host[slot].alphabet_size; ++a)
-        for (int b = 0; b < h->sc_host[slot].alphabet_size; ++b)
-            smax_entry = std::max<int>(smax_entry, h->sc_host[slot].matrix[a * LX_ALPH + b]);
+    int const smax_entry = h->facts[slot].smax_entry;
     // checkpoint mode (lx_ckpt.hip): shared-profile geometries (8,19) / (16,13), scores that fit int16; queries wider
     // than 208 columns take several (16,13) panels
     bool const ckpt = !h->opt_band && h->opt_pass2 >= 1 && share_slots >= 2 && (uint64_t)smax_entry * std::min(max_q, max_s) < 32000 && max_s <= 65535; // (longer windows: direction bits)
@@ -375,7 +438,7 @@ int lxi::align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * 
             return rc0;
         int const  scfg  = pick_cfg((uint32_t)std::min<uint64_t>(max_q, 0xffffffffu), false);
         bool const multi = max_q > (uint64_t)lx::score_cfg_panel(scfg);
-        if ((rc0 = launch_score_list(h, slot, d_q, d_s, d_ext, n, h->d_trace_score.ptr, scfg, multi, false, stream)))
+        if ((rc0 = launch_score_list(h, slot, d_q, d_s, d_ext, n, h->d_trace_score.ptr, scfg, multi, false, stream, lim.band_diag)))
             return rc0;
         d_score_in = static_cast<int32_t const *>(h->d_trace_score.ptr);
     }
@@ -422,11 +485,11 @@ int lxi::align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * 
         p.ws_top         = h->d_ws_top;
         p.ws_cap         = (uint32_t)std::min<uint64_t>(h->d_ws.cap / 8, 0xffffffffu);
         p.err            = reinterpret_cast<int32_t *>(h->d_ws_top + 1);
-        p.nrows          = ((h->sc_host[slot].alphabet_size + 1 + 3) / 4) * 4;
-        p.bs_match_rule  = (int32_t)h->opt_bs_rule;
+        p.nrows          = h->facts[slot].nrows();
+        p.bs_match_rule  = (int32_t)lim.bs_rule;
         p.work_counter   = h->d_ws_top + 5;
         p.band           = (int32_t)h->opt_band;
-        p.band_diag      = h->band_dev ? (d_src ? h->band_dev : h->band_dev + c0) : nullptr; // indexed like the caller's list
+        p.band_diag      = lim.band_diag ? (d_src ? lim.band_diag : lim.band_diag + c0) : nullptr; // indexed like the caller's list
         p.shared_profile = (h->opt_band && cfg == 0) ? 0 : share_slots;
         p.cfg            = cfg;
         if (panels_cap > 1) // each chunk starts with an empty carry workspace
@@ -452,41 +515,37 @@ int lxi::align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * 
 
 // ---- fused: pass 1 -> survivor selection -> pass 2, all on the device ------------------------------------
 
-// phases: 1 = pass 1 (or the sweep) + selection, 2 = pass 2 (or the sweep's backtrace), 3 = both.  by_pos: records and
-// ops offsets are indexed by the position in the survivor list instead of by extension (the host entry point assigns
-// compact ops offsets between the two phases and downloads only the survivors' records).
-
 // after the backtrace (records and slots by list position): the survivors' ops as run-length codes, the list's original
 // indices next to them
-static int fused_pack(lx_handle * h, FusedExtra const * fx, uint64_t cap, void * d_out_hsp, void * d_out_ops, void const * d_ops_off,
-                      void * d_out_count, hipStream_t stream, bool packed_already = false)
+static int fused_pack(lx_handle * h, StepCall const & c, uint64_t cap, hipStream_t stream, bool packed_already = false)
 {
-    if (!fx || !fx->d_rle)
+    FusedExtra const & fx = c.fx;
+    if (!fx.d_rle)
         return LX_OK;
-    if (fx->d_src_out)
-        LX_HIP(h, hipMemcpyAsync(fx->d_src_out, h->d_sel_src.ptr, cap * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    if (fx.d_src_out)
+        LX_HIP(h, hipMemcpyAsync(fx.d_src_out, h->d_sel_src.ptr, cap * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
     if (packed_already) // (the checkpoint backtrace emits the codes itself)
         return LX_OK;
     lx::PackParams pp{};
-    pp.hsp        = static_cast<lx::Hsp *>(d_out_hsp);
-    pp.ops        = static_cast<uint8_t const *>(d_out_ops);
-    pp.ops_off    = static_cast<uint64_t const *>(d_ops_off);
-    pp.ops_stride = fx->ops_stride;
+    pp.hsp        = static_cast<lx::Hsp *>(c.d_out_hsp);
+    pp.ops        = static_cast<uint8_t const *>(c.d_out_ops);
+    pp.ops_off    = static_cast<uint64_t const *>(c.d_ops_off);
+    pp.ops_stride = fx.ops_stride;
     pp.src        = static_cast<uint32_t const *>(h->d_sel_src.ptr);
-    pp.count_ptr  = static_cast<uint64_t const *>(d_out_count);
+    pp.count_ptr  = static_cast<uint64_t const *>(c.d_out_count);
     pp.n          = cap;
-    pp.rle        = fx->d_rle;
-    pp.rle_top    = fx->d_rle_top;
-    pp.rle_cap    = fx->rle_cap;
-    pp.rle_len    = fx->d_rle_len;
+    pp.rle        = fx.d_rle;
+    pp.rle_top    = fx.d_rle_top;
+    pp.rle_cap    = fx.rle_cap;
+    pp.rle_len    = fx.d_rle_len;
     pp.err        = reinterpret_cast<int32_t *>(h->d_ws_top + 1);
-    LX_HIP(h, hipMemsetAsync(fx->d_rle_top, 0, sizeof(unsigned long long), stream));
+    LX_HIP(h, hipMemsetAsync(fx.d_rle_top, 0, sizeof(unsigned long long), stream));
     LX_HIP(h, lx::launch_rle_pack(pp, stream));
     return LX_OK;
 }
 
 // ---- the ONE place that decides how a fused step runs: which sweep kernel family (if any), geometry, panel count, slot
-// layout, queries per wavefront.  A pure function of the scheme's facts and the handle's options -- fused_impl follows it, and
+// layout, queries per wavefront.  A pure function of the scheme's facts and the step's options -- fused_impl follows it, and
 // lx_plan_step() shows it to tests/test_plan.py, which walks it over query widths, run lengths and schemes on the CPU.
 lxi::StepPlan lxi::plan_step(SchemeFacts const & sc, StepOptions const & o)
 {
@@ -503,7 +562,7 @@ lxi::StepPlan lxi::plan_step(SchemeFacts const & sc, StepOptions const & o)
     uint64_t ovf_cap = 0;
     int      sweep_share = 0;
     bool     half_sweep = false, may_decline = true, wide_compact = false, mq_wide = false;
-    int const nrows_sc = ((sc.alph + 1 + 3) / 4) * 4;
+    int const nrows_sc = sc.nrows();
     // Multi-query sweep (lx_sweep_mq.hip): query runs of 4 or 8 (2 / 4 lane groups per LDS profile) -- what lx_extend_batch
     // makes of a ragged list --, or any multiple of 4 when LX_OPT_MQ_SWEEP = 2 asks for it.  Needs byte profiles (no
     // substitution dearer than a gap's first character) and compact codes (that character costs at most 31).
@@ -527,7 +586,7 @@ lxi::StepPlan lxi::plan_step(SchemeFacts const & sc, StepOptions const & o)
     if (mq)
     {
         int const smax_entry = sc.smax_entry;
-        sweep_cfg    = o.mq_cfg_call ? o.mq_cfg_call : mq_cfg_for(o.max_qlen);
+        sweep_cfg    = o.mq_cfg ? o.mq_cfg : mq_cfg_for(o.max_qlen);
         sweep_panels = (uint32_t)std::max<uint64_t>(1, (o.max_qlen + lx::trace_cfg_panel(sweep_cfg) - 1) / lx::trace_cfg_panel(sweep_cfg));
         mq           = (uint64_t)smax_entry * std::min(o.max_qlen, o.max_slen) < 32000 && o.max_slen <= 65535;
         if (mq)
@@ -673,34 +732,56 @@ void lxi::describe_plan(StepPlan const & pl, char * buf, size_t len)
     }
 }
 
-int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * d_s_res, void const * d_ext, uint64_t n,
-                      void const * d_min_score, int32_t min_score_all, void * d_out_score, void * d_out_hsp, void * d_out_ops,
-                      void const * d_ops_off, void * d_out_count, void * stream_, int phases, bool by_pos,
-                      FusedExtra const * fx)
+// the ScoreParams of a packed sweep: what it shares with the checkpoint launch `p` of the same step (carry: it sweeps panel by
+// panel with the carry workspace)
+static lx::ScoreParams sweep_params(lx::TraceParams const & p, bool carry)
 {
-    if (!h)
-        return LX_EINVAL;
+    lx::ScoreParams sp{};
+    sp.q_res       = p.q_res;
+    sp.s_res       = p.s_res;
+    sp.ext         = p.ext;
+    sp.n           = p.n;
+    sp.sc          = p.sc;
+    sp.out_score   = p.score_out;
+    sp.err         = p.err;
+    sp.nrows       = p.nrows;
+    sp.ckpt        = p.trace;
+    sp.ckpt_stride = p.slot_stride;
+    sp.steps_cap   = p.steps_cap;
+    sp.ends        = p.ends;
+    if (carry)
+    {
+        sp.ws         = p.ws;
+        sp.ws_top     = p.ws_top;
+        sp.ws_cap     = p.ws_cap;
+        sp.panels_cap = p.panels_cap;
+    }
+    return sp;
+}
+
+int lxi::fused_impl(lx_handle * h, int slot, StepCall const & c)
+{
     if (slot < 0 || slot > 1 || !h->have_sc[slot])
         return fail(h, LX_ESTATE, "scoring slot %d not set", slot);
+    uint64_t const n = c.n;
     if (n == 0)
         return LX_OK;
-    if (!d_q_res || !d_s_res || !d_ext || !d_out_score || !d_out_count ||
-        ((phases & 2) && (!d_out_hsp || !d_out_ops || (!d_ops_off && !(fx && fx->ops_stride)))))
+    if (!c.d_q || !c.d_s || !c.d_ext || !c.d_out_score || !c.d_out_count || !c.d_out_hsp || !c.d_out_ops || (!c.d_ops_off && !c.fx.ops_stride))
         return fail(h, LX_EINVAL, "NULL device pointer");
-    if (h->opt_max_qlen == 0 || h->opt_max_slen == 0)
+    if (c.lim.max_qlen == 0 || c.lim.max_slen == 0)
         return fail(h, LX_ESTATE, "lx_extend_batch_dev needs LX_OPT_MAX_QLEN and LX_OPT_MAX_SLEN (it never synchronises)");
     if (n > 0xfffffff0ull)
         return fail(h, LX_EINVAL, "at most 2^32-16 extensions per call");
     int rc = bind(h);
     if (rc)
         return rc;
-    hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : h->stream;
+    hipStream_t const stream = c.stream;
 
-    lx_handle::MqTab const tab = h->mq_tab; // (slots by wavefront: lx_extend_batch's multi-query chunks)
-    bool       tab_on = tab.dev != nullptr;
-    if ((phases & 1) && !(tab_on && tab.part == 2))
+    MqTab const & tab    = c.tab; // (slots by wavefront: lx_extend_batch's multi-query chunks)
+    bool          tab_on = tab.dev != nullptr;
+    if (!(tab_on && tab.part == 2))
     {
-        if (!h->keep_phase_events) // (lx_extend_batch's pipeline collects the events of all its chunks)
+        if (!c.keep_events)
         {
             h->phase_ev.clear();
             h->ev_pool_used = 0;
@@ -708,23 +789,11 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
         LX_HIP(h, hipEventRecord(h->ev0, stream));
     }
     // how this step runs: plan_step() decides, this function follows
-    SchemeFacts facts{};
-    facts.alph       = h->sc_host[slot].alphabet_size;
-    facts.gap_open   = h->sc_host[slot].gap_open;
-    facts.gap_extend = h->sc_host[slot].gap_extend;
-    facts.trace_ok   = h->trace_ok[slot];
-    facts.b8_ok      = h->b8_ok[slot];
-    for (int a = 0; a < facts.alph; ++a)
-        for (int b = 0; b < facts.alph; ++b)
-            facts.smax_entry = std::max<int>(facts.smax_entry, h->sc_host[slot].matrix[a * LX_ALPH + b]);
-    StepOptions so{};
-    so.max_qlen = h->opt_max_qlen, so.max_slen = h->opt_max_slen, so.query_run = h->opt_query_run, so.pass2 = h->opt_pass2;
+    SchemeFacts const & facts = h->facts[slot];
+    StepOptions         so{};
+    so.max_qlen = c.lim.max_qlen, so.max_slen = c.lim.max_slen, so.query_run = c.lim.query_run, so.pass2 = h->opt_pass2;
     so.mq = h->opt_mq, so.f16 = h->opt_f16, so.band = h->opt_band, so.trace_bytes = h->opt_trace_bytes, so.n = n;
-    so.mq_cfg_call = h->mq_cfg_call, so.adapt = h->opt_adapt, so.mq_wide = h->mq_wide_call;
-    // (phase 2 of a split step follows what phase 1 decided: it sees the survivor share phase 1 saw)
-    if (phases & 1)
-        h->plan_surv_frac = h->surv_frac;
-    so.surv_frac = h->plan_surv_frac;
+    so.mq_cfg = c.mq_cfg, so.adapt = h->opt_adapt, so.mq_wide = c.mq_wide, so.surv_frac = h->surv_frac;
     StepPlan plan{};
     if (tab_on)
     {
@@ -746,81 +815,63 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
     }
     else
         plan = plan_step(facts, so);
-    bool const     shared = plan.shared;
-    bool const     sweep = plan.sweep, mq = plan.family == kMqSweep, wide_compact = plan.family == kI16CompactWide;
-    bool const     half_sweep = plan.packed, i16_sweep = plan.family == kI16Pairs, may_decline = plan.may_decline;
-    int const      sweep_cfg = plan.cfg, sweep_share = plan.share;
-    uint32_t const sweep_steps = plan.steps, sweep_panels = plan.panels;
-    uint64_t const sweep_stride = plan.stride, sweep_stride32 = plan.stride32, ovf_cap = plan.ovf_cap;
-    int const      nrows_sc = ((h->sc_host[slot].alphabet_size + 1 + 3) / 4) * 4;
+    bool const mq = plan.family == kMqSweep, wide_compact = plan.family == kI16CompactWide;
     // the packed-half sweep of one-panel queries interleaves the compact slots of a wavefront's windows (ScoreParams::wave_slots):
     // what one store instruction writes is then one contiguous piece (headline sweep 11.87 -> 11.6 ms)
-    bool const     wave_slots = half_sweep && !mq && !wide_compact; // (= launch_score_pair: always one panel)
-    uint64_t const wave_w     = 128 / (uint64_t)lx::trace_cfg_group(sweep_cfg); // windows of a packed-half wavefront
+    bool const     wave_slots = plan.packed && !mq && !wide_compact; // (= launch_score_pair: always one panel)
+    uint64_t const wave_w     = 128 / (uint64_t)lx::trace_cfg_group(plan.cfg); // windows of a packed-half wavefront
     // the batch's slots (+ the spare slot of the compact layouts; whole wavefronts of slots when they are interleaved)
     // (slots by wavefront: [the wavefronts before slot n0][overflow slots][the wavefronts from n0 on])
-    uint64_t const tab_ovf_dw = tab_on ? ovf_cap * sweep_stride32 : 0;
+    uint64_t const tab_ovf_dw = tab_on ? plan.ovf_cap * plan.stride32 : 0;
     uint64_t const batch_dw = tab_on       ? tab.dw0
-                              : wave_slots ? (n + wave_w - 1) / wave_w * wave_w * sweep_stride
-                              : half_sweep ? (n + 1) * sweep_stride
-                                           : n * sweep_stride;
-    if (sweep && (phases & 1))
+                              : wave_slots ? (n + wave_w - 1) / wave_w * wave_w * plan.stride
+                              : plan.packed ? (n + 1) * plan.stride
+                                            : n * plan.stride;
+    if (plan.sweep)
     {
         bool const second = tab_on && tab.part == 2; // (the first call sized the buffers and reset the counters: its sweep may still be running)
         if (tab_on && std::max(tab.total_dw, tab.dw0 + tab_ovf_dw + tab.dw1) * 4 > h->d_trace.cap && second)
             return fail(h, LX_ESTATE, "the second sweep of a chunk needs more slot memory than its first reserved");
-        if (!second && ((rc = ensure(h, h->d_trace, (tab_on ? std::max(tab.total_dw, tab.dw0 + tab_ovf_dw + tab.dw1) : batch_dw + ovf_cap * sweep_stride32) * 4)) ||
+        if (!second && ((rc = ensure(h, h->d_trace, (tab_on ? std::max(tab.total_dw, tab.dw0 + tab_ovf_dw + tab.dw1) : batch_dw + plan.ovf_cap * plan.stride32) * 4)) ||
                         (rc = ensure(h, h->d_ends, n * sizeof(lx::EndCell)))))
             return rc;
-        if (!second && (rc = prepare_workspace(h, stream, sweep_panels > 1 ? n * ((h->opt_max_slen + 3) & ~3ull) : 0)))
+        if (!second && (rc = prepare_workspace(h, stream, plan.panels > 1 ? n * ((c.lim.max_slen + 3) & ~3ull) : 0)))
             return rc;
         if (!second)
             LX_HIP(h, hipMemsetAsync(h->d_ws_top + 4, 0, sizeof(uint32_t), stream));
         lx::TraceParams p{};
-        p.q_res          = static_cast<uint8_t const *>(d_q_res);
-        p.s_res          = static_cast<uint8_t const *>(d_s_res);
-        p.ext            = static_cast<lx::Extension const *>(d_ext);
+        p.q_res          = static_cast<uint8_t const *>(c.d_q);
+        p.s_res          = static_cast<uint8_t const *>(c.d_s);
+        p.ext            = static_cast<lx::Extension const *>(c.d_ext);
         p.n              = n;
         p.sc             = h->sc_dev[slot];
         p.trace          = static_cast<uint32_t *>(h->d_trace.ptr);
-        p.slot_stride    = sweep_stride;
-        p.steps_cap      = sweep_steps;
-        p.panels_cap     = sweep_panels;
+        p.slot_stride    = plan.stride;
+        p.steps_cap      = plan.steps;
+        p.panels_cap     = plan.panels;
         p.ws             = static_cast<int32_t *>(h->d_ws.ptr);
         p.ws_top         = h->d_ws_top;
         p.ws_cap         = (uint32_t)std::min<uint64_t>(h->d_ws.cap / 8, 0xffffffffu);
         p.ends           = static_cast<lx::EndCell *>(h->d_ends.ptr);
-        p.score_out      = static_cast<int32_t *>(d_out_score);
+        p.score_out      = static_cast<int32_t *>(c.d_out_score);
         p.err            = reinterpret_cast<int32_t *>(h->d_ws_top + 1);
-        p.nrows          = nrows_sc;
+        p.nrows          = facts.nrows();
         // every wavefront holds one query (mq: every run; the solo packing: every window its own)
-        p.shared_profile = mq ? (sweep_share < 0 ? 1 : std::min(2 * sweep_share, 8)) : 64 / lx::trace_cfg_group(sweep_cfg);
-        p.cfg            = sweep_cfg;
-        if (half_sweep)
+        p.shared_profile = mq ? (plan.share < 0 ? 1 : std::min(2 * plan.share, 8)) : 64 / lx::trace_cfg_group(plan.cfg);
+        p.cfg            = plan.cfg;
+        if (plan.packed)
         {
             p.ovf        = p.trace + batch_dw;
-            p.ovf_stride = sweep_stride32;
-            p.ovf_cap    = (uint32_t)ovf_cap;
+            p.ovf_stride = plan.stride32;
+            p.ovf_cap    = (uint32_t)plan.ovf_cap;
             p.ovf_count  = h->d_ws_top + 4;
         }
-        int const sweep_pair = sweep_cfg == 1 ? 0 : sweep_cfg == 3 ? 1 : sweep_cfg == 4 ? 7 : 5; // pair geometry with the same (G, C): (8,19) / (8,13) / (8,25) / (16,13)
+        int const sweep_pair = plan.cfg == 1 ? 0 : plan.cfg == 3 ? 1 : plan.cfg == 4 ? 7 : 5; // pair geometry with the same (G, C): (8,19) / (8,13) / (8,25) / (16,13)
         PhaseTimer pt0(h, stream, 0);
-        if (half_sweep)
+        if (plan.packed)
         {
-            lx::ScoreParams sp1{};
-            sp1.q_res       = p.q_res;
-            sp1.s_res       = p.s_res;
-            sp1.ext         = p.ext;
-            sp1.n           = n;
-            sp1.sc          = p.sc;
-            sp1.out_score   = static_cast<int32_t *>(d_out_score);
-            sp1.err         = p.err;
-            sp1.nrows       = p.nrows;
-            sp1.ckpt        = p.trace;
-            sp1.ckpt_stride = sweep_stride;
-            sp1.steps_cap   = sweep_steps;
-            sp1.ends        = p.ends;
-            sp1.pair_share  = std::max(sweep_share, 0);
+            lx::ScoreParams sp1 = sweep_params(p, !wave_slots);
+            sp1.pair_share      = std::max(plan.share, 0);
             if (mq)
             {
                 if (tab_on)
@@ -834,67 +885,42 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
                 sp1.stat_beyond = h->d_ws_top + 6;
                 if (!second)
                     LX_HIP(h, hipMemsetAsync(h->d_ws_top + 6, 0, sizeof(uint32_t), stream));
-                if (sweep_share < 0) // the solo packing: rows for the alphabet's letters and the pad letter, no more
+                if (plan.share < 0) // the solo packing: rows for the alphabet's letters and the pad letter, no more
                 {
                     sp1.solo  = 1;
-                    sp1.nrows = h->sc_host[slot].alphabet_size + 1;
+                    sp1.nrows = facts.alph + 1;
                 }
-                sp1.narrow     = 1;
-                sp1.ws         = p.ws;
-                sp1.ws_top     = p.ws_top;
-                sp1.ws_cap     = p.ws_cap;
-                sp1.panels_cap = sweep_panels;
-                LX_HIP(h, lx::launch_sweep_mq(sweep_cfg, sp1, stream));
+                sp1.narrow = 1;
+                LX_HIP(h, lx::launch_sweep_mq(plan.cfg, sp1, stream));
                 if (tab_on && tab.part == 1)
                 {
                     // the first of a chunk's two sweeps: the rest of the chunk is still being planned -- the second call goes on from here
                     pt0.close();
                     return LX_OK;
                 }
-                if (sweep_panels > 1) // the fix-up launch starts with an empty carry workspace
+                if (plan.panels > 1) // the fix-up launch starts with an empty carry workspace
                     LX_HIP(h, hipMemsetAsync(h->d_ws_top, 0, sizeof(uint32_t), stream));
             }
             else if (wide_compact)
             {
-                sp1.ws         = p.ws;
-                sp1.ws_top     = p.ws_top;
-                sp1.ws_cap     = p.ws_cap;
-                sp1.panels_cap = sweep_panels;
-                LX_HIP(h, lx::launch_sweep_pair16_compact(sweep_cfg, sp1, stream));
+                LX_HIP(h, lx::launch_sweep_pair16_compact(plan.cfg, sp1, stream));
                 LX_HIP(h, hipMemsetAsync(h->d_ws_top, 0, sizeof(uint32_t), stream)); // the fix-up launch starts with an empty carry workspace
             }
             else
             {
-                sp1.wave_slots = wave_slots ? 1 : 0;
+                sp1.wave_slots = 1;
                 LX_HIP(h, lx::launch_score_pair(sweep_pair, sp1, stream));
             }
             p.fixup = 1;
         }
-        if (i16_sweep)
+        if (plan.family == kI16Pairs)
         {
-            lx::ScoreParams sp1{};
-            sp1.q_res       = p.q_res;
-            sp1.s_res       = p.s_res;
-            sp1.ext         = p.ext;
-            sp1.n           = n;
-            sp1.sc          = p.sc;
-            sp1.out_score   = static_cast<int32_t *>(d_out_score);
-            sp1.ws          = p.ws;
-            sp1.ws_top      = p.ws_top;
-            sp1.ws_cap      = p.ws_cap;
-            sp1.err         = p.err;
-            sp1.nrows       = p.nrows;
-            sp1.ckpt        = p.trace;
-            sp1.ckpt_stride = sweep_stride;
-            sp1.steps_cap   = sweep_steps;
-            sp1.ends        = p.ends;
-            sp1.panels_cap  = sweep_panels;
-            LX_HIP(h, lx::launch_sweep_pair16(sweep_cfg, sp1, stream));
-            if (sweep_panels > 1) // the fix-up launch starts with an empty carry workspace
+            LX_HIP(h, lx::launch_sweep_pair16(plan.cfg, sweep_params(p, true), stream));
+            if (plan.panels > 1) // the fix-up launch starts with an empty carry workspace
                 LX_HIP(h, hipMemsetAsync(h->d_ws_top, 0, sizeof(uint32_t), stream));
             p.fixup = 1;
         }
-        if (!half_sweep || may_decline) // (the packed-half kernel declines nothing when even the worst query passes its test)
+        if (!plan.packed || plan.may_decline) // (the packed-half kernel declines nothing when even the worst query passes its test)
             LX_HIP(h, lx::launch_ckpt_forward(p, stream));
         pt0.close();
         char buf[200];
@@ -902,37 +928,33 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
         h->last_kernel       = buf;
         h->last_trace_kernel = buf;
     }
-    else if (phases & 1)
+    else
     {
         // pass 1 (src/search_algo.hpp:1246).  Pass 2 may need the carry workspace even where pass 1 does not (its panels
         // are narrower): size it now, while nothing is in flight
-        if (h->opt_max_qlen > (uint64_t)lx::trace_cfg_panel(1) && (rc = prepare_workspace(h, stream, n * ((h->opt_max_slen + 3) & ~3ull))))
+        if (c.lim.max_qlen > (uint64_t)lx::trace_cfg_panel(1) && (rc = prepare_workspace(h, stream, n * ((c.lim.max_slen + 3) & ~3ull))))
             return rc;
-        h->in_fused = true;
-        rc          = lx_score_batch_dev(h, slot, d_q_res, d_s_res, d_ext, n, d_out_score, stream);
-        h->in_fused = false;
-        if (rc)
+        if ((rc = prepare_workspace(h, stream, score_ws_pairs(h, c.lim, n))) ||
+            (rc = score_dev_impl(h, slot, c.d_q, c.d_s, c.d_ext, n, c.d_out_score, stream, c.lim)))
             return rc;
     }
 
     // filter (:1251-1283) as an integer cut-off, compaction in input order, runs padded to whole wavefronts
-    uint32_t const run    = shared ? (uint32_t)h->opt_query_run : 1u;
+    uint32_t const run    = plan.shared ? (uint32_t)c.lim.query_run : 1u;
     // half a wavefront of the 8-lane geometry, a whole one of the 16-lane; the single sweep's backtrace needs no padding
     // (the adaptive step has few survivors, one or two to a query: its lists pad every query's to 2 slots -- four LDS profiles
     // per wavefront of the int32 forward kernel -- instead of 4: 2.6 x -> 1.9 x the survivors' cells at 2 % survivors)
-    uint32_t const pad_to = (shared && !sweep) ? (plan.adapted ? 2u : 4u) : 1u;
+    uint32_t const pad_to = (plan.shared && !plan.sweep) ? (plan.adapted ? 2u : 4u) : 1u;
     uint64_t const nruns  = (n + run - 1) / run;
-    uint64_t const cap    = (n + (shared ? nruns * 3 : 0) + 7) / 8 * 8;
+    uint64_t const cap    = (n + (plan.shared ? nruns * 3 : 0) + 7) / 8 * 8;
     if ((rc = ensure(h, h->d_sel_ext, cap * sizeof(lx_extension))) || (rc = ensure(h, h->d_sel_src, cap * sizeof(uint32_t))) ||
         (rc = ensure(h, h->d_sel_runs, (nruns + 2 * lx::select_blocks(pad_to <= 1 ? n : nruns) + 2) * sizeof(uint64_t))) || (rc = ensure(h, h->d_sel_score, cap * sizeof(int32_t))))
         return rc;
-    if (phases & 1)
-    {
     lx::SelectParams sp{};
-    sp.ext           = static_cast<lx::Extension const *>(d_ext);
-    sp.score         = static_cast<int32_t const *>(d_out_score);
-    sp.min_score     = static_cast<int32_t const *>(d_min_score);
-    sp.min_score_all = min_score_all;
+    sp.ext           = static_cast<lx::Extension const *>(c.d_ext);
+    sp.score         = static_cast<int32_t const *>(c.d_out_score);
+    sp.min_score     = static_cast<int32_t const *>(c.d_min_score);
+    sp.min_score_all = c.min_score_all;
     sp.n             = n;
     sp.run           = run;
     sp.pad_to        = pad_to;
@@ -941,57 +963,54 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
     sp.out_ext       = static_cast<lx::Extension *>(h->d_sel_ext.ptr);
     sp.out_src       = static_cast<uint32_t *>(h->d_sel_src.ptr);
     sp.out_score     = static_cast<int32_t *>(h->d_sel_score.ptr);
-    sp.out_count     = static_cast<uint64_t *>(d_out_count);
-    sp.out_hsp       = by_pos ? nullptr : static_cast<lx::Hsp *>(d_out_hsp); // rows of the filtered-out extensions
+    sp.out_count     = static_cast<uint64_t *>(c.d_out_count);
+    sp.out_hsp       = c.by_pos ? nullptr : static_cast<lx::Hsp *>(c.d_out_hsp); // rows of the filtered-out extensions
     PhaseTimer pts(h, stream, 1);
     LX_HIP(h, lx::launch_select(sp, stream));
     pts.close();
-    }
-    if (!(phases & 2))
-        return LX_OK;
 
-    if (sweep)
+    if (plan.sweep)
     {
         // backtrace of the survivors straight from the checkpoints of the sweep (slots and end cells by original index)
         lx::TraceParams p{};
-        p.q_res         = static_cast<uint8_t const *>(d_q_res);
-        p.s_res         = static_cast<uint8_t const *>(d_s_res);
+        p.q_res         = static_cast<uint8_t const *>(c.d_q);
+        p.s_res         = static_cast<uint8_t const *>(c.d_s);
         p.ext           = static_cast<lx::Extension const *>(h->d_sel_ext.ptr);
         p.n             = cap;
         p.sc            = h->sc_dev[slot];
         p.trace         = static_cast<uint32_t *>(h->d_trace.ptr);
-        p.slot_stride   = sweep_stride;
-        p.steps_cap     = sweep_steps;
-        p.panels_cap    = sweep_panels;
+        p.slot_stride   = plan.stride;
+        p.steps_cap     = plan.steps;
+        p.panels_cap    = plan.panels;
         p.ends          = static_cast<lx::EndCell *>(h->d_ends.ptr);
-        p.out_hsp       = static_cast<lx::Hsp *>(d_out_hsp);
-        p.out_ops       = static_cast<uint8_t *>(d_out_ops);
-        p.ops_off       = static_cast<uint64_t const *>(d_ops_off);
-        p.ops_stride    = fx ? fx->ops_stride : 0;
-        if (fx && fx->d_rle) // the backtrace writes run-length codes itself
+        p.out_hsp       = static_cast<lx::Hsp *>(c.d_out_hsp);
+        p.out_ops       = static_cast<uint8_t *>(c.d_out_ops);
+        p.ops_off       = static_cast<uint64_t const *>(c.d_ops_off);
+        p.ops_stride    = c.fx.ops_stride;
+        if (c.fx.d_rle) // the backtrace writes run-length codes itself
         {
-            p.rle     = fx->d_rle;
-            p.rle_top = fx->d_rle_top;
-            p.rle_cap = fx->rle_cap;
-            p.rle_len = fx->d_rle_len;
-            LX_HIP(h, hipMemsetAsync(fx->d_rle_top, 0, sizeof(unsigned long long), stream));
-            if (fx->d_rle_len) // (positions the backtrace never visits -- padding, score-less -- read 0)
-                LX_HIP(h, hipMemsetAsync(fx->d_rle_len, 0, cap * sizeof(uint32_t), stream));
+            p.rle     = c.fx.d_rle;
+            p.rle_top = c.fx.d_rle_top;
+            p.rle_cap = c.fx.rle_cap;
+            p.rle_len = c.fx.d_rle_len;
+            LX_HIP(h, hipMemsetAsync(c.fx.d_rle_top, 0, sizeof(unsigned long long), stream));
+            if (c.fx.d_rle_len) // (positions the backtrace never visits -- padding, score-less -- read 0)
+                LX_HIP(h, hipMemsetAsync(c.fx.d_rle_len, 0, cap * sizeof(uint32_t), stream));
         }
         p.src           = static_cast<uint32_t const *>(h->d_sel_src.ptr);
-        p.count_ptr     = static_cast<uint64_t const *>(d_out_count);
+        p.count_ptr     = static_cast<uint64_t const *>(c.d_out_count);
         p.chunk_start   = 0;
         p.err           = reinterpret_cast<int32_t *>(h->d_ws_top + 1);
-        p.nrows         = ((h->sc_host[slot].alphabet_size + 1 + 3) / 4) * 4;
-        p.bs_match_rule = (int32_t)h->opt_bs_rule;
+        p.nrows         = facts.nrows();
+        p.bs_match_rule = (int32_t)c.lim.bs_rule;
         p.work_counter  = h->d_ws_top + 5;
-        p.cfg           = sweep_cfg;
+        p.cfg           = plan.cfg;
         p.slot_by_src   = 1;
-        p.out_by_pos    = by_pos ? 1 : 0;
-        if (half_sweep)
+        p.out_by_pos    = c.by_pos ? 1 : 0;
+        if (plan.packed)
         {
             p.ovf        = p.trace + batch_dw; // int16-pair slots of what the packed kernel declined
-            p.ovf_stride = sweep_stride32;
+            p.ovf_stride = plan.stride32;
         }
         if (tab_on)
         {
@@ -1002,7 +1021,7 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
         PhaseTimer ptb(h, stream, 3);
         LX_HIP(h, lx::launch_ckpt_backtrace(p, stream));
         ptb.close();
-        if ((rc = fused_pack(h, fx, cap, d_out_hsp, d_out_ops, d_ops_off, d_out_count, stream, true)))
+        if ((rc = fused_pack(h, c, cap, stream, true)))
             return rc;
         LX_HIP(h, hipEventRecord(h->ev1, stream));
         h->timed = true;
@@ -1010,14 +1029,13 @@ int lxi::fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * 
     }
 
     // pass 2 on the survivors (:1293-1296); the grid covers the worst case, wavefronts beyond *d_out_count exit
-    rc = align_dev_impl(h, slot, d_q_res, d_s_res, static_cast<lx::Extension const *>(h->d_sel_ext.ptr), cap,
-                        static_cast<lx::Hsp *>(d_out_hsp), static_cast<uint8_t *>(d_out_ops),
-                        static_cast<uint64_t const *>(d_ops_off), stream, h->opt_max_qlen, h->opt_max_slen, shared ? (int)pad_to : 0,
-                        static_cast<uint32_t const *>(h->d_sel_src.ptr), static_cast<uint64_t const *>(d_out_count),
-                        static_cast<int32_t const *>(h->d_sel_score.ptr), by_pos, fx ? fx->ops_stride : 0);
+    rc = align_dev_impl(h, slot, c.d_q, c.d_s, static_cast<lx::Extension const *>(h->d_sel_ext.ptr), cap, static_cast<lx::Hsp *>(c.d_out_hsp),
+                        static_cast<uint8_t *>(c.d_out_ops), static_cast<uint64_t const *>(c.d_ops_off), stream, c.lim, plan.shared ? (int)pad_to : 0,
+                        static_cast<uint32_t const *>(h->d_sel_src.ptr), static_cast<uint64_t const *>(c.d_out_count),
+                        static_cast<int32_t const *>(h->d_sel_score.ptr), c.by_pos, c.fx.ops_stride);
     if (rc)
         return rc;
-    if ((rc = fused_pack(h, fx, cap, d_out_hsp, d_out_ops, d_ops_off, d_out_count, stream)))
+    if ((rc = fused_pack(h, c, cap, stream)))
         return rc;
     LX_HIP(h, hipEventRecord(h->ev1, stream));
     h->timed = true;
@@ -1229,7 +1247,6 @@ int lx_set_option(lx_handle * h, int option, uint64_t value)
         case LX_OPT_MQ_SWEEP:
             h->opt_mq       = value > 2 ? 1 : value;
             h->mq_decl_frac = 0.0; // (what the last chunks taught about compact codes against int16 pairs starts over)
-            h->mq_wide_call = false;
             return LX_OK;
         case LX_OPT_ADAPT_PERMILLE: h->opt_adapt = std::min<uint64_t>(value, 1000); h->surv_frac = -1.0; return LX_OK;
         case LX_OPT_ITERATE_RECORDS: h->opt_iterate_records = value ? 1 : 0; return LX_OK;
@@ -1303,8 +1320,7 @@ int lx_builtin_scoring(int scoring_method, int match, int mismatch, int gap_open
     return LX_OK;
 }
 
-// what lx_set_scoring derives from a scheme besides the tables: pass 2 applies (every matrix - gap_extend in [-31, 31]),
-// byte profiles apply (0 <= matrix - gap_open <= 255), the largest entry
+// what lx_set_scoring derives from a scheme besides the tables (lxi::SchemeFacts)
 static void scheme_facts(lx_scoring const * sc, lxi::SchemeFacts & f)
 {
     f.alph       = sc->alphabet_size;
@@ -1344,7 +1360,7 @@ int lx_plan_step(lx_scoring const * sc, uint64_t max_qlen, uint64_t max_slen, ui
     lxi::describe_plan(pl, out->name, sizeof(out->name));
     if (pl.family == lxi::kNoSweep)
         return LX_OK;
-    int const G = lx::trace_cfg_group(pl.cfg), C = lx::trace_cfg_panel(pl.cfg) / G, nrows = ((sc->alphabet_size + 1 + 3) / 4) * 4;
+    int const G = lx::trace_cfg_group(pl.cfg), C = lx::trace_cfg_panel(pl.cfg) / G, nrows = f.nrows();
     out->group_lanes           = G;
     out->strip_cols            = C;
     out->panels                = (int32_t)pl.panels;
@@ -1382,8 +1398,9 @@ int lx_set_scoring(lx_handle * h, int slot, lx_scoring const * sc)
         return fail(h, LX_EINVAL, "need gap_open <= gap_extend < 0 (got %d / %d)", sc->gap_open, sc->gap_extend);
     if (sc->gap_open < -120 || sc->gap_extend < -27)
         return fail(h, LX_EINVAL, "gap costs out of the supported range");
+    lxi::SchemeFacts f{};
+    scheme_facts(sc, f);
     lx::ScoringDev d{};
-    int            trace_ok = 1;
     d.alph = sc->alphabet_size;
     d.go   = sc->gap_open;
     d.ge   = sc->gap_extend;
@@ -1398,20 +1415,16 @@ int lx_set_scoring(lx_handle * h, int slot, lx_scoring const * sc)
             d.mat[a * lx::kAlph + b]     = (int8_t)v;
             d.mat_adj[a * lx::kAlph + b] = (int8_t)(pad ? lx::kNegPad : v - sc->gap_extend);
             int const adj                = v - sc->gap_extend;
-            if (!pad && (adj < -31 || adj > 31))
-                trace_ok = 0;
             d.mat_trace[a * lx::kAlph + b] = (int8_t)(pad || adj < -31 || adj > 31 ? -125 : 4 * adj + 3);
         }
-    d.trace_ok = trace_ok;
+    d.trace_ok = f.trace_ok ? 1 : 0;
     d.smax     = 0;
-    d.b8_ok    = 1;
+    d.b8_ok    = f.b8_ok ? 1 : 0;
     for (int a = 0; a < lx::kAlph; ++a)
         for (int b = 0; b < lx::kAlph; ++b)
         {
             bool const pad = a >= sc->alphabet_size || b >= sc->alphabet_size;
             int const  v   = pad ? 0 : sc->matrix[a * LX_ALPH + b] - sc->gap_open;
-            if (v < 0 || v > 255)
-                d.b8_ok = 0;
             d.mat_b8[a * lx::kAlph + b] = (uint8_t)std::min(std::max(v, 0), 255);
         }
     for (int a = 0; a < lx::kAlph; ++a)
@@ -1442,8 +1455,7 @@ int lx_set_scoring(lx_handle * h, int slot, lx_scoring const * sc)
     LX_HIP(h, hipMemcpy(h->sc_dev[slot], &d, sizeof(d), hipMemcpyHostToDevice));
     h->sc_host[slot] = *sc;
     h->have_sc[slot] = true;
-    h->trace_ok[slot] = trace_ok != 0;
-    h->b8_ok[slot]    = d.b8_ok != 0;
+    h->facts[slot]   = f;
     return LX_OK;
 }
 
@@ -1519,55 +1531,17 @@ int lx_score_batch_dev(lx_handle * h, int slot, void const * d_q_res, void const
     int rc = bind(h);
     if (rc)
         return rc;
-    hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : h->stream;
-    // geometry from the caller's hints; any geometry is correct for any query length (multi-panel path)
-    bool const want_shared = h->opt_query_run != 0 && h->opt_query_run % 8 == 0;
-    int const  cfg    = h->opt_max_qlen ? pick_cfg((uint32_t)std::min<uint64_t>(h->opt_max_qlen, 0xffffffffu), want_shared) : 0;
-    bool const multi  = h->opt_max_qlen == 0 || h->opt_max_qlen > (uint64_t)lx::score_cfg_panel(cfg);
-    // (the packed 16-bit kernel sweeps wide queries in (8,19) panels even where the int32 geometry is a single one)
-    bool const wide16 = h->opt_f16 && h->opt_query_run % 16 == 0 && h->opt_query_run != 0 && h->opt_max_qlen > (uint64_t)lx::trace_cfg_panel(2);
-    if ((rc = prepare_workspace(h, stream, (multi || wide16 || (h->opt_band && (h->opt_max_qlen == 0 || h->opt_max_qlen > 160))) ? n * ((h->opt_max_slen + 3) & ~3ull) : 0)))
+    hipStream_t const stream = stream_ ? static_cast<hipStream_t>(stream_) : h->stream;
+    ListLimits const  lim    = option_limits(h);
+    if ((rc = prepare_workspace(h, stream, score_ws_pairs(h, lim, n))))
         return rc;
-    bool const shared = h->opt_query_run != 0 && (h->opt_query_run % (uint64_t)lx::score_cfg_groups(cfg)) == 0;
-    if (!h->in_fused)
-    {
-        h->phase_ev.clear();
-        h->ev_pool_used = 0;
-        LX_HIP(h, hipEventRecord(h->ev0, stream));
-    }
-    // packed-half path: the extensions of a wavefront (or, where two LDS profiles fit, of each half of it) must
-    // share their query and the query must fit one panel
-    int pair_cfg = -1, pair_share = 0;
-    if (h->opt_f16 && shared && h->opt_max_qlen != 0)
-    {
-        int const pc = lx::score_pair_cfg_for((uint32_t)std::min<uint64_t>(h->opt_max_qlen, 0xffffffffu));
-        if (pc >= 0)
-        {
-            int const      groups   = 64 / lx::score_pair_cfg_group(pc);
-            uint64_t const per_wave = 2ull * groups;
-            int const      nrows    = ((h->sc_host[slot].alphabet_size + 1 + 3) / 4) * 4;
-            if (h->opt_query_run % per_wave == 0)
-                pair_cfg = pc;
-            else if (groups >= 2 && h->opt_query_run % (per_wave / 2) == 0 && 2 * lx::score_pair_profile_bytes(pc, nrows) <= pair_lds_limit())
-            {
-                pair_cfg   = pc;
-                pair_share = groups / 2;
-            }
-            else if (h->opt_query_run % 8 == 0) // two profiles do not fit: a 16-lane geometry holds 8 extensions per wavefront
-                pair_cfg = lx::score_pair_cfg_for_runs_of_8((uint32_t)std::min<uint64_t>(h->opt_max_qlen, 0xffffffffu));
-        }
-        else if (h->opt_query_run % 16 == 0 && h->opt_max_slen != 0) // wider than any packed-half geometry
-            pair_cfg = kPair16;
-    }
-    PhaseTimer pt(h, stream, 0);
-    if ((rc = launch_score_list(h, slot, d_q_res, d_s_res, d_ext, n, d_out_score, cfg, multi, shared, stream, pair_cfg, pair_share)))
+    h->phase_ev.clear();
+    h->ev_pool_used = 0;
+    LX_HIP(h, hipEventRecord(h->ev0, stream));
+    if ((rc = score_dev_impl(h, slot, d_q_res, d_s_res, d_ext, n, d_out_score, stream, lim)))
         return rc;
-    pt.close();
-    if (!h->in_fused)
-    {
-        LX_HIP(h, hipEventRecord(h->ev1, stream));
-        h->timed = true;
-    }
+    LX_HIP(h, hipEventRecord(h->ev1, stream));
+    h->timed = true;
     return LX_OK;
 }
 
@@ -1622,9 +1596,11 @@ int lx_align_batch_dev(lx_handle * h, int slot, void const * d_q_res, void const
     h->phase_ev.clear();
     h->ev_pool_used = 0;
     LX_HIP(h, hipEventRecord(h->ev0, stream));
-    rc = align_dev_impl(h, slot, d_q_res, d_s_res, static_cast<lx::Extension const *>(d_ext), n,
-                        static_cast<lx::Hsp *>(d_out_hsp), static_cast<uint8_t *>(d_out_ops),
-                        static_cast<uint64_t const *>(d_ops_off), stream, max_q, max_s, 0);
+    ListLimits lim = option_limits(h);
+    lim.max_qlen   = max_q;
+    lim.max_slen   = max_s;
+    rc = align_dev_impl(h, slot, d_q_res, d_s_res, static_cast<lx::Extension const *>(d_ext), n, static_cast<lx::Hsp *>(d_out_hsp),
+                        static_cast<uint8_t *>(d_out_ops), static_cast<uint64_t const *>(d_ops_off), stream, lim, 0);
     if (rc)
         return rc;
     LX_HIP(h, hipEventRecord(h->ev1, stream));
@@ -1636,18 +1612,24 @@ int lx_extend_batch_dev(lx_handle * h, int slot, void const * d_q_res, void cons
                         uint64_t n, void const * d_min_score, int32_t min_score_all, void * d_out_score,
                         void * d_out_hsp, void * d_out_ops, void const * d_ops_off, void * d_out_count, void * stream_)
 {
-    if (h && h->count_pending && hipEventQuery(h->ev_count) == hipSuccess)
+    if (!h)
+        return LX_EINVAL;
+    if (h->count_pending && hipEventQuery(h->ev_count) == hipSuccess)
     {
         // the previous call's survivor count has arrived: the adaptive choice of pass-2 mode (fused_impl) goes by it
         h->count_pending = false;
         if (h->count_n)
             h->surv_frac = (double)h->p_count[1] / (double)h->count_n;
     }
-    int const rc = fused_impl(h, slot, d_q_res, d_s_res, d_ext, n, d_min_score, min_score_all, d_out_score, d_out_hsp, d_out_ops, d_ops_off,
-                              d_out_count, stream_, 3, false);
+    StepCall c;
+    c.d_q = d_q_res, c.d_s = d_s_res, c.d_ext = d_ext, c.n = n, c.d_min_score = d_min_score, c.min_score_all = min_score_all;
+    c.d_out_score = d_out_score, c.d_out_hsp = d_out_hsp, c.d_out_ops = d_out_ops, c.d_ops_off = d_ops_off, c.d_out_count = d_out_count;
+    c.stream = stream_ ? static_cast<hipStream_t>(stream_) : h->stream;
+    c.lim    = option_limits(h);
+    int const rc = fused_impl(h, slot, c);
     if (rc == LX_OK && n != 0 && h->p_count && !h->count_pending)
     {
-        hipStream_t const stream = stream_ ? static_cast<hipStream_t>(stream_) : h->stream;
+        hipStream_t const stream = c.stream;
         if (hipMemcpyAsync(h->p_count, d_out_count, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
             hipEventRecord(h->ev_count, stream) == hipSuccess)
         {

@@ -102,7 +102,7 @@ public:
                    ResidentInput const * ri_, HostMarks & hm_)
         : h(h_), slot(slot_), ext(ext_), n(n_), min_score(min_score_), min_score_all(min_score_all_), out_score(out_score_), out_hsp(out_hsp_),
           out_ops_off(out_ops_off_), out_ops(out_ops_), out_ops_bytes(out_ops_bytes_), want_rle(mode >= 1), as_list(mode == 2), ri(ri_),
-          preplanned(ri_ && ri_->d_plan), p(h_->plan), hm(hm_), nthreads(host_threads(n_))
+          preplanned(ri_ && ri_->d_plan), p(h_->plan), hm(hm_), nthreads(host_threads(n_)), bs_rule(ri_ ? ri_->bs_rule : h_->opt_bs_rule)
     {
     }
 
@@ -182,6 +182,7 @@ private:
     HostPlan const &            p;
     HostMarks &                 hm;
     unsigned const              nthreads;
+    uint64_t const              bs_rule; // the backtrace's match rule
     void const *                d_q = nullptr, *d_s = nullptr; // query and subject residues on the device
     XbPrep                      prep[2];                       // the two lanes
     bool                        in_flight[2] = {false, false};
@@ -191,6 +192,7 @@ private:
     uint64_t chunk_target = 0, per_chunk = 0, ops_total = 0; // (ops_total: bytes handed out in h->ext_bytes so far)
     bool     dev_list = false, want_codes = true, by_range = false; // (set where the multi-query plan is known: ResidentInput::keep_on_device)
     bool     list_uploaded = false, rows_cleared = false, stream_planned = false, merge_pool = false;
+    bool     mq_wide = false; // the multi-query chunks' sweep writes int16-pair slots (decided chunk by chunk, with hysteresis: enqueue_mq)
     double   t_upload = 0, t_prep = 0, t_issue = 0, t_wait = 0, t_unpack = 0, t_u1 = 0, t_u2 = 0; // LX_HOST_TIMING: where the host's time goes
 
     bool     wide_ok() const { return p.mq_cfg == 1 && !lx::dev_aids().mq_no_wide; }
@@ -258,28 +260,29 @@ private:
         return LX_OK;
     }
 
-    // what fused_impl may assume of the chunk (the caller's values come back when the call ends: Guard in extend_pipeline)
-    void promise(uint64_t max_q, uint64_t max_s, uint64_t run)
-    {
-        h->opt_max_qlen  = max_q;
-        h->opt_max_slen  = max_s;
-        h->opt_query_run = run;
-    }
-
-    // the fused step over lane L's first `slots` slots, on the kernel stream
-    int run_fused(int L, uint64_t slots, uint64_t stride)
+    // the fused step over lane L's first `slots` slots, on the kernel stream: what it may assume of the chunk -- its widest query, its
+    // longest window, its query run (1: the solo packing, 2: the free packing) -- and, for multi-query chunks, its slots by wavefront
+    int run_fused(int L, uint64_t slots, uint64_t stride, uint64_t max_q, uint64_t max_s, uint64_t run, MqTab const & tab = MqTab{})
     {
         lx_handle::XbLane & ln    = h->xb[L];
         uint64_t * const    d_cnt = static_cast<uint64_t *>(ln.d_cnt.ptr);
-        FusedExtra          fx;
-        fx.ops_stride = stride; // one ops slot per position of the survivor list
-        fx.d_rle      = static_cast<uint8_t *>(ln.d_rle.ptr);
-        fx.d_rle_top  = reinterpret_cast<unsigned long long *>(d_cnt + 2);
-        fx.rle_cap    = prep[L].cap_sel * stride;
-        fx.d_src_out  = static_cast<uint32_t *>(ln.d_src.ptr);
-        fx.d_rle_len  = static_cast<uint32_t *>(ln.d_len.ptr);
-        return fused_impl(h, slot, d_q, d_s, ln.d_ext.ptr, slots, ln.d_min.ptr, 0, ln.d_score.ptr, ln.d_hsp.ptr, ln.d_ops.ptr, nullptr, d_cnt, h->stream, 3,
-                          true, &fx);
+        StepCall            c;
+        c.d_q = d_q, c.d_s = d_s, c.d_ext = ln.d_ext.ptr, c.n = slots, c.d_min_score = ln.d_min.ptr;
+        c.d_out_score = ln.d_score.ptr, c.d_out_hsp = ln.d_hsp.ptr, c.d_out_ops = ln.d_ops.ptr, c.d_out_count = d_cnt;
+        c.stream       = h->stream;
+        c.by_pos       = true;
+        c.fx.ops_stride = stride; // one ops slot per position of the survivor list
+        c.fx.d_rle      = static_cast<uint8_t *>(ln.d_rle.ptr);
+        c.fx.d_rle_top  = reinterpret_cast<unsigned long long *>(d_cnt + 2);
+        c.fx.rle_cap    = prep[L].cap_sel * stride;
+        c.fx.d_src_out  = static_cast<uint32_t *>(ln.d_src.ptr);
+        c.fx.d_rle_len  = static_cast<uint32_t *>(ln.d_len.ptr);
+        c.lim           = ListLimits{max_q, max_s, run, h->band_dev, bs_rule};
+        c.tab           = tab;
+        c.mq_cfg        = p.use_mq ? p.mq_cfg : 0;
+        c.mq_wide       = mq_wide;
+        c.keep_events   = true; // (the call's phase list holds every chunk's events)
+        return fused_impl(h, slot, c);
     }
 
     // ---- device side of a chunk whose padded slots stand in lane L's pinned staging: uploads and kernels queued
@@ -298,8 +301,7 @@ private:
         LX_HIP(h, hipEventRecord(ln.ev_up, h->stream3));
         hipStream_t const ks = h->stream; // (all chunks' kernels in one stream: side by side they were measured slower, see extend_pipeline)
         LX_HIP(h, hipStreamWaitEvent(ks, ln.ev_up, 0));
-        promise(max_q, max_s, kRun);
-        if ((rc2 = run_fused(L, slots, stride)))
+        if ((rc2 = run_fused(L, slots, stride, max_q, max_s, kRun)))
             return rc2;
         // the device's error word of THIS chunk, saved in stream order (the next chunk's prepare_workspace clears it): it comes
         // back with the counts and is checked in collect()
@@ -969,16 +971,14 @@ private:
             LX_HIP(h, hipStreamWaitEvent(h->stream, ln.ev_up, 0));
         }
         LX_HIP(h, gather(d_orig, slots, L, 0));
-        promise(max_q, max_s, p.use_solo ? 1 : 2); // (the solo packing: no run promise; the free packing: pairs of one query, at most four queries per wavefront)
         // Compact codes hold scores up to 2046; a window beyond them is redone by the int32 launch, one profile per pair, at a tenth
         // of the sweep's speed.  Where the last chunks had more than a few such windows (long queries with strong hits: a 600-residue
         // query against its homologue scores ~3 000) the sweep writes int16 pairs itself (lx_sweep_mq.hip: WIDE) -- twice the
         // checkpoint bytes, no second launch; it goes back to the codes when fewer than 1 % of a chunk's windows need more.
         // (force_wide: a chunk that runs again because its overflow area filled up -- said by the caller, not inferred from the fraction
         // the OTHER lane's collect may have overwritten meanwhile)
-        h->mq_wide_call = wide_ok() && (force_wide || (h->mq_wide_call ? h->mq_decl_frac > 0.01 : h->mq_decl_frac > 0.03));
-        pr.wide         = h->mq_wide_call;
-        h->mq_tab       = lx_handle::MqTab{};
+        mq_wide = wide_ok() && (force_wide || (mq_wide ? h->mq_decl_frac > 0.01 : h->mq_decl_frac > 0.03));
+        pr.wide = mq_wide;
         // the chunk's slots by wavefront (lx::WfSlots)
         uint64_t const nw = w1 - w0;
         if ((rc2 = ensure_pinned(h, ln.p_wft, nw * sizeof(lx::WfSlots))) || (rc2 = ensure(h, ln.d_wft, nw * sizeof(lx::WfSlots))))
@@ -989,9 +989,8 @@ private:
         LX_HIP(h, hipEventRecord(ln.ev_up, h->stream3));
         LX_HIP(h, hipStreamWaitEvent(h->stream, ln.ev_up, 0));
         // (ovf_cap: what the chunk's budget reserved, an eighth of its slots)
-        h->mq_tab = lx_handle::MqTab{ln.d_wft.ptr, slots, off, 0, std::min<uint64_t>(slots, slots / 8 + 64), 0, 0};
-        rc2               = run_fused(L, slots, stride);
-        h->mq_tab         = lx_handle::MqTab{};
+        // (the solo packing: no run promise; the free packing: pairs of one query, at most four queries per wavefront)
+        rc2 = run_fused(L, slots, stride, max_q, max_s, p.use_solo ? 1 : 2, MqTab{ln.d_wft.ptr, slots, off, 0, std::min<uint64_t>(slots, slots / 8 + 64), 0, 0});
         if (rc2 || (rc2 = finish_mq(L, d_orig, slots)))
             return rc2;
         t_issue += ms(t1, now());
@@ -1046,9 +1045,8 @@ private:
         auto const t1 = now();
         if ((rc2 = size_lane(L, cap_slots, two.stride, true, true)) || (rc2 = ensure(h, ln.d_wft, (cap_slots / kWave + 1) * sizeof(lx::WfSlots))))
             return rc2;
-        promise(two.max_q, two.max_s, 2);
-        h->mq_wide_call         = wide_ok() && (h->mq_wide_call ? h->mq_decl_frac > 0.01 : h->mq_decl_frac > 0.03);
-        pr.wide                 = h->mq_wide_call;
+        mq_wide                 = wide_ok() && (mq_wide ? h->mq_decl_frac > 0.01 : h->mq_decl_frac > 0.03);
+        pr.wide                 = mq_wide;
         lx::WfSlots * const tab = static_cast<lx::WfSlots *>(ln.p_wft.ptr);
         two.dw0                 = fill_table(tab, 0, w1, pr.wide);
         // (overflow slots have the size of the chunk's widest query and longest window: an eighth of the slots, within 16 GiB)
@@ -1062,9 +1060,7 @@ private:
         LX_HIP(h, hipEventRecord(ln.ev_up, h->stream3));
         LX_HIP(h, hipStreamWaitEvent(h->stream, ln.ev_up, 0));
         LX_HIP(h, gather(static_cast<uint32_t const *>(ln.d_orig.ptr), slots1, L, 0));
-        h->mq_tab          = lx_handle::MqTab{ln.d_wft.ptr, slots1, two.dw0, 0, two.ovf_cap, two.total_dw, 1};
-        rc2                = run_fused(L, cap_slots, two.stride);
-        h->mq_tab          = lx_handle::MqTab{};
+        rc2 = run_fused(L, cap_slots, two.stride, two.max_q, two.max_s, 2, MqTab{ln.d_wft.ptr, slots1, two.dw0, 0, two.ovf_cap, two.total_dw, 1});
         t_issue += ms(t1, now());
         return rc2;
     }
@@ -1095,11 +1091,8 @@ private:
             LX_HIP(h, hipStreamWaitEvent(h->stream, ln.ev_up, 0));
             LX_HIP(h, gather(static_cast<uint32_t const *>(ln.d_orig.ptr) + two.n1, slots2, L, two.n1));
         }
-        promise(two.max_q, two.max_s, 2);
-        h->mq_wide_call    = pr.wide;
-        h->mq_tab          = lx_handle::MqTab{ln.d_wft.ptr, two.n1, two.dw0, dw1, two.ovf_cap, two.total_dw, 2};
-        rc2                = run_fused(L, total, two.stride);
-        h->mq_tab          = lx_handle::MqTab{};
+        mq_wide = pr.wide;
+        rc2     = run_fused(L, total, two.stride, two.max_q, two.max_s, 2, MqTab{ln.d_wft.ptr, two.n1, two.dw0, dw1, two.ovf_cap, two.total_dw, 2});
         if (rc2 || (rc2 = finish_mq(L, static_cast<uint32_t const *>(ln.d_orig.ptr), total)))
             return rc2;
         t_issue += ms(t1, now());
@@ -1314,30 +1307,20 @@ static int extend_pipeline(lx_handle * h, int slot, uint8_t const * q_res, uint6
         return rc;
     plan.sort(hm);
     plan.plan_pool(ri, hm);
-    if (plan.use_mq)
-        h->mq_cfg_call = plan.mq_cfg;
 
-    // ---- the caller's option values come back on every exit; the streams are drained before anything is torn down
+    // ---- the phase list collects every chunk's events; the streams are drained on every exit, before anything is torn down
     h->phase_ev.clear();
-    h->ev_pool_used      = 0;
-    h->keep_phase_events = true;
+    h->ev_pool_used = 0;
     struct Guard
     {
         lx_handle * h;
-        uint64_t    qlen, slen, run;
         ~Guard()
         {
-            h->keep_phase_events = false;
             (void)hipStreamSynchronize(h->stream);
             (void)hipStreamSynchronize(h->stream2);
             (void)hipStreamSynchronize(h->stream3);
-            h->mq_cfg_call   = 0;
-            h->mq_wide_call  = false;
-            h->opt_max_qlen  = qlen;
-            h->opt_max_slen  = slen;
-            h->opt_query_run = run;
         }
-    } const guard{h, h->opt_max_qlen, h->opt_max_slen, h->opt_query_run};
+    } const guard{h};
 
     if (!ri)
     {

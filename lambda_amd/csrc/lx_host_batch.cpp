@@ -272,7 +272,7 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
         rc = launch_score_list(h, slot, h->d_q.ptr, sref.dev,
                                static_cast<lx_extension const *>(h->d_ext.ptr) + seg.first, seg.count,
                                static_cast<int32_t *>(h->d_out.ptr) + seg.first, seg.cfg, seg.multi, seg.shared,
-                               h->stream, seg.pair_cfg);
+                               h->stream, h->band_dev, seg.pair_cfg);
         if (rc)
             return rc;
     }
@@ -436,7 +436,7 @@ int lx_align_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
     LX_HIP(h, hipEventRecord(h->ev0, h->stream));
     rc = align_dev_impl(h, slot, h->d_q.ptr, sref.dev, static_cast<lx::Extension const *>(h->d_ext.ptr), slots,
                         static_cast<lx::Hsp *>(h->d_hsp.ptr), static_cast<uint8_t *>(h->d_ops.ptr),
-                        static_cast<uint64_t const *>(h->d_opsoff.ptr), h->stream, max_q, max_s, share ? 4 : 0,
+                        static_cast<uint64_t const *>(h->d_opsoff.ptr), h->stream, ListLimits{max_q, max_s, 0, h->band_dev, h->opt_bs_rule}, share ? 4 : 0,
                         share ? static_cast<uint32_t const *>(h->d_sel_src.ptr) : nullptr, nullptr,
                         known_score ? static_cast<int32_t const *>(h->d_sel_score.ptr) : nullptr);
     if (rc)
@@ -506,31 +506,30 @@ int lxi::host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, u
     LX_HIP(h, hipMemcpyAsync(h->d_ext.ptr, ext, n * sizeof(lx_extension), hipMemcpyHostToDevice, h->stream));
     if (!h->band_host.empty())
         LX_HIP(h, hipMemcpyAsync(h->d_band.ptr, h->band_host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    struct Restore
+    struct Consume
     {
-        lx_handle *     h;
-        uint64_t        qlen, slen, run;
-        int32_t const * band_dev;
-        ~Restore()
+        lx_handle * h;
+        ~Consume()
         {
-            h->opt_max_qlen  = qlen;
-            h->opt_max_slen  = slen;
-            h->opt_query_run = run;
-            h->band_dev      = band_dev;
             // lx_set_band_centres applies to ONE host-buffer call (include/lambda_ext.h): consumed here, whatever the outcome --
             // a later call of another size must not fail on them, one of the same size must not reuse them silently
             (void)hipStreamSynchronize(h->stream);
             h->band_host.clear();
         }
-    } const restore{h, h->opt_max_qlen, h->opt_max_slen, h->opt_query_run, h->band_dev};
-    h->opt_max_qlen  = max_q;
-    h->opt_max_slen  = max_s;
-    h->opt_query_run = 0;
-    h->band_dev      = h->band_host.empty() ? nullptr : static_cast<int32_t const *>(h->d_band.ptr);
+    } const consume{h};
+    // the list as it is (no query runs), the centres of this call
+    ListLimits const lim{max_q, max_s, 0, h->band_host.empty() ? nullptr : static_cast<int32_t const *>(h->d_band.ptr), h->opt_bs_rule};
     if (what == 0)
     {
-        if ((rc = lx_score_batch_dev(h, slot, h->d_q.ptr, sref.dev, h->d_ext.ptr, n, h->d_out.ptr, h->stream)))
+        if ((rc = prepare_workspace(h, h->stream, score_ws_pairs(h, lim, n))))
             return rc;
+        h->phase_ev.clear();
+        h->ev_pool_used = 0;
+        LX_HIP(h, hipEventRecord(h->ev0, h->stream));
+        if ((rc = score_dev_impl(h, slot, h->d_q.ptr, sref.dev, h->d_ext.ptr, n, h->d_out.ptr, h->stream, lim)))
+            return rc;
+        LX_HIP(h, hipEventRecord(h->ev1, h->stream));
+        h->timed = true;
         LX_HIP(h, hipMemcpyAsync(out_score, h->d_out.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         return check_async_error(h);
     }
@@ -553,13 +552,12 @@ int lxi::host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, u
         h->ev_pool_used = 0;
         if ((rc = align_dev_impl(h, slot, h->d_q.ptr, sref.dev, static_cast<lx::Extension const *>(h->d_ext.ptr), n,
                                  static_cast<lx::Hsp *>(h->d_hsp.ptr), static_cast<uint8_t *>(h->d_ops.ptr),
-                                 static_cast<uint64_t const *>(h->d_opsoff.ptr), h->stream, max_q, max_s, 0, nullptr, nullptr, d_known)))
+                                 static_cast<uint64_t const *>(h->d_opsoff.ptr), h->stream, lim, 0, nullptr, nullptr, d_known)))
             return rc;
     }
     else
     {
-        uint64_t * const d_count = static_cast<uint64_t *>(h->d_keep.ptr);
-        int32_t *        d_min   = nullptr;
+        int32_t * d_min = nullptr;
         if (min_score)
         {
             if ((rc = ensure(h, h->d_keep, 16 + n * sizeof(int32_t))))
@@ -567,10 +565,13 @@ int lxi::host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, u
             d_min = reinterpret_cast<int32_t *>(static_cast<uint64_t *>(h->d_keep.ptr) + 2);
             LX_HIP(h, hipMemcpyAsync(d_min, min_score, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         }
-        if ((rc = fused_impl(h, slot, h->d_q.ptr, sref.dev, h->d_ext.ptr, n, d_min, min_score_all, h->d_out.ptr, h->d_hsp.ptr, h->d_ops.ptr,
-                             h->d_opsoff.ptr, static_cast<uint64_t *>(h->d_keep.ptr), h->stream, 3, false)))
+        StepCall c;
+        c.d_q = h->d_q.ptr, c.d_s = sref.dev, c.d_ext = h->d_ext.ptr, c.n = n, c.d_min_score = d_min, c.min_score_all = min_score_all;
+        c.d_out_score = h->d_out.ptr, c.d_out_hsp = h->d_hsp.ptr, c.d_out_ops = h->d_ops.ptr, c.d_ops_off = h->d_opsoff.ptr, c.d_out_count = h->d_keep.ptr;
+        c.stream = h->stream;
+        c.lim    = lim;
+        if ((rc = fused_impl(h, slot, c)))
             return rc;
-        (void)d_count;
         LX_HIP(h, hipMemcpyAsync(out_score, h->d_out.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     }
     LX_HIP(h, hipMemcpyAsync(out_hsp, h->d_hsp.ptr, n * sizeof(lx_hsp), hipMemcpyDeviceToHost, h->stream));

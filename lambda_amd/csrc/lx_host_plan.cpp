@@ -44,9 +44,9 @@ uint64_t lxi::slot_dwords(int cfg, uint64_t pan, uint64_t maxs, bool wide, bool 
 
 bool lxi::mq_sweep_applies(lx_handle const * h, int slot)
 {
-    lx_scoring const & sh = h->sc_host[slot];
-    return h->opt_mq >= 1 && h->opt_pass2 == 2 && h->opt_f16 && h->trace_ok[slot] && h->b8_ok[slot] && -sh.gap_open <= lx::kC16MaxGap &&
-           sh.gap_open <= sh.gap_extend;
+    SchemeFacts const & f = h->facts[slot];
+    return h->opt_mq >= 1 && h->opt_pass2 == 2 && h->opt_f16 && f.trace_ok && f.b8_ok && -f.gap_open <= lx::kC16MaxGap &&
+           f.gap_open <= f.gap_extend;
 }
 
 // the solo packing needs 16 byte profiles in a wavefront's share of the LDS: the alphabets of at most six rows

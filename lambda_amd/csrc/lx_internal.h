@@ -76,6 +76,15 @@ struct DevBuf
     size_t cap = 0;
 };
 
+// what lx_set_scoring derives from a scheme besides the tables (one per scoring slot; plan_step decides by them): pass 2 applies
+// (every matrix - gap_extend in [-31, 31]), byte profiles apply (0 <= matrix - gap_open <= 255), the largest entry
+struct SchemeFacts
+{
+    int  alph = 0, gap_open = 0, gap_extend = 0, smax_entry = 0;
+    bool trace_ok = false, b8_ok = false;
+    int  nrows() const { return (alph + 1 + 3) / 4 * 4; } // rows of a query profile: the letters and the pad letter, in whole groups of 4
+};
+
 } // namespace lxi
 using lxi::DevBuf;
 
@@ -149,8 +158,7 @@ struct lx_handle
     size_t                  ev_pool_used = 0;
 
     bool             have_sc[2] = {false, false};
-    bool             trace_ok[2] = {false, false};
-    bool             b8_ok[2]    = {false, false}; // byte profiles of lx_sweep_mq.hip apply (no substitution dearer than a gap's first character)
+    lxi::SchemeFacts facts[2];
     lx_scoring       sc_host[2];
     lx::ScoringDev * sc_dev[2] = {nullptr, nullptr};
 
@@ -179,22 +187,8 @@ struct lx_handle
     hipEvent_t  ev_count         = nullptr;
     uint64_t    count_n          = 0;
     bool        count_pending    = false;
-    double      plan_surv_frac   = -1.0;   // the share phase 1 of the current step planned with (phase 2 follows it)
     uint64_t    opt_adapt        = 30;     // LX_OPT_ADAPT_PERMILLE
-    // lx_extend_batch: the chunk's slots BY WAVEFRONT (lx::WfSlots, lx_device.h) instead of by region: `dev` = the table of the chunk's
-    // wavefronts on the device; the slots of the wavefronts before slot n0 take dw0 uint32 at the trace buffer's start, room for ovf_cap
-    // int16-pair overflow slots follows, then the dw1 uint32 of the wavefronts from n0 on.  part: 0 = the chunk in one call, 1 = the
-    // first of two calls (sweep of the slots before n0, nothing else), 2 = the second (sweep of the rest, then what follows a sweep,
-    // over all slots).  total_dw: what the trace buffer must hold (fixed by the first call).
-    struct MqTab
-    {
-        void const * dev = nullptr;
-        uint64_t     n0 = 0, dw0 = 0, dw1 = 0, ovf_cap = 0, total_dw = 0;
-        int          part = 0;
-    } mq_tab;
-    bool     mq_wide_call  = false; // lx_extend_batch: this chunk's sweep writes int16-pair slots (many windows of the last chunks scored beyond the compact codes)
-    double   mq_decl_frac  = 0.0;   // ... the share of the last multi-panel chunk's windows that the compact sweep declined
-    int      mq_cfg_call   = 0; // lx_extend_batch: the strip geometry (trace cfg) it chose for this call's chunks (0 = fused_impl picks per chunk)
+    double   mq_decl_frac  = 0.0;   // lx_extend_batch: the share of the last multi-panel chunk's windows that the compact sweep declined
     uint64_t opt_extend_chunk = 0; // LX_OPT_EXTEND_CHUNK: extensions per chunk of lx_extend_batch's pipeline (0 = default)
     uint64_t opt_band      = 0; // LX_OPT_BAND: half width in diagonals, 0 = full rectangle (the reference's BandOff)
     int32_t const * band_dev = nullptr;  // lx_set_band_centres_dev: the caller's device array for the *_dev calls
@@ -247,8 +241,6 @@ struct lx_handle
         DevBuf d_in, d_mem, d_status, d_out;
         Pinned p_in[2], p_mem[2], p_status[2];
     } gunzip;
-    bool     keep_phase_events = false; // lx_extend_batch: the phase events of every chunk of the call stay (lx_last_phase_ms sums them)
-    bool     in_fused      = false; // lx_extend_batch_dev is driving the sub-steps (it owns ev0/ev1 and the phase list)
 };
 
 namespace lxi
@@ -334,15 +326,10 @@ int    check_async_error(lx_handle * h);
 int    error_for_flag(lx_handle * h, uint32_t flag);
 
 // ---- the plan of a fused step (plan_step in lx_api.cpp is the one place that makes it)
-struct SchemeFacts
-{
-    int  alph = 0, gap_open = 0, gap_extend = 0, smax_entry = 0;
-    bool trace_ok = false, b8_ok = false;
-};
 struct StepOptions
 {
     uint64_t max_qlen = 0, max_slen = 0, query_run = 0, pass2 = 2, mq = 1, f16 = 1, band = 0, trace_bytes = 0, n = 0, adapt = 0;
-    int      mq_cfg_call = 0;
+    int      mq_cfg = 0;
     bool     mq_wide     = false; // the multi-query sweep writes int16-pair slots (lx_sweep_mq.hip: WIDE)
     double   surv_frac   = -1.0;
 };
@@ -368,9 +355,25 @@ struct StepPlan
 StepPlan plan_step(SchemeFacts const & sc, StepOptions const & o);
 void     describe_plan(StepPlan const & pl, char * buf, size_t len);
 int    mq_cfg_for(uint64_t max_q);
+// band_diag: band mode's centres, indexed like the list (NULL: the default diagonal)
 int    launch_score_list(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out, int cfg,
-                         bool multi, bool shared, hipStream_t stream, int pair_cfg = -1, int pair_share = 0);
+                         bool multi, bool shared, hipStream_t stream, int32_t const * band_diag, int pair_cfg = -1, int pair_share = 0);
 int    prepare_workspace(lx_handle * h, hipStream_t stream, uint64_t pairs_hint = 0);
+
+// What the caller of a device-list step states about the list: its widest query and longest window (0: unknown), the run of
+// consecutive extensions that share a query (LX_OPT_QUERY_RUN), band mode's centres indexed like the list, the match rule of the
+// backtrace (LX_OPT_BS_MATCH_RULE).  The device entry points take them from the handle's options; the pipelines from their chunks.
+struct ListLimits
+{
+    uint64_t        max_qlen = 0, max_slen = 0, query_run = 0;
+    int32_t const * band_diag = nullptr;
+    uint64_t        bs_rule   = 0;
+};
+// pass 1 over a device list: the carry pairs its launch may need (prepare_workspace's hint), then the launch itself (phase 0 of
+// the phase list; ev0 / ev1 are the caller's)
+uint64_t score_ws_pairs(lx_handle const * h, ListLimits const & lim, uint64_t n);
+int      score_dev_impl(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out,
+                        hipStream_t stream, ListLimits const & lim);
 
 // padding of q/s staging buffers so that clamped / prefetching loads never leave the allocation
 constexpr size_t kSlack = 256;
@@ -402,12 +405,44 @@ struct FusedExtra
 };
 
 int align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * d_s, lx::Extension const * d_ext, uint64_t n, lx::Hsp * d_hsp,
-                   uint8_t * d_ops, uint64_t const * d_ops_off, hipStream_t stream, uint64_t max_q, uint64_t max_s, int share_slots,
+                   uint8_t * d_ops, uint64_t const * d_ops_off, hipStream_t stream, ListLimits const & lim, int share_slots,
                    uint32_t const * d_src = nullptr, uint64_t const * d_count = nullptr, int32_t const * d_score_in = nullptr,
                    bool by_pos = false, uint64_t ops_stride = 0);
-int fused_impl(lx_handle * h, int slot, void const * d_q_res, void const * d_s_res, void const * d_ext, uint64_t n, void const * d_min_score,
-               int32_t min_score_all, void * d_out_score, void * d_out_hsp, void * d_out_ops, void const * d_ops_off, void * d_out_count,
-               void * stream_, int phases, bool by_pos, FusedExtra const * fx = nullptr);
+
+// lx_extend_batch's multi-query chunks: the chunk's slots BY WAVEFRONT (lx::WfSlots, lx_device.h) instead of by region: `dev` = the
+// table of the chunk's wavefronts on the device; the slots of the wavefronts before slot n0 take dw0 uint32 at the trace buffer's start,
+// room for ovf_cap int16-pair overflow slots follows, then the dw1 uint32 of the wavefronts from n0 on.  part: 0 = the chunk in one
+// call, 1 = the first of two calls (sweep of the slots before n0, nothing else), 2 = the second (sweep of the rest, then what follows
+// a sweep, over all slots).  total_dw: what the trace buffer must hold (fixed by the first call).
+struct MqTab
+{
+    void const * dev = nullptr;
+    uint64_t     n0 = 0, dw0 = 0, dw1 = 0, ovf_cap = 0, total_dw = 0;
+    int          part = 0;
+};
+
+// One call of the fused step (fused_impl): the list and its outputs, what the caller states about the list, and what the chunk
+// pipeline of lx_extend_batch adds.  by_pos: records and ops offsets are indexed by the position in the survivor list instead of by
+// extension.
+struct StepCall
+{
+    void const * d_q = nullptr, *d_s = nullptr, *d_ext = nullptr;
+    uint64_t     n = 0;
+    void const * d_min_score   = nullptr;
+    int32_t      min_score_all = 0;
+    void *       d_out_score = nullptr, *d_out_hsp = nullptr, *d_out_ops = nullptr;
+    void const * d_ops_off   = nullptr;
+    void *       d_out_count = nullptr;
+    hipStream_t  stream      = nullptr;
+    bool         by_pos      = false;
+    FusedExtra   fx;
+    ListLimits   lim;
+    MqTab        tab;                 // (dev == NULL: slots by region)
+    int          mq_cfg      = 0;     // the strip geometry (trace cfg) the call chose for its chunks (0 = plan_step picks per chunk)
+    bool         mq_wide     = false; // the multi-query sweep writes int16-pair slots (many windows of the last chunks scored beyond the compact codes)
+    bool         keep_events = false; // the phase events of earlier steps stay (lx_extend_batch: lx_last_phase_ms sums its chunks')
+};
+int fused_impl(lx_handle * h, int slot, StepCall const & c);
 
 // what stands on the device already when the Level-2 driver (lx_level2_host.cpp) calls the extension pipeline
 struct ResidentInput
@@ -441,6 +476,7 @@ struct ResidentInput
         std::function<int(uint64_t range, uint64_t code_base, bool gpu_busy)>                                         collect; // gpu_busy: another chunk computes meanwhile
     };
     ChunkRecords const * chunk_records = nullptr;
+    uint64_t             bs_rule       = 0; // the backtrace's match rule (bisulfite lists: 1, whatever the handle's LX_OPT_BS_MATCH_RULE says)
 };
 // band mode's plain path of the host-buffer entry points (lx_host_batch.cpp; what: 0 = scores, 1 = alignments of known scores, 2 = both)
 int  host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, uint64_t q_bytes, uint8_t const * s_res, uint64_t s_bytes,

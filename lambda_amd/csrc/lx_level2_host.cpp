@@ -603,6 +603,8 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
         ri.q_bytes   = l2.q_bytes;
         ri.d_ext_all = static_cast<lx_extension const *>(h->d_ext_all.ptr) + pt.lo;
         ri.d_min_all = static_cast<int32_t const *>(h->d_min_all.ptr) + pt.lo;
+        // the bisulfite overload of computeAlignmentStats (src/evaluate_bisulfite_alignment.hpp:97) for bisulfite lists
+        ri.bs_rule   = params->bisulfite ? 1 : h->opt_bs_rule;
         lx_survivor_list list{};
         // The plan of the sweep on the device: the solo packing where 16 profiles fit a wavefront's share of the LDS (nucleotides,
         // bisulfite), else the free packing (protein lists: four queries per wavefront) -- nothing of size n comes to the host either way
@@ -1023,12 +1025,7 @@ int lxi::iterate_host_list_on_device(lx_handle * h, int slot, uint8_t const * q_
     LX_HIP(h, hipMemcpyAsync(l2.d_pair[0].ptr, pair, n_matches * 8, hipMemcpyHostToDevice, h->stream));
     LX_HIP(h, hipMemcpyAsync(l2.d_s0[0].ptr, s0, n_matches * 8, hipMemcpyHostToDevice, h->stream));
     hm.mark("sort words");
-    uint64_t const ruleBefore = h->opt_bs_rule;
-    if (bs)
-        h->opt_bs_rule = 1; // the bisulfite overload of computeAlignmentStats for the duration of the call
-    rc             = level2_sorted_tail(h, slot, n_matches, params, res, true);
-    h->opt_bs_rule = ruleBefore;
-    if (rc)
+    if ((rc = level2_sorted_tail(h, slot, n_matches, params, res, true)))
         return rc;
     // ---- the reference's span now holds the windows (:1173-1174 shrinks it): the first n_windows records of `matches`
     uint64_t const             nw  = n_matches - (res->stats.hits_duplicate - l2.dup_before);
@@ -1078,13 +1075,8 @@ int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint
         *out = res;
         return LX_OK;
     }
-    // the bisulfite overload of computeAlignmentStats for the duration of the call (src/evaluate_bisulfite_alignment.hpp:97)
-    uint64_t const ruleBefore = h->opt_bs_rule;
-    if (params->bisulfite)
-        h->opt_bs_rule = 1;
     if ((rc = level2_keys(h, d_matches, n_matches, params->bisulfite != 0)) == LX_OK)
         rc = level2_sorted_tail(h, slot, n_matches, params, res, false);
-    h->opt_bs_rule = ruleBefore;
     if (rc != LX_OK)
     {
         delete res;
@@ -1210,16 +1202,14 @@ int lx_reserve(lx_handle * h, uint64_t n_matches, uint64_t n_windows, uint64_t n
         sp.flags           = n_columns ? 0 : LX_ITERATE_NO_OPS;
         lx_iterate_result * r = nullptr;
         // (the dummy call must not teach the handle anything: what the adaptive pass 2 and the wide sweep learnt from real lists stays)
-        double const   surv_before = h->surv_frac, plan_before = h->plan_surv_frac, decl_before = h->mq_decl_frac;
-        bool const     wide_before = h->mq_wide_call, pending_before = h->count_pending;
-        uint64_t const res_before  = h->res_count;
+        double const   surv_before = h->surv_frac, decl_before = h->mq_decl_frac;
+        bool const     pending_before = h->count_pending;
+        uint64_t const res_before     = h->res_count;
         rc = lx_iterate_matches_dev(h, h->have_sc[0] ? 0 : 1, l2.d_up.ptr, 1, &sp, &r);
-        h->surv_frac      = surv_before;
-        h->plan_surv_frac = plan_before;
-        h->mq_decl_frac   = decl_before;
-        h->mq_wide_call   = wide_before;
-        h->count_pending  = pending_before;
-        h->res_count      = res_before;
+        h->surv_frac     = surv_before;
+        h->mq_decl_frac  = decl_before;
+        h->count_pending = pending_before;
+        h->res_count     = res_before;
         h->phase_ev.clear();
         h->ev_pool_used   = 0;
         if (r)

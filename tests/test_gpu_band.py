@@ -171,9 +171,12 @@ def test_band_centres_apply_to_one_call_only(banded, oracle):
     q, s, ext = synth.make_batch_np(6, 120, 4, seed=8)
     centres = np.full(len(ext), 30, dtype=np.int32)
     h.set_band(5, centres)
+    limits = (capi.LX_OPT_MAX_QLEN, capi.LX_OPT_MAX_SLEN, capi.LX_OPT_QUERY_RUN)
+    before = [h.get_option(o) for o in limits]
     with_centres = h.score_batch(q, s, ext)
     again = h.score_batch(q, s, ext)            # same size: default centres now
     shorter = h.score_batch(q, s, ext[:10])     # another size: no LX_EINVAL
+    assert [h.get_option(o) for o in limits] == before  # the calls' limits are their own: the caller's options stay as they were
     for i, x in enumerate(ext):
         qq, ss = _slices(q, s, x)
         d0 = min(int(np.sqrt(x["q_len"])) + 1, int(x["s_len"]) - int(x["q_len"]))

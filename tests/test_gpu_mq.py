@@ -195,11 +195,15 @@ def test_host_plan_on_ragged_lists(handle, oracle, seed, lq_range, merged, nq, c
     mins = np.where(np.arange(len(ext)) % 5 == 0, cutoff + 40, cutoff).astype(np.int32)  # per-extension cut-offs
     handle.set_option(capi.LX_OPT_PASS2_MODE, 2)  # (the session's handle: other tests leave mode 1 behind)
     handle.set_option(capi.LX_OPT_EXTEND_CHUNK, chunk)  # small chunks: the pipeline's two lanes, several chunks per panel count
+    limits = (capi.LX_OPT_MAX_QLEN, capi.LX_OPT_MAX_SLEN, capi.LX_OPT_QUERY_RUN)
+    before = [handle.get_option(o) for o in limits]
     try:
         score, hsp, off, ops = handle.extend_batch(q, s, ext, mins)
+        after = [handle.get_option(o) for o in limits]
     finally:
         handle.set_option(capi.LX_OPT_PASS2_MODE, 1)
         handle.set_option(capi.LX_OPT_EXTEND_CHUNK, 0)
+    assert after == before  # the chunks' limits are the pipeline's own: the caller's options stay as they were
     assert "sweep_mq_kernel" in handle.last_trace_kernel_name()
     assert (score == want).all()
     surv = np.nonzero((want >= mins) & (ext["s_len"] > 0))[0]
