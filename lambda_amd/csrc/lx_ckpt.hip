@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "lx_aids.h"
@@ -43,7 +44,7 @@ constexpr int kCkptEvery = LX_CKPT_EVERY;
 #define LX_CKPT_UNROLL_N(n) LX_CKPT_PRAGMA(unroll n)
 #define LX_CKPT_UNROLL_PRAGMA LX_CKPT_UNROLL_N(LX_CKPT_UNROLL)
 #ifndef LX_BT_TILE_AT
-#define LX_BT_TILE_AT 40   // backtrace: lanes waiting for a tile that trigger a tile phase
+#define LX_BT_TILE_AT 40   // backtrace: live + parked extensions waiting for a tile that trigger a tile phase
 #endif
 #ifndef LX_BT_WAVES
 #define LX_BT_WAVES 2      // backtrace: wavefronts per SIMD the register budget is set for (2: 256 VGPRs, no spills)
@@ -52,10 +53,20 @@ constexpr int kCkptEvery = LX_CKPT_EVERY;
 #define LX_BT_HOPS 2       // backtrace: tile borders a diagonal shortcut pass may cross
 #endif
 #ifndef LX_BT_REFILL_AT
-#define LX_BT_REFILL_AT 12 // backtrace: finished / empty lanes that trigger a refill outside a tile phase
+#define LX_BT_REFILL_AT 24 // backtrace: finished / empty lanes that trigger a refill outside a tile phase (with the pool:
+                           // 40/24 3.41 ms, 40/12 3.47, 48/16 3.41, 32/16 3.57, 64/12 3.58 on the headline; 40/12 without it 3.71)
+#endif
+#ifndef LX_BT_POOL
+#define LX_BT_POOL 32      // backtrace: extensions a wavefront may park in LDS beside its 64 live ones (0 = no pool)
 #endif
 #ifndef LX_CKPT_FWD_WAVES
 #define LX_CKPT_FWD_WAVES 4
+#endif
+// LX_BT_COUNT (measurement only, off by default): the backtrace counts its shortcut passes and tile phases and the lanes
+// that take part in them; the launcher waits for the kernel and prints the sums of the call to stderr.
+#ifdef LX_BT_COUNT
+// [0] shortcut passes, [1] lanes in them, [2] tile phases, [3] lanes in them, [4] wavefronts
+__device__ unsigned long long lx_bt_counts[5];
 #endif
 
 // slot layout in uint32 units: boundary quads (4 steps = 4 dwords each) [step / 4][lane] -- lane-minor: the G lanes of a
@@ -573,6 +584,13 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     __shared__ int8_t   smat4[kAlph * kAlph]; // 4 s + 3: diagonal step of the tile DP with its tag (the walk divides it back)
     __shared__ int8_t   smat1n[kAlph * kAlph]; // -s for the diagonal runs; the pair (31, 31) -- rank 31 is the reserved pad rank -- scores 0 there
     __shared__ uint32_t tiles[kCkptEvery * kNibDw * 64]; // [tile row][word][lane]: lane-minor, conflict-free
+    // Parked extensions: kRecQ uint4 per context, [quad][entry].  The pool takes what the LDS leaves at 8 wavefronts per CU
+    // (20 KiB per workgroup): 32 contexts beside the (8,19) tiles, 12 beside the (8,25) ones.
+    constexpr int kRecQ  = 10;
+    constexpr int kLdsWg = 20 * 1024 - (int)sizeof(uint32_t) * kCkptEvery * kNibDw * 64 - 2 * kAlph * kAlph;
+    constexpr int kPool  = LX_BT_POOL < kLdsWg / (16 * kRecQ) ? LX_BT_POOL : kLdsWg / (16 * kRecQ);
+    static_assert(kPool >= 0 && kPool <= 64, "pool masks are 64 bits wide");
+    __shared__ uint4 pool[kRecQ][kPool > 0 ? kPool : 1];
     for (int x = threadIdx.x; x < kAlph * kAlph; x += blockDim.x)
     {
         int const v = p.sc->mat[x];
@@ -869,6 +887,97 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         have          = false;
     };
 
+    // ---- the state of a live extension as a parked record (pool entry e) and back: every field above that outlives
+    // begin_extension.  The small ones share one flag word; pointers and 64-bit offsets keep their value.
+    auto park = [&](uint32_t e)
+    {
+        uint32_t const flags = (blocked ? 1u : 0u) | (done ? 2u : 0u) | (need_col ? 4u : 0u) | (scan ? 8u : 0u) | (c16 ? 16u : 0u) |
+                               ((uint32_t)mode << 5) | (run_op << 7) | (run_len << 9) | (a0 << 16) | ((uint32_t)nar_cw << 18) |
+                               ((uint32_t)res_col << 24);
+        uint64_t const sp = reinterpret_cast<uintptr_t>(slot), qp = reinterpret_cast<uintptr_t>(q), spp = reinterpret_cast<uintptr_t>(s),
+                       op = reinterpret_cast<uintptr_t>(ops_al);
+        pool[0][e] = make_uint4(flags, (uint32_t)pos, (uint32_t)po, (uint32_t)ec.score);
+        pool[1][e] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), oct_mul, ck_mul);
+        pool[2][e] = make_uint4((uint32_t)ck16_off, (uint32_t)panel_dw, (uint32_t)panel16_dw, (uint32_t)bnd_dw);
+        pool[3][e] = make_uint4((uint32_t)qp, (uint32_t)(qp >> 32), (uint32_t)spp, (uint32_t)(spp >> 32));
+        pool[4][e] = make_uint4((uint32_t)op, (uint32_t)(op >> 32), cap, apos);
+        pool[5][e] = make_uint4(acc, n, (uint32_t)lq, (uint32_t)ls);
+        pool[6][e] = make_uint4((uint32_t)i, (uint32_t)j, (uint32_t)end_i, (uint32_t)end_j);
+        pool[7][e] = make_uint4((uint32_t)res_row, (uint32_t)nar_j0, (uint32_t)nar_st0, (uint32_t)left);
+        pool[8][e] = make_uint4((uint32_t)nm, (uint32_t)nx, (uint32_t)np, (uint32_t)go);
+        pool[9][e] = make_uint4((uint32_t)gx, ncodes, 0u, 0u);
+    };
+    auto unpark = [&](uint4 const (&r)[kRecQ])
+    {
+        uint32_t const flags = r[0].x;
+        blocked  = (flags & 1u) != 0;
+        done     = (flags & 2u) != 0;
+        need_col = (flags & 4u) != 0;
+        scan     = (flags & 8u) != 0;
+        c16      = (flags & 16u) != 0;
+        mode     = (int)((flags >> 5) & 3u);
+        run_op   = (flags >> 7) & 3u;
+        run_len  = (flags >> 9) & 127u;
+        a0       = (flags >> 16) & 3u;
+        nar_cw   = (int)((flags >> 18) & 63u);
+        res_col  = (int)((flags >> 24) & 63u);
+        pos      = r[0].y;
+        po       = r[0].z;
+        ec.score = (int32_t)r[0].w;
+        slot     = reinterpret_cast<uint32_t const *>(((uint64_t)r[1].y << 32) | r[1].x);
+        oct_mul  = r[1].z;
+        ck_mul   = r[1].w;
+        ck16_off   = r[2].x;
+        panel_dw   = r[2].y;
+        panel16_dw = r[2].z;
+        bnd_dw     = r[2].w;
+        q      = reinterpret_cast<uint8_t const *>(((uint64_t)r[3].y << 32) | r[3].x);
+        s      = reinterpret_cast<uint8_t const *>(((uint64_t)r[3].w << 32) | r[3].z);
+        ops_al = reinterpret_cast<uint8_t *>(((uint64_t)r[4].y << 32) | r[4].x);
+        cap    = r[4].z;
+        apos   = r[4].w;
+        acc    = r[5].x;
+        n      = r[5].y;
+        lq     = (int)r[5].z;
+        ls     = (int)r[5].w;
+        i      = (int)r[6].x;
+        j      = (int)r[6].y;
+        end_i  = (int)r[6].z;
+        end_j  = (int)r[6].w;
+        res_row = (int)r[7].x;
+        nar_j0  = (int)r[7].y;
+        nar_st0 = (int)r[7].z;
+        left    = (int)r[7].w;
+        nm      = (int32_t)r[8].x;
+        nx      = (int32_t)r[8].y;
+        np      = (int32_t)r[8].z;
+        go      = (int32_t)r[8].w;
+        gx      = (int32_t)r[9].x;
+        ncodes  = r[9].y;
+        have    = true;
+    };
+    // position of the r-th set bit of m (r < popcount(m)); the r lowest set bits of m
+    auto nth_bit = [](uint64_t m, uint32_t r) -> uint32_t
+    {
+        uint32_t at = 0;
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1)
+        {
+            uint32_t const lo = (uint32_t)__popcll(m & ((1ull << w) - 1ull));
+            if (r >= lo)
+            {
+                r -= lo;
+                m >>= w;
+                at += (uint32_t)w;
+            }
+        }
+        return at;
+    };
+    auto low_bits = [&](uint64_t m, uint32_t r) -> uint64_t
+    {
+        return r >= (uint32_t)__popcll(m) ? m : (m & ((1ull << nth_bit(m, r)) - 1ull));
+    };
+
 
     // ---- k cells up the diagonal from (i, j) in state H, 1 <= k <= 16: the walk takes them if the piece is the traceback's
     // path -- verify: L after k cells equals Hb, the stored H of the cell beyond (see above); !verify: the caller knows
@@ -1001,9 +1110,18 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
 
     // Scheduling of the wavefront: a shortcut pass costs ~1/8 of a tile phase, so shortcuts run while enough lanes can use
     // them; a tile phase runs when LX_BT_TILE_AT lanes wait for one (or nobody can do anything else), right after the
-    // finished lanes have been retired and refilled (a new extension starts with a tile).
+    // finished lanes have been retired and refilled (a new extension starts with a tile).  With the pool, lanes per pass on the
+    // headline (LX_BT_COUNT, thresholds 40/12): 38.6 -> 52.1 of 64 in a shortcut pass, 45.8 -> 51.1 in a tile phase.
     bool queue_empty = false; // wave-uniform
     int const tile_at = p.bt_tile_at > 0 ? p.bt_tile_at : LX_BT_TILE_AT, refill_at = p.bt_refill_at > 0 ? p.bt_refill_at : LX_BT_REFILL_AT;
+#ifdef LX_BT_COUNT
+    uint32_t cnt_sc = 0, cnt_sc_lanes = 0, cnt_tile = 0, cnt_tile_lanes = 0; // (wave-uniform)
+#endif
+    // Parked extensions (pool, kPool entries): pool_used = entries that hold one, pool_tile = those of them that wait for a
+    // tile (wave-uniform).  A parked extension is never finished.  Passes are chosen by live and parked extensions together;
+    // before each pass the lanes that would sit it out trade places with parked extensions that can take part.
+    uint64_t pool_used = 0, pool_tile = 0;
+    uint64_t const lanes_below = (1ull << lane) - 1ull;
     for (;;)
     {
         bool fin       = have && (done || i < 0 || j < 0 || n >= cap);
@@ -1011,8 +1129,9 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         bool tile_need = have && !fin && !can;
         int  n_can = __popcll(__ballot(can)), n_tile = __popcll(__ballot(tile_need));
         int const n_idle = 64 - n_can - n_tile; // finished or empty lanes
-        bool run_tile = n_can == 0 || n_tile >= tile_at;
-        if (n_idle > 0 && (run_tile || n_idle >= refill_at))
+        int  p_tile = __popcll(pool_tile), p_can = __popcll(pool_used) - p_tile;
+        bool run_tile = n_can + p_can == 0 || n_tile + p_tile >= tile_at;
+        if (n_idle > 0 && (run_tile || n_idle >= refill_at || n_can == 0))
         {
             // ================= retire and refill
             if (fin)
@@ -1041,6 +1160,27 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                 finish_extension(at);
             if (!queue_empty)
             {
+                if constexpr (kPool > 0)
+                {
+                    // while the queue lasts, live extensions that sit out the coming pass go to free entries and their lanes
+                    // take new ones
+                    bool const     out = have && !(run_tile ? tile_need : can); // (finished lanes are empty by now)
+                    uint64_t const mo  = __ballot(out);
+                    uint64_t const fr  = ~pool_used & (kPool == 64 ? ~0ull : ((1ull << kPool) - 1ull));
+                    uint32_t const npk = min((uint32_t)__popcll(mo), (uint32_t)__popcll(fr));
+                    if (npk > 0)
+                    {
+                        uint32_t const rank = (uint32_t)__popcll(mo & lanes_below);
+                        if (out && rank < npk)
+                        {
+                            park(nth_bit(fr, rank));
+                            have = false;
+                        }
+                        uint64_t const got = low_bits(fr, npk);
+                        pool_used |= got;
+                        pool_tile |= run_tile ? 0ull : got;
+                    }
+                }
                 uint64_t const want = __ballot(!have);
                 if (want != 0)
                 {
@@ -1064,15 +1204,73 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             tile_need = have && !fin && !can;
             n_can     = __popcll(__ballot(can));
             n_tile    = __popcll(__ballot(tile_need));
-            if (n_can == 0 && n_tile == 0)
+            if (n_can == 0 && n_tile == 0 && pool_used == 0)
             {
                 if (__ballot(have) == 0 && queue_empty)
+                {
+#ifdef LX_BT_COUNT
+                    if (lane == 0)
+                    {
+                        atomicAdd(&lx_bt_counts[0], (unsigned long long)cnt_sc);
+                        atomicAdd(&lx_bt_counts[1], (unsigned long long)cnt_sc_lanes);
+                        atomicAdd(&lx_bt_counts[2], (unsigned long long)cnt_tile);
+                        atomicAdd(&lx_bt_counts[3], (unsigned long long)cnt_tile_lanes);
+                        atomicAdd(&lx_bt_counts[4], 1ull);
+                    }
+#endif
                     break;
+                }
                 if (__ballot(have) == 0)
                     continue; // (only padding slots or score-less extensions came out of the queue: take more)
             }
-            run_tile = n_can == 0 || n_tile >= tile_at;
+            p_tile   = __popcll(pool_tile);
+            p_can    = __popcll(pool_used) - p_tile;
+            run_tile = n_can + p_can == 0 || n_tile + p_tile >= tile_at;
         }
+        if constexpr (kPool > 0)
+        {
+            // ================= exchange: the k-th lane that sits out the pass (empty lanes first, then those whose extension
+            // waits for the other kind of pass) takes the k-th parked extension that can take part, and parks its own in that
+            // entry.  Finished lanes wait for their retirement.
+            uint64_t const px = run_tile ? pool_tile : (pool_used & ~pool_tile);
+            if (px != 0)
+            {
+                bool const     empty = !have, other = have && !fin && !(run_tile ? tile_need : can);
+                uint64_t const me = __ballot(empty), mo = __ballot(other);
+                uint32_t const ne = (uint32_t)__popcll(me);
+                uint32_t const ns = min((uint32_t)__popcll(px), ne + (uint32_t)__popcll(mo));
+                if (ns > 0)
+                {
+                    uint32_t const rank = empty ? (uint32_t)__popcll(me & lanes_below) : (other ? ne + (uint32_t)__popcll(mo & lanes_below) : 64u);
+                    if (rank < ns)
+                    {
+                        uint32_t const e = nth_bit(px, rank);
+                        uint4          r[kRecQ];
+#pragma unroll
+                        for (int f = 0; f < kRecQ; ++f)
+                            r[f] = pool[f][e];
+                        if (other)
+                            park(e);
+                        unpark(r);
+                    }
+                    // entries taken by empty lanes are free now; the others hold an extension of the other kind
+                    uint64_t const taken = low_bits(px, ns), freed = low_bits(px, min(ne, ns));
+                    pool_used &= ~freed;
+                    pool_tile = (pool_tile & ~freed) ^ (taken & ~freed);
+                    fin       = have && (done || i < 0 || j < 0 || n >= cap);
+                    can       = have && !fin && !blocked && !need_col && mode == 0;
+                    tile_need = have && !fin && !can;
+                    n_can     = __popcll(__ballot(can));
+                    n_tile    = __popcll(__ballot(tile_need));
+                }
+            }
+        }
+#ifdef LX_BT_COUNT
+        cnt_sc += run_tile ? 0u : 1u;
+        cnt_sc_lanes += run_tile ? 0u : (uint32_t)n_can;
+        cnt_tile += run_tile ? 1u : 0u;
+        cnt_tile_lanes += run_tile ? (uint32_t)n_tile : 0u;
+#endif
 
         if (!run_tile)
         {
@@ -1505,6 +1703,24 @@ hipError_t launch_ckpt_backtrace(TraceParams const & p_in, hipStream_t stream)
         hipLaunchKernelGGL((ckpt_backtrace_kernel<8, 11>), dim3((unsigned)b2), dim3(64), 0, stream, p);
     else
         hipLaunchKernelGGL((ckpt_backtrace_kernel<8, 19>), dim3((unsigned)b2), dim3(64), 0, stream, p);
+#ifdef LX_BT_COUNT
+    {
+        unsigned long long c[5] = {};
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(stream);
+        if (e == hipSuccess)
+            e = hipMemcpyFromSymbol(c, HIP_SYMBOL(lx_bt_counts), sizeof(c));
+        unsigned long long const z[5] = {};
+        if (e == hipSuccess)
+            e = hipMemcpyToSymbol(HIP_SYMBOL(lx_bt_counts), z, sizeof(z));
+        if (e != hipSuccess)
+            return e;
+        fprintf(stderr, "LX_BT_COUNT cfg %d n %llu waves %llu: shortcut passes %llu, lanes/pass %.2f; tile phases %llu, lanes/phase %.2f\n",
+                p.cfg, (unsigned long long)p.n, c[4], c[0], c[0] ? (double)c[1] / (double)c[0] : 0.0, c[2],
+                c[2] ? (double)c[3] / (double)c[2] : 0.0);
+    }
+#endif
     return hipGetLastError();
 }
 
