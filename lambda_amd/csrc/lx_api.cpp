@@ -63,10 +63,10 @@ hipEvent_t pool_event(lx_handle * h)
 {
     if (h->ev_pool_used == h->ev_pool.size())
     {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess)
+        lxi::Event e;
+        if (hipEventCreate(e.out()) != hipSuccess)
             return nullptr;
-        h->ev_pool.push_back(e);
+        h->ev_pool.push_back(std::move(e));
     }
     return h->ev_pool[h->ev_pool_used++];
 }
@@ -92,6 +92,22 @@ int ensure(lx_handle * h, DevBuf & b, size_t bytes)
         fprintf(stderr, "[lx host ms]   device buffer %+ld in the handle grows from %.1f to %.1f MB\n", (long)(reinterpret_cast<char *>(&b) - reinterpret_cast<char *>(h)),
                 (double)had / 1e6, (double)want / 1e6);
     LX_HIP(h, hipMalloc(&b.ptr, want));
+    b.cap = want;
+    return LX_OK;
+}
+
+int ensure_pinned(lx_handle * h, Pinned & b, size_t bytes, PinGrowth growth, unsigned flags)
+{
+    if (bytes <= b.cap)
+        return LX_OK;
+    if (b.ptr)
+    {
+        LX_HIP(h, hipHostFree(b.ptr));
+        b.ptr = nullptr;
+        b.cap = 0;
+    }
+    size_t const want = growth == kRoom ? bytes + bytes / 4 + 4096 : bytes;
+    LX_HIP(h, hipHostMalloc(&b.ptr, want, flags));
     b.cap = want;
     return LX_OK;
 }
@@ -1095,32 +1111,32 @@ int lx_create(int device_id, lx_handle ** out)
     auto bail     = [&](char const * what, hipError_t err)
     {
         int rc = fail(nullptr, LX_EHIP, "%s: %s", what, hipGetErrorString(err));
-        lx_destroy(h);
+        delete h; // (gives back what the steps before made)
         return rc;
     };
     if ((e = hipSetDevice(device_id)) != hipSuccess)
         return bail("hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking)) != hipSuccess)
         return bail("hipStreamCreate", e);
-    if ((e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess)
+    if ((e = hipEventCreate(h->ev0.out())) != hipSuccess || (e = hipEventCreate(h->ev1.out())) != hipSuccess)
         return bail("hipEventCreate", e);
-    if ((e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = hipStreamCreateWithFlags(h->stream2.out(), hipStreamNonBlocking)) != hipSuccess ||
+        (e = hipStreamCreateWithFlags(h->stream3.out(), hipStreamNonBlocking)) != hipSuccess)
         return bail("hipStreamCreate", e);
     for (auto & ln : h->xb)
-        for (hipEvent_t * ev : {&ln.ev_up, &ln.ev_k, &ln.ev_cnt})
-            if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess)
+        for (lxi::Event * ev : {&ln.ev_up, &ln.ev_k, &ln.ev_cnt})
+            if ((e = hipEventCreateWithFlags(ev->out(), hipEventDisableTiming)) != hipSuccess)
                 return bail("hipEventCreate", e);
-    if ((e = hipMalloc(reinterpret_cast<void **>(&h->d_ws_top), 8 * sizeof(uint32_t))) != hipSuccess)
+    if ((e = hipMalloc(h->d_ws_top.out(), 8 * sizeof(uint32_t))) != hipSuccess)
         return bail("hipMalloc", e);
     if ((e = hipMemset(h->d_ws_top, 0, 8 * sizeof(uint32_t))) != hipSuccess)
         return bail("hipMemset", e);
     for (int s = 0; s < 2; ++s)
-        if ((e = hipMalloc(reinterpret_cast<void **>(&h->sc_dev[s]), sizeof(lx::ScoringDev))) != hipSuccess)
+        if ((e = hipMalloc(h->sc_dev[s].out(), sizeof(lx::ScoringDev))) != hipSuccess)
             return bail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void **>(&h->p_count), 2 * sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess)
+    if ((e = hipHostMalloc(h->p_count.out(), 2 * sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess)
         return bail("hipHostMalloc", e);
-    if ((e = hipEventCreateWithFlags(&h->ev_count, hipEventDisableTiming)) != hipSuccess)
+    if ((e = hipEventCreateWithFlags(h->ev_count.out(), hipEventDisableTiming)) != hipSuccess)
         return bail("hipEventCreate", e);
     *out = h;
     return LX_OK;
@@ -1128,88 +1144,17 @@ int lx_create(int device_id, lx_handle ** out)
 
 void lx_destroy(lx_handle * h)
 {
-    if (!h)
-        return;
-    if (h->device >= 0)
-        (void)hipSetDevice(h->device);
-    if (h->stream)
-        (void)hipStreamSynchronize(h->stream);
-    for (DevBuf * b : {&h->d_q, &h->d_s, &h->d_ext, &h->d_out, &h->d_ops, &h->d_opsoff, &h->d_keep, &h->d_trace, &h->d_ends,
-                       &h->d_hsp, &h->d_seeds, &h->d_sel_ext, &h->d_sel_src, &h->d_sel_runs, &h->d_sel_score, &h->d_trace_score, &h->d_db, &h->d_ws, &h->d_band})
-        if (b->ptr)
-            (void)hipFree(b->ptr);
-    for (int s = 0; s < 2; ++s)
-        if (h->sc_dev[s])
-            (void)hipFree(h->sc_dev[s]);
-    if (h->d_ws_top)
-        (void)hipFree(h->d_ws_top);
-    if (h->ev_count)
-        (void)hipEventDestroy(h->ev_count);
-    if (h->p_count)
-        (void)hipHostFree(h->p_count);
-    for (hipStream_t st : {h->stream2, h->stream3})
-        if (st)
-        {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    for (auto & ln : h->xb)
-    {
-        for (DevBuf * b : {&ln.d_ext, &ln.d_min, &ln.d_score, &ln.d_hsp, &ln.d_ops, &ln.d_rle, &ln.d_src, &ln.d_cnt, &ln.d_len, &ln.d_orig, &ln.d_wft})
-            if (b->ptr)
-                (void)hipFree(b->ptr);
-        for (lx_handle::Pinned * b : {&ln.p_ext, &ln.p_min, &ln.p_score, &ln.p_cnt, &ln.p_hsp, &ln.p_src, &ln.p_rle, &ln.p_len, &ln.p_orig, &ln.p_wft})
-            if (b->ptr)
-                (void)hipHostFree(b->ptr);
-        for (hipEvent_t ev : {ln.ev_up, ln.ev_k, ln.ev_cnt})
-            if (ev)
-                (void)hipEventDestroy(ev);
-    }
-    for (DevBuf * b : {&h->d_ext_all, &h->d_min_all, &h->d_score_all})
-        if (b->ptr)
-            (void)hipFree(b->ptr);
-    {
-        auto & l2 = h->l2;
-        for (DevBuf * b : {&l2.d_qres, &l2.d_qoff, &l2.d_qlen, &l2.d_qband, &l2.d_qevlen, &l2.d_soff, &l2.d_slen, &l2.d_pair[0], &l2.d_pair[1], &l2.d_s0[0],
-                           &l2.d_s0[1], &l2.d_hist, &l2.d_head, &l2.d_tail, &l2.d_tot, &l2.d_win, &l2.d_cut, &l2.d_cnt, &l2.d_up, &l2.d_plan, &l2.d_wf, &l2.d_qevidx,
-                           &l2.d_surv_hsp, &l2.d_surv_src, &l2.d_surv_codes, &l2.d_listat, &l2.d_rec, &l2.d_reccodes, &l2.d_reccnt, &l2.d_tilekeep, &l2.d_tileops,
-                           &l2.d_pre, &l2.d_exp, &l2.d_rank, &l2.d_fp})
-            if (b->ptr)
-                (void)hipFree(b->ptr);
-        for (lx_handle::Pinned * b : {&l2.p_cnt, &l2.p_win, &l2.p_up, &l2.p_reccnt, &l2.p_reccodes, &l2.p_rows, &l2.p_plan})
-            if (b->ptr)
-                (void)hipHostFree(b->ptr);
-        if (l2.ev_win)
-            (void)hipEventDestroy(l2.ev_win);
-        for (hipEvent_t ev : l2.ev_rank)
-            if (ev)
-                (void)hipEventDestroy(ev);
-    }
-    for (DevBuf * b : {&h->bgzf.d_in, &h->bgzf.d_slots, &h->bgzf.d_dist, &h->bgzf.d_sym, &h->bgzf.d_sizes, &h->bgzf.d_out, &h->bgzf.d_total})
-        if (b->ptr)
-            (void)hipFree(b->ptr);
-    for (lx_handle::Pinned * b : {&h->bgzf.p_in[0], &h->bgzf.p_in[1], &h->bgzf.p_out, &h->bgzf.p_total})
-        if (b->ptr)
-            (void)hipHostFree(b->ptr);
-    for (DevBuf * b : {&h->gunzip.d_in, &h->gunzip.d_mem, &h->gunzip.d_status, &h->gunzip.d_out})
-        if (b->ptr)
-            (void)hipFree(b->ptr);
-    for (lx_handle::Pinned * b : {&h->gunzip.p_in[0], &h->gunzip.p_in[1], &h->gunzip.p_mem[0], &h->gunzip.p_mem[1], &h->gunzip.p_status[0],
-                                  &h->gunzip.p_status[1]})
-        if (b->ptr)
-            (void)hipHostFree(b->ptr);
-    for (lx_handle::Pinned * b : {&h->p_all, &h->p_score_all})
-        if (b->ptr)
-            (void)hipHostFree(b->ptr);
-    for (hipEvent_t ev : h->ev_pool)
-        (void)hipEventDestroy(ev);
-    if (h->ev0)
-        (void)hipEventDestroy(h->ev0);
-    if (h->ev1)
-        (void)hipEventDestroy(h->ev1);
-    if (h->stream)
-        (void)hipStreamDestroy(h->stream);
     delete h;
+}
+
+// All three streams are through before the first member goes: the copies of stream2 / stream3 use the buffers too.
+lx_handle::~lx_handle()
+{
+    if (device >= 0)
+        (void)hipSetDevice(device);
+    for (hipStream_t st : {stream.raw, stream2.raw, stream3.raw})
+        if (st)
+            (void)hipStreamSynchronize(st);
 }
 
 char const * lx_last_error(lx_handle const * h)

@@ -18,21 +18,6 @@ constexpr uint64_t kChunkBytes  = (uint64_t)kChunkBlocks * lx::kBgzfBlock;
 // the empty member that ends a BGZF file (SAM/BAM specification 4.1.2)
 constexpr uint8_t kEofMember[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-int ensure_pinned(lx_handle * h, lx_handle::Pinned & b, size_t bytes)
-{
-    if (bytes <= b.cap)
-        return LX_OK;
-    if (b.ptr)
-    {
-        LX_HIP(h, hipHostFree(b.ptr));
-        b.ptr = nullptr;
-        b.cap = 0;
-    }
-    LX_HIP(h, hipHostMalloc(&b.ptr, bytes, hipHostMallocDefault));
-    b.cap = bytes;
-    return LX_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -64,8 +49,8 @@ int lx_bgzf_compress(lx_handle * h, uint8_t const * in, uint64_t n, uint8_t * ou
         ((rc = ensure(h, B.d_in, blocks * lx::kBgzfBlock)) || (rc = ensure(h, B.d_slots, blocks * lx::kBgzfSlot)) ||
          (rc = ensure(h, B.d_dist, blocks * lx::kBgzfBlock * 2)) || (rc = ensure(h, B.d_sym, blocks * lx::kBgzfBlock * 2)) ||
          (rc = ensure(h, B.d_sizes, blocks * 4)) || (rc = ensure(h, B.d_out, blocks * lx::kBgzfSlot)) || (rc = ensure(h, B.d_total, 8)) ||
-         (rc = ensure_pinned(h, B.p_in[0], first)) || (rc = ensure_pinned(h, B.p_in[1], first)) ||
-         (rc = ensure_pinned(h, B.p_out, blocks * lx::kBgzfSlot)) || (rc = ensure_pinned(h, B.p_total, 8))))
+         (rc = ensure_pinned(h, B.p_in[0], first, kExact)) || (rc = ensure_pinned(h, B.p_in[1], first, kExact)) ||
+         (rc = ensure_pinned(h, B.p_out, blocks * lx::kBgzfSlot, kExact)) || (rc = ensure_pinned(h, B.p_total, 8, kExact))))
         return rc;
     hipStream_t const s     = h->stream;
     uint64_t * const  total = static_cast<uint64_t *>(B.p_total.ptr);

@@ -22,21 +22,6 @@ namespace
 
 constexpr uint32_t kChunkMembers = 512; // 32 MiB of input and output at most per chunk
 
-int ensure_pinned(lx_handle * h, lx_handle::Pinned & b, size_t bytes)
-{
-    if (bytes <= b.cap)
-        return LX_OK;
-    if (b.ptr)
-    {
-        LX_HIP(h, hipHostFree(b.ptr));
-        b.ptr = nullptr;
-        b.cap = 0;
-    }
-    LX_HIP(h, hipHostMalloc(&b.ptr, bytes, hipHostMallocDefault));
-    b.cap = bytes;
-    return LX_OK;
-}
-
 struct CrcTable
 {
     uint32_t t[256];
@@ -217,8 +202,8 @@ struct Walk
             (rc = ensure(h, G.d_mem, cap * sizeof(lx::GunzipMember))) || (rc = ensure(h, G.d_status, cap * 4)))
             return rc;
         for (int l = 0; l < 2; ++l)
-            if ((rc = ensure_pinned(h, G.p_in[l], cap * 65536)) || (rc = ensure_pinned(h, G.p_mem[l], cap * sizeof(lx::GunzipMember))) ||
-                (rc = ensure_pinned(h, G.p_status[l], cap * 4)))
+            if ((rc = ensure_pinned(h, G.p_in[l], cap * 65536, kExact)) || (rc = ensure_pinned(h, G.p_mem[l], cap * sizeof(lx::GunzipMember), kExact)) ||
+                (rc = ensure_pinned(h, G.p_status[l], cap * 4, kExact)))
                 return rc;
         struct Chunk
         {

@@ -49,22 +49,6 @@ inline void rle_expand(uint8_t const * codes, int32_t n_ops, uint8_t * out)
     }
 }
 
-int ensure_pinned(lx_handle * h, lx_handle::Pinned & b, size_t bytes)
-{
-    if (bytes <= b.cap)
-        return LX_OK;
-    if (b.ptr)
-    {
-        LX_HIP(h, hipHostFree(b.ptr));
-        b.ptr = nullptr;
-        b.cap = 0;
-    }
-    size_t const want = bytes + bytes / 4 + 4096;
-    LX_HIP(h, hipHostMalloc(&b.ptr, want, hipHostMallocDefault));
-    b.cap = want;
-    return LX_OK;
-}
-
 using Clock = std::chrono::steady_clock;
 inline Clock::time_point now() { return Clock::now(); }
 inline double            ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
@@ -114,11 +98,11 @@ public:
         uint64_t const ext_bytes = n * sizeof(lx_extension), min_bytes = min_score ? n * sizeof(int32_t) : 0;
         // (the scores of a list whose records are made on the device stay there: no pinned block for their way down)
         if ((rc2 = ensure(h, h->d_score_all, n * sizeof(int32_t) + 16)) ||
-            (!(as_list && ri && ri->keep_on_device) && (rc2 = ensure_pinned(h, h->p_score_all, n * sizeof(int32_t) + 16))))
+            (!(as_list && ri && ri->keep_on_device) && (rc2 = ensure_pinned(h, h->p_score_all, n * sizeof(int32_t) + 16, kRoom))))
             return rc2;
         if (!ri) // (a resident list stands where the Level-2 kernels wrote it)
         {
-            if ((rc2 = ensure_pinned(h, h->p_all, ext_bytes + min_bytes + 16)) || (rc2 = ensure(h, h->d_ext_all, ext_bytes + 16)) ||
+            if ((rc2 = ensure_pinned(h, h->p_all, ext_bytes + min_bytes + 16, kRoom)) || (rc2 = ensure(h, h->d_ext_all, ext_bytes + 16)) ||
                 (rc2 = ensure(h, h->d_min_all, min_bytes + 16)))
                 return rc2;
             uint8_t * const stage_all = static_cast<uint8_t *>(h->p_all.ptr);
@@ -255,7 +239,7 @@ private:
             (rc2 = ensure(h, ln.d_hsp, cap_sel * sizeof(lx_hsp))) || (rc2 = ensure(h, ln.d_ops, cap_sel * stride + 16)) ||
             (rc2 = ensure(h, ln.d_rle, cap_sel * stride + 16)) || (rc2 = ensure(h, ln.d_src, cap_sel * sizeof(uint32_t))) ||
             (rc2 = ensure(h, ln.d_len, cap_sel * sizeof(uint32_t))) || (rc2 = ensure(h, ln.d_cnt, words * sizeof(uint64_t))) ||
-            (!mq && (rc2 = ensure_pinned(h, ln.p_score, slots * sizeof(int32_t)))) || (rc2 = ensure_pinned(h, ln.p_cnt, words * sizeof(uint64_t))))
+            (!mq && (rc2 = ensure_pinned(h, ln.p_score, slots * sizeof(int32_t), kRoom))) || (rc2 = ensure_pinned(h, ln.p_cnt, words * sizeof(uint64_t), kRoom)))
             return rc2;
         return LX_OK;
     }
@@ -366,7 +350,7 @@ private:
         pr.cap_sel = (slots + slots / kRun * 3 + 7) / 8 * 8 + 8;
         pr.slot_src.resize(slots);
         int rc2;
-        if ((rc2 = ensure_pinned(h, ln.p_ext, slots * sizeof(lx_extension))) || (rc2 = ensure_pinned(h, ln.p_min, slots * sizeof(int32_t))))
+        if ((rc2 = ensure_pinned(h, ln.p_ext, slots * sizeof(lx_extension), kRoom)) || (rc2 = ensure_pinned(h, ln.p_min, slots * sizeof(int32_t), kRoom)))
             return rc2;
         lx_extension * const  slot_ext = static_cast<lx_extension *>(ln.p_ext.ptr);
         int32_t * const       slot_min = static_cast<int32_t *>(ln.p_min.ptr);
@@ -456,8 +440,8 @@ private:
     {
         lx_handle::XbLane & ln = h->xb[L];
         int                 rc2;
-        if ((rc2 = ensure_pinned(h, ln.p_hsp, count * sizeof(lx_hsp) + 16)) || (rc2 = ensure_pinned(h, ln.p_src, count * sizeof(uint32_t) + 16)) ||
-            (rc2 = ensure_pinned(h, ln.p_len, count * sizeof(uint32_t) + 16)) || (rc2 = ensure_pinned(h, ln.p_rle, nrle + 16)))
+        if ((rc2 = ensure_pinned(h, ln.p_hsp, count * sizeof(lx_hsp) + 16, kRoom)) || (rc2 = ensure_pinned(h, ln.p_src, count * sizeof(uint32_t) + 16, kRoom)) ||
+            (rc2 = ensure_pinned(h, ln.p_len, count * sizeof(uint32_t) + 16, kRoom)) || (rc2 = ensure_pinned(h, ln.p_rle, nrle + 16, kRoom)))
             return rc2;
         if (count)
         {
@@ -919,7 +903,7 @@ private:
         pr.slots               = slots;
         pr.cap_sel             = (slots + 7) / 8 * 8 + 8;
         int rc2;
-        if (!preplanned && (rc2 = ensure_pinned(h, ln.p_orig, slots * sizeof(uint32_t))))
+        if (!preplanned && (rc2 = ensure_pinned(h, ln.p_orig, slots * sizeof(uint32_t), kRoom)))
             return rc2;
         uint32_t * const      slot_orig = static_cast<uint32_t *>(ln.p_orig.ptr);
         uint64_t const        panel     = (uint64_t)lx::trace_cfg_panel(p.mq_cfg);
@@ -981,7 +965,7 @@ private:
         pr.wide = mq_wide;
         // the chunk's slots by wavefront (lx::WfSlots)
         uint64_t const nw = w1 - w0;
-        if ((rc2 = ensure_pinned(h, ln.p_wft, nw * sizeof(lx::WfSlots))) || (rc2 = ensure(h, ln.d_wft, nw * sizeof(lx::WfSlots))))
+        if ((rc2 = ensure_pinned(h, ln.p_wft, nw * sizeof(lx::WfSlots), kRoom)) || (rc2 = ensure(h, ln.d_wft, nw * sizeof(lx::WfSlots))))
             return rc2;
         lx::WfSlots * const tab = static_cast<lx::WfSlots *>(ln.p_wft.ptr);
         uint64_t const      off = fill_table(tab, w0, w1, pr.wide);
@@ -1029,7 +1013,7 @@ private:
         uint64_t const      panel = (uint64_t)lx::trace_cfg_panel(p.mq_cfg), slots1 = w1 * kWave;
         pr.k0 = 0, pr.k1 = w1, pr.slots = slots1, pr.cap_sel = (cap_slots + 7) / 8 * 8 + 8, pr.exec_cells = 0, pr.max_s = cap_s, pr.max_pan = cap_pan;
         int rc2;
-        if ((rc2 = ensure_pinned(h, ln.p_orig, cap_slots * sizeof(uint32_t))) || (rc2 = ensure_pinned(h, ln.p_wft, (cap_slots / kWave + 1) * sizeof(lx::WfSlots))))
+        if ((rc2 = ensure_pinned(h, ln.p_orig, cap_slots * sizeof(uint32_t), kRoom)) || (rc2 = ensure_pinned(h, ln.p_wft, (cap_slots / kWave + 1) * sizeof(lx::WfSlots), kRoom)))
             return rc2;
         uint32_t * const slot_orig = static_cast<uint32_t *>(ln.p_orig.ptr);
         std::memcpy(slot_orig, p.plan_slot.data(), slots1 * sizeof(uint32_t));

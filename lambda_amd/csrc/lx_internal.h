@@ -28,6 +28,7 @@
 #include "lx_device.h"
 #include "lx_host_plan.h"
 #include "lx_host_pool.h"
+#include "lx_resources.h"
 
 
 namespace lx
@@ -70,12 +71,6 @@ hipError_t launch_rle_pack(PackParams const & p, hipStream_t stream);
 namespace lxi
 {
 
-struct DevBuf
-{
-    void * ptr = nullptr;
-    size_t cap = 0;
-};
-
 // what lx_set_scoring derives from a scheme besides the tables (one per scoring slot; plan_step decides by them): pass 2 applies
 // (every matrix - gap_extend in [-31, 31]), byte profiles apply (0 <= matrix - gap_open <= 255), the largest entry
 struct SchemeFacts
@@ -87,13 +82,17 @@ struct SchemeFacts
 
 } // namespace lxi
 using lxi::DevBuf;
+using lxi::Pinned;
 
+// Every buffer, event and stream below is an owner (lx_resources.h): the destructor binds the device and waits for the three streams,
+// then the members give back what they hold.
 struct lx_handle
 {
+    ~lx_handle();
     int         device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t  ev0 = nullptr, ev1 = nullptr;
-    hipStream_t stream2 = nullptr;                       // downloads of lx_extend_batch
+    lxi::Stream stream;
+    lxi::Event  ev0, ev1;
+    lxi::Stream stream2;                                 // downloads of lx_extend_batch
     bool        timed = false;
     std::string error;
     // lx_extend_batch: host staging that keeps its pages between calls
@@ -130,21 +129,16 @@ struct lx_handle
     Bytes    res_index, res_hsp, res_off;
     uint64_t res_count = 0, xb_ops_total = 0;
     // lx_extend_batch's two chunks in flight: pinned staging, device buffers, events
-    struct Pinned
-    {
-        void * ptr = nullptr;
-        size_t cap = 0;
-    };
     struct XbLane
     {
         Pinned     p_ext, p_min, p_score, p_cnt, p_hsp, p_src, p_rle, p_len, p_orig, p_wft;
         DevBuf     d_ext, d_min, d_score, d_hsp, d_ops, d_rle, d_src, d_cnt, d_len, d_orig, d_wft; // (wft: the chunk's lx::WfSlots table)
-        hipEvent_t ev_up = nullptr, ev_k = nullptr, ev_cnt = nullptr;
+        lxi::Event ev_up, ev_k, ev_cnt;
     } xb[2];
     // multi-query plan: the caller's whole list, its cut-offs and the scores in caller order, on the device / in pinned staging
     DevBuf      d_ext_all, d_min_all, d_score_all;
     Pinned      p_all, p_score_all;
-    hipStream_t stream3 = nullptr; // uploads of lx_extend_batch (stream2 carries its downloads)
+    lxi::Stream stream3; // uploads of lx_extend_batch (stream2 carries its downloads)
     std::string last_kernel; // human-readable name of the most recent DP kernel geometry (profiling aid)
     std::string last_trace_kernel;
     // per-phase HIP events of the most recent call: phase 0 score, 1 select, 2 trace forward, 3 backtrace
@@ -154,19 +148,19 @@ struct lx_handle
         hipEvent_t a, b;
     };
     std::vector<PhaseEv>    phase_ev;      // events recorded by the last call
-    std::vector<hipEvent_t> ev_pool;       // reusable timing events
+    std::vector<lxi::Event> ev_pool;       // reusable timing events
     size_t                  ev_pool_used = 0;
 
     bool             have_sc[2] = {false, false};
     lxi::SchemeFacts facts[2];
     lx_scoring       sc_host[2];
-    lx::ScoringDev * sc_dev[2] = {nullptr, nullptr};
+    lxi::DevBlock<lx::ScoringDev> sc_dev[2];
 
     // staging for the host-buffer entry points
     DevBuf d_q, d_s, d_ext, d_out, d_ops, d_opsoff, d_keep, d_trace, d_ends, d_hsp, d_seeds, d_sel_ext, d_sel_src, d_sel_runs, d_sel_score, d_trace_score, d_db;
     // multi-panel carry workspace
     DevBuf     d_ws;
-    uint32_t * d_ws_top = nullptr; // [0] = bump pointer, [1] = error flag, [2..3] = MaxLens, [4] = overflow checkpoint slots handed out, [5] = backtrace work queue
+    lxi::DevBlock<uint32_t> d_ws_top; // [0] = bump pointer, [1] = error flag, [2..3] = MaxLens, [4] = overflow checkpoint slots handed out, [5] = backtrace work queue
     // options
     uint64_t opt_max_qlen  = 0;
     uint64_t opt_query_run = 0;
@@ -183,8 +177,8 @@ struct lx_handle
     // checkpoints for the survivors only (mode 1) until the share rises again.  The device entry point never synchronises: it
     // copies the count back behind its kernels and reads it at the next call if it has arrived by then.
     double      surv_frac        = -1.0;   // < 0: unknown
-    uint64_t *  p_count          = nullptr; // pinned: [0] = slots, [1] = survivors of the last device-resident call
-    hipEvent_t  ev_count         = nullptr;
+    lxi::PinnedBlock<uint64_t> p_count;    // pinned: [0] = slots, [1] = survivors of the last device-resident call
+    lxi::Event  ev_count;
     uint64_t    count_n          = 0;
     bool        count_pending    = false;
     uint64_t    opt_adapt        = 30;     // LX_OPT_ADAPT_PERMILLE
@@ -212,8 +206,8 @@ struct lx_handle
         std::vector<lx_extension> ext;   // host copies of the window list, its cut-offs and scores
         std::vector<int32_t>      min, score;
         std::vector<uint32_t>     wf_pan, wf_maxs; // a device plan's wavefronts
-        hipEvent_t                ev_win = nullptr; // the window list has arrived on the host
-        hipEvent_t                ev_rank[2] = {nullptr, nullptr}; // the window list is complete / the rank kernel (second stream) is through
+        lxi::Event                ev_win;    // the window list has arrived on the host
+        lxi::Event                ev_rank[2]; // the window list is complete / the rank kernel (second stream) is through
         // records on the device (lx_records.hip): the call's survivors as the pipeline's chunks left them (alignment, window, where the
         // codes begin), the key / scan / record buffers, the host-made tables of the e-value
         uint32_t              max_qlen = 0;
@@ -314,7 +308,6 @@ struct PhaseTimer
                         hipGetErrorString(_e));                                                                 \
     } while (0)
 
-int    ensure(lx_handle * h, DevBuf & b, size_t bytes);
 int    bind(lx_handle * h);
 // (host/lx_output.cpp) an lx_bytes that takes over s; the message lx_last_output_error() returns
 lx_bytes * bytes_adopt(std::string && s);

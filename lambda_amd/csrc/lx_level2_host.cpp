@@ -19,22 +19,6 @@ using namespace lxi;
 namespace
 {
 
-int ensure_pinned(lx_handle * h, lx_handle::Pinned & b, size_t bytes, unsigned flags = hipHostMallocDefault)
-{
-    if (bytes <= b.cap)
-        return LX_OK;
-    if (b.ptr)
-    {
-        LX_HIP(h, hipHostFree(b.ptr));
-        b.ptr = nullptr;
-        b.cap = 0;
-    }
-    size_t const want = bytes + bytes / 4 + 4096;
-    LX_HIP(h, hipHostMalloc(&b.ptr, want, flags));
-    b.cap = want;
-    return LX_OK;
-}
-
 template <class T>
 int upload(lx_handle * h, DevBuf & b, std::vector<T> const & v)
 {
@@ -197,7 +181,7 @@ static int level2_windows(lx_handle * h, uint64_t n_matches, bool bisulfite, std
         (rc = ensure(h, l2.d_hist, (tiles + 2) * 256 * sizeof(uint32_t))) || (rc = ensure(h, l2.d_head, n_matches * 16 + 16)) ||
         (rc = ensure(h, l2.d_tot, (stiles + 2) * sizeof(uint32_t))) ||
         (rc = ensure(h, l2.d_win, n_matches * sizeof(lx::L2Window) + 16)) || (rc = ensure(h, h->d_ext_all, n_matches * sizeof(lx_extension) + 16)) ||
-        (rc = ensure(h, h->d_min_all, n_matches * sizeof(int32_t) + 16)) || (rc = ensure_pinned(h, l2.p_cnt, 16 * sizeof(uint64_t))))
+        (rc = ensure(h, h->d_min_all, n_matches * sizeof(int32_t) + 16)) || (rc = ensure_pinned(h, l2.p_cnt, 16 * sizeof(uint64_t), kRoom)))
         return rc;
     uint64_t * pair = static_cast<uint64_t *>(l2.d_pair[0].ptr), * pair_tmp = static_cast<uint64_t *>(l2.d_pair[1].ptr);
     uint64_t * s0 = static_cast<uint64_t *>(l2.d_s0[0].ptr), * s0_tmp = static_cast<uint64_t *>(l2.d_s0[1].ptr);
@@ -367,7 +351,7 @@ struct RecordsJob
             (rc = ensure(h, l2.d_tilekeep, (tiles + 1) * sizeof(uint32_t))) || (rc = ensure(h, l2.d_tileops, (tiles + 1) * sizeof(uint64_t))) ||
             (rc = ensure(h, l2.d_pair[0], sort_n * 8 + 16)) || (rc = ensure(h, l2.d_pair[1], sort_n * 8 + 16)) || (rc = ensure(h, l2.d_s0[0], sort_n * 8 + 16)) ||
             (rc = ensure(h, l2.d_s0[1], sort_n * 8 + 16)) || (rc = ensure(h, l2.d_hist, (lx::l2_sort_tiles(sort_n) + 2) * 256 * sizeof(uint32_t))) ||
-            (rc = ensure_pinned(h, l2.p_reccnt, nr * lx::kRecCounters * sizeof(uint64_t))))
+            (rc = ensure_pinned(h, l2.p_reccnt, nr * lx::kRecCounters * sizeof(uint64_t), kRoom)))
         {
             (void)hipStreamSynchronize(st);
             return rc;
@@ -504,7 +488,7 @@ struct RecordsJob
         // 4.1 instead of 1.1 ms for half a million rows) and from there into the result by the host threads (2.0 ms with the columns,
         // hidden behind the chunk).  With the GPU idle -- the last range -- straight into the result (1.1 ms).
         hipError_t e_rows = hipSuccess;
-        int        rc_pin = gpu_busy ? ensure_pinned(h, l2.p_rows, nkeep * sizeof(lx_blast_match) + 16, hipHostMallocNonCoherent) : LX_OK;
+        int        rc_pin = gpu_busy ? ensure_pinned(h, l2.p_rows, nkeep * sizeof(lx_blast_match) + 16, kRoom, hipHostMallocNonCoherent) : LX_OK;
         if (rc_pin == LX_OK)
         {
             e_rows = hipMemcpyAsync(gpu_busy ? l2.p_rows.ptr : static_cast<void *>(res->matches.data() + rec0), d_rows, nkeep * sizeof(lx_blast_match), hipMemcpyDeviceToHost, cs);
@@ -556,7 +540,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
     // (lx_iterate_matches).  Records made on the device over a device plan need none of it.
     bool const records_on_device = h->opt_iterate_records == 0;
     if (!l2.ev_win)
-        LX_HIP(h, hipEventCreateWithFlags(&l2.ev_win, hipEventDisableTiming));
+        LX_HIP(h, hipEventCreateWithFlags(l2.ev_win.out(), hipEventDisableTiming));
     // (queued behind what `st` holds at that moment: where the plan is made on the device, behind the plan's kernels -- beside them
     // the copy's writes over PCIe held the first of them up for the whole 0.5 ms it takes -- and so beside the sweep)
     bool win_queued = false;
@@ -566,7 +550,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
             return LX_OK;
         win_queued = true;
         int rcw;
-        if ((rcw = ensure_pinned(h, l2.p_win, nw * sizeof(lx::L2Window) + 16)))
+        if ((rcw = ensure_pinned(h, l2.p_win, nw * sizeof(lx::L2Window) + 16, kRoom)))
             return rcw;
         LX_HIP(h, hipEventRecord(l2.ev_win, st));
         LX_HIP(h, hipStreamWaitEvent(h->stream2, l2.ev_win, 0));
@@ -674,7 +658,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
                 if (!probes.empty())
                 {
                     // (into pinned memory: a copy into ordinary memory is staged by the runtime, 40 us of an idle GPU each)
-                    if ((rc = ensure_pinned(h, l2.p_plan, kPlanHead)))
+                    if ((rc = ensure_pinned(h, l2.p_plan, kPlanHead, kRoom)))
                         return rc;
                     lx::L2Window * const probe = reinterpret_cast<lx::L2Window *>(static_cast<uint8_t *>(l2.p_plan.ptr) + kPlanProbe);
                     for (size_t k = 0; k < probes.size(); ++k)
@@ -712,7 +696,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
             else
                 cap_wf = lx::fp_wavefront_bound(n, l2.q_len.size(), (uint32_t)ranges.size());
             if ((rc = ensure(h, l2.d_plan, cap_wf * 16 * sizeof(uint32_t) + 16)) || (rc = ensure(h, l2.d_wf, 2 * cap_wf * sizeof(uint32_t) + 64)) ||
-                (rc = ensure_pinned(h, l2.p_plan, kPlanHead)))
+                (rc = ensure_pinned(h, l2.p_plan, kPlanHead, kRoom)))
                 return rc;
             uint32_t * const d_pan = static_cast<uint32_t *>(l2.d_wf.ptr), * const d_maxs = d_pan + cap_wf;
             uint32_t * const h_report = static_cast<uint32_t *>(l2.p_plan.ptr) + 16;
@@ -725,9 +709,9 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
             {
                 if ((rc = ensure(h, l2.d_rank, (n + 1) * sizeof(uint32_t) + 16)))
                     return rc;
-                for (hipEvent_t & ev : l2.ev_rank)
+                for (Event & ev : l2.ev_rank)
                     if (!ev)
-                        LX_HIP(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                        LX_HIP(h, hipEventCreateWithFlags(ev.out(), hipEventDisableTiming));
                 uint32_t * const d_rank = static_cast<uint32_t *>(l2.d_rank.ptr);
                 LX_HIP(h, hipEventRecord(l2.ev_rank[0], st)); // (the window list is complete behind what `st` holds now)
                 LX_HIP(h, hipStreamWaitEvent(h->stream2, l2.ev_rank[0], 0));
@@ -790,7 +774,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
                     return fail(h, LX_ESTATE, "the free-packing plan's ranges end at wavefront %llu of %llu", (unsigned long long)l2.cut_wf.back(), (unsigned long long)nwf);
             }
             // (no copy into the block is pending here: it may move)
-            if ((rc = ensure_pinned(h, l2.p_plan, kPlanHead + 2 * nwf * sizeof(uint32_t))))
+            if ((rc = ensure_pinned(h, l2.p_plan, kPlanHead + 2 * nwf * sizeof(uint32_t), kRoom)))
                 return rc;
             uint32_t * const h_pan = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(l2.p_plan.ptr) + kPlanHead), * const h_maxs = h_pan + nwf;
             LX_HIP(h, hipMemcpyAsync(h_pan, d_pan, nwf * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -999,7 +983,7 @@ int lxi::iterate_host_list_on_device(lx_handle * h, int slot, uint8_t const * q_
         return kNotTaken;
     hm.mark("sets");
     // ---- the matches as sort words (lx_level2.h), made by the host threads straight into pinned memory, 16 bytes each
-    if ((rc = ensure_pinned(h, l2.p_up, n_matches * 16 + 16)) || (rc = ensure(h, l2.d_pair[0], n_matches * 8 + 16)) || (rc = ensure(h, l2.d_s0[0], n_matches * 8 + 16)) ||
+    if ((rc = ensure_pinned(h, l2.p_up, n_matches * 16 + 16, kRoom)) || (rc = ensure(h, l2.d_pair[0], n_matches * 8 + 16)) || (rc = ensure(h, l2.d_s0[0], n_matches * 8 + 16)) ||
         (rc = ensure(h, l2.d_cnt, 16 * sizeof(uint64_t))))
         return rc;
     uint64_t * const      pair = static_cast<uint64_t *>(l2.p_up.ptr), * const s0 = pair + n_matches;
@@ -1109,7 +1093,7 @@ int lx_reserve(lx_handle * h, uint64_t n_matches, uint64_t n_windows, uint64_t n
         (rc = ensure(h, l2.d_hist, (tiles + 2) * 256 * sizeof(uint32_t))) || (rc = ensure(h, l2.d_head, n_matches * 16 + 16)) ||
         (rc = ensure(h, l2.d_tot, (stiles + 2) * sizeof(uint32_t))) || (rc = ensure(h, l2.d_win, n_matches * sizeof(lx::L2Window) + 16)) ||
         (rc = ensure(h, h->d_ext_all, n_matches * sizeof(lx_extension) + 16)) || (rc = ensure(h, h->d_min_all, n_matches * sizeof(int32_t) + 16)) ||
-        (rc = ensure_pinned(h, l2.p_cnt, 16 * sizeof(uint64_t))) || (rc = ensure(h, l2.d_cut, ((size_t)l2.max_evlen + 1) * sizeof(int32_t) + 16)))
+        (rc = ensure_pinned(h, l2.p_cnt, 16 * sizeof(uint64_t), kRoom)) || (rc = ensure(h, l2.d_cut, ((size_t)l2.max_evlen + 1) * sizeof(int32_t) + 16)))
         return rc;
     // (the plan: the solo packing takes a wavefront per 16 windows; the free packing of a protein list is bounded by its own formula and
     // has a workspace)
@@ -1128,9 +1112,9 @@ int lx_reserve(lx_handle * h, uint64_t n_matches, uint64_t n_windows, uint64_t n
         (rc = ensure(h, l2.d_surv_codes, entries * sizeof(uint64_t))) || (rc = ensure(h, l2.d_listat, n_windows * sizeof(uint32_t) + 16)) ||
         (rc = ensure(h, l2.d_reccnt, lx::kRecCounters * sizeof(uint64_t))) || (rc = ensure(h, l2.d_rec, entries * sizeof(lx_blast_match) + 16)) ||
         (rc = ensure(h, l2.d_reccodes, 3 * entries * sizeof(uint64_t) + 16)) || (rc = ensure(h, l2.d_tilekeep, ((entries + 255) / 256 + 1) * sizeof(uint32_t))) ||
-        (rc = ensure(h, l2.d_tileops, ((entries + 255) / 256 + 1) * sizeof(uint64_t))) || (rc = ensure_pinned(h, l2.p_reccnt, 8 * lx::kRecCounters * sizeof(uint64_t))) ||
-        (rc = ensure_pinned(h, l2.p_rows, (n_hsps * 3 / 4) * sizeof(lx_blast_match) + 16, hipHostMallocNonCoherent)) ||
-        (rc = ensure(h, l2.d_rank, (n_windows + 1) * sizeof(uint32_t) + 16)) || (rc = ensure_pinned(h, l2.p_plan, kPlanHead + 2 * (nwf + 8) * sizeof(uint32_t))) || (rc = ensure(h, l2.d_pre, std::max<size_t>(l2.evlens.size(), 1) * sizeof(double) + 16)) || (rc = ensure(h, l2.d_exp, (1u << 13) * sizeof(double))))
+        (rc = ensure(h, l2.d_tileops, ((entries + 255) / 256 + 1) * sizeof(uint64_t))) || (rc = ensure_pinned(h, l2.p_reccnt, 8 * lx::kRecCounters * sizeof(uint64_t), kRoom)) ||
+        (rc = ensure_pinned(h, l2.p_rows, (n_hsps * 3 / 4) * sizeof(lx_blast_match) + 16, kRoom, hipHostMallocNonCoherent)) ||
+        (rc = ensure(h, l2.d_rank, (n_windows + 1) * sizeof(uint32_t) + 16)) || (rc = ensure_pinned(h, l2.p_plan, kPlanHead + 2 * (nwf + 8) * sizeof(uint32_t), kRoom)) || (rc = ensure(h, l2.d_pre, std::max<size_t>(l2.evlens.size(), 1) * sizeof(double) + 16)) || (rc = ensure(h, l2.d_exp, (1u << 13) * sizeof(double))))
         return rc;
     if (n_columns)
     {
@@ -1170,7 +1154,7 @@ int lx_reserve(lx_handle * h, uint64_t n_matches, uint64_t n_windows, uint64_t n
                 (rc = ensure(h, ln.d_score, slots * sizeof(int32_t))) || (rc = ensure(h, ln.d_hsp, cap_sel * sizeof(lx_hsp))) ||
                 (rc = ensure(h, ln.d_ops, cap_sel * stride + 16)) || (rc = ensure(h, ln.d_rle, cap_sel * stride + 16)) ||
                 (rc = ensure(h, ln.d_src, cap_sel * sizeof(uint32_t))) || (rc = ensure(h, ln.d_len, cap_sel * sizeof(uint32_t))) ||
-                (rc = ensure(h, ln.d_cnt, 5 * sizeof(uint64_t))) || (rc = ensure_pinned(h, ln.p_cnt, 5 * sizeof(uint64_t))))
+                (rc = ensure(h, ln.d_cnt, 5 * sizeof(uint64_t))) || (rc = ensure_pinned(h, ln.p_cnt, 5 * sizeof(uint64_t), kRoom)))
                 return rc;
         }
         hm.mark("lanes");
@@ -1259,7 +1243,9 @@ int lx_sort_words_dev(int device, uint64_t * key[2], uint64_t * value[2], uint64
     } const restore{before == device ? -1 : before};
     if (hipSetDevice(device) != hipSuccess)
         return LX_EHIP;
-    // the digit counts: one allocation per (process, device), kept and grown -- a hipMalloc + hipFree per call synchronises the device
+    // the digit counts: one allocation per (process, device), kept and grown -- a hipMalloc + hipFree per call synchronises the device.
+    // Raw and never given back, on purpose: an owner (lx_resources.h) with static storage would call hipFree while the process
+    // exits, when the runtime may be gone already.
     static std::mutex  hist_m[64];
     static uint32_t *  hist_buf[64] = {nullptr};
     static size_t      hist_cap[64] = {0};
@@ -1359,7 +1345,7 @@ int lx_widen_and_preprocess_dev(lx_handle * h, void const * d_matches, uint64_t 
         return rc;
     if (nw)
     {
-        if ((rc = ensure_pinned(h, l2.p_win, nw * sizeof(lx::L2Window) + 16)))
+        if ((rc = ensure_pinned(h, l2.p_win, nw * sizeof(lx::L2Window) + 16, kRoom)))
             return rc;
         LX_HIP(h, hipMemcpyAsync(l2.p_win.ptr, l2.d_win.ptr, nw * sizeof(lx::L2Window), hipMemcpyDeviceToHost, h->stream));
         LX_HIP(h, hipStreamSynchronize(h->stream));

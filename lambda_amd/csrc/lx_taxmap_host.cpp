@@ -56,15 +56,17 @@ struct lx_taxmap
     lx::taxmap::TableView host_view{};
     lx::taxmap::TableView dev_view{};
     // the device's buffers (a handle was given)
-    void *       d_slots = nullptr, *d_keys = nullptr, *d_bytes = nullptr, *d_scratch = nullptr, *d_tile_cnt = nullptr, *d_tile_off = nullptr,
-         *d_block_tot = nullptr, *d_counters = nullptr;
-    void *       d_text[2]  = {nullptr, nullptr};
-    void *       d_pairs[2] = {nullptr, nullptr};
-    hipStream_t  down       = nullptr;
-    hipEvent_t   ev[2]      = {nullptr, nullptr};
-    lx::taxmap::JoinCounters * p_cnt = nullptr; // pinned: [lane]
-    uint32_t *                 p_total = nullptr; // pinned: [lane]
-    // the staging lanes (pinned with a handle)
+    DevBlock<uint64_t> d_slots;
+    DevBlock<Key>      d_keys;
+    DevBlock<uint8_t>  d_bytes, d_text[2];
+    DevBlock<Pair>     d_scratch, d_pairs[2];
+    DevBlock<uint32_t> d_tile_cnt, d_tile_off, d_block_tot;
+    DevBlock<lx::taxmap::JoinCounters>    d_counters;
+    Stream                                down;
+    Event                                 ev[2];
+    PinnedBlock<lx::taxmap::JoinCounters> p_cnt;   // [lane]
+    PinnedBlock<uint32_t>                 p_total; // [lane]
+    // the staging lanes: pinned with a handle, malloc'ed without one, so given back by hand (the destructor)
     uint8_t * lane[2] = {nullptr, nullptr};
     uint64_t  fill    = 0;
     int       cur     = 0;
@@ -87,6 +89,23 @@ struct lx_taxmap
     std::vector<uint64_t> off;
     std::vector<uint32_t> ids, present;
     lx_taxmap_result      res{};
+
+    // with a handle: its device bound and the streams through before the lanes and then the members go
+    ~lx_taxmap()
+    {
+        if (h)
+        {
+            (void)bind(h);
+            (void)hipStreamSynchronize(h->stream);
+            if (down)
+                (void)hipStreamSynchronize(down);
+        }
+        for (uint8_t * l : lane)
+            if (l && h)
+                (void)hipHostFree(l);
+            else
+                std::free(l);
+    }
 };
 
 namespace
@@ -186,25 +205,25 @@ int dispatch(lx_taxmap * tm, int L, uint64_t len)
     lx_handle * const h = tm->h;
     hipStream_t const s = h->stream;
     TM_HIP(tm, hipMemsetAsync(tm->d_counters, 0, sizeof(lx::taxmap::JoinCounters), s));
-    TM_HIP(tm, hipMemsetAsync(static_cast<uint8_t *>(tm->d_counters) + offsetof(lx::taxmap::JoinCounters, bad_off), 0xff, 4, s));
+    TM_HIP(tm, hipMemsetAsync(reinterpret_cast<uint8_t *>(tm->d_counters.raw) + offsetof(lx::taxmap::JoinCounters, bad_off), 0xff, 4, s));
     TM_HIP(tm, hipMemcpyAsync(tm->d_text[L], tm->lane[L], len, hipMemcpyHostToDevice, s));
     lx::taxmap::JoinParams p{};
     p.table     = tm->dev_view;
     p.format    = tm->format;
-    p.text      = static_cast<uint8_t const *>(tm->d_text[L]);
+    p.text      = tm->d_text[L];
     p.n         = (uint32_t)len;
-    p.scratch   = static_cast<Pair *>(tm->d_scratch);
-    p.tile_cnt  = static_cast<uint32_t *>(tm->d_tile_cnt);
-    p.tile_off  = static_cast<uint32_t *>(tm->d_tile_off);
-    p.block_tot = static_cast<uint32_t *>(tm->d_block_tot);
-    p.pairs     = static_cast<Pair *>(tm->d_pairs[L]);
-    p.counters  = static_cast<lx::taxmap::JoinCounters *>(tm->d_counters);
+    p.scratch   = tm->d_scratch;
+    p.tile_cnt  = tm->d_tile_cnt;
+    p.tile_off  = tm->d_tile_off;
+    p.block_tot = tm->d_block_tot;
+    p.pairs     = tm->d_pairs[L];
+    p.counters  = tm->d_counters;
     PhaseTimer t(h, s, 6);
     TM_HIP(tm, lx::taxmap::launch_taxmap_join(p, s));
     t.close();
     TM_HIP(tm, hipMemcpyAsync(&tm->p_cnt[L], tm->d_counters, sizeof(lx::taxmap::JoinCounters), hipMemcpyDeviceToHost, s));
     uint64_t const sb = lx::taxmap::join_scan_blocks(lx::taxmap::join_tiles(len));
-    TM_HIP(tm, hipMemcpyAsync(&tm->p_total[L], static_cast<uint32_t *>(tm->d_block_tot) + sb, 4, hipMemcpyDeviceToHost, s));
+    TM_HIP(tm, hipMemcpyAsync(&tm->p_total[L], tm->d_block_tot + sb, 4, hipMemcpyDeviceToHost, s));
     TM_HIP(tm, hipEventRecord(tm->ev[L], s));
     return LX_OK;
 }
@@ -355,29 +374,28 @@ int setup_device(lx_taxmap * tm)
     h->ev_pool_used = 0;
     uint64_t const tiles = lx::taxmap::join_tiles(tm->chunk), sb = lx::taxmap::join_scan_blocks(tiles);
     size_t const   pair_bytes = (size_t)tiles * lx::taxmap::kJoinTileCap * sizeof(Pair);
-    TM_HIP(tm, hipMalloc(&tm->d_slots, tm->slots.size() * 8));
-    TM_HIP(tm, hipMalloc(&tm->d_keys, tm->keys.size() * sizeof(Key)));
-    TM_HIP(tm, hipMalloc(&tm->d_bytes, tm->kbytes.size()));
-    TM_HIP(tm, hipMalloc(&tm->d_scratch, pair_bytes));
-    TM_HIP(tm, hipMalloc(&tm->d_tile_cnt, tiles * 4));
-    TM_HIP(tm, hipMalloc(&tm->d_tile_off, tiles * 4));
-    TM_HIP(tm, hipMalloc(&tm->d_block_tot, (sb + 1) * 4));
-    TM_HIP(tm, hipMalloc(&tm->d_counters, sizeof(lx::taxmap::JoinCounters)));
+    TM_HIP(tm, hipMalloc(tm->d_slots.out(), tm->slots.size() * 8));
+    TM_HIP(tm, hipMalloc(tm->d_keys.out(), tm->keys.size() * sizeof(Key)));
+    TM_HIP(tm, hipMalloc(tm->d_bytes.out(), tm->kbytes.size()));
+    TM_HIP(tm, hipMalloc(tm->d_scratch.out(), pair_bytes));
+    TM_HIP(tm, hipMalloc(tm->d_tile_cnt.out(), tiles * 4));
+    TM_HIP(tm, hipMalloc(tm->d_tile_off.out(), tiles * 4));
+    TM_HIP(tm, hipMalloc(tm->d_block_tot.out(), (sb + 1) * 4));
+    TM_HIP(tm, hipMalloc(tm->d_counters.out(), sizeof(lx::taxmap::JoinCounters)));
     for (int l = 0; l < 2; ++l)
     {
-        TM_HIP(tm, hipMalloc(&tm->d_text[l], tm->chunk + 16));
-        TM_HIP(tm, hipMalloc(&tm->d_pairs[l], pair_bytes));
+        TM_HIP(tm, hipMalloc(tm->d_text[l].out(), tm->chunk + 16));
+        TM_HIP(tm, hipMalloc(tm->d_pairs[l].out(), pair_bytes));
         TM_HIP(tm, hipHostMalloc(reinterpret_cast<void **>(&tm->lane[l]), tm->chunk + 16, hipHostMallocDefault));
-        TM_HIP(tm, hipEventCreateWithFlags(&tm->ev[l], hipEventDisableTiming));
+        TM_HIP(tm, hipEventCreateWithFlags(tm->ev[l].out(), hipEventDisableTiming));
     }
-    TM_HIP(tm, hipHostMalloc(reinterpret_cast<void **>(&tm->p_cnt), 2 * sizeof(lx::taxmap::JoinCounters), hipHostMallocDefault));
-    TM_HIP(tm, hipHostMalloc(reinterpret_cast<void **>(&tm->p_total), 2 * 4, hipHostMallocDefault));
-    TM_HIP(tm, hipStreamCreateWithFlags(&tm->down, hipStreamNonBlocking));
+    TM_HIP(tm, hipHostMalloc(tm->p_cnt.out(), 2 * sizeof(lx::taxmap::JoinCounters), hipHostMallocDefault));
+    TM_HIP(tm, hipHostMalloc(tm->p_total.out(), 2 * 4, hipHostMallocDefault));
+    TM_HIP(tm, hipStreamCreateWithFlags(tm->down.out(), hipStreamNonBlocking));
     TM_HIP(tm, hipMemcpy(tm->d_slots, tm->slots.data(), tm->slots.size() * 8, hipMemcpyHostToDevice));
     TM_HIP(tm, hipMemcpy(tm->d_keys, tm->keys.data(), tm->keys.size() * sizeof(Key), hipMemcpyHostToDevice));
     TM_HIP(tm, hipMemcpy(tm->d_bytes, tm->kbytes.data(), tm->kbytes.size(), hipMemcpyHostToDevice));
-    tm->dev_view = lx::taxmap::TableView{static_cast<uint64_t const *>(tm->d_slots), tm->host_view.mask, static_cast<Key const *>(tm->d_keys),
-                                         static_cast<uint8_t const *>(tm->d_bytes), tm->max_len};
+    tm->dev_view = lx::taxmap::TableView{tm->d_slots, tm->host_view.mask, tm->d_keys, tm->d_bytes, tm->max_len};
     return LX_OK;
 }
 
@@ -556,36 +574,6 @@ int lx_taxmap_finish(lx_taxmap * tm, lx_taxmap_result * out)
 
 void lx_taxmap_destroy(lx_taxmap * tm)
 {
-    if (!tm)
-        return;
-    if (tm->h)
-    {
-        (void)bind(tm->h);
-        (void)hipStreamSynchronize(tm->h->stream);
-        if (tm->down)
-        {
-            (void)hipStreamSynchronize(tm->down);
-            (void)hipStreamDestroy(tm->down);
-        }
-        for (void * p : {tm->d_slots, tm->d_keys, tm->d_bytes, tm->d_scratch, tm->d_tile_cnt, tm->d_tile_off, tm->d_block_tot, tm->d_counters,
-                         tm->d_text[0], tm->d_text[1], tm->d_pairs[0], tm->d_pairs[1]})
-            if (p)
-                (void)hipFree(p);
-        for (int l = 0; l < 2; ++l)
-        {
-            if (tm->lane[l])
-                (void)hipHostFree(tm->lane[l]);
-            if (tm->ev[l])
-                (void)hipEventDestroy(tm->ev[l]);
-        }
-        if (tm->p_cnt)
-            (void)hipHostFree(tm->p_cnt);
-        if (tm->p_total)
-            (void)hipHostFree(tm->p_total);
-    }
-    else
-        for (int l = 0; l < 2; ++l)
-            std::free(tm->lane[l]);
     delete tm;
 }
 
