@@ -64,9 +64,41 @@ constexpr int kCkptEvery = LX_CKPT_EVERY;
 #endif
 // LX_BT_COUNT (measurement only, off by default): the backtrace counts its shortcut passes and tile phases and the lanes
 // that take part in them; the launcher waits for the kernel and prints the sums of the call to stderr.
+// It also attributes the wavefront's clock to sections of the outer loop: LX_BT_MARK(section) charges the cycles since the
+// previous mark to `section` (clock64 deltas, summed per wavefront and added once at exit; wave cycles, i.e. the other
+// wavefront of the SIMD runs in them too), and it counts the iterations of the single-step walk.
 #ifdef LX_BT_COUNT
 // [0] shortcut passes, [1] lanes in them, [2] tile phases, [3] lanes in them, [4] wavefronts
 __device__ unsigned long long lx_bt_counts[5];
+enum BtSection
+{
+    kBtCtrl = 0,   // loop head: states, ballots, choice of the pass; what no other section claims
+    kBtRetire,     // retire and refill: close_ops, finish_extension, parking at a refill, queue, begin_extension
+    kBtExchange,   // pool exchange
+    kBtHopSetup,   // shortcut pass: locate, border addresses, the loads' issue
+    kBtHopBody,    // shortcut pass: take_diagonal of every hop (the wait for the loads lands here)
+    kBtTileSetup,  // tile phase: top edge, query offsets, left edge
+    kBtTileDp,     // tile phase: the DP rows
+    kBtTileScan,   // tile phase: end cell, nibble scan, leading diagonal run
+    kBtTileWalk,   // tile phase: the single-step walk
+    kBtSections
+};
+// cycles by section; then [kBtSections] iterations of the walk loop as the wavefront runs them (the longest lane's of every phase),
+// [+ 1] the same summed over lanes, [+ 2] tile phases, [+ 3] most iterations in one phase, [+ 4] cycles from kernel entry to exit
+__device__ unsigned long long lx_bt_cycles[kBtSections + 5];
+// (marks stand inside lane-divergent branches too, so the sums live in LDS and the first active lane keeps them: one wavefront per workgroup)
+#define LX_BT_MARK(sec)                                                    \
+    do                                                                     \
+    {                                                                      \
+        unsigned long long const bt_now_ = (unsigned long long)clock64();  \
+        if (lane == (uint32_t)(__ffsll(__ballot(true)) - 1))               \
+        {                                                                  \
+            bt_lds[sec] += bt_now_ - bt_lds[kBtSections];                  \
+            bt_lds[kBtSections] = bt_now_;                                 \
+        }                                                                  \
+    } while (0)
+#else
+#define LX_BT_MARK(sec) do {} while (0)
 #endif
 
 // slot layout in uint32 units: boundary quads (4 steps = 4 dwords each) [step / 4][lane] -- lane-minor: the G lanes of a
@@ -591,6 +623,9 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     constexpr int kPool  = LX_BT_POOL < kLdsWg / (16 * kRecQ) ? LX_BT_POOL : kLdsWg / (16 * kRecQ);
     static_assert(kPool >= 0 && kPool <= 64, "pool masks are 64 bits wide");
     __shared__ uint4 pool[kRecQ][kPool > 0 ? kPool : 1];
+#ifdef LX_BT_COUNT
+    unsigned long long const bt_entry = (unsigned long long)clock64();
+#endif
     for (int x = threadIdx.x; x < kAlph * kAlph; x += blockDim.x)
     {
         int const v = p.sc->mat[x];
@@ -675,18 +710,28 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     // Ckpt16Layout's index functions with the slots' spacing
     auto oct16_index = [&](uint32_t o, uint32_t g_) -> uint32_t { return o * oct_mul + g_; };
     auto ck16_index  = [&](uint32_t m_, uint32_t g_, uint32_t x_) -> uint32_t { return m_ * ck_mul + g_ * (L16::kCkDw / 4) + x_; };
-    // word (H, F) of column c of strip st's row checkpoint m; word (H, E) of strip st's boundary at step k
-    auto rowck_word = [&](uint32_t m, uint32_t st, uint32_t c) -> uint32_t
+    // Word (H, F) of column c of strip st's row checkpoint m; word (H, E) of strip st's boundary at step k.  The shortcut pass wants
+    // their H without waiting for it where it asks: the address of the word (a 16-bit code or an int16 pair), the load of the
+    // dword around it, and the H taken from that dword later on.
+    auto rowck_word_addr = [&](uint32_t m, uint32_t st, uint32_t c) -> uint8_t const *
     {
         if (c16)
-            return expand(reinterpret_cast<uint16_t const *>(rowck_of(st / G) + ck16_index(m, st % G, c / 8))[c % 8]);
-        return reinterpret_cast<uint32_t const *>(rowck_of(st / G) + rowck_quad_index<G, Lay::kCkDw>(m, st % G, c / 4))[c % 4];
+            return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint16_t const *>(rowck_of(st / G) + ck16_index(m, st % G, c / 8)) + c % 8);
+        return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint32_t const *>(rowck_of(st / G) + rowck_quad_index<G, Lay::kCkDw>(m, st % G, c / 4)) + c % 4);
     };
-    auto bnd_word_of = [&](uint32_t st, uint32_t k) -> uint32_t
+    auto bnd_word_addr = [&](uint32_t st, uint32_t k) -> uint8_t const *
     {
         if (c16)
-            return expand(reinterpret_cast<uint16_t const *>(bnd_of(st / G) + oct16_index(k / 8, st % G))[k & 7]);
-        return reinterpret_cast<uint32_t const *>(bnd_of(st / G) + bnd_quad_index<G>(k / 4, st % G))[k & 3];
+            return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint16_t const *>(bnd_of(st / G) + oct16_index(k / 8, st % G)) + (k & 7));
+        return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint32_t const *>(bnd_of(st / G) + bnd_quad_index<G>(k / 4, st % G)) + (k & 3));
+    };
+    auto dword_around = [](uint8_t const * a) -> uint32_t
+    {
+        return *reinterpret_cast<uint32_t const *>(reinterpret_cast<uintptr_t>(a) & ~(uintptr_t)3);
+    };
+    auto h_of_dword = [&](uint32_t dw, uint32_t upper_half) -> int // upper_half: bit 1 of the word's address
+    {
+        return c16 ? (int)((dw >> (upper_half ? 16 : 0)) & 0x7ffu) : (int)(int16_t)(dw & 0xffffu);
     };
     // ops are produced end -> begin into the slot [0, cap): apos = misalignment of the slot start + offset of the next byte
     auto put_byte = [&](uint32_t byte)
@@ -956,26 +1001,19 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         ncodes  = r[9].y;
         have    = true;
     };
-    // position of the r-th set bit of m (r < popcount(m)); the r lowest set bits of m
-    auto nth_bit = [](uint64_t m, uint32_t r) -> uint32_t
+    // Position of the r-th set bit of a wave-uniform set m (r < popcount(m)): lane e knows the rank of bit e in m, so one permute
+    // deals the set bits' positions to the lanes 0, 1, ... in order (the other lanes' numbers go behind them: a permutation) and a
+    // lane fetches the r-th with one more.  And the r lowest set bits of m.  Every lane must call them.
+    auto nth_bit = [&](uint64_t m, uint32_t r) -> uint32_t
     {
-        uint32_t at = 0;
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1)
-        {
-            uint32_t const lo = (uint32_t)__popcll(m & ((1ull << w) - 1ull));
-            if (r >= lo)
-            {
-                r -= lo;
-                m >>= w;
-                at += (uint32_t)w;
-            }
-        }
-        return at;
+        uint32_t const below = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        uint32_t const dest  = ((m >> lane) & 1ull) ? below : (uint32_t)__popcll(m) + (lane - below);
+        int const      nth   = __builtin_amdgcn_ds_permute((int)(dest << 2), (int)lane);
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), nth);
     };
     auto low_bits = [&](uint64_t m, uint32_t r) -> uint64_t
     {
-        return r >= (uint32_t)__popcll(m) ? m : (m & ((1ull << nth_bit(m, r)) - 1ull));
+        return __ballot(((m >> lane) & 1ull) != 0 && (uint32_t)__popcll(m & ((1ull << lane) - 1ull)) < r);
     };
 
 
@@ -1039,16 +1077,18 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         int32_t tm = tmb;
         if (!bs)
         {
+            // the pad bytes (>= k) are equal pairs above every counted byte: count them along and take them off
             int const lo = k - cnt;
 #pragma unroll
             for (int d = 0; d < 4; ++d)
             {
                 uint32_t const x   = qw[d] ^ sw[d];
                 uint32_t const nz  = (x + 0x7f7f7f7fu) & 0x80808080u;  // bit 7 of every non-zero byte (bytes < 0x80)
-                int const      b0  = max(lo - 4 * d, 0), b1 = min(k - 4 * d, 4); // bytes [b0, b1) of this dword count
-                uint32_t const msk = b1 > b0 ? ((b1 >= 4 ? 0xffffffffu : ((1u << (8 * b1)) - 1u)) & ~((1u << (8 * b0)) - 1u)) : 0u;
+                int const      b0  = min(max(lo - 4 * d, 0), 4);       // bytes [b0, 4) of this dword count
+                uint32_t const msk = b0 >= 4 ? 0u : (0xffffffffu << (8 * b0));
                 tm += __popc(~nz & 0x80808080u & msk);
             }
+            tm -= kCkptEvery - k;
         }
         left = L;
         nm += tm;
@@ -1074,30 +1114,25 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                 left_m -= take;
             }
         }
-        else if (cnt > 0) // cnt bytes 'M' below apos: at most five dwords, the lowest one may stay open in acc
+        else if (cnt > 0) // cnt bytes 'M' from apos down: the open dword, whole dwords, and a new open dword kept in acc
         {
-            uint32_t const hi = apos, lo = apos + 1 - (uint32_t)cnt, Dtop = hi & ~3u, Dlow = lo & ~3u;
-#pragma unroll
-            for (int sl = 0; sl < 5; ++sl)
+            uint32_t const top = apos & 3u, D = apos & ~3u; // bytes 0 .. top of dword D are free
+            if ((uint32_t)cnt <= top)
+                acc |= (0x4d4d4d4du >> (8 * (4 - cnt))) << (8 * (top + 1 - (uint32_t)cnt)); // the run ends inside the open dword
+            else
             {
-                uint32_t const D = Dtop - 4u * sl;
-                if (Dtop >= 4u * sl && D >= Dlow)
-                {
-                    uint32_t const b0  = lo > D ? lo - D : 0, b1 = sl == 0 ? hi - D : 3u; // bytes b0 .. b1 of dword D
-                    uint32_t const msk = (b1 >= 3 ? 0xffffffffu : ((1u << (8 * (b1 + 1))) - 1u)) & ~((1u << (8 * b0)) - 1u);
-                    uint32_t const val = (sl == 0 ? acc : 0u) | (0x4d4d4d4du & msk);
-                    if (lo <= D) // byte 0 of the dword written: the dword is complete
-                    {
-                        if (sl != 0 || D + 3 <= a0 + cap - 1)
-                            *reinterpret_cast<uint32_t *>(ops_al + D) = val;
-                        else
-                            for (uint32_t bb = 0; bb < 4 && D + bb <= a0 + cap - 1; ++bb)
-                                ops_al[D + bb] = (uint8_t)(val >> (8 * bb));
-                        acc = 0;
-                    }
-                    else
-                        acc = val;
-                }
+                uint32_t const val = acc | (0x4d4d4d4du >> (8 * (3 - top)));
+                if (D + 3 <= a0 + cap - 1)
+                    *reinterpret_cast<uint32_t *>(ops_al + D) = val;
+                else // (the slot's last dword may reach beyond it)
+                    for (uint32_t bb = 0; bb < 4 && D + bb <= a0 + cap - 1; ++bb)
+                        ops_al[D + bb] = (uint8_t)(val >> (8 * bb));
+                uint32_t const rem = (uint32_t)cnt - (top + 1), whole = rem >> 2, tail = rem & 3u; // rem <= 15
+#pragma unroll
+                for (uint32_t w = 1; w <= 3; ++w)
+                    if (w <= whole)
+                        *reinterpret_cast<uint32_t *>(ops_al + D - 4u * w) = 0x4d4d4d4du;
+                acc = tail ? 0x4d4d4d4du << (8 * (4 - tail)) : 0u;
             }
             apos -= (uint32_t)cnt;
         }
@@ -1116,6 +1151,14 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     int const tile_at = p.bt_tile_at > 0 ? p.bt_tile_at : LX_BT_TILE_AT, refill_at = p.bt_refill_at > 0 ? p.bt_refill_at : LX_BT_REFILL_AT;
 #ifdef LX_BT_COUNT
     uint32_t cnt_sc = 0, cnt_sc_lanes = 0, cnt_tile = 0, cnt_tile_lanes = 0; // (wave-uniform)
+    __shared__ unsigned long long bt_lds[kBtSections + 1]; // [kBtSections]: the clock at the previous mark
+    uint32_t walk_iters = 0, walk_lane_iters = 0, walk_max = 0; // (wave-uniform)
+    if (lane == 0)
+    {
+        for (int x = 0; x < kBtSections; ++x)
+            bt_lds[x] = 0;
+        bt_lds[kBtSections] = (unsigned long long)clock64();
+    }
 #endif
     // Parked extensions (pool, kPool entries): pool_used = entries that hold one, pool_tile = those of them that wait for a
     // tile (wave-uniform).  A parked extension is never finished.  Passes are chosen by live and parked extensions together;
@@ -1134,6 +1177,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         if (n_idle > 0 && (run_tile || n_idle >= refill_at || n_can == 0))
         {
             // ================= retire and refill
+            LX_BT_MARK(kBtCtrl);
             if (fin)
                 close_ops();
             uint64_t at = 0;
@@ -1171,9 +1215,10 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                     if (npk > 0)
                     {
                         uint32_t const rank = (uint32_t)__popcll(mo & lanes_below);
+                        uint32_t const to = nth_bit(fr, rank);
                         if (out && rank < npk)
                         {
-                            park(nth_bit(fr, rank));
+                            park(to);
                             have = false;
                         }
                         uint64_t const got = low_bits(fr, npk);
@@ -1209,6 +1254,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                 if (__ballot(have) == 0 && queue_empty)
                 {
 #ifdef LX_BT_COUNT
+                    LX_BT_MARK(kBtRetire);
                     if (lane == 0)
                     {
                         atomicAdd(&lx_bt_counts[0], (unsigned long long)cnt_sc);
@@ -1216,16 +1262,27 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                         atomicAdd(&lx_bt_counts[2], (unsigned long long)cnt_tile);
                         atomicAdd(&lx_bt_counts[3], (unsigned long long)cnt_tile_lanes);
                         atomicAdd(&lx_bt_counts[4], 1ull);
+                        for (int x = 0; x < kBtSections; ++x)
+                            atomicAdd(&lx_bt_cycles[x], bt_lds[x]);
+                        atomicAdd(&lx_bt_cycles[kBtSections], (unsigned long long)walk_iters);
+                        atomicAdd(&lx_bt_cycles[kBtSections + 1], (unsigned long long)walk_lane_iters);
+                        atomicAdd(&lx_bt_cycles[kBtSections + 2], (unsigned long long)cnt_tile);
+                        atomicMax(&lx_bt_cycles[kBtSections + 3], (unsigned long long)walk_max);
+                        atomicAdd(&lx_bt_cycles[kBtSections + 4], (unsigned long long)clock64() - bt_entry);
                     }
 #endif
                     break;
                 }
                 if (__ballot(have) == 0)
+                {
+                    LX_BT_MARK(kBtRetire);
                     continue; // (only padding slots or score-less extensions came out of the queue: take more)
+                }
             }
             p_tile   = __popcll(pool_tile);
             p_can    = __popcll(pool_used) - p_tile;
             run_tile = n_can + p_can == 0 || n_tile + p_tile >= tile_at;
+            LX_BT_MARK(kBtRetire);
         }
         if constexpr (kPool > 0)
         {
@@ -1233,6 +1290,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             // waits for the other kind of pass) takes the k-th parked extension that can take part, and parks its own in that
             // entry.  Finished lanes wait for their retirement.
             uint64_t const px = run_tile ? pool_tile : (pool_used & ~pool_tile);
+            LX_BT_MARK(kBtCtrl);
             if (px != 0)
             {
                 bool const     empty = !have, other = have && !fin && !(run_tile ? tile_need : can);
@@ -1242,9 +1300,10 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                 if (ns > 0)
                 {
                     uint32_t const rank = empty ? (uint32_t)__popcll(me & lanes_below) : (other ? ne + (uint32_t)__popcll(mo & lanes_below) : 64u);
+                    uint32_t const from = nth_bit(px, rank);
                     if (rank < ns)
                     {
-                        uint32_t const e = nth_bit(px, rank);
+                        uint32_t const e = from;
                         uint4          r[kRecQ];
 #pragma unroll
                         for (int f = 0; f < kRecQ; ++f)
@@ -1264,6 +1323,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                     n_tile    = __popcll(__ballot(tile_need));
                 }
             }
+            LX_BT_MARK(kBtExchange);
         }
 #ifdef LX_BT_COUNT
         cnt_sc += run_tile ? 0u : 1u;
@@ -1278,10 +1338,12 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             // one pass.  Where the hops end is geometry alone (the diagonal through (i, j)), so the border words and the
             // residues of all of them are requested at once -- one round trip to memory for the lot; hop h + 1 counts only if
             // hop h reached its border.
+            LX_BT_MARK(kBtCtrl);
             if (can)
             {
                 int      hk[LX_BT_HOPS];
                 uint32_t hw[LX_BT_HOPS], hqw[LX_BT_HOPS][4], hsw[LX_BT_HOPS][4];
+                uint32_t hf[LX_BT_HOPS]; // bit 0: the border cell lies inside the matrix, bit 1: bit 1 of its word's address
                 int      ci = i, cj = j;
 #pragma unroll
                 for (int h = 0; h < LX_BT_HOPS; ++h)
@@ -1298,24 +1360,35 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                     int const k  = min(min(kt, kl), ai + 1);      // 1 .. 16; never above the matrix (block 0 has virtual rows)
                     int const bi = ai - k, bj = aj - k;           // the border cell
                     hk[h] = on ? k : 0;
-                    hw[h] = 0;                                    // (beyond the matrix: H = 0)
-                    if (on && bi >= 0 && bj >= 0)
-                        hw[h] = (kl <= kt) ? bnd_word_of((uint32_t)(st - 1), (uint32_t)(bi + (st - 1) % G))
-                                           : rowck_word((uint32_t)(m - 1), (uint32_t)st, (uint32_t)(bj - j0));
+                    // (the address alone depends on the slot kind: the load stands outside that branch, so nothing waits for it here
+                    // and the words of all hops are in flight together)
+                    bool const           inside = on && bi >= 0 && bj >= 0; // (beyond the matrix: H = 0)
+                    uint8_t const *      wa     = reinterpret_cast<uint8_t const *>(slot);
+                    if (inside)
+                        wa = (kl <= kt) ? bnd_word_addr((uint32_t)(st - 1), (uint32_t)(bi + (st - 1) % G))
+                                        : rowck_word_addr((uint32_t)(m - 1), (uint32_t)st, (uint32_t)(bj - j0));
+                    hw[h] = dword_around(wa);
+                    hf[h] = (inside ? 1u : 0u) | ((uint32_t)(reinterpret_cast<uintptr_t>(wa) & 2u));
                     load_diagonal(ai, aj, k, hqw[h], hsw[h]);
                     ci -= k;
                     cj -= k;
                 }
+                LX_BT_MARK(kBtHopSetup);
 #pragma unroll
                 for (int h = 0; h < LX_BT_HOPS; ++h)
                     if (hk[h] > 0 && !blocked && !done)
-                        if (!take_diagonal(hk[h], dec(hw[h] & 0xffffu), true, hqw[h], hsw[h]))
+                        if (!take_diagonal(hk[h], (hf[h] & 1u) ? h_of_dword(hw[h], hf[h] & 2u) : 0, true, hqw[h], hsw[h]))
                             blocked = true;
+                LX_BT_MARK(kBtHopBody);
             }
             continue;
         }
 
         // ================= (2) one tile for every lane that cannot go on without it
+        LX_BT_MARK(kBtCtrl);
+#ifdef LX_BT_COUNT
+        uint32_t my_walk = 0;
+#endif
         if (tile_need)
         {
         // ---- the tile of the current cell: strip st, step block m (step k = row + strip)
@@ -1418,6 +1491,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         // (the walk starts at i, the end-cell search below stops there), virtual rows of block 0 (row < 0) see the pad
         // letter and no left neighbour, which leaves H = 0 and F at its floor.  The loop ends when no lane has rows left.
         uint32_t snext = *reinterpret_cast<unaligned_u32 const *>(s + max(r_base, 0));
+        LX_BT_MARK(kBtTileSetup);
 #pragma unroll 1
         for (int t = 0; t < kCkptEvery / 4; ++t)
         {
@@ -1490,6 +1564,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             qprev = qcur;
             qcur  = qnext;
         }
+        LX_BT_MARK(kBtTileDp);
 
         bool walk_ok = true;
         if (scan && r_base + kCkptEvery < ls)
@@ -1552,8 +1627,12 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                 (void)take_diagonal(d, 0, false, qw, sw);
             }
         }
+        LX_BT_MARK(kBtTileScan);
         while (walk_ok && !done && i >= 0 && j >= j0 && i >= r_base && n < cap && !(passed && mode == 0))
         {
+#ifdef LX_BT_COUNT
+            ++my_walk;
+#endif
             int const      kk   = i - r_base, c = j - j0;
             int const      xw   = c >> 3;
             int const      cnt  = (xw == kNibDw - 1) ? (C - 8 * xw) : 8; // cells held by this word (funnel-shifted in from the top)
@@ -1593,7 +1672,22 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             j -= (diag || !vert) ? 1 : 0;
         }
         blocked = false;
+        LX_BT_MARK(kBtTileWalk);
         } // tile_need
+#ifdef LX_BT_COUNT
+        {
+            uint32_t wmax = my_walk, wsum = my_walk;
+            for (int off = 32; off >= 1; off >>= 1)
+            {
+                wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, off));
+                wsum += (uint32_t)__shfl_xor((int)wsum, off);
+            }
+            wmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)wmax);
+            walk_iters += wmax;
+            walk_lane_iters += (uint32_t)__builtin_amdgcn_readfirstlane((int)wsum);
+            walk_max = max(walk_max, wmax);
+        }
+#endif
     }
 }
 
@@ -1719,6 +1813,24 @@ hipError_t launch_ckpt_backtrace(TraceParams const & p_in, hipStream_t stream)
         fprintf(stderr, "LX_BT_COUNT cfg %d n %llu waves %llu: shortcut passes %llu, lanes/pass %.2f; tile phases %llu, lanes/phase %.2f\n",
                 p.cfg, (unsigned long long)p.n, c[4], c[0], c[0] ? (double)c[1] / (double)c[0] : 0.0, c[2],
                 c[2] ? (double)c[3] / (double)c[2] : 0.0);
+        unsigned long long cy[kBtSections + 5] = {};
+        e = hipMemcpyFromSymbol(cy, HIP_SYMBOL(lx_bt_cycles), sizeof(cy));
+        unsigned long long const zc[kBtSections + 5] = {};
+        if (e == hipSuccess)
+            e = hipMemcpyToSymbol(HIP_SYMBOL(lx_bt_cycles), zc, sizeof(zc));
+        if (e != hipSuccess)
+            return e;
+        static char const * const names[kBtSections] = {"control", "retire/refill", "pool exchange", "hop setup", "hop body", "tile setup",
+                                                         "tile DP rows", "tile scan", "tile walk"};
+        double total = 0;
+        for (int x = 0; x < kBtSections; ++x)
+            total += (double)cy[x];
+        fprintf(stderr, "LX_BT_COUNT wave cycles by section (sum %.4g = %.1f %% of the wavefronts' %.4g from entry to exit):", total,
+                cy[kBtSections + 4] ? 100.0 * total / (double)cy[kBtSections + 4] : 0.0, (double)cy[kBtSections + 4]);
+        for (int x = 0; x < kBtSections; ++x)
+            fprintf(stderr, " %s %.4g (%.1f %%);", names[x], (double)cy[x], total > 0 ? 100.0 * (double)cy[x] / total : 0.0);
+        fprintf(stderr, "\nLX_BT_COUNT walk: %llu iterations of the wavefronts (%llu of single lanes) in %llu tile phases, at most %llu in one phase\n",
+                cy[kBtSections], cy[kBtSections + 1], cy[kBtSections + 2], cy[kBtSections + 3]);
     }
 #endif
     return hipGetLastError();
