@@ -538,6 +538,21 @@ typedef struct lx_record_stats
     uint64_t qrys_with_hit, hits_duplicate2, hits_abundant, hits_final, pairs;
 } lx_record_stats;
 uint64_t lx_postprocess_records(lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats);
+/* _writeRecord's sort / unique / sort / cut (src/search_algo.hpp:820-882) on h's device for n rows in HOST memory grouped by n_qid:
+ * uploads, runs the kernels, brings the kept rows back into m[0 .. *out_n).  Same rows, order and stats as lx_postprocess_records
+ * (rows that are not grouped: every run of equal n_qid is a query, as there).  stats may be NULL.  LX_EINVAL, before any device
+ * work: NULL h, NULL m with n > 0, NULL out_n, n >= 2^31 - 16.  lx_last_phase_ms(h, 7, ...) = device time of the kernels. */
+int lx_postprocess_records_dev(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n);
+/* lx_iterate_matches_dev followed by that step, before anything comes down: the result holds only the kept records
+ * (count, rows, ops with re-based ops_off; LX_ITERATE_NO_OPS as before), *rstats (may be NULL) what lx_postprocess_records would
+ * report for lx_iterate_matches_dev's result.  lx_iterate_result_stats() is unchanged (it counts what the extension did, not what
+ * the cut removed).  Where the call's records are made on the device and every query's records come out of one range of the
+ * list (every list but bisulfite ones, whose two strand directions are extended apart), the step runs range by range behind the
+ * records kernels and only the kept rows come down, only their columns are expanded; elsewhere (bisulfite, LX_OPT_ITERATE_RECORDS =
+ * 1, lists served without the multi-query plan) the finished result goes through lx_postprocess_records_dev and its columns are
+ * moved together on the host.  lx_last_phase_ms(h, 7, ...) = device time of the step's kernels in the call. */
+int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params,
+                               uint64_t max_matches, lx_record_stats * rstats, lx_iterate_result ** out);
 
 /* The taxonomy the reference keeps in its index (indexFile.taxonParentIDs / taxonHeights / sTaxIds): parents[t] and heights[t]
  * for taxon t < n_taxa (parent 0 = unassigned or the root), and per true subject id the taxa it is assigned to in CSR form:
@@ -757,7 +772,8 @@ char const * lx_last_kernel_name(lx_handle const * h);
 char const * lx_last_trace_kernel_name(lx_handle const * h);
 /* Device time (HIP events on the launch stream) the most recent call spent in one phase, summed over its launches:
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
- * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*). */
+ * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*),
+ * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

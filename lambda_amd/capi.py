@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = [
     "lx_iterate_matches", "lx_set_queries", "lx_set_subject_seqs", "lx_iterate_matches_dev", "lx_widen_and_preprocess_dev", "lx_reserve", "lx_sort_words_dev", "lx_trim_result_cache",
     "lx_iterate_result_count", "lx_iterate_result_matches", "lx_iterate_result_ops", "lx_iterate_result_stats",
     "lx_iterate_result_free", "lx_karlin_params", "lx_length_adjustment", "lx_evalue", "lx_bitscore",
-    "lx_widen_and_preprocess", "lx_postprocess_records", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
+    "lx_widen_and_preprocess", "lx_postprocess_records", "lx_postprocess_records_dev", "lx_iterate_matches_dev_top", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
     "lx_write_records_bgzf", "lx_gunzip", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
@@ -234,6 +234,8 @@ def load():
     lib.lx_iterate_result_free.restype = None
     lib.lx_postprocess_records.argtypes = [vp, u64, u64, C.POINTER(RecordStats)]
     lib.lx_postprocess_records.restype = u64
+    lib.lx_postprocess_records_dev.argtypes = [vp, vp, u64, u64, C.POINTER(RecordStats), C.POINTER(u64)]
+    lib.lx_iterate_matches_dev_top.argtypes = [vp, i32, vp, u64, C.POINTER(SearchParams), u64, C.POINTER(RecordStats), C.POINTER(vp)]
     lib.lx_write_records.argtypes = [C.c_char_p, i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp]
     lib.lx_write_records_ex.argtypes = [C.c_char_p, i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions)]
     lib.lx_write_footer.argtypes = [C.c_char_p, i32, u64]
@@ -291,6 +293,15 @@ def postprocess_records(bms: np.ndarray, max_matches: int = 25):
     st = RecordStats()
     n = load().lx_postprocess_records(_ptr(m), len(m), max_matches, C.byref(st))
     return m[: int(n)], st
+
+
+def postprocess_records_dev(handle, bms: np.ndarray, max_matches: int = 25):
+    """lx_postprocess_records_dev: postprocess_records with the sort / dedupe / top-N as kernels on `handle`'s device; (rows, stats)."""
+    m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE).copy()
+    st = RecordStats()
+    n = C.c_uint64(0)
+    handle._check(handle.lib.lx_postprocess_records_dev(handle.h, _ptr(m) if len(m) else None, len(m), max_matches, C.byref(st), C.byref(n)))
+    return m[: int(n.value)], st
 
 
 class OutputOptions(C.Structure):
@@ -787,6 +798,14 @@ class Handle:
         res = C.c_void_p()
         self._check(self.lib.lx_iterate_matches_dev(self.h, slot, d_matches.data_ptr() if n else None, n, C.byref(params), C.byref(res)))
         return self._take_iterate_result(res)
+
+    def iterate_matches_dev_top(self, d_matches, n: int, params: "SearchParams", max_matches: int = 25, slot: int = 0):
+        """lx_iterate_matches_dev_top: iterate_matches_dev with _writeRecord's sort / dedupe / top-N on the device before the result
+        comes down; (records, ops, stats, record stats)."""
+        res = C.c_void_p()
+        rst = RecordStats()
+        self._check(self.lib.lx_iterate_matches_dev_top(self.h, slot, d_matches.data_ptr() if n else None, n, C.byref(params), max_matches, C.byref(rst), C.byref(res)))
+        return (*self._take_iterate_result(res), rst)
 
     def plan_free_packing_dev(self, d_ext, n: int, n_qseq: int, strip_cols: int = 19, cuts=None):
         """lx_plan_free_packing_dev: (plan [nwf, 16], wf_pan [nwf], wf_maxs [nwf], report [16]) for n lx_extension records in a device tensor."""

@@ -2,7 +2,17 @@
 // section 8f rows N2/N3): plumbing for BASELINE.json configs[0], not a port of the reference's driver.
 //
 //   lambda3 searchp -q queries.fasta -d db.fasta -o out.m8 [-e 1e-2] [-n 25] [--seed-length 10] [--seed-offset 5]
-//                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--seeding gpu|host]
+//                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--seeding gpu|host] [--records gpu|host|auto]
+//
+// --records: where _writeRecord's sort / unique / sort / cut to -n (src/search_algo.hpp:820-882) runs.  host: lx_postprocess_records
+// once, over the records of all workers (what this front end always did).  gpu: a worker's Level-2 call on a DEVICE match list
+// (the passes whose seeding ran on its GPU) goes through lx_iterate_matches_dev_top, so that only the records that stay come down;
+// that is legitimate because every record of a query comes out of ONE call -- the workers own disjoint ranges of reads, the exact
+// pass and the half-exact pass work on disjoint queries, a bisulfite call holds both strand directions (and runs the step over its
+// finished result) --; a pass whose matches stand in host memory (host seeding, reads the device declined, LAMBDA3_HOST_LIST) keeps
+// the host step, applied to that pass's records alone; the statistics of the parts are summed; -n 0 keeps the host step (the second
+// pass searches the queries WITHOUT records).  auto: see DESIGN.md ("_writeRecord on the device") for the measurement behind it.
+// LCA and the writers stay on the host, fed with the kept records; the output is byte-identical either way.
 //
 // Inputs (-q, -d of search* and mkindex*) are FASTA or FASTQ, plain or gzip-compressed, as the reference's (fa, fq, fasta, fastq,
 // fna, faa, each optionally .gz: src/search_options.hpp:157-167, src/mkindex_options.hpp:96-105); the format comes from the bytes
@@ -368,6 +378,7 @@ struct Options
     std::string table       = "auto"; // --table gpu | host | auto: where the word table is made (auto: search* on the GPU, mkindex* on the host)
     std::string seeding     = "gpu";  // --seeding gpu | host: where search() runs (host/lx_seeding_gpu.hpp -- one lane per read, reads the
                                       // device declines go to the host --, host/lx_seeding.hpp on the -t threads)
+    std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
     int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     // mkindex* (src/mkindex_options.hpp:96-262): -d the database (FASTA), -i the index file to write
     std::string index;                // -i of mkindex* (default: DATABASE.lba, :132, :249-250)
@@ -576,6 +587,12 @@ Options parse(int argc, char ** argv)
             o.table = val();
             if (o.table != "gpu" && o.table != "host" && o.table != "auto")
                 throw std::runtime_error("--table takes gpu, host or auto");
+        }
+        else if (a == "--records")
+        {
+            o.records = val();
+            if (o.records != "gpu" && o.records != "host" && o.records != "auto")
+                throw std::runtime_error("--records takes gpu, host or auto");
         }
         else if (a == "--seeding")
         {
@@ -1366,13 +1383,16 @@ int main(int argc, char ** argv)
             lx_iterate_stats            ist{};
             lambda_amd::SeedingStats    sst{};
             size_t                      nPromising = 0;
-            double                      msSeed = 0, msExtend = 0;
+            double                      msSeed = 0, msExtend = 0, msRecords = 0;
+            lx_record_stats             rst{}; // --records gpu: _writeRecord's statistics of this worker's passes
             bool                        gpuSeeding = false; // the seeding stage of this worker ran on its device
             size_t                      nDeclined = 0, nPassesOnHost = 0; // reads the GPU seeding stage left to the host; passes whose match buffer was full
             std::string                 error;
         };
         std::vector<Part> parts(nWorkers);
         uint64_t const    nReads = qs.ids.size();
+        // --records (the header comment): auto = host -- the measured rule of DESIGN.md ("_writeRecord on the device")
+        bool const recordsOnGpu = opt.records == "gpu" && opt.maxMatches > 0;
         auto worker = [&](size_t w)
         {
             Part & pt = parts[w];
@@ -1470,15 +1490,36 @@ int main(int argc, char ** argv)
                         return;
                     lx_iterate_result * res = nullptr;
                     auto const          tExt = std::chrono::steady_clock::now();
-                    if (onDevice) // the Level-2 driver on the list where the seeding kernel left it (include/lambda_ext.h)
+                    lx_record_stats passRst{};
+                    bool            cutDone = false;
+                    if (onDevice && recordsOnGpu) // ... with _writeRecord's cut before the records come down
+                    {
+                        eng.check(lx_iterate_matches_dev_top(eng.raw(), 0, gpuSeeder->devMatches(), onDevice, &sp, opt.maxMatches, &passRst, &res));
+                        float msTop = 0;
+                        if (lx_last_phase_ms(eng.raw(), 7, &msTop, nullptr) == LX_OK)
+                            pt.msRecords += msTop;
+                        cutDone = true;
+                    }
+                    else if (onDevice) // the Level-2 driver on the list where the seeding kernel left it (include/lambda_ext.h)
                         eng.check(lx_iterate_matches_dev(eng.raw(), 0, gpuSeeder->devMatches(), onDevice, &sp, &res));
                     else
                         eng.check(lx_iterate_matches(eng.raw(), 0, qs.res.data(), qs.res.size(), qs.off.data(), qs.len.data(), qs.off.size(),
                                                      qs.orig_len.data(), nullptr, 0, db.off.data(), db.len.data(), db.off.size(), matches.data(),
                                                      matches.size(), &sp, &res));
                     pt.msExtend += msSince(tExt);
-                    uint64_t const         n  = lx_iterate_result_count(res);
+                    uint64_t               n  = lx_iterate_result_count(res);
                     lx_blast_match const * bm = lx_iterate_result_matches(res);
+                    std::vector<lx_blast_match> cutRows;
+                    if (recordsOnGpu && !cutDone) // (a list in host memory: the host step, on this pass's records -- all a query has)
+                    {
+                        auto const tRec = std::chrono::steady_clock::now();
+                        cutRows.assign(bm, bm + n);
+                        n  = lx_postprocess_records(cutRows.data(), n, opt.maxMatches, &passRst);
+                        bm = cutRows.data();
+                        pt.msRecords += msSince(tRec);
+                    }
+                    pt.rst.qrys_with_hit += passRst.qrys_with_hit, pt.rst.hits_duplicate2 += passRst.hits_duplicate2, pt.rst.hits_abundant += passRst.hits_abundant;
+                    pt.rst.hits_final += passRst.hits_final, pt.rst.pairs += passRst.pairs;
                     uint64_t const         ob = pt.ops.size();
                     uint64_t opsEnd = 0; // (the records are ordered by query, their ops as the passes produced them: bisulfite runs two)
                     for (uint64_t k = 0; k < n && wantOps; ++k)
@@ -1539,7 +1580,9 @@ int main(int argc, char ** argv)
         lx_iterate_stats            ist{};
         lambda_amd::SeedingStats    sst{};
         size_t                      nPromising = 0;
-        double                      msSeedMax = 0, msExtendMax = 0;
+        double                      msSeedMax = 0, msExtendMax = 0, msRecords = 0;
+        lx_record_stats             rst{};
+        uint64_t                    nHspParts = 0; // --records gpu: the records before the cut
         size_t                      nDeclined = 0, nPassesOnHost = 0;
         bool                        anyGpuSeeding = false;
         for (Part & pt : parts)
@@ -1561,13 +1604,22 @@ int main(int argc, char ** argv)
             anyGpuSeeding = anyGpuSeeding || pt.gpuSeeding;
             msSeedMax   = std::max(msSeedMax, pt.msSeed);
             msExtendMax = std::max(msExtendMax, pt.msExtend);
+            msRecords   = std::max(msRecords, pt.msRecords);
+            rst.qrys_with_hit += pt.rst.qrys_with_hit, rst.hits_duplicate2 += pt.rst.hits_duplicate2, rst.hits_abundant += pt.rst.hits_abundant;
+            rst.hits_final += pt.rst.hits_final, rst.pairs += pt.rst.pairs;
         }
-        uint64_t const nHsp   = bms.size();
+        nHspParts = rst.hits_final + rst.hits_duplicate2 + rst.hits_abundant;
+        uint64_t const nHsp   = recordsOnGpu ? nHspParts : bms.size();
         size_t const   nSeeds = (size_t)sst.hitsAfterSeeding;
 
         // ---- _writeRecord + writer
-        lx_record_stats rst{};
-        uint64_t const  nOut = lx_postprocess_records(bms.data(), bms.size(), opt.maxMatches, &rst);
+        uint64_t nOut = bms.size(); // (--records gpu: every pass's records are cut already)
+        if (!recordsOnGpu)
+        {
+            auto const tRec = std::chrono::steady_clock::now();
+            nOut      = lx_postprocess_records(bms.data(), bms.size(), opt.maxMatches, &rst);
+            msRecords = msSince(tRec);
+        }
         std::vector<char const *> qid, sid;
         for (auto const & s : qs.ids)
             qid.push_back(s.c_str());
@@ -1663,9 +1715,9 @@ int main(int argc, char ** argv)
         // where the wall clock went (the reference prints its own at verbosity 2, src/search.cpp): per worker the slowest counts
         std::fprintf(stderr,
                      "lambda3 times [ms]: read %.0f%s, reduce + word table %s%.0f, search %.0f (seeding on the %s %.0f [%zu read(s) and %zu launch(es) left to "
-                     "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records + output %.0f%s, total %.0f\n",
+                     "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records %.1f (%s), records + output %.0f%s, total %.0f\n",
                      msRead, gunzipNote.c_str(), fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
-                     nPassesOnHost, msExtendMax, msSince(tOut) - msCompress,
+                     nPassesOnHost, msExtendMax, msRecords, recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msSince(tOut) - msCompress,
                      (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str() : "", msSince(tStart));
         return 0;
     }

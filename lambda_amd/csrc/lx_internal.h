@@ -222,6 +222,10 @@ struct lx_handle
         std::vector<uint64_t> cut_wf;                 // the ranges' first wavefronts
         double                exp_lambda = 0;         // the scheme d_exp was made for
         uint32_t              exp_n      = 0;
+        // _writeRecord's sort / unique / sort / cut on the device (lx_toprec.hip): the rows that stay and their code words, the step's
+        // scratch, its counters (per range of a Level-2 call) and the rows of lx_postprocess_records_dev on their way up and down
+        DevBuf                d_toprows, d_topcodes, d_topwork, d_topcnt, d_topin;
+        Pinned                p_topcnt;
     } l2;
     // lx_bgzf_compress (lx_bgzf_host.cpp): one chunk's device buffers, its input in two pinned lanes, its members on the way out
     struct Bgzf

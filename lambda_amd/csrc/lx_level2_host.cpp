@@ -11,6 +11,7 @@
 
 #include "lx_internal.h"
 #include "lx_level2.h"
+#include "lx_toprec.h"
 
 #include "host/lx_iterate_common.hpp"
 
@@ -259,6 +260,15 @@ constexpr size_t kPlanProbe = 128;                                 // l2.p_plan:
 constexpr size_t kPlanProbes = lx::kFpMaxRanges;                                    // cuts a part's ranges may have: 512 probe windows each
 constexpr size_t kPlanHead   = kPlanProbe + kPlanProbes * 512 * sizeof(lx::L2Window); // ... in front of the per-wavefront arrays
 
+// what lx_iterate_matches_dev_top asks of a call: the cut, and where the parts' lx_record_stats add up (done: the step ran on
+// the device for every record of the result; else the caller runs it on the finished result)
+struct TopRequest
+{
+    uint64_t        max_matches = 0;
+    lx_record_stats stats{};
+    bool            done = false;
+};
+
 struct RecordsJob
 {
     struct Range
@@ -279,6 +289,9 @@ struct RecordsJob
     bool                     want_ops  = true;
     std::vector<double>      pre_host; // the e-value factors per distinct length, until their upload is through
     bool                     use_rank = false; // the survivors are sorted by their windows' ranks (l2.d_rank: rec_launch_rank over the part)
+    // lx_iterate_matches_dev_top: every range's rows go through _writeRecord's sort / unique / sort / cut (lx_toprec.hip) behind its
+    // records kernels; what stays -- rows and code words in l2.d_toprows / d_topcodes -- is what comes down
+    TopRequest *             top = nullptr;
 
     RecordsJob(lx_handle * h_, lx_search_params const * p_, lx_iterate_result * r_, HostMarks & hm_, uint64_t part_lo_, uint64_t n_part_)
         : h(h_), params(p_), res(r_), hm(hm_), part_lo(part_lo_), n_part(n_part_)
@@ -357,6 +370,13 @@ struct RecordsJob
             return rc;
         }
         LX_HIP(h, hipMemsetAsync(l2.d_reccnt.ptr, 0, nr * lx::kRecCounters * sizeof(uint64_t), st));
+        if (top && ((rc = ensure(h, l2.d_toprows, (n_part + 16) * sizeof(lx_blast_match) + 16)) || (rc = ensure(h, l2.d_topcodes, 3 * (n_part + 16) * sizeof(uint64_t) + 16)) ||
+                    (rc = ensure(h, l2.d_topwork, lx::toprec_work_bytes(max_win))) || (rc = ensure(h, l2.d_topcnt, nr * lx::kTopCounters * sizeof(uint64_t))) ||
+                    (rc = ensure_pinned(h, l2.p_topcnt, nr * lx::kTopCounters * sizeof(uint64_t), kRoom))))
+        {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
         base.q_len      = static_cast<uint32_t const *>(l2.d_qlen.ptr);
         base.q_evidx    = static_cast<uint32_t const *>(l2.d_qevidx.ptr);
         base.q_frames   = (uint32_t)qFrames;
@@ -413,6 +433,24 @@ struct RecordsJob
                                  static_cast<uint32_t *>(l2.d_tilekeep.ptr),
                                  static_cast<uint64_t *>(l2.d_tileops.ptr), st));
         LX_HIP(h, hipMemcpyAsync(static_cast<uint64_t *>(l2.p_reccnt.ptr) + r * lx::kRecCounters, p.counters, lx::kRecCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (top)
+        {
+            // the range's records stand in p.rec, counters[kRecKept] of them: sorted, made unique, sorted and cut where they are
+            lx::TopParams tp{};
+            tp.in          = p.rec;
+            tp.out         = static_cast<lx::BlastMatchDev *>(l2.d_toprows.ptr) + rg.lo;
+            tp.codes_in    = want_ops ? p.rec_codes : nullptr;
+            tp.codes_out   = want_ops ? static_cast<uint64_t *>(l2.d_topcodes.ptr) + 3 * rg.lo : nullptr;
+            tp.n_ptr       = p.counters + lx::kRecKept;
+            tp.n_cap       = p.n_win;
+            tp.max_matches = top->max_matches;
+            tp.rebase_ops  = want_ops ? 1 : 0;
+            tp.counters    = static_cast<uint64_t *>(l2.d_topcnt.ptr) + r * lx::kTopCounters;
+            PhaseTimer pt(h, st, 7);
+            LX_HIP(h, lx::toprec_launch(tp, l2.d_topwork.ptr, st));
+            pt.close();
+            LX_HIP(h, hipMemcpyAsync(static_cast<uint64_t *>(l2.p_topcnt.ptr) + r * lx::kTopCounters, tp.counters, lx::kTopCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        }
         return LX_OK;
     }
 
@@ -437,7 +475,8 @@ struct RecordsJob
             return fail(h, LX_EOVERFLOW, "an extension of the list could not be traced");
         if (cnt[lx::kRecErr] & 2)
             return fail(h, LX_ESTATE, "a survivor names a window outside its range of the list");
-        uint64_t const ns = cnt[lx::kRecSurvivors], nkeep = cnt[lx::kRecKept], nops = cnt[lx::kRecOps];
+        uint64_t const ns = cnt[lx::kRecSurvivors], nrec = cnt[lx::kRecKept];
+        uint64_t       nkeep = nrec, nops = cnt[lx::kRecOps]; // what comes down
         if (ns > rg.hi - rg.lo || nkeep > ns)
             return fail(h, LX_ESTATE, "the records kernels report %llu records of %llu survivors of %llu windows", (unsigned long long)nkeep, (unsigned long long)ns,
                         (unsigned long long)(rg.hi - rg.lo));
@@ -446,7 +485,18 @@ struct RecordsJob
         if (ns == 0)
             return LX_OK;
         res->stats.num_ext_ali += ns; // :1287
-        res->stats.failed_identity += ns - nkeep;
+        res->stats.failed_identity += ns - nrec;
+        if (top && nrec)
+        {
+            uint64_t const * const tc = static_cast<uint64_t const *>(l2.p_topcnt.ptr) + r * lx::kTopCounters;
+            if (tc[lx::kTopFinal] + tc[lx::kTopDuplicate] + tc[lx::kTopAbundant] != nrec || (want_ops && tc[lx::kTopOps] > nops))
+                return fail(h, LX_ESTATE, "the cut's kernels account for %llu of %llu records", (unsigned long long)(tc[lx::kTopFinal] + tc[lx::kTopDuplicate] + tc[lx::kTopAbundant]),
+                            (unsigned long long)nrec);
+            top->stats.qrys_with_hit += tc[lx::kTopQueries], top->stats.hits_duplicate2 += tc[lx::kTopDuplicate], top->stats.hits_abundant += tc[lx::kTopAbundant];
+            top->stats.hits_final += tc[lx::kTopFinal], top->stats.pairs += tc[lx::kTopPairs];
+            nkeep = tc[lx::kTopFinal];
+            nops  = want_ops ? tc[lx::kTopOps] : nops;
+        }
         uint64_t const rec0 = res->matches.size(), ops0 = res->ops.size();
         if (!res->matches.resize(rec0 + nkeep) || !res->ops.resize(ops0 + nops))
             return fail(h, LX_ENOMEM, "out of host memory for the result records");
@@ -456,7 +506,7 @@ struct RecordsJob
         // the result's, then -- 24 bytes per record -- where the records' codes begin and their columns go: the host threads expand the
         // columns from the run-length codes WHILE the rows themselves come down (1.8 ms of copy beside 2.0 ms of expansion on a million reads)
         hipStream_t const      cs = h->stream3;
-        lx::BlastMatchDev *    d_rows = static_cast<lx::BlastMatchDev *>(l2.d_rec.ptr) + rg.lo;
+        lx::BlastMatchDev *    d_rows = static_cast<lx::BlastMatchDev *>(top ? l2.d_toprows.ptr : l2.d_rec.ptr) + rg.lo;
         std::vector<uint64_t> & codes_at = l2.rec_codes;
         std::thread             expander;
         if (want_ops)
@@ -464,7 +514,7 @@ struct RecordsJob
             if (ops0)
                 LX_HIP(h, lx::rec_launch_add_ops_base(d_rows, nkeep, ops0, cs));
             codes_at.resize(3 * nkeep);
-            LX_HIP(h, hipMemcpyAsync(codes_at.data(), static_cast<uint64_t const *>(l2.d_reccodes.ptr) + 3 * rg.lo, 3 * nkeep * sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
+            LX_HIP(h, hipMemcpyAsync(codes_at.data(), static_cast<uint64_t const *>(top ? l2.d_topcodes.ptr : l2.d_reccodes.ptr) + 3 * rg.lo, 3 * nkeep * sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
             LX_HIP(h, hipStreamSynchronize(cs));
             uint8_t const * const codes = h->ext_bytes.data() + rg.code_base;
             uint8_t * const       ops   = res->ops.data() + ops0;
@@ -513,8 +563,11 @@ struct RecordsJob
 };
 
 // The list work and the extension for matches that stand on the device as sort words already.  Appends to *res.
-static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_search_params const * params, lx_iterate_result * res, bool windows_to_host)
+static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_search_params const * params, lx_iterate_result * res, bool windows_to_host,
+                              TopRequest * top_req = nullptr)
 {
+    // a bisulfite list's two strand directions are extended apart and a query has records in both: its cut needs the finished result
+    TopRequest * const top = top_req && !params->bisulfite ? top_req : nullptr;
     using namespace lambda_amd;
     auto &            l2 = h->l2;
     hipStream_t const st = h->stream;
@@ -793,6 +846,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
             ri.keep_on_device = records_on_device;
             ri.want_codes     = !(params->flags & LX_ITERATE_NO_OPS);
             RecordsJob                  job(h, params, res, hm, pt.lo, n);
+            job.top = top;
             ResidentInput::ChunkRecords cr;
             if (records_on_device)
             {
@@ -820,6 +874,8 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
                     return fail(h, LX_ESTATE, "the pipeline finished with %llu of %llu ranges' records made", (unsigned long long)job.next_flush,
                                 (unsigned long long)job.ranges.size());
                 hm.mark("extension + records (range by range)");
+                if (top)
+                    top->done = true;
                 continue;
             }
         }
@@ -861,6 +917,7 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
         {
             // the survivors of all chunks stand in l2.d_surv_*: one range, its kernels now
             RecordsJob whole(h, params, res, hm, pt.lo, n);
+            whole.top = top;
             if ((rc = whole.prepare(cutOffFor, {RecordsJob::Range{0, n}}, l2.surv_total)) ||
                 (rc = whole.enqueue(0, l2.d_surv_hsp.ptr, l2.d_surv_src.ptr, nullptr, l2.d_surv_codes.ptr, l2.surv_total)))
                 return rc;
@@ -869,6 +926,8 @@ static int level2_sorted_tail(lx_handle * h, int slot, uint64_t n_matches, lx_se
             if ((rc = whole.collect(0, 0, false)))
                 return rc;
             hm.mark("rows + columns");
+            if (top)
+                top->done = true;
             continue;
         }
         // (else the pipeline served the list without the multi-query plan -- a handful of windows, LX_OPT_MQ_SWEEP = 0 -- and its survivors
@@ -1025,7 +1084,7 @@ int lxi::iterate_host_list_on_device(lx_handle * h, int slot, uint8_t const * q_
 
 extern "C" {
 
-int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, lx_iterate_result ** out)
+static int iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, TopRequest * top, lx_iterate_result ** out)
 {
     if (!h || !out || !params)
         return LX_EINVAL;
@@ -1060,13 +1119,130 @@ int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint
         return LX_OK;
     }
     if ((rc = level2_keys(h, d_matches, n_matches, params->bisulfite != 0)) == LX_OK)
-        rc = level2_sorted_tail(h, slot, n_matches, params, res, false);
+        rc = level2_sorted_tail(h, slot, n_matches, params, res, false, top);
     if (rc != LX_OK)
     {
         delete res;
         return rc;
     }
     *out = res;
+    return LX_OK;
+}
+
+// _writeRecord's sort / unique / sort / cut for rows in host memory: up, the kernels of lx_toprec.hip, the rows that stay down
+static int toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n)
+{
+    auto &            l2 = h->l2;
+    hipStream_t const st = h->stream;
+    int               rc;
+    lx_record_stats   rs{};
+    *out_n = 0;
+    if (n)
+    {
+        if ((rc = ensure(h, l2.d_topin, n * sizeof(lx_blast_match) + 16)) || (rc = ensure(h, l2.d_toprows, n * sizeof(lx_blast_match) + 16)) ||
+            (rc = ensure(h, l2.d_topwork, lx::toprec_work_bytes(n))) || (rc = ensure(h, l2.d_topcnt, lx::kTopCounters * sizeof(uint64_t))))
+            return rc;
+        LX_HIP(h, hipMemcpyAsync(l2.d_topin.ptr, m, n * sizeof(lx_blast_match), hipMemcpyHostToDevice, st));
+        lx::TopParams tp{};
+        tp.in          = static_cast<lx::BlastMatchDev const *>(l2.d_topin.ptr);
+        tp.out         = static_cast<lx::BlastMatchDev *>(l2.d_toprows.ptr);
+        tp.n_cap       = n;
+        tp.max_matches = max_matches;
+        tp.counters    = static_cast<uint64_t *>(l2.d_topcnt.ptr);
+        PhaseTimer pt(h, st, 7);
+        LX_HIP(h, lx::toprec_launch(tp, l2.d_topwork.ptr, st));
+        pt.close();
+        uint64_t cnt[lx::kTopCounters];
+        LX_HIP(h, hipMemcpyAsync(cnt, tp.counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        LX_HIP(h, hipStreamSynchronize(st));
+        if (cnt[lx::kTopFinal] + cnt[lx::kTopDuplicate] + cnt[lx::kTopAbundant] != n)
+            return fail(h, LX_ESTATE, "the cut's kernels account for %llu of %llu records", (unsigned long long)(cnt[lx::kTopFinal] + cnt[lx::kTopDuplicate] + cnt[lx::kTopAbundant]),
+                        (unsigned long long)n);
+        if (cnt[lx::kTopFinal])
+        {
+            LX_HIP(h, hipMemcpyAsync(m, tp.out, cnt[lx::kTopFinal] * sizeof(lx_blast_match), hipMemcpyDeviceToHost, st));
+            LX_HIP(h, hipStreamSynchronize(st));
+        }
+        rs     = lx_record_stats{cnt[lx::kTopQueries], cnt[lx::kTopDuplicate], cnt[lx::kTopAbundant], cnt[lx::kTopFinal], cnt[lx::kTopPairs]};
+        *out_n = cnt[lx::kTopFinal];
+    }
+    if (stats)
+        *stats = rs;
+    return LX_OK;
+}
+
+int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, lx_iterate_result ** out)
+{
+    return iterate_matches_dev(h, slot, d_matches, n_matches, params, nullptr, out);
+}
+
+int lx_postprocess_records_dev(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n)
+{
+    if (!h || !out_n || (!m && n))
+        return LX_EINVAL;
+    *out_n = 0;
+    if (n >= 0x7ffffff0ull)
+        return fail(h, LX_EINVAL, "lx_postprocess_records_dev: at most 2^31 - 16 rows per call");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    h->phase_ev.clear();
+    return toprec_host_rows(h, m, n, max_matches, stats, out_n);
+}
+
+int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, uint64_t max_matches,
+                               lx_record_stats * rstats, lx_iterate_result ** out)
+{
+    if (!h || !out || !params)
+        return LX_EINVAL;
+    TopRequest top;
+    top.max_matches = max_matches;
+    int rc = iterate_matches_dev(h, slot, d_matches, n_matches, params, &top, out);
+    if (rc != LX_OK)
+        return rc;
+    if (!top.done)
+    {
+        // the finished result (a query's records came out of more than one part of the call, or were made on the host): the same
+        // kernels over its rows, then the columns of the rows that stay moved together
+        lx_iterate_result * const res = *out;
+        uint64_t                  kept = 0;
+        if (res->matches.size() >= 0x7ffffff0ull)
+            rc = fail(h, LX_EINVAL, "lx_iterate_matches_dev_top: at most 2^31 - 16 records per call");
+        else
+            rc = toprec_host_rows(h, res->matches.data(), res->matches.size(), max_matches, &top.stats, &kept);
+        if (rc == LX_OK && kept && res->ops.size())
+        {
+            lambda_amd::RawVec<uint8_t> packed;
+            uint64_t                    total = 0;
+            for (uint64_t k = 0; k < kept; ++k)
+                total += res->matches[k].n_ops;
+            if (!packed.resize(total))
+                rc = fail(h, LX_ENOMEM, "out of host memory for the result records");
+            else
+            {
+                uint64_t at = 0;
+                for (uint64_t k = 0; k < kept; ++k)
+                {
+                    lx_blast_match & r = res->matches[k];
+                    std::memcpy(packed.data() + at, res->ops.data() + r.ops_off, r.n_ops);
+                    r.ops_off = at;
+                    at += r.n_ops;
+                }
+                std::swap(res->ops.p, packed.p), std::swap(res->ops.n, packed.n), std::swap(res->ops.cap, packed.cap);
+            }
+        }
+        else if (rc == LX_OK && !kept)
+            (void)res->ops.resize(0);
+        if (rc != LX_OK)
+        {
+            delete res;
+            *out = nullptr;
+            return rc;
+        }
+        (void)res->matches.resize(kept);
+    }
+    if (rstats)
+        *rstats = top.stats;
     return LX_OK;
 }
 
