@@ -504,7 +504,7 @@ int      lx_plan_free_packing_dev(lx_handle * h, void const * d_ext, uint64_t n,
                                   uint32_t * out_plan, uint32_t * out_pan, uint32_t * out_maxs, uint32_t * out_report);
 /* The library's own radix sort (least significant digit first, 8 bits per pass, only the digits set in key_bits; stable) for n (key, value)
  * word pairs in device memory: key[0] / value[0] hold the input, key[1] / value[1] are scratch of the same size; *sorted_in says which of
- * the two holds the sorted words afterwards.  Synchronises `stream`; the caller's current device is left as it was.  n < 2^31.  (The stand-alone front end sorts its word table with it;
+ * the two holds the sorted words afterwards.  Synchronises `stream`; the caller's current device is left as it was.  n < 2^31.  (lx_index_build sorts its word table with it;
  * the Level-2 driver sorts matches and survivors with the same kernels.) */
 int lx_sort_words_dev(int device, uint64_t * key[2], uint64_t * value[2], uint64_t n, uint64_t key_bits, void * stream, int * sorted_in);
 /* Ahead of a handle's first lx_iterate_matches_dev (or large lx_iterate_matches) call: allocates -- and, on the host side, touches -- the
@@ -760,6 +760,99 @@ typedef struct lx_taxonomy_info
 int  lx_taxonomy_get(lx_taxonomy const * t, lx_taxonomy_info * out);
 void lx_taxonomy_free(lx_taxonomy * t);
 
+/* ---- Level 3: the word index and search() (row N3: seeding) ------------------------------------------------ */
+/* What the reference's FM-index answers for search() (src/search_algo.hpp:611-762) -- how often does this reduced word occur, and
+ * where -- is answered here by a sorted table of packed words over the reduced, frame-expanded subjects: per subject position the key
+ * of its next key_len reduced letters (base alph + 1; the extra digit pads sequence ends), entries in (key, sequence, position)
+ * order, and a prefix table (n_prefix = (alph + 1)^prefix_len + 1 entries: where the words with every prefix of prefix_len letters
+ * begin).  key_len is the largest with (alph + 1)^key_len < 2^63: 18 for ten letters, 27 for four.  The caller reduces: s_red holds
+ * letters 0 .. alph - 1 (Li-10, Murphy-10, dna4, the bisulfite pair -- src/mkindex_options.hpp:182-185), sequence i at
+ * s_red[s_off[i] .. s_off[i] + s_len[i]).  The index keeps its own copy of s_red / s_off / s_len. */
+typedef struct lx_index lx_index;
+typedef struct lx_index_info
+{
+    uint64_t n_entries, n_prefix;
+    int32_t  alph, key_len, prefix_len, built_on_device;
+} lx_index_info;
+typedef struct lx_index_entry /* one row of the table */
+{
+    uint64_t key;
+    uint32_t seq, pos;
+} lx_index_entry;
+
+/* The table the reference's mkindex step would put into its index (src/mkindex_algo.hpp generateIndexAndDump; the FM-index's place).
+ * h != NULL: keys, the library's radix sort, entries and prefix table as kernels on h's device and stream (lx_last_phase_ms phase 8),
+ * and the table and the reduced subjects stay resident there for lx_seed_queries on h.  That needs fewer than 2^31 words in all and
+ * fewer than 2^32 - 1 sequences: beyond, LX_EINVAL with a text (LX_ENOMEM: the device has no room for the build) -- build with h ==
+ * NULL then.  h == NULL: on host_threads host threads (0 = the library's share of the CPUs), no device is touched.  The same table
+ * entry for entry either way.  Needs every sequence shorter than 2^32 - 1 letters and at most 2^32 - 1 sequences. */
+int lx_index_build(lx_handle * h, uint8_t const * s_red, uint64_t const * s_off, uint64_t const * s_len, uint64_t n_sseq, int32_t alph,
+                   uint32_t host_threads, lx_index ** out);
+/* An index file's table: exactly the bytes lx_index_save writes -- int32 {alph, key_len, prefix_len, 0}, uint64 {n_entries,
+ * n_prefix}, the entries (16 bytes each), the prefix table --, over the sequences they were made from.  LX_EINVAL for truncated
+ * bytes, bytes that are left over, a geometry or counts that do not fit the sequences, a prefix table that does not ascend, an entry
+ * outside its sequence.  h != NULL: the table becomes resident on h's device as after lx_index_build. */
+int lx_index_load(lx_handle * h, uint8_t const * bytes, uint64_t n, uint8_t const * s_red, uint64_t const * s_off, uint64_t const * s_len,
+                  uint64_t n_sseq, lx_index ** out);
+int lx_index_save(lx_index const * ix, lx_bytes ** out);
+/* The same table for another handle (h == NULL: for no device): shares the host copy with ix, uploads its own device copy.  Either
+ * index may be destroyed first.  (One handle per host thread and device: the table is built once and attached to each.) */
+int lx_index_attach(lx_index const * ix, lx_handle * h, lx_index ** out);
+int lx_index_get_info(lx_index const * ix, lx_index_info * out);
+/* entries [first, first + n) of the table (for checks and tools); LX_EINVAL beyond its end */
+int lx_index_copy_entries(lx_index const * ix, uint64_t first, uint64_t n, lx_index_entry * out);
+/* Destroy an index before the handle it was made with. */
+void lx_index_destroy(lx_index * ix);
+
+/* SearchOptions' seeding part (src/search_options.hpp:309-337) and what search() reads from LambdaOptions: seeds of seed_length
+ * letters every seed_offset letters, up to max_seed_dist substitutions (0: exact, :505-535; half_exact != 0: only in the second half,
+ * searchHalfExactImpl :537-604), adaptive elongation (:679-727), seedLooksPromising (:426-481) with pre_scoring /
+ * pre_scoring_thresh, the over-abundance cut (:729) from max_matches.  The ranges are the bundled front end's: seed_length 2 .. 63,
+ * seed_offset >= 1, max_seed_dist 0 .. 5, pre_scoring >= 0, q_num_frames 1 .. 6, unknown_rank 0 .. 31. */
+typedef struct lx_seed_params
+{
+    int32_t        seed_length, seed_offset, max_seed_dist, half_exact, adaptive, pre_scoring;
+    double         pre_scoring_thresh;
+    uint64_t       max_matches;
+    int32_t        q_num_frames, unknown_rank; /* frames per read (adjacent sequences); 'X' / 'N' in alignment ranks: no seed starts there */
+    int8_t const * matrix;                     /* LX_ALPH x LX_ALPH: matrix[q_rank * LX_ALPH + s_rank] */
+    int8_t const * matrix_rev;                 /* bisulfite: the reverse scheme, for hits on odd subject frames (:464-466); else NULL */
+    uint32_t       host_threads;               /* host threads of the h == NULL path and of the reads the device declines (0 = the library's share) */
+} lx_seed_params;
+typedef struct lx_seed_stats
+{
+    uint64_t n_matches, hits_after_seeding, hits_failed_pre_extend; /* the list's length; stats.hitsAfterSeeding, hitsFailedPreExtendTest */
+    uint64_t reads_declined, launches_full; /* reads the host threads finished inside the call (those of full launches included); launches whose match buffer filled up */
+} lx_seed_stats;
+typedef struct lx_seed_result lx_seed_result;
+
+/* search() (src/search_algo.hpp:611-762) for the reads whose first frame sequences are listed in `reads` (NULL: every read of the
+ * set): the match list iterateMatches consumes.  Sequence i of the queries lies at q_res / q_red[q_off[i] .. q_off[i] + q_len[i])
+ * (alignment ranks / reduced letters); s_res are the subjects in alignment ranks at the index's offsets.
+ *   h != NULL  (the handle the index was built, loaded or attached with): one lane per read on h's device and stream (phase 9 of
+ *              lx_last_phase_ms), launches of at most 4 Mi reads with room for 64 matches per read.  The device declines what it
+ *              cannot hold: a read with a word beyond key_len letters that occurs more than 32 times or with more than 24 letters
+ *              behind a seed's exact part, and all reads of a launch whose match buffer filled up.  Those reads are seeded on the
+ *              host threads inside the call and their matches appended, so the result is always the complete list, contiguous in
+ *              device memory.  Only the queries are uploaded: the table and s_red are resident with the index; s_res == NULL
+ *              means the subjects lx_set_subjects made resident on h (else s_res is uploaded for the call).
+ *   h == NULL  (any index): seedQueries on the host threads; s_res must be given.
+ * The ORDER of the list carries no meaning -- the lanes' on the device, the reads' on the host --: iterateMatches sorts its span
+ * before use (src/search_algo.hpp:1141), and so do lx_iterate_matches*.  Two results are compared as sorted lists.
+ * LX_EINVAL before any device work, with a text (lx_last_error(h); lx_last_output_error() when h is NULL): NULL buffers, parameters
+ * outside the ranges above, a read id that is not a first frame or outside the set, a handle that is not the index's. */
+int lx_seed_queries(lx_handle * h, lx_index const * ix, uint8_t const * s_res, uint8_t const * q_res, uint8_t const * q_red, uint64_t const * q_off,
+                    uint64_t const * q_len, uint64_t n_qseq, uint64_t const * reads, uint64_t n_reads, lx_seed_params const * p, lx_seed_result ** out);
+lx_seed_stats lx_seed_result_stats(lx_seed_result const * r);
+/* the list in host memory (a device result's copy is made on first use; NULL: out of memory).  The caller may modify it
+ * (lx_iterate_matches does). */
+lx_match *    lx_seed_result_matches(lx_seed_result * r);
+/* the list in device memory, n_matches records: d_matches of lx_iterate_matches_dev / lx_iterate_matches_dev_top on the same handle,
+ * without a copy.  NULL for a host-path result.  Valid until the result is freed. */
+void const *  lx_seed_result_matches_dev(lx_seed_result const * r);
+/* Results are freed in any order, before their handle is destroyed (a freed result's device block is kept by the handle for the next call). */
+void          lx_seed_result_free(lx_seed_result * r);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Blocks until everything queued on the handle's stream has finished. */
 int lx_synchronize(lx_handle * h);
@@ -773,7 +866,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
 /* Device time (HIP events on the launch stream) the most recent call spent in one phase, summed over its launches:
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
  * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*),
- * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top). */
+ * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top),
+ * 8 = the word table's kernels (lx_index_build on a handle), 9 = the seeding kernel (lx_seed_queries on a handle). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = [
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
     "lx_write_records_bgzf", "lx_gunzip", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
+    "lx_index_build", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
+    "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -97,6 +99,26 @@ class TaxonomyInfo(C.Structure):
 
 
 LX_TAXMAP_NCBI, LX_TAXMAP_UNIPROT = 0, 1
+
+
+class IndexInfo(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_prefix", C.c_uint64), ("alph", C.c_int32), ("key_len", C.c_int32), ("prefix_len", C.c_int32),
+                ("built_on_device", C.c_int32)]
+
+
+INDEX_ENTRY_DTYPE = np.dtype([("key", "<u8"), ("seq", "<u4"), ("pos", "<u4")])
+
+
+class SeedParams(C.Structure):
+    """lx_seed_params (include/lambda_ext.h); seed_params() fills one from keywords."""
+    _fields_ = [("seed_length", C.c_int32), ("seed_offset", C.c_int32), ("max_seed_dist", C.c_int32), ("half_exact", C.c_int32),
+                ("adaptive", C.c_int32), ("pre_scoring", C.c_int32), ("pre_scoring_thresh", C.c_double), ("max_matches", C.c_uint64),
+                ("q_num_frames", C.c_int32), ("unknown_rank", C.c_int32), ("matrix", C.c_void_p), ("matrix_rev", C.c_void_p),
+                ("host_threads", C.c_uint32)]
+
+
+class SeedStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_matches", "hits_after_seeding", "hits_failed_pre_extend", "reads_declined", "launches_full")]
 
 
 class SeqNames(C.Structure):
@@ -264,6 +286,23 @@ def load():
     lib.lx_taxonomy_get.argtypes = [vp, C.POINTER(TaxonomyInfo)]
     lib.lx_taxonomy_free.argtypes = [vp]
     lib.lx_taxonomy_free.restype = None
+    lib.lx_index_build.argtypes = [vp, vp, vp, vp, u64, i32, C.c_uint32, C.POINTER(vp)]
+    lib.lx_index_load.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(vp)]
+    lib.lx_index_save.argtypes = [vp, C.POINTER(vp)]
+    lib.lx_index_attach.argtypes = [vp, vp, C.POINTER(vp)]
+    lib.lx_index_get_info.argtypes = [vp, C.POINTER(IndexInfo)]
+    lib.lx_index_copy_entries.argtypes = [vp, u64, u64, vp]
+    lib.lx_index_destroy.argtypes = [vp]
+    lib.lx_index_destroy.restype = None
+    lib.lx_seed_queries.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, C.POINTER(SeedParams), C.POINTER(vp)]
+    lib.lx_seed_result_stats.argtypes = [vp]
+    lib.lx_seed_result_stats.restype = SeedStats
+    lib.lx_seed_result_matches.argtypes = [vp]
+    lib.lx_seed_result_matches.restype = vp
+    lib.lx_seed_result_matches_dev.argtypes = [vp]
+    lib.lx_seed_result_matches_dev.restype = vp
+    lib.lx_seed_result_free.argtypes = [vp]
+    lib.lx_seed_result_free.restype = None
     lib.lx_write_records_bgzf.argtypes = [vp, C.c_char_p, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
                                           C.c_int64]
     _lib = lib
@@ -450,6 +489,156 @@ class TaxMap:
 
     def __del__(self):
         self.close()
+
+
+def _raise(lib, h, rc):
+    raise LambdaExtError(rc, lib.lx_last_error(h).decode() if h is not None else last_output_error())
+
+
+class Index:
+    """lx_index: the sorted word table over reduced, frame-expanded subjects (Level 3).  Index.build / Index.load / attach make
+    one; handle None = on the host threads, no device; with a handle the table and the reduced subjects stay on its device.
+    Destroy (close) an index before its handle."""
+
+    def __init__(self, ix, handle):
+        self.lib, self.ix, self.handle = load(), ix, handle
+
+    @staticmethod
+    def _seqs(s_red, s_off, s_len):
+        red = np.ascontiguousarray(s_red, dtype=np.uint8)
+        return (red if red.size else np.zeros(1, np.uint8)), np.ascontiguousarray(s_off, dtype=np.uint64), np.ascontiguousarray(s_len, dtype=np.uint64)
+
+    @classmethod
+    def build(cls, handle: "Handle | None", s_red, s_off, s_len, alph: int, host_threads: int = 0):
+        lib = load()
+        red, off, ln = cls._seqs(s_red, s_off, s_len)
+        h, out = (handle.h if handle is not None else None), C.c_void_p()
+        rc = lib.lx_index_build(h, _ptr(red), _ptr(off), _ptr(ln), len(off), alph, host_threads, C.byref(out))
+        if rc != LX_OK:
+            _raise(lib, h, rc)
+        return cls(out, handle)
+
+    @classmethod
+    def load(cls, handle: "Handle | None", data: bytes, s_red, s_off, s_len):
+        lib = load()
+        red, off, ln = cls._seqs(s_red, s_off, s_len)
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+        h, out = (handle.h if handle is not None else None), C.c_void_p()
+        rc = lib.lx_index_load(h, _ptr(buf), len(data), _ptr(red), _ptr(off), _ptr(ln), len(off), C.byref(out))
+        if rc != LX_OK:
+            _raise(lib, h, rc)
+        return cls(out, handle)
+
+    def attach(self, handle: "Handle | None"):
+        """lx_index_attach: the same table for another handle (shares the host copy)."""
+        h, out = (handle.h if handle is not None else None), C.c_void_p()
+        rc = self.lib.lx_index_attach(self.ix, h, C.byref(out))
+        if rc != LX_OK:
+            _raise(self.lib, h, rc)
+        return Index(out, handle)
+
+    def save(self) -> bytes:
+        out = C.c_void_p()
+        rc = self.lib.lx_index_save(self.ix, C.byref(out))
+        if rc != LX_OK:
+            _raise(self.lib, None, rc)
+        try:
+            return C.string_at(self.lib.lx_bytes_data(out), self.lib.lx_bytes_size(out))
+        finally:
+            self.lib.lx_bytes_free(out)
+
+    def info(self) -> IndexInfo:
+        r = IndexInfo()
+        if self.lib.lx_index_get_info(self.ix, C.byref(r)) != LX_OK:
+            raise LambdaExtError(LX_EINVAL, "lx_index_get_info")
+        return r
+
+    def entries(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        n = int(self.info().n_entries) - first if n is None else n
+        out = np.zeros(max(n, 1), dtype=INDEX_ENTRY_DTYPE)
+        if self.lib.lx_index_copy_entries(self.ix, first, n, _ptr(out)) != LX_OK:
+            raise LambdaExtError(LX_EINVAL, "lx_index_copy_entries: range outside the table")
+        return out[:n]
+
+    def close(self):
+        if getattr(self, "ix", None):
+            self.lib.lx_index_destroy(self.ix)
+            self.ix = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def seed_params(matrix, seed_length=10, seed_offset=5, max_seed_dist=0, half_exact=True, adaptive=True, pre_scoring=2, pre_scoring_thresh=2.0,
+                max_matches=256, q_num_frames=1, unknown_rank=25, matrix_rev=None, host_threads=0) -> SeedParams:
+    """lx_seed_params; matrix / matrix_rev: LX_ALPH x LX_ALPH int8 arrays (kept alive by the returned object)."""
+    p = SeedParams(seed_length, seed_offset, max_seed_dist, int(half_exact), int(adaptive), pre_scoring, pre_scoring_thresh, max_matches,
+                   q_num_frames, unknown_rank, None, None, host_threads)
+    p._keep = [None if m is None else np.ascontiguousarray(m, dtype=np.int8).reshape(LX_ALPH * LX_ALPH) for m in (matrix, matrix_rev)]
+    p.matrix = None if p._keep[0] is None else p._keep[0].ctypes.data
+    p.matrix_rev = None if p._keep[1] is None else p._keep[1].ctypes.data
+    return p
+
+
+class _DevList:
+    """A device address with torch's data_ptr() spelling: what Handle.iterate_matches_dev* take."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def data_ptr(self):
+        return self.ptr
+
+
+class SeedResult:
+    """lx_seed_result: stats, matches() (host copy, MATCH_DTYPE), dev() (the list in device memory; None for a host-path result).
+    Free (close) results before their handle."""
+
+    def __init__(self, r):
+        self.lib, self.r = load(), r
+
+    @property
+    def stats(self) -> SeedStats:
+        return self.lib.lx_seed_result_stats(self.r)
+
+    def matches(self) -> np.ndarray:
+        n = int(self.stats.n_matches)
+        p = self.lib.lx_seed_result_matches(self.r)
+        if not p:
+            raise LambdaExtError(-3, "lx_seed_result_matches")
+        return np.frombuffer(C.string_at(p, n * MATCH_DTYPE.itemsize), dtype=MATCH_DTYPE).copy() if n else np.zeros(0, MATCH_DTYPE)
+
+    def dev(self):
+        p = self.lib.lx_seed_result_matches_dev(self.r)
+        return _DevList(p) if p else None
+
+    def close(self):
+        if getattr(self, "r", None):
+            self.lib.lx_seed_result_free(self.r)
+            self.r = None
+
+    __del__ = close
+
+
+def seed_queries(handle: "Handle | None", index: Index, s_res, q_res, q_red, q_off, q_len, params: SeedParams, reads=None) -> SeedResult:
+    """lx_seed_queries: search() for the reads whose first frame sequences are listed (None: all).  s_res None with a handle: the
+    subjects lx_set_subjects made resident."""
+    lib = load()
+    keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8) for a in (s_res, q_res, q_red)]
+    keep = [a if a is None or a.size else np.zeros(1, np.uint8) for a in keep]
+    off, ln = np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(q_len, dtype=np.uint64)
+    rd = None if reads is None else np.ascontiguousarray(reads, dtype=np.uint64)
+    h, out = (handle.h if handle is not None else None), C.c_void_p()
+    rc = lib.lx_seed_queries(h, index.ix, *[None if a is None else _ptr(a) for a in keep], _ptr(off), _ptr(ln), len(off),
+                             None if rd is None else _ptr(rd), 0 if rd is None else len(rd), C.byref(params), C.byref(out))
+    if rc != LX_OK:
+        _raise(lib, h, rc)
+    return SeedResult(out)
 
 
 def taxonomy_build(nodes: bytes, names: bytes, present):

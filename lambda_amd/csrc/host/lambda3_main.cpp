@@ -9,7 +9,8 @@
 // (the passes whose seeding ran on its GPU) goes through lx_iterate_matches_dev_top, so that only the records that stay come down;
 // that is legitimate because every record of a query comes out of ONE call -- the workers own disjoint ranges of reads, the exact
 // pass and the half-exact pass work on disjoint queries, a bisulfite call holds both strand directions (and runs the step over its
-// finished result) --; a pass whose matches stand in host memory (host seeding, reads the device declined, LAMBDA3_HOST_LIST) keeps
+// finished result) --; a pass whose matches stand in host memory (host seeding, LAMBDA3_HOST_LIST; reads the device declined no longer: lx_seed_queries
+// appends their matches to its device list) keeps
 // the host step, applied to that pass's records alone; the statistics of the parts are summed; -n 0 keeps the host step (the second
 // pass searches the queries WITHOUT records).  auto: see DESIGN.md ("_writeRecord on the device") for the measurement behind it.
 // LCA and the writers stay on the host, fed with the kept records; the output is byte-identical either way.
@@ -72,7 +73,6 @@
 #include "blast_stats.hpp"
 #include "lambda_ext.hpp"
 #include "lx_seeding.hpp"
-#include "lx_seeding_gpu.hpp"
 #include "scoring_tables.hpp"
 
 namespace
@@ -376,8 +376,8 @@ struct Options
     std::string commandLine;
     std::vector<int> devices;         // --devices (default: every visible device)
     std::string table       = "auto"; // --table gpu | host | auto: where the word table is made (auto: search* on the GPU, mkindex* on the host)
-    std::string seeding     = "gpu";  // --seeding gpu | host: where search() runs (host/lx_seeding_gpu.hpp -- one lane per read, reads the
-                                      // device declines go to the host --, host/lx_seeding.hpp on the -t threads)
+    std::string seeding     = "gpu";  // --seeding gpu | host: where search() runs (lx_seed_queries on the worker's handle -- one lane per read, reads
+                                      // the device declines are finished on the host threads inside the call --, or on the -t threads)
     std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
     int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     // mkindex* (src/mkindex_options.hpp:96-262): -d the database (FASTA), -i the index file to write
@@ -754,9 +754,12 @@ constexpr char kTaxonMagic[8] = {'L', 'X', 'T', 'A', 'X', 'O', 'N', '1'};
 //   "LXTAXON1"; u64 n_s; u64 s_tax_off[n_s + 1]; u32 s_tax_ids[s_tax_off[n_s]] (subject s's taxa, in the map's order);
 //   u64 has_tree (0 or 1); if 1: u64 n_taxa, u32 parents[n_taxa], u32 heights[n_taxa], u32 name_len[n_taxa], then the names'
 //   bytes one after another (no terminators; "" for the taxa the tree does not keep).
-void writeIndexFile(std::string const & path, IndexFileOptions const & io, SeqSet const & db, lambda_amd::ReducedIndex const & ix,
-                    IndexTaxonomy const & tax)
+void writeIndexFile(std::string const & path, IndexFileOptions const & io, SeqSet const & db, lx_index const * ix, IndexTaxonomy const & tax)
 {
+    lx_bytes * table = nullptr; // (lx_index_save writes ReducedIndex::save's bytes)
+    if (lx_index_save(ix, &table) != LX_OK)
+        throw std::runtime_error(lx_last_output_error());
+    std::unique_ptr<lx_bytes, void (*)(lx_bytes *)> keepTable(table, lx_bytes_free);
     FILE * f = std::fopen(path.c_str(), "wb");
     if (!f)
         throw std::runtime_error("cannot write " + path);
@@ -778,7 +781,7 @@ void writeIndexFile(std::string const & path, IndexFileOptions const & io, SeqSe
     write(db.orig_len.data(), db.orig_len.size() * sizeof(uint64_t));
     u64(db.res.size());
     write(db.res.data(), db.res.size());
-    ix.save(write);
+    write(lx_bytes_data(table), lx_bytes_size(table));
     if (tax.has)
     {
         write(kTaxonMagic, 8);
@@ -1234,13 +1237,49 @@ int main(int argc, char ** argv)
         };
         bool const wantLca = !mk && (hasWord(opt.outputColumns, "lcataxid") || hasWord(opt.samTags, "lt") || hasWord(opt.samTags, "ls"));
         std::vector<uint8_t> const dbRed = reduce(db);
-        lambda_amd::ReducedIndex   ix;
-        bool                       tableOnGpu = false;
-        lambda_amd::DeviceTable    deviceTable; // (the table where the GPU builder left it, for the seeding stage on that device)
+        // the word table (Level 3 of include/lambda_ext.h): made or loaded with the first device's handle where the seeding or the
+        // table is the GPU's -- table and reduced subjects then stay on that device, and worker 0 works with that handle --, else on
+        // the -t host threads
+        using IndexOwner = std::unique_ptr<lx_index, void (*)(lx_index *)>;
+        std::unique_ptr<lx_handle, void (*)(lx_handle *)> firstHandle(nullptr, lx_destroy);
+        IndexOwner                                        ix(nullptr, lx_index_destroy);
+        bool                                              tableOnGpu = false;
+        bool const gpuSeedingWanted = !mk && opt.seeding == "gpu";
+        auto       makeFirstHandle  = [&]()
+        {
+            lx_handle * h = nullptr;
+            if (lx_create(opt.devices.empty() ? 0 : opt.devices[0], &h) != LX_OK)
+                throw std::runtime_error(std::string("lambda_ext: ") + lx_last_error(nullptr));
+            firstHandle.reset(h);
+        };
         if (fromIndex)
         {
-            bool const ok = ix.load([&](void * p, size_t bytes) { return bytes == 0 || std::fread(p, 1, bytes, indexFile) == bytes; }, dbRed, db.off, db.len) &&
-                            ix.alphabet() == alph;
+            // the table's bytes: its header says how many (ReducedIndex::save: 16 + 16 bytes, the entries, the prefix table)
+            std::vector<uint8_t> bytes(32);
+            bool                 ok = std::fread(bytes.data(), 1, 32, indexFile) == 32;
+            if (ok)
+            {
+                uint64_t cnt[2];
+                std::memcpy(cnt, bytes.data() + 16, sizeof(cnt));
+                uint64_t dbLetters = 0;
+                for (uint64_t l : db.len)
+                    dbLetters += l;
+                ok = cnt[0] == dbLetters && cnt[1] <= (1ull << 32);
+                if (ok)
+                {
+                    bytes.resize(32 + cnt[0] * 16 + cnt[1] * 8);
+                    ok = std::fread(bytes.data() + 32, 1, bytes.size() - 32, indexFile) == bytes.size() - 32;
+                }
+            }
+            lx_index * raw = nullptr;
+            if (ok && gpuSeedingWanted && lx_device_count() > 0)
+                makeFirstHandle();
+            if (ok && firstHandle && lx_index_load(firstHandle.get(), bytes.data(), bytes.size(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), &raw) != LX_OK)
+                firstHandle.reset(); // (no room on the device, ...: the host copy alone; a table that is wrong fails again below)
+            ok = ok && (raw || lx_index_load(nullptr, bytes.data(), bytes.size(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), &raw) == LX_OK);
+            ix.reset(raw);
+            lx_index_info info{};
+            ok = ok && lx_index_get_info(raw, &info) == LX_OK && info.alph == alph;
             if (!ok)
                 throw std::runtime_error("index file " + opt.db + ": the word table is truncated or does not fit the sequences");
             readIndexTaxonomy(opt.db, indexFile, db.ids.size(), indexTax);
@@ -1251,28 +1290,43 @@ int main(int argc, char ** argv)
         }
         else
         {
-            // on the GPU (keys, one radix sort, prefix table: host/lx_seeding_gpu.hpp) where there is one to take it, else on the -t
-            // host threads; the same table either way
+            // on the GPU (keys, one radix sort, prefix table: lx_seed.hip) where there is one to take it, else on the -t host threads;
+            // the same table either way
             bool const wantGpu = opt.table == "gpu" || (opt.table == "auto" && !mk);
+            lx_index * raw     = nullptr;
             if (wantGpu && lx_device_count() > 0)
             {
-                try
-                {
-                    tableOnGpu = lambda_amd::buildTableOnGpu(opt.devices.empty() ? 0 : opt.devices[0], ix, dbRed, db.off, db.len, alph,
-                                                             (!mk && opt.seeding == "gpu") ? &deviceTable : nullptr);
-                }
-                catch (std::exception const & e) // (e.g. the device ran out of memory after all: the host threads make the table)
+                makeFirstHandle();
+                int const rc = lx_index_build(firstHandle.get(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), alph, nThreads, &raw);
+                tableOnGpu   = rc == LX_OK;
+                if (rc != LX_OK && rc != LX_EINVAL && rc != LX_ENOMEM) // (too large for the device build or for its memory: the host threads make it)
                 {
                     if (opt.table == "gpu")
-                        throw;
-                    std::cerr << "WARNING: the word table is made on the host threads (" << e.what() << ")\n";
-                    tableOnGpu = false;
+                        throw std::runtime_error(std::string("lambda_ext: ") + lx_last_error(firstHandle.get()));
+                    std::cerr << "WARNING: the word table is made on the host threads (" << lx_last_error(firstHandle.get()) << ")\n";
                 }
             }
             else if (opt.table == "gpu")
                 throw std::runtime_error("--table gpu: no HIP device available");
             if (!tableOnGpu)
-                ix.build(dbRed, db.off, db.len, alph, nThreads);
+            {
+                if (lx_index_build(nullptr, dbRed.data(), db.off.data(), db.len.data(), db.off.size(), alph, nThreads, &raw) != LX_OK)
+                    throw std::runtime_error(std::string("lambda_ext: ") + lx_last_output_error());
+                if (firstHandle && gpuSeedingWanted) // the seeding is the GPU's all the same: the host-made table becomes resident
+                {
+                    lx_index * att = nullptr;
+                    if (lx_index_attach(raw, firstHandle.get(), &att) == LX_OK)
+                    {
+                        lx_index_destroy(raw);
+                        raw = att;
+                    }
+                    else
+                        firstHandle.reset();
+                }
+                else
+                    firstHandle.reset();
+            }
+            ix.reset(raw);
         }
         double const msIndex = msSince(tIndex);
         if (mk)
@@ -1299,7 +1353,7 @@ int main(int argc, char ** argv)
                              th ? ("join on the GPU, kernels " + std::to_string((long)(msTaxKernel + 0.5))).c_str() : (std::to_string(nThreads) + " host thread(s)").c_str());
             }
             auto const tWrite = std::chrono::steady_clock::now();
-            writeIndexFile(opt.index, out, db, ix, tax);
+            writeIndexFile(opt.index, out, db, ix.get(), tax);
             uint64_t residues = 0;
             for (auto l : db.len)
                 residues += l;
@@ -1402,28 +1456,34 @@ int main(int argc, char ** argv)
                 uint64_t const rLo = nReads * w / nWorkers, rHi = nReads * (w + 1) / nWorkers;
                 if (rLo == rHi)
                     return;
-                lambda_amd::Engine eng(devices[w % devices.size()]);
+                // worker 0 works with the handle the table is resident on; the others make their own and attach the table to it
+                bool const         borrow = w == 0 && firstHandle;
+                lambda_amd::Engine eng(borrow ? firstHandle.get() : nullptr, devices[w % devices.size()]);
                 eng.setScoring(sc, 0);
                 if (bs)
                     eng.setScoring(scRev, 1);
                 // the database stays on the GPU for the whole run (the reference keeps it in the index file it maps at start-up)
                 eng.check(lx_set_subjects(eng.raw(), db.res.data(), db.res.size()));
                 // one pass of the batch loop of realMain (src/search.cpp:426-459): seed, extend (GPU), collect
-                std::unique_ptr<lambda_amd::GpuSeeder> gpuSeeder;
-                if (opt.seeding == "gpu" && lambda_amd::GpuSeeder::canTake(ix))
-                    try
+                IndexOwner       attached(nullptr, lx_index_destroy);
+                lx_index const * gpuIndex = nullptr; // the table on this worker's handle (NULL: the seeding is the host threads')
+                if (opt.seeding == "gpu")
+                {
+                    if (borrow)
+                        gpuIndex = ix.get();
+                    else
                     {
-                        gpuSeeder.reset(new lambda_amd::GpuSeeder(devices[w % devices.size()], ix, sin, dbRed, db.off.size(), db.res.size(), qs.res.size(), &deviceTable));
+                        lx_index * att = nullptr;
+                        if (lx_index_attach(ix.get(), eng.raw(), &att) == LX_OK)
+                            attached.reset(att), gpuIndex = att;
+                        else // (the table and the sequences did not fit beside the extension's buffers: host threads)
+                            std::cerr << "WARNING: seeding on the host threads (" << lx_last_error(eng.raw()) << ")\n";
                     }
-                    catch (std::exception const & e) // (the table and the sequences did not fit beside the extension's buffers: host threads)
-                    {
-                        std::cerr << "WARNING: seeding on the host threads (" << e.what() << ")\n";
-                        gpuSeeder.reset();
-                    }
-                pt.gpuSeeding = gpuSeeder != nullptr;
+                }
+                pt.gpuSeeding = gpuIndex != nullptr;
                 // with the seeding on the device its matches stay there: the sequence sets become resident for the Level-2 kernels
                 // (LAMBDA3_HOST_LIST=1: the matches come down and go through lx_iterate_matches, the A/B switch of the tests)
-                bool const deviceList = gpuSeeder && !std::getenv("LAMBDA3_HOST_LIST");
+                bool const deviceList = gpuIndex && !std::getenv("LAMBDA3_HOST_LIST");
                 if (deviceList)
                 {
                     eng.check(lx_set_subject_seqs(eng.raw(), db.off.data(), db.len.data(), db.off.size()));
@@ -1438,74 +1498,68 @@ int main(int argc, char ** argv)
                     if (est >= 100000)
                         eng.check(lx_reserve(eng.raw(), est, est / 7, est / 12, wantOps ? est / 12 * (len + len / 16) : 0));
                 }
+                lx_seed_params spar{};
+                spar.half_exact = sin.halfExact ? 1 : 0, spar.adaptive = sin.adaptive ? 1 : 0, spar.pre_scoring = sin.preScoring;
+                spar.pre_scoring_thresh = sin.preScoringThresh, spar.max_matches = sin.maxMatches, spar.q_num_frames = sin.qNumFrames;
+                spar.unknown_rank = sin.unknownRank, spar.matrix = sin.matrix, spar.matrix_rev = sin.matrixRev, spar.host_threads = seedThreads;
                 auto pass = [&](lambda_amd::SeedParams const & so, std::vector<uint64_t> const & which)
                 {
-                    std::vector<lx_match> matches;
                     if (std::getenv("LAMBDA3_TRACE"))
                         std::fprintf(stderr, "[worker %zu] seeding %zu frame sequences (seed %d/%d, delta %d)\n", w, which.size(), so.seedLength, so.seedOffset, so.maxSeedDist);
-                    auto const tSeed = std::chrono::steady_clock::now();
-                    bool     onHost   = !gpuSeeder;
-                    uint64_t onDevice = 0; // matches the seeding kernel left in device memory (a pass of one launch, nothing declined)
-                    if (gpuSeeder)
+                    auto const            tSeed = std::chrono::steady_clock::now();
+                    std::vector<uint64_t> reads; // (lx_seed_queries takes a read by its first frame sequence)
+                    for (uint64_t i : which)
+                        if (i % (uint64_t)qFrames == 0)
+                            reads.push_back(i);
+                    spar.seed_length = so.seedLength, spar.seed_offset = so.seedOffset, spar.max_seed_dist = so.maxSeedDist;
+                    lx_seed_result * sr = nullptr;
+                    // the device takes the reads; those it declines (words far beyond the table's keys with many occurrences) and those of
+                    // a launch whose match buffer filled up are finished on the host threads inside the call
+                    if (gpuIndex && lx_seed_queries(eng.raw(), gpuIndex, nullptr, qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(), reads.data(),
+                                                    reads.size(), &spar, &sr) != LX_OK)
                     {
-                        // the device takes the reads; those it declines (words far beyond the table's keys with many occurrences) and
-                        // those of a launch whose match buffer filled up are seeded here
-                        std::vector<uint64_t>          declined;
-                        lambda_amd::SeedingStats const sstBefore = pt.sst;
-                        try
-                        {
-                            pt.nPassesOnHost += gpuSeeder->seed(so, which, matches, pt.sst, declined, deviceList ? &onDevice : nullptr);
-                        }
-                        catch (std::exception const & e)
-                        {
-                            // a HIP error in the seeding stage (its match buffer did not fit, ...): this pass and the following ones are
-                            // seeded on the host threads, from a clean slate
-                            std::cerr << "WARNING: seeding on the host threads from here on (" << e.what() << ")\n";
-                            gpuSeeder.reset();
-                            pt.gpuSeeding = false;
-                            matches.clear();
-                            declined.clear();
-                            onDevice = 0;
-                            pt.sst   = sstBefore;
-                            onHost   = true;
-                        }
-                        if (!declined.empty())
-                        {
-                            std::sort(declined.begin(), declined.end());
-                            std::vector<uint64_t> rest;
-                            for (uint64_t rd : declined)
-                                for (int f = 0; f < qFrames && rd + (uint64_t)f < qs.off.size(); ++f)
-                                    rest.push_back(rd + (uint64_t)f);
-                            lambda_amd::seedQueriesParallel(ix, sin, so, rest, matches, pt.sst, seedThreads);
-                            pt.nDeclined += declined.size();
-                        }
+                        // a HIP error in the seeding stage (its match buffer did not fit, ...): this pass and the following ones are
+                        // seeded on the host threads, from a clean slate
+                        std::cerr << "WARNING: seeding on the host threads from here on (" << lx_last_error(eng.raw()) << ")\n";
+                        gpuIndex      = nullptr;
+                        pt.gpuSeeding = false;
                     }
-                    if (onHost)
-                        lambda_amd::seedQueriesParallel(ix, sin, so, which, matches, pt.sst, seedThreads);
+                    if (!sr && lx_seed_queries(nullptr, ix.get(), db.res.data(), qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(), reads.data(),
+                                               reads.size(), &spar, &sr) != LX_OK)
+                        throw std::runtime_error(std::string("lambda_ext: ") + lx_last_output_error());
+                    std::unique_ptr<lx_seed_result, void (*)(lx_seed_result *)> keepSeeds(sr, lx_seed_result_free);
+                    lx_seed_stats const sst = lx_seed_result_stats(sr);
+                    pt.sst.hitsAfterSeeding += sst.hits_after_seeding, pt.sst.hitsFailedPreExtendTest += sst.hits_failed_pre_extend;
+                    pt.nDeclined += sst.reads_declined, pt.nPassesOnHost += sst.launches_full;
+                    // the matches where the seeding left them: the device list for the Level-2 kernels, else the list in host memory
+                    void const * const dList    = deviceList ? lx_seed_result_matches_dev(sr) : nullptr;
+                    uint64_t const     nMatches = sst.n_matches;
+                    lx_match * const   hList    = dList || nMatches == 0 ? nullptr : lx_seed_result_matches(sr);
+                    if (!dList && nMatches && !hList)
+                        throw std::runtime_error("the match list did not fit into host memory");
                     pt.msSeed += msSince(tSeed);
-                    pt.nPromising += matches.size() + onDevice;
+                    pt.nPromising += nMatches;
                     if (std::getenv("LAMBDA3_TRACE"))
-                        std::fprintf(stderr, "[worker %zu] %zu promising seeds -> extension\n", w, matches.size() + (size_t)onDevice);
-                    if (matches.empty() && onDevice == 0)
+                        std::fprintf(stderr, "[worker %zu] %zu promising seeds -> extension\n", w, (size_t)nMatches);
+                    if (nMatches == 0)
                         return;
                     lx_iterate_result * res = nullptr;
                     auto const          tExt = std::chrono::steady_clock::now();
                     lx_record_stats passRst{};
                     bool            cutDone = false;
-                    if (onDevice && recordsOnGpu) // ... with _writeRecord's cut before the records come down
+                    if (dList && recordsOnGpu) // ... with _writeRecord's cut before the records come down
                     {
-                        eng.check(lx_iterate_matches_dev_top(eng.raw(), 0, gpuSeeder->devMatches(), onDevice, &sp, opt.maxMatches, &passRst, &res));
+                        eng.check(lx_iterate_matches_dev_top(eng.raw(), 0, dList, nMatches, &sp, opt.maxMatches, &passRst, &res));
                         float msTop = 0;
                         if (lx_last_phase_ms(eng.raw(), 7, &msTop, nullptr) == LX_OK)
                             pt.msRecords += msTop;
                         cutDone = true;
                     }
-                    else if (onDevice) // the Level-2 driver on the list where the seeding kernel left it (include/lambda_ext.h)
-                        eng.check(lx_iterate_matches_dev(eng.raw(), 0, gpuSeeder->devMatches(), onDevice, &sp, &res));
+                    else if (dList) // the Level-2 driver on the list where the seeding kernel left it (include/lambda_ext.h)
+                        eng.check(lx_iterate_matches_dev(eng.raw(), 0, dList, nMatches, &sp, &res));
                     else
                         eng.check(lx_iterate_matches(eng.raw(), 0, qs.res.data(), qs.res.size(), qs.off.data(), qs.len.data(), qs.off.size(),
-                                                     qs.orig_len.data(), nullptr, 0, db.off.data(), db.len.data(), db.off.size(), matches.data(),
-                                                     matches.size(), &sp, &res));
+                                                     qs.orig_len.data(), nullptr, 0, db.off.data(), db.len.data(), db.off.size(), hList, nMatches, &sp, &res));
                     pt.msExtend += msSince(tExt);
                     uint64_t               n  = lx_iterate_result_count(res);
                     lx_blast_match const * bm = lx_iterate_result_matches(res);

@@ -18,7 +18,18 @@ public:
         if (int rc = lx_create(device, &h_); rc != LX_OK)
             throw std::runtime_error(std::string("lambda_ext: ") + lx_last_error(nullptr));
     }
-    ~Engine() { lx_destroy(h_); }
+    // on a handle that is someone else's (borrowed != NULL: used, not destroyed), else on one of its own on `device`
+    Engine(lx_handle * borrowed, int device) : h_(borrowed), owned_(borrowed == nullptr)
+    {
+        if (!h_)
+            if (int rc = lx_create(device, &h_); rc != LX_OK)
+                throw std::runtime_error(std::string("lambda_ext: ") + lx_last_error(nullptr));
+    }
+    ~Engine()
+    {
+        if (owned_)
+            lx_destroy(h_);
+    }
     Engine(Engine const &)             = delete;
     Engine & operator=(Engine const &) = delete;
 
@@ -57,7 +68,8 @@ public:
     }
 
 private:
-    lx_handle * h_ = nullptr;
+    lx_handle * h_     = nullptr;
+    bool        owned_ = true;
 };
 
 } // namespace lambda_amd

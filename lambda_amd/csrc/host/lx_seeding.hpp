@@ -282,7 +282,7 @@ public:
         mark("prefix table");
     }
 
-    // For a table made elsewhere (the GPU builder, host/lx_seeding_gpu.hpp): the geometry build() would choose for this database,
+    // For a table made elsewhere (the GPU builder, lx_seed_host.cpp): the geometry build() would choose for this database,
     // then room for the entries and the prefix table, which the caller fills -- sorted by (word, sequence, position) -- before
     // the first search.  total = number of residues.
     void prepareExternal(std::vector<uint8_t> const & red, std::vector<uint64_t> const & off, std::vector<uint64_t> const & len, int alph)
@@ -466,7 +466,7 @@ public:
         uint64_t key;
         uint32_t seq, pos;
     };
-    // the table's parts as they stand (what the GPU seeding stage uploads, host/lx_seeding_gpu.hpp)
+    // the table's parts as they stand (what the GPU seeding stage uploads, lx_seed_host.cpp)
     Entry const *    entriesData() const { return entries_.data(); }
     uint64_t         entriesCount() const { return entries_.size(); }
     uint64_t const * prefixData() const { return pre_.data(); }

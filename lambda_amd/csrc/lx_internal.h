@@ -239,6 +239,12 @@ struct lx_handle
         DevBuf d_in, d_mem, d_status, d_out;
         Pinned p_in[2], p_mem[2], p_status[2];
     } gunzip;
+    // lx_seed_queries (lx_seed_host.cpp): a call's queries, reads, decline flags, counters, the two scoring matrices, subjects the
+    // caller handed in; the match block of the last freed result, kept for the next call
+    struct Seed
+    {
+        DevBuf d_qres, d_qred, d_qoff, d_qlen, d_reads, d_declined, d_cnt, d_matrix, d_sres, d_spare;
+    } seed;
 };
 
 namespace lxi

@@ -1396,7 +1396,7 @@ int lx_reserve(lx_handle * h, uint64_t n_matches, uint64_t n_windows, uint64_t n
 }
 
 // The Level-2 radix sort (lx_level2.hip: l2_launch_sort) for a caller's own (key, value) words in device memory -- what the front end's
-// word table is sorted with (host/lx_seeding_gpu.hpp), instead of a library primitive.
+// word table is sorted with (lx_index_build, lx_seed_host.cpp), instead of a library primitive.
 int lx_sort_words_dev(int device, uint64_t * key[2], uint64_t * value[2], uint64_t n, uint64_t key_bits, void * stream, int * sorted_in)
 {
     if (!key || !value || !sorted_in || (n && (!key[0] || !key[1] || !value[0] || !value[1])) || n > 0x7fffffffull || device < 0 || device >= 64)
