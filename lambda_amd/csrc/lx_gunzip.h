@@ -41,6 +41,32 @@ struct GunzipParams
     uint32_t *           status; // nmem words
 };
 
+// the member's output in the kernel's LDS, at most cap (= ISIZE) bytes: the only guard of those writes.  __host__ too, so that
+// tests/native/inflate_check.cpp runs this very code on heap blocks of exactly cap bytes under the sanitizers
+struct LdsSink
+{
+    uint8_t * o;
+    uint32_t  pos, cap;
+    __host__ __device__ bool put(uint8_t b)
+    {
+        if (pos >= cap)
+            return false;
+        o[pos++] = b;
+        return true;
+    }
+    __host__ __device__ bool dist_ok(uint32_t d) const { return d <= pos; }
+    __host__ __device__ bool copy(uint32_t d, uint32_t len)
+    {
+        if (d > pos || len > cap - pos)
+            return false;
+        uint8_t * dst = o + pos;
+        for (uint32_t i = 0; i < len; ++i) // (overlapping: byte by byte, as the format defines it)
+            dst[i] = dst[(int32_t)i - (int32_t)d];
+        pos += len;
+        return true;
+    }
+};
+
 hipError_t launch_gunzip(GunzipParams const & p, hipStream_t stream);
 
 } // namespace lx

@@ -29,31 +29,6 @@ constexpr uint32_t kLdsBytes = kOutLds + kInLds + sizeof(inflate::Tables) + 256 
 static_assert(kLdsBytes <= 160 * 1024 - 64, "the decoder's LDS exceeds what gfx950 gives a workgroup");
 static_assert(sizeof(inflate::Tables) % 4 == 0, "the CRC table must be aligned");
 
-// the member's output in LDS, at most cap (= ISIZE) bytes
-struct LdsSink
-{
-    uint8_t * o;
-    uint32_t  pos, cap;
-    __device__ bool put(uint8_t b)
-    {
-        if (pos >= cap)
-            return false;
-        o[pos++] = b;
-        return true;
-    }
-    __device__ bool dist_ok(uint32_t d) const { return d <= pos; }
-    __device__ bool copy(uint32_t d, uint32_t len)
-    {
-        if (d > pos || len > cap - pos)
-            return false;
-        uint8_t * dst = o + pos;
-        for (uint32_t i = 0; i < len; ++i) // (overlapping: byte by byte, as the format defines it)
-            dst[i] = dst[(int32_t)i - (int32_t)d];
-        pos += len;
-        return true;
-    }
-};
-
 __global__ __launch_bounds__(kThreads) void member_kernel(GunzipParams p)
 {
     extern __shared__ __align__(16) uint8_t lds[];

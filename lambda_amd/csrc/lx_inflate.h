@@ -3,10 +3,10 @@
 //
 // Every read stays inside in[0, n) and every write goes through the Sink, which owns the bounds of the output: whatever the bits
 // say, a malformed stream ends in a status, never in an access outside those ranges.  Bad input this catches: a reserved block
-// type, a stored length whose complement does not match, an over-subscribed or incomplete code (the single-code distance tree
-// RFC 1951 allows excepted), a code that is not in its table, a length or distance symbol beyond 285 / 29, a repeat of the code
-// lengths with nothing before it or past their number, a distance before the start of the output, output past the sink's
-// capacity, a stream that ends before its final block.
+// type, a stored length whose complement does not match, an over-subscribed or incomplete code (a distance or literal / length
+// code of a single 1-bit code, and an empty distance code, excepted as in zlib), a code that is not in its table, a length or
+// distance symbol beyond 285 / 29, a repeat of the code lengths with nothing before it or past their number, a distance before
+// the start of the output, output past the sink's capacity, a stream that ends before its final block.
 //
 // Sink: __host__ __device__ members
 //   bool put(uint8_t b)                     -- false: no room
@@ -72,7 +72,9 @@ struct Tables
 };
 
 // builds c from lens[0, n); false for an over-subscribed code, or an incomplete one -- unless `incomplete_ok` and the code has no
-// symbol or a single one of length 1 (what zlib accepts for the literal / length and distance codes)
+// symbol or a single one of length 1.  That is zlib's rule for the literal / length and the distance code (never for the
+// code-length code): dynamic_tables() passes true for both, and has refused a literal / length code without end-of-block before.
+// The bits that would select the missing half of such a code are in no table and decode() refuses them.
 __host__ __device__ inline bool build(Code & c, uint8_t const * lens, uint32_t n, bool incomplete_ok)
 {
     for (uint32_t l = 0; l < 16; ++l)
@@ -333,7 +335,7 @@ struct Inflater
         if (T.lens[256] == 0) // no end-of-block code
             return kBadCode;
         // (the distance lengths first: the literal table is rebuilt over T.lens[0, nlen) after)
-        if (!build(T.dist, T.lens + nlen, ndist, true) || !build(T.lit, T.lens, nlen, false))
+        if (!build(T.dist, T.lens + nlen, ndist, true) || !build(T.lit, T.lens, nlen, true))
             return kBadCode;
         return kOk;
     }
