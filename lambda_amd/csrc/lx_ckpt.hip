@@ -86,6 +86,12 @@ enum BtSection
 // cycles by section; then [kBtSections] iterations of the walk loop as the wavefront runs them (the longest lane's of every phase),
 // [+ 1] the same summed over lanes, [+ 2] tile phases, [+ 3] most iterations in one phase, [+ 4] cycles from kernel entry to exit
 __device__ unsigned long long lx_bt_cycles[kBtSections + 5];
+// The walk by iteration of a tile phase: [x] lanes that made iteration x + 1 (summed over phases; the last bin takes the rest), then
+// [kBtWalkBins + x] phases whose longest lane made x iterations.  The drain: [0] wave cycles the wavefronts spent after their queue ran
+// dry, [1] / [2] the first and the last wavefront's exit on the wall clock (its ticks), [3] the first entry.
+constexpr int kBtWalkBins = 32;
+__device__ unsigned long long lx_bt_walk[2 * kBtWalkBins];
+__device__ unsigned long long lx_bt_drain[4];
 // (marks stand inside lane-divergent branches too, so the sums live in LDS and the first active lane keeps them: one wavefront per workgroup)
 #define LX_BT_MARK(sec)                                                    \
     do                                                                     \
@@ -1045,29 +1051,41 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         }
         // One pass over the 16 byte positions, the cells beyond the piece first (they score 0 and change nothing but the
         // count), then the entry cell, then up the diagonal: P = sum of the scores taken so far, frozen once the cell at
-        // hand has H = 0 (L = left - P <= 0).  Per cell: index, LDS read, compare, carry, select, subtract, shift.
-        int      P = 0, cnt = 0;
-        uint32_t posbits = 0;
-        int32_t  tmb = 0;
+        // hand has H = 0 (L = left - P <= 0).  The freeze is mask arithmetic, not a compare and two selects on VCC (6.9 T lane
+        // instructions/s against 37-67 T, profiles/r03_ubench_valu_issue_rates.txt): with D = P - left a cell is taken while
+        // D < 0, i.e. under the mask D >> 31; a frozen D changes no more, so the mask stays 0 by itself.  Per cell the chain is
+        // shift, and, subtract; the masks' top bits are collected like the positive scores' and counted at the end.  The 16
+        // matrix reads stand ahead of the chain (one LDS round trip), and the match rule is one branch, not one per cell.
+        int      nv[kCkptEvery]; // (cell (i - t, j - t) is byte u = k - 1 - t)
+        uint32_t eqbits = 0;     // bit u: the cell's letters match
         bool const bs = p.bs_match_rule != 0; // (uniform)
 #pragma unroll
-        for (int u = kCkptEvery - 1; u >= 0; --u) // cell (i - t, j - t) is byte u = k - 1 - t
+        for (int u = 0; u < kCkptEvery; ++u)
+            nv[u] = (int)smat1n[(((qw[u >> 2] >> (8 * (u & 3))) & 0x1fu) << 5) | ((sw[u >> 2] >> (8 * (u & 3))) & 0x1fu)];
+        if (bs) // the bisulfite overload of computeAlignmentStats: a match scores what the letter scores with itself
         {
-            int const      d   = u >> 2, b = u & 3;
-            uint32_t const idx = (((qw[d] >> (8 * b)) & 0x1fu) << 5) | ((sw[d] >> (8 * b)) & 0x1fu);
-            int const      nv  = (int)smat1n[idx];
-            bool const     take = P < left;
-            int const      nve = take ? nv : 0;
-            cnt += take ? 1 : 0;
-            P -= nve;
-            posbits = __builtin_amdgcn_alignbit(posbits, (uint32_t)nve, 31); // bit = the score taken is positive
-            if (bs) // the bisulfite overload of computeAlignmentStats: a match scores what the letter scores with itself
-                tmb += (take && nv == (int)smat1n[(idx >> 5) * (kAlph + 1)]) ? 1 : 0;
+#pragma unroll
+            for (int u = kCkptEvery - 1; u >= 0; --u)
+            {
+                int const x = nv[u] - (int)smat1n[((qw[u >> 2] >> (8 * (u & 3))) & 0x1fu) * (kAlph + 1)]; // x | -x has its top bit set unless x == 0
+                eqbits      = __builtin_amdgcn_alignbit(eqbits, (uint32_t)~(x | -x), 31);
+            }
         }
-        int const beyond = left > 0 ? kCkptEvery - k : 0; // cells beyond the piece that were counted
-        cnt -= beyond;
-        tmb -= bs ? beyond : 0;
-        int const  L       = left - P;
+        int      D = -left; // (|left| and the 16 scores are far from 2^31)
+        uint32_t posbits = 0, takebits = 0; // bit u: the score taken is positive / the cell is taken
+#pragma unroll
+        for (int u = kCkptEvery - 1; u >= 0; --u)
+        {
+            int const msk = D >> 31; // -1: the cell is taken
+            int const nve = nv[u] & msk;
+            D -= nve;
+            takebits = __builtin_amdgcn_alignbit(takebits, (uint32_t)msk, 31);
+            posbits  = __builtin_amdgcn_alignbit(posbits, (uint32_t)nve, 31);
+        }
+        int const     beyond = left > 0 ? kCkptEvery - k : 0; // cells beyond the piece that were counted
+        int const     cnt    = __popc(takebits) - beyond;
+        int32_t const tmb    = bs ? __popc(eqbits & takebits) - beyond : 0;
+        int const  L       = -D;
         bool const stopped = cnt < k;
         // L < 0 cannot happen (L_t >= H >= 0); were it to, the piece is left to the tile DP, never guessed
         if (!(stopped ? (L == 0) : (!verify || L == Hb)))
@@ -1153,8 +1171,13 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     uint32_t cnt_sc = 0, cnt_sc_lanes = 0, cnt_tile = 0, cnt_tile_lanes = 0; // (wave-uniform)
     __shared__ unsigned long long bt_lds[kBtSections + 1]; // [kBtSections]: the clock at the previous mark
     uint32_t walk_iters = 0, walk_lane_iters = 0, walk_max = 0; // (wave-uniform)
+    __shared__ uint32_t bt_walk_lanes[kBtWalkBins], bt_walk_phases[kBtWalkBins];
+    unsigned long long  bt_dry = 0; // the clock when the queue ran dry (wave-uniform)
     if (lane == 0)
     {
+        atomicMin(&lx_bt_drain[3], (unsigned long long)wall_clock64());
+        for (int x = 0; x < kBtWalkBins; ++x)
+            bt_walk_lanes[x] = bt_walk_phases[x] = 0;
         for (int x = 0; x < kBtSections; ++x)
             bt_lds[x] = 0;
         bt_lds[kBtSections] = (unsigned long long)clock64();
@@ -1235,7 +1258,12 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                         base = atomicAdd(p.work_counter, (uint32_t)__popcll(want));
                     base = (uint32_t)__shfl((int)base, leader);
                     if ((uint64_t)base + (uint32_t)__popcll(want) >= limit)
+                    {
                         queue_empty = true;
+#ifdef LX_BT_COUNT
+                        bt_dry = (unsigned long long)clock64();
+#endif
+                    }
                     if (!have)
                     {
                         uint64_t const e = (uint64_t)base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull));
@@ -1269,6 +1297,15 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
                         atomicAdd(&lx_bt_cycles[kBtSections + 2], (unsigned long long)cnt_tile);
                         atomicMax(&lx_bt_cycles[kBtSections + 3], (unsigned long long)walk_max);
                         atomicAdd(&lx_bt_cycles[kBtSections + 4], (unsigned long long)clock64() - bt_entry);
+                        for (int x = 0; x < kBtWalkBins; ++x)
+                        {
+                            atomicAdd(&lx_bt_walk[x], (unsigned long long)bt_walk_lanes[x]);
+                            atomicAdd(&lx_bt_walk[kBtWalkBins + x], (unsigned long long)bt_walk_phases[x]);
+                        }
+                        unsigned long long const wall = (unsigned long long)wall_clock64();
+                        atomicAdd(&lx_bt_drain[0], (unsigned long long)clock64() - bt_dry);
+                        atomicMin(&lx_bt_drain[1], wall);
+                        atomicMax(&lx_bt_drain[2], wall);
                     }
 #endif
                     break;
@@ -1628,10 +1665,20 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             }
         }
         LX_BT_MARK(kBtTileScan);
+        // A lane that resumes inside a gap (mode != 0: the gap left the previous tile) has passed it already: it hands back at the
+        // gap's end like a lane that entered the gap in this tile, instead of single-stepping the diagonal behind it up to the
+        // next gap or the tile's border -- those were the long walks the wavefront's lockstep paid for.  (The nibbles alone say
+        // which cells are taken; `passed` only says where the loop hands back.)
+        passed = mode != 0;
         while (walk_ok && !done && i >= 0 && j >= j0 && i >= r_base && n < cap && !(passed && mode == 0))
         {
 #ifdef LX_BT_COUNT
-            ++my_walk;
+            {
+                uint64_t const in = __ballot(true); // iteration my_walk + 1 of the phase, the same for every lane in the loop
+                if (lane == (uint32_t)(__ffsll((unsigned long long)in) - 1))
+                    bt_walk_lanes[min(my_walk, (uint32_t)kBtWalkBins - 1)] += (uint32_t)__popcll(in);
+                ++my_walk;
+            }
 #endif
             int const      kk   = i - r_base, c = j - j0;
             int const      xw   = c >> 3;
@@ -1686,6 +1733,8 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             walk_iters += wmax;
             walk_lane_iters += (uint32_t)__builtin_amdgcn_readfirstlane((int)wsum);
             walk_max = max(walk_max, wmax);
+            if (run_tile && lane == 0)
+                bt_walk_phases[min(wmax, (uint32_t)kBtWalkBins - 1)] += 1;
         }
 #endif
     }
@@ -1831,6 +1880,27 @@ hipError_t launch_ckpt_backtrace(TraceParams const & p_in, hipStream_t stream)
             fprintf(stderr, " %s %.4g (%.1f %%);", names[x], (double)cy[x], total > 0 ? 100.0 * (double)cy[x] / total : 0.0);
         fprintf(stderr, "\nLX_BT_COUNT walk: %llu iterations of the wavefronts (%llu of single lanes) in %llu tile phases, at most %llu in one phase\n",
                 cy[kBtSections], cy[kBtSections + 1], cy[kBtSections + 2], cy[kBtSections + 3]);
+        unsigned long long wk[2 * kBtWalkBins] = {}, dr[4] = {};
+        e = hipMemcpyFromSymbol(wk, HIP_SYMBOL(lx_bt_walk), sizeof(wk));
+        if (e == hipSuccess)
+            e = hipMemcpyFromSymbol(dr, HIP_SYMBOL(lx_bt_drain), sizeof(dr));
+        unsigned long long const zw[2 * kBtWalkBins] = {}, zd[4] = {0, ~0ull, 0, ~0ull};
+        if (e == hipSuccess)
+            e = hipMemcpyToSymbol(HIP_SYMBOL(lx_bt_walk), zw, sizeof(zw));
+        if (e == hipSuccess)
+            e = hipMemcpyToSymbol(HIP_SYMBOL(lx_bt_drain), zd, sizeof(zd));
+        if (e != hipSuccess)
+            return e;
+        fprintf(stderr, "LX_BT_COUNT walk, lanes in iteration 1, 2, ... of their phase (the last bin: the rest):");
+        for (int x = 0; x < kBtWalkBins; ++x)
+            fprintf(stderr, " %llu", wk[x]);
+        fprintf(stderr, "\nLX_BT_COUNT walk, phases whose longest lane made 0, 1, ... iterations:");
+        for (int x = 0; x < kBtWalkBins; ++x)
+            fprintf(stderr, " %llu", wk[kBtWalkBins + x]);
+        // (the first launch of a process finds the minima at 0: its exit spread is not meaningful)
+        fprintf(stderr, "\nLX_BT_COUNT drain: %.4g wave cycles after the wavefronts' queue ran dry (%.1f %% of entry to exit); wall clock ticks "
+                        "from the first entry to the first / last exit: %llu / %llu\n",
+                (double)dr[0], cy[kBtSections + 4] ? 100.0 * (double)dr[0] / (double)cy[kBtSections + 4] : 0.0, dr[1] - dr[3], dr[2] - dr[3]);
     }
 #endif
     return hipGetLastError();
