@@ -165,6 +165,12 @@ enum
                                    as the reference keeps one LocalDataHolder per OpenMP thread, src/search.cpp:379-385 -- share them part
                                    by part, side by side.  0 (default) = min(CPU affinity mask, cgroup CPU quota) / LOCAL_WORLD_SIZE (the
                                    ranks of a node, one process per GPU, share its CPUs), at most 16; at most 64.  Never changes results */
+    LX_OPT_GUNZIP_CHUNK    = 15, /* lx_gunzip, plain members on the device: compressed bytes per chunk (0 = default, 64 KiB; accepted
+                                    from 32 KiB to 4 MiB).  Like the next it changes where the work runs, never the result */
+    LX_OPT_GUNZIP_PARALLEL_FROM = 16, /* lx_gunzip: DEFLATE bytes left in the input from which a plain member takes the device path
+                                         (0 = default, 8 MiB: above the measured crossover against the host thread; UINT64_MAX = never).  The input behind a
+                                         header may be many small members, so the host tries the first 64 KiB (or this many bytes,
+                                         if fewer) itself and keeps a member that ends inside them */
     LX_OPT_BAND            = 9  /* band mode -- NOT the reference's configuration (src/search_algo.hpp:1081 runs BandOff, :1102
                                    says why; _bandSize only pads the window, src/search_misc.hpp:46-50) and therefore not a
                                    parity mode: 0 (default) = full rectangle; b > 0 = only cells whose diagonal i - j (row i of
@@ -692,8 +698,52 @@ int lx_write_records_bgzf(lx_handle * h, char const * path, int format, char con
  * when h is NULL.  Every member's CRC32, ISIZE and final block are checked; a malformed one (invalid code, distance before the
  * start of the output, output past ISIZE, truncation, BSIZE past the end of the data, bytes that are no gzip member) fails the
  * call with a message that names the member and its byte offset: lx_last_error(h), or lx_last_output_error() when h is NULL.
- * lx_last_phase_ms(h, 5, ...) = device time of the decoder's kernel in the last call. */
+ * lx_last_phase_ms(h, 5, ...) = device time of the decoder's kernel in the last call.
+ *
+ * A plain member (no BC subfield, or one beyond those limits) with at least LX_OPT_GUNZIP_PARALLEL_FROM bytes of input left behind
+ * its header, and not ending inside the first 64 KiB of them, is decoded on h's device in parallel: its DEFLATE bytes are cut into chunks of LX_OPT_GUNZIP_CHUNK bytes and handled in
+ * waves of at most 512 chunks.  Per wave a finder kernel looks in every chunk but the first for the first bit where a
+ * non-final dynamic-Huffman block begins; a decode kernel runs one decoder per found chunk up to the next found bit, writing 16-bit
+ * symbols in which a back-reference into the unknown 32 KiB in front of the chunk is a marker; the host keeps the chunks that
+ * begin on the very bit their predecessor ended on and starts the next wave where the last of them ended; a window pass and a byte
+ * pass turn the symbols into bytes at their final offsets and take the CRC32.  Only bytes that passed the trailer's CRC32 and
+ * ISIZE are returned: in every other case (no block boundary in four chunks on end, a chunk that ends in a decode status or runs out of room --
+ * ten symbols per compressed byte --, a chain that keeps breaking, a CRC32, ISIZE, BSIZE or trailer difference) the member is
+ * DECLINED and decoded on the calling thread from its first byte, which gives the bytes or the error text that path gives.  The
+ * options move work between the device and the host and never change a byte or a verdict.  lx_last_phase_ms(h, 10, ...) = device
+ * time of the plain-member kernels in the last call (101, 102, 103 = its find, decode and resolve kernels alone). */
 int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out);
+
+/* Why the parallel path declined a plain member. */
+enum
+{
+    LX_GUNZIP_DECLINE_NONE        = 0,
+    LX_GUNZIP_DECLINE_NO_BOUNDARY = 1, /* no dynamic-Huffman block start found (stored or fixed-Huffman blocks only) */
+    LX_GUNZIP_DECLINE_ROOM        = 2, /* a chunk's output exceeds its room */
+    LX_GUNZIP_DECLINE_STATUS      = 3, /* a chunk that starts on a true boundary ends in a decode status */
+    LX_GUNZIP_DECLINE_CHAIN       = 4, /* the chain check keeps dropping chunks (block starts inside stored data) */
+    LX_GUNZIP_DECLINE_TRAILER     = 5, /* fewer than 8 bytes behind the final block, or a BSIZE that says otherwise */
+    LX_GUNZIP_DECLINE_CRC         = 6,
+    LX_GUNZIP_DECLINE_ISIZE       = 7
+};
+typedef struct lx_gunzip_stats
+{
+    uint64_t bgzf_members;   /* BGZF members decoded by the BGZF kernel */
+    uint64_t plain_parallel; /* plain members decoded in parallel on the device */
+    uint64_t plain_host;     /* plain members decoded on the calling thread: below the threshold, or declined */
+    uint64_t chunks;         /* chunks decoded and verified, of the members in plain_parallel and of the declined ones */
+    uint64_t chunks_dropped; /* found chunks the chain check dropped */
+    uint64_t waves;
+    uint64_t declined;       /* plain members the parallel path began and gave to the host */
+    uint64_t bytes_up;       /* bytes the plain path moved to the device ... */
+    uint64_t bytes_down;     /* ... and from it */
+    int32_t  last_decline;   /* LX_GUNZIP_DECLINE_* of the last declined member */
+    int32_t  reserved;
+} lx_gunzip_stats;
+/* The counts of h's last lx_gunzip call. */
+int lx_last_gunzip_stats(lx_handle const * h, lx_gunzip_stats * stats);
+/* A decline reason in words ("no boundary", "room", ...). */
+char const * lx_gunzip_decline_text(int reason);
 
 /* ---- taxonomy of an index (mkindex -m / -x: src/mkindex_algo.hpp:68-107, :277-598, src/mkindex_misc.hpp:69-144) ----------- */
 /* Every non-overlapping match of the reference's accession regex in text[0, n) (UniProt, NCBI nucleotide / protein / WGS / MGA,
@@ -867,7 +917,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
  * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*),
  * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top),
- * 8 = the word table's kernels (lx_index_build on a handle), 9 = the seeding kernel (lx_seed_queries on a handle). */
+ * 8 = the word table's kernels (lx_index_build on a handle), 9 = the seeding kernel (lx_seed_queries on a handle),
+ * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

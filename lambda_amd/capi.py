@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "lx_widen_and_preprocess", "lx_postprocess_records", "lx_postprocess_records_dev", "lx_iterate_matches_dev_top", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
-    "lx_write_records_bgzf", "lx_gunzip", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
+    "lx_write_records_bgzf", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
     "lx_index_build", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
@@ -49,6 +49,10 @@ LX_OPT_MQ_SWEEP = 11
 LX_OPT_ITERATE_RECORDS = 13
 LX_OPT_HOST_THREADS = 14
 LX_OPT_ADAPT_PERMILLE = 12
+LX_OPT_GUNZIP_CHUNK = 15
+LX_OPT_GUNZIP_PARALLEL_FROM = 16
+OPT_GUNZIP_WAVE_TEST = 1017  # not part of the ABI (lx_internal.h): chunks per wave, for the tests of lx_gunzip's waves
+LX_GUNZIP_NEVER = (1 << 64) - 1  # LX_OPT_GUNZIP_PARALLEL_FROM: no plain member takes the device path
 
 
 class Karlin(C.Structure):
@@ -81,6 +85,12 @@ BLAST_MATCH_DTYPE = np.dtype([
 
 class RecordStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("qrys_with_hit", "hits_duplicate2", "hits_abundant", "hits_final", "pairs")]
+
+
+class GunzipStats(C.Structure):
+    """lx_gunzip_stats: where the members of the last lx_gunzip call were decoded."""
+    _fields_ = [(n, C.c_uint64) for n in ("bgzf_members", "plain_parallel", "plain_host", "chunks", "chunks_dropped", "waves", "declined",
+                                          "bytes_up", "bytes_down")] + [("last_decline", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TaxTree(C.Structure):
@@ -276,6 +286,9 @@ def load():
     lib.lx_bgzf_bound.restype = u64
     lib.lx_bgzf_compress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), i32]
     lib.lx_gunzip.argtypes = [vp, vp, u64, C.POINTER(vp)]
+    lib.lx_last_gunzip_stats.argtypes = [vp, C.POINTER(GunzipStats)]
+    lib.lx_gunzip_decline_text.argtypes = [i32]
+    lib.lx_gunzip_decline_text.restype = C.c_char_p
     lib.lx_find_accessions.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
     lib.lx_taxmap_create.argtypes = [vp, i32, vp, vp, u64, u64, C.c_uint32, C.POINTER(vp)]
     lib.lx_taxmap_feed.argtypes = [vp, vp, u64]
@@ -410,8 +423,9 @@ def bgzf_bound(n: int) -> int:
 
 
 def gunzip(handle: "Handle | None", data: bytes) -> bytes:
-    """lx_gunzip: the bytes of a gzip stream of one or more members.  BGZF members are decoded on the handle's device, every other
-    member on this thread; handle None = every member on the host.  Malformed input raises LambdaExtError(LX_EINVAL) with the
+    """lx_gunzip: the bytes of a gzip stream of one or more members.  BGZF members are decoded on the handle's device, and so are
+    plain members of LX_OPT_GUNZIP_PARALLEL_FROM bytes or more (in chunks, in parallel; Handle.last_gunzip_stats() says what went
+    where); every other member on this thread; handle None = every member on the host.  Malformed input raises LambdaExtError(LX_EINVAL) with the
     library's message, which names the member and its byte offset."""
     lib = load()
     buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
@@ -1056,6 +1070,13 @@ class Handle:
         """lx_write_records_bgzf: header, records and footer (footer_records >= 0) of `fmt`, BGZF-compressed into `path`."""
         args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
         self._check(self.lib.lx_write_records_bgzf(self.h, str(path).encode(), fmt, program.encode(), *args, footer_records))
+
+    def last_gunzip_stats(self) -> GunzipStats:
+        """lx_last_gunzip_stats: the counts of the last gunzip(handle, ...); .decline_text is the last decline reason in words."""
+        st = GunzipStats()
+        self._check(self.lib.lx_last_gunzip_stats(self.h, C.byref(st)))
+        st.decline_text = self.lib.lx_gunzip_decline_text(st.last_decline).decode()
+        return st
 
     def last_kernel_name(self) -> str:
         return self.lib.lx_last_kernel_name(self.h).decode()

@@ -133,10 +133,12 @@ struct InputText
     std::string text;
     double      msGunzip = 0; // decompression time (0: the file was not compressed)
     bool        onDevice = false;
+    uint64_t    plainMembers = 0, plainChunks = 0; // plain members lx_gunzip decoded in parallel on the device, and their chunks
 };
 
 // the file's bytes, decompressed by lx_gunzip when they start with the gzip magic: BGZF members on `device` (< 0: every member on the
-// host), other members on this thread.  One handle per call, so that the two reader threads never share one.
+// host) and so the large plain members, in parallel chunks; other members on this thread.  One handle per call, so that the two
+// reader threads never share one.
 InputText readInput(std::string const & path, int device)
 {
     std::FILE * f = std::fopen(path.c_str(), "rb");
@@ -170,6 +172,12 @@ InputText readInput(std::string const & path, int device)
     r.text.assign(reinterpret_cast<char const *>(lx_bytes_data(out)), lx_bytes_size(out));
     r.msGunzip = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     r.onDevice = h != nullptr;
+    lx_gunzip_stats st;
+    if (h && lx_last_gunzip_stats(h, &st) == LX_OK)
+    {
+        r.plainMembers = st.plain_parallel;
+        r.plainChunks  = st.chunks;
+    }
     return r;
 }
 
@@ -1118,6 +1126,7 @@ int main(int argc, char ** argv)
             throw std::runtime_error(loadError);
         double const msGunzip = std::max(qIn.msGunzip, dIn.msGunzip);
         bool const   gunzipOnDevice = qIn.onDevice || dIn.onDevice;
+        uint64_t const plainMembers = qIn.plainMembers + dIn.plainMembers, plainChunks = qIn.plainChunks + dIn.plainChunks;
         std::string const reduction = !fromIndex ? opt.reduction : ifo.redAlph == kAlphLi10 ? "li10" : ifo.redAlph == kAlphMurphy10 ? "murphy10" : "none";
         // searchp with nucleotide queries is BLASTX: six translated frames per query against the protein database
         bool const    blastx = !mk && prot && (opt.qryAlphabet == "dna5" || (opt.qryAlphabet == "auto" && looksLikeDna(qIn.text, opt.query)));
@@ -1184,7 +1193,8 @@ int main(int argc, char ** argv)
                 id.resize(std::min(id.size(), id.find_first_of(" \t")));
         double const      msRead = msSince(tStart);
         std::string const gunzipNote = msGunzip > 0 ? " (gzip decompression " + std::string(gunzipOnDevice ? "of BGZF on the GPU " : "on the host ") +
-                                                          std::to_string((long)(msGunzip + 0.5)) + ")"
+                                                          std::to_string((long)(msGunzip + 0.5)) +
+                                                          (plainMembers ? ", " + std::to_string(plainMembers) + " plain member(s) in " + std::to_string(plainChunks) + " chunks on the GPU" : std::string()) + ")"
                                                     : std::string();
         unsigned const nThreads = opt.threads > 0 ? (unsigned)opt.threads : grantedThreads();
 

@@ -1200,6 +1200,17 @@ int lx_set_option(lx_handle * h, int option, uint64_t value)
                 return fail(h, LX_EINVAL, "LX_OPT_HOST_THREADS: at most %u", lxi::HostPool::kMaxParts);
             lxi::HostPool::instance().set_width((unsigned)value); // (the host threads are the process's, not the handle's)
             return LX_OK;
+        case LX_OPT_GUNZIP_CHUNK:
+            if (value && (value < (32u << 10) || value > (4u << 20)))
+                return fail(h, LX_EINVAL, "LX_OPT_GUNZIP_CHUNK: 0, or 32 KiB to 4 MiB");
+            h->opt_gunzip_chunk = value;
+            return LX_OK;
+        case LX_OPT_GUNZIP_PARALLEL_FROM: h->opt_gunzip_from = value; return LX_OK;
+        case lxi::kOptGunzipWaveTest:
+            if (value == 1 || value > 512)
+                return fail(h, LX_EINVAL, "chunks per wave: 0, or 2 to 512");
+            h->gunzip_wave = value;
+            return LX_OK;
         case LX_OPT_BAND:
             if (value > (1u << 20))
                 return fail(h, LX_EINVAL, "LX_OPT_BAND: at most 2^20 diagonals on either side");
@@ -1229,6 +1240,8 @@ int lx_get_option(lx_handle const * h, int option, uint64_t * value)
         case LX_OPT_ADAPT_PERMILLE: *value = h->opt_adapt; return LX_OK;
         case LX_OPT_ITERATE_RECORDS: *value = h->opt_iterate_records; return LX_OK;
         case LX_OPT_HOST_THREADS: *value = lxi::HostPool::instance().width(); return LX_OK;
+        case LX_OPT_GUNZIP_CHUNK: *value = h->opt_gunzip_chunk; return LX_OK;
+        case LX_OPT_GUNZIP_PARALLEL_FROM: *value = h->opt_gunzip_from; return LX_OK;
         default: return LX_EINVAL;
     }
 }
@@ -1441,6 +1454,12 @@ int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches)
             LX_HIP(h, hipEventElapsedTime(&t, pe.a, pe.b));
             total += t;
             ++cnt;
+        }
+    for (int i = 0; i < 3; ++i) // (lx_gunzip's plain-member kernels: summed per wave by the call itself)
+        if (phase == 10 || phase == 101 + i)
+        {
+            total += h->gunzip.phase_ms[i];
+            cnt += h->gunzip.phase_launches[i];
         }
     *ms = total;
     if (launches)

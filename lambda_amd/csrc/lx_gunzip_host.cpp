@@ -7,10 +7,16 @@
 // pinned lane, the kernel, its status words down to the pinned lane, its output down into the result itself.  The host fills the
 // other pinned lane with the next chunk while the device decodes this one.  A member without BSIZE ends where its DEFLATE stream
 // ends, so it is decoded here, in order, before the walk goes on; so is every member when no handle is given.
+//
+// A plain member with enough input behind its header goes to the device first (parallel_member, lx_pgunzip.h / .hip): its DEFLATE
+// bytes in waves of chunks -- find, decode with markers, chain check here, resolve -- and its bytes down into the result.  Nothing
+// of it counts before the trailer's CRC32 and ISIZE agree; in every other case the member is declined, the result is where it was,
+// and host_member decodes it from its first byte: today's bytes or today's error text.
 #include "lx_crc32.h"
 #include "lx_gunzip.h"
 #include "lx_inflate.h"
 #include "lx_internal.h"
+#include "lx_pgunzip.h"
 
 #include <string>
 #include <vector>
@@ -21,6 +27,13 @@ namespace
 {
 
 constexpr uint32_t kChunkMembers = 512; // 32 MiB of input and output at most per chunk
+
+// the parallel path of a plain member (DESIGN 4.10 has the sums)
+constexpr uint64_t kPlainChunk     = 64u << 10; // compressed bytes per chunk unless LX_OPT_GUNZIP_CHUNK says otherwise
+constexpr uint32_t kPlainWave      = 512;       // chunks per wave at most: two decoders on each of 256 CUs
+constexpr uint64_t kPlainWaveBytes = 32u << 20; // ... and compressed bytes per wave at most
+constexpr uint64_t kPlainFrom      = 8u << 20;  // LX_OPT_GUNZIP_PARALLEL_FROM's default: above the measured crossover
+constexpr uint64_t kPlainProbe     = 64u << 10; // DEFLATE bytes the host tries first: a member that ends inside them stays on the host
 
 struct CrcTable
 {
@@ -158,13 +171,19 @@ struct Walk
         return LX_EINVAL;
     }
 
-    // a member decoded here; *next = the byte after its trailer
-    int host_member(uint64_t k, uint64_t at, Header const & hd, uint64_t * next)
+    // a member decoded here; *next = the byte after its trailer.  With a limit (the probe in front of the parallel path) the decoder
+    // sees that many DEFLATE bytes only, and a stream that does not end inside them leaves the result where it was: *small = false
+    int host_member(uint64_t k, uint64_t at, Header const & hd, uint64_t * next, uint64_t limit = UINT64_MAX, bool * small = nullptr)
     {
         lx::inflate::Tables                            T;
         HostSink                                   sink{res, res.size};
-        lx::inflate::Inflater<HostSink, uint64_t>      inf(in + hd.end, n - hd.end, sink, T);
+        lx::inflate::Inflater<HostSink, uint64_t>      inf(in + hd.end, std::min(n - hd.end, limit), sink, T);
         uint32_t const                             st = inf.run();
+        if (small && !(*small = st == lx::inflate::kOk))
+        {
+            res.size = sink.base;
+            return LX_OK;
+        }
         if (st != lx::inflate::kOk)
             return error(k, at, lx::inflate::status_text(st));
         uint64_t const t = hd.end + inf.consumed();
@@ -179,6 +198,162 @@ struct Walk
             return error(k, at, "BSIZE does not match the member's DEFLATE stream");
         *next = t + 8;
         return LX_OK;
+    }
+
+    // a plain member through the device; *reason = 0: done, *next = the byte after its trailer; else declined (the result untouched)
+    int parallel_member(uint64_t at, Header const & hd, uint64_t * next, int * reason)
+    {
+        namespace pg = lx::pgunzip;
+        auto &                G = h->gunzip;
+        lx_gunzip_stats &     S = G.stats;
+        uint8_t const * const d = in + hd.end;
+        uint64_t const        dlen = n - hd.end;
+        uint64_t const        C    = h->opt_gunzip_chunk ? h->opt_gunzip_chunk : kPlainChunk;
+        uint32_t const        W    = (uint32_t)std::min<uint64_t>(h->gunzip_wave ? h->gunzip_wave : kPlainWave, std::max<uint64_t>(2, kPlainWaveBytes / C));
+        uint32_t const        room = (uint32_t)(pg::kRoomPerByte * C);
+        auto decline = [&](int why)
+        {
+            *reason = why;
+            return LX_OK;
+        };
+        *reason = LX_GUNZIP_DECLINE_NONE;
+        int rc = bind(h);
+        if (rc)
+            return rc;
+        hipStream_t const s      = h->stream;
+        uint32_t const    wslots = (uint32_t)std::min<uint64_t>(W, (dlen + C - 1) / C);
+        size_t const      slot_bytes = sizeof(uint64_t) + sizeof(pg::ChunkResult);
+        if ((rc = ensure(h, G.d_pin, (size_t)std::min<uint64_t>(dlen, (uint64_t)(wslots + 1) * C))) || (rc = ensure(h, G.d_slots, wslots * slot_bytes)) ||
+            (rc = ensure(h, G.d_sym, (size_t)wslots * room * 2)) || (rc = ensure(h, G.d_win, (size_t)(wslots + 1) * pg::kWindow)) ||
+            (rc = ensure(h, G.d_ver, wslots * sizeof(pg::Verified))) || (rc = ensure(h, G.d_crc, 8)) ||
+            (rc = ensure_pinned(h, G.p_slots, wslots * slot_bytes, kRoom)) || (rc = ensure_pinned(h, G.p_ver, wslots * sizeof(pg::Verified), kRoom)) ||
+            (rc = ensure_pinned(h, G.p_crc, 8, kExact)))
+            return rc;
+        // (room for the whole member at once where the input's last four bytes can be its ISIZE: a hint, never a fact)
+        if (n >= 4 && le32(in + n - 4) <= 1032 * dlen)
+            res.reserve(le32(in + n - 4));
+        uint64_t start_bit = 0, out_len = 0, verified = 0, dropped = 0;
+        uint32_t crc_raw = 0, carry = 0;
+        std::vector<uint32_t> ver(wslots);
+        for (bool first = true;; first = false)
+        {
+            uint64_t const base   = start_bit >> 3;
+            uint64_t const remain = dlen - base;
+            if (remain == 0)
+                return decline(LX_GUNZIP_DECLINE_STATUS);
+            uint32_t const nslots = (uint32_t)std::min<uint64_t>(W, (remain + C - 1) / C);
+            uint64_t const wave_n = std::min<uint64_t>(remain, (uint64_t)(nslots + 1) * C);
+            auto * const   d_found = static_cast<uint64_t *>(G.d_slots.ptr);
+            auto * const   d_res   = reinterpret_cast<pg::ChunkResult *>(d_found + nslots);
+            auto * const   p_found = static_cast<uint64_t *>(G.p_slots.ptr);
+            auto * const   p_res   = reinterpret_cast<pg::ChunkResult *>(p_found + nslots);
+            pg::WaveParams wp{};
+            wp.in         = static_cast<uint8_t const *>(G.d_pin.ptr);
+            wp.n          = (uint32_t)wave_n;
+            wp.chunk      = (uint32_t)C;
+            wp.nslots     = nslots;
+            wp.room       = room;
+            wp.first_wave = first;
+            wp.stop_bit   = 8 * std::min<uint64_t>(wave_n, (uint64_t)nslots * C);
+            wp.found      = d_found;
+            wp.res        = d_res;
+            wp.sym        = static_cast<uint16_t *>(G.d_sym.ptr);
+            p_found[0]    = start_bit - 8 * base;
+            LX_HIP(h, hipMemcpyAsync(G.d_pin.ptr, d + base, wave_n, hipMemcpyHostToDevice, s));
+            LX_HIP(h, hipMemcpyAsync(d_found, p_found, 8, hipMemcpyHostToDevice, s));
+            // (three events per wave, read and given back at the wave's end: a member of any length keeps its phase times)
+            size_t const   ev_mark = h->ev_pool_used;
+            hipEvent_t const e0 = pool_event(h), e1 = pool_event(h), e2 = pool_event(h), e3 = pool_event(h), e4 = pool_event(h);
+            if (!e0 || !e1 || !e2 || !e3 || !e4)
+                return fail(h, LX_EHIP, "lx_gunzip: no event");
+            LX_HIP(h, hipEventRecord(e0, s));
+            LX_HIP(h, pg::launch_find(wp, s));
+            LX_HIP(h, hipEventRecord(e1, s));
+            LX_HIP(h, pg::launch_decode(wp, s));
+            LX_HIP(h, hipEventRecord(e2, s));
+            LX_HIP(h, hipMemcpyAsync(p_found, d_found, nslots * slot_bytes, hipMemcpyDeviceToHost, s));
+            LX_HIP(h, hipStreamSynchronize(s));
+            S.bytes_up += wave_n;
+            ++S.waves;
+            pg::Chain const c = pg::chain(p_found, p_res, nslots, ver.data());
+            if (c.nver == 0)
+                return decline(p_res[0].status == pg::kChunkNoBoundary          ? LX_GUNZIP_DECLINE_NO_BOUNDARY
+                               : p_res[0].status == lx::inflate::kOutputFull ? LX_GUNZIP_DECLINE_ROOM
+                                                                             : LX_GUNZIP_DECLINE_STATUS);
+            S.chunks += c.nver;
+            S.chunks_dropped += c.dropped;
+            verified += c.nver;
+            dropped += c.dropped;
+            if (pg::chain_gives_up(dropped, verified))
+                return decline(LX_GUNZIP_DECLINE_CHAIN);
+            // ---- resolve: the verified chunks' places, windows, bytes
+            auto *   pv = static_cast<pg::Verified *>(G.p_ver.ptr);
+            uint64_t wave_len = 0;
+            uint32_t longest = 0;
+            for (uint32_t v = 0; v < c.nver; ++v)
+            {
+                pg::ChunkResult const & r = p_res[ver[v]];
+                pv[v] = pg::Verified{(uint64_t)ver[v] * room, wave_len, r.count, (uint32_t)std::min<uint64_t>(pg::kWindow, out_len + wave_len)};
+                wave_len += r.count;
+                longest = std::max(longest, r.count);
+            }
+            if ((rc = ensure(h, G.d_bytes, (size_t)wave_len)))
+                return rc;
+            auto * const win = static_cast<uint8_t *>(G.d_win.ptr);
+            if (!first && carry) // (the window behind the last wave's last chunk lies in front of this wave's first)
+                LX_HIP(h, hipMemcpyAsync(win, win + (uint64_t)carry * pg::kWindow, pg::kWindow, hipMemcpyDeviceToDevice, s));
+            LX_HIP(h, hipMemsetAsync(G.d_crc.ptr, 0, 8, s));
+            LX_HIP(h, hipMemcpyAsync(G.d_ver.ptr, pv, c.nver * sizeof(pg::Verified), hipMemcpyHostToDevice, s));
+            pg::ResolveParams rp{};
+            rp.sym      = static_cast<uint16_t const *>(G.d_sym.ptr);
+            rp.ver      = static_cast<pg::Verified const *>(G.d_ver.ptr);
+            rp.nver     = c.nver;
+            rp.segs     = (longest + pg::kWindow - 1) / pg::kWindow;
+            rp.win      = win;
+            rp.out      = static_cast<uint8_t *>(G.d_bytes.ptr);
+            rp.wave_len = (uint32_t)wave_len;
+            rp.crc      = static_cast<uint32_t *>(G.d_crc.ptr);
+            LX_HIP(h, hipEventRecord(e3, s));
+            LX_HIP(h, pg::launch_resolve(rp, s));
+            LX_HIP(h, hipEventRecord(e4, s));
+            carry = c.nver;
+            uint8_t * const dst = res.reserve(out_len + wave_len) + out_len; // (no copy is in flight: the last wave's was waited for)
+            if (wave_len)
+                LX_HIP(h, hipMemcpyAsync(dst, G.d_bytes.ptr, wave_len, hipMemcpyDeviceToHost, s));
+            LX_HIP(h, hipMemcpyAsync(G.p_crc.ptr, G.d_crc.ptr, 8, hipMemcpyDeviceToHost, s));
+            LX_HIP(h, hipStreamSynchronize(s));
+            S.bytes_down += wave_len;
+            {
+                hipEvent_t const ev[3][2] = {{e0, e1}, {e1, e2}, {e3, e4}};
+                for (int i = 0; i < 3; ++i)
+                {
+                    float ms = 0.f;
+                    LX_HIP(h, hipEventElapsedTime(&ms, ev[i][0], ev[i][1]));
+                    G.phase_ms[i] += ms;
+                    ++G.phase_launches[i];
+                }
+                h->ev_pool_used = ev_mark;
+            }
+            uint32_t const * const pc = static_cast<uint32_t const *>(G.p_crc.ptr);
+            if (pc[1]) // a distance before the start of the member's output
+                return decline(LX_GUNZIP_DECLINE_STATUS);
+            crc_raw = lx::mul_mod_p(pg::x_pow_8n64(wave_len), crc_raw) ^ pc[0];
+            out_len += wave_len;
+            if (c.final)
+            {
+                uint64_t const t = hd.end + base + (c.end_bit + 7) / 8;
+                if (n - t < 8 || (hd.bsize >= 0 && t + 8 != at + (uint64_t)hd.bsize + 1))
+                    return decline(LX_GUNZIP_DECLINE_TRAILER);
+                if ((crc_raw ^ lx::mul_mod_p(pg::x_pow_8n64(out_len), 0xffffffffu) ^ 0xffffffffu) != le32(in + t))
+                    return decline(LX_GUNZIP_DECLINE_CRC);
+                if ((uint32_t)out_len != le32(in + t + 4))
+                    return decline(LX_GUNZIP_DECLINE_ISIZE);
+                res.size += out_len;
+                *next = t + 8;
+                return LX_OK;
+            }
+            start_bit = 8 * base + c.end_bit;
+        }
     }
 
     // a run of BGZF members (offsets absolute in `in`, output from res.size on) through the device
@@ -286,6 +461,7 @@ struct Walk
                 return rc;
         }
         res.size += total;
+        h->gunzip.stats.bgzf_members += nm;
         return LX_OK;
     }
 
@@ -342,8 +518,36 @@ struct Walk
             if (rc)
                 return rc;
             uint64_t next = 0;
+            uint64_t const from = h ? (h->opt_gunzip_from ? h->opt_gunzip_from : kPlainFrom) : 0;
+            if (h && from != UINT64_MAX && n - hd.end >= from)
+            {
+                // (what follows the header may be many small members: one whose stream ends inside kPlainProbe bytes, or before `from`
+                // bytes with its trailer, is the host's.  The probe is what a large member pays: 64 KiB of host decoding, ~0.4 ms)
+                bool small = false;
+                if (from > 9 && (rc = host_member(k, at, hd, &next, std::min(from - 9, kPlainProbe), &small)))
+                    return rc;
+                if (small)
+                {
+                    ++h->gunzip.stats.plain_host;
+                    at = next;
+                    continue;
+                }
+                int why = 0;
+                if ((rc = parallel_member(at, hd, &next, &why)))
+                    return rc;
+                if (!why)
+                {
+                    ++h->gunzip.stats.plain_parallel;
+                    at = next;
+                    continue;
+                }
+                ++h->gunzip.stats.declined;
+                h->gunzip.stats.last_decline = why;
+            }
             if ((rc = host_member(k, at, hd, &next)))
                 return rc;
+            if (h)
+                ++h->gunzip.stats.plain_host;
             at = next;
         }
         return flush();
@@ -370,6 +574,9 @@ int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out)
     {
         h->phase_ev.clear();
         h->ev_pool_used = 0;
+        h->gunzip.stats = lx_gunzip_stats{};
+        for (int i = 0; i < 3; ++i)
+            h->gunzip.phase_ms[i] = 0.f, h->gunzip.phase_launches[i] = 0;
     }
     Result r;
     int    rc = LX_OK;
@@ -390,6 +597,30 @@ int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out)
         return LX_ENOMEM;
     }
     return rc;
+}
+
+int lx_last_gunzip_stats(lx_handle const * h, lx_gunzip_stats * stats)
+{
+    if (!h || !stats)
+        return LX_EINVAL;
+    *stats = h->gunzip.stats;
+    return LX_OK;
+}
+
+char const * lx_gunzip_decline_text(int reason)
+{
+    switch (reason)
+    {
+    case LX_GUNZIP_DECLINE_NONE: return "none";
+    case LX_GUNZIP_DECLINE_NO_BOUNDARY: return "no boundary";
+    case LX_GUNZIP_DECLINE_ROOM: return "room";
+    case LX_GUNZIP_DECLINE_STATUS: return "decode status";
+    case LX_GUNZIP_DECLINE_CHAIN: return "chain";
+    case LX_GUNZIP_DECLINE_TRAILER: return "trailer";
+    case LX_GUNZIP_DECLINE_CRC: return "CRC32";
+    case LX_GUNZIP_DECLINE_ISIZE: return "ISIZE";
+    default: return "?";
+    }
 }
 
 } // extern "C"

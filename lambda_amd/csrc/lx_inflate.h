@@ -340,28 +340,48 @@ struct Inflater
         return kOk;
     }
 
+    // one block, header included; last = its BFINAL bit
+    __host__ __device__ uint32_t block(uint32_t & last)
+    {
+        uint32_t type, rc;
+        if (!take(1, last) || !take(2, type))
+            return kTruncated;
+        if (type == 0)
+            rc = stored();
+        else if (type == 1)
+            rc = fixed_tables() ? kBadCode : codes();
+        else if (type == 2)
+            rc = (rc = dynamic_tables()) ? rc : codes();
+        else
+            rc = kBadBlockType;
+        return rc;
+    }
+
     // the whole stream up to and including its final block
     __host__ __device__ uint32_t run()
     {
         for (;;)
         {
-            uint32_t last, type, rc;
-            if (!take(1, last) || !take(2, type))
-                return kTruncated;
-            if (type == 0)
-                rc = stored();
-            else if (type == 1)
-                rc = fixed_tables() ? kBadCode : codes();
-            else if (type == 2)
-                rc = (rc = dynamic_tables()) ? rc : codes();
-            else
-                rc = kBadBlockType;
-            if (rc)
+            uint32_t last, rc;
+            if ((rc = block(last)))
                 return rc;
             if (last)
                 return kOk;
         }
     }
+
+    // decoding goes on at bit b of the input (lx_pgunzip.h: a chunk in the middle of a stream); beyond the input every take fails
+    __host__ __device__ void seek_bit(uint64_t b)
+    {
+        pos   = (b >> 3) < (uint64_t)n ? (Index)(b >> 3) : n;
+        bits  = 0;
+        nbits = 0;
+        uint32_t v;
+        if ((b & 7) && !take((uint32_t)(b & 7), v))
+            pos = n, nbits = 0, bits = 0;
+    }
+    // the bit of the input the next take reads
+    __host__ __device__ uint64_t bit_pos() const { return 8 * (uint64_t)pos - nbits; }
 
     // input bytes the stream took (its last byte counted whole); valid after run() returned kOk
     __host__ __device__ Index consumed() const { return pos - nbits / 8; }

@@ -238,7 +238,17 @@ struct lx_handle
     {
         DevBuf d_in, d_mem, d_status, d_out;
         Pinned p_in[2], p_mem[2], p_status[2];
+        // a plain member in parallel (lx_pgunzip.hip): one wave's input, found bits + chunk results, symbol pool, windows, verified
+        // chunks, bytes, CRC words; what the host reads of a wave in a pinned block
+        DevBuf d_pin, d_slots, d_sym, d_win, d_ver, d_bytes, d_crc;
+        Pinned p_slots, p_ver, p_crc;
+        lx_gunzip_stats stats{}; // of the last lx_gunzip call (lx_last_gunzip_stats)
+        float           phase_ms[3] = {0, 0, 0};      // ... its find, decode and resolve kernels (lx_last_phase_ms 101..103, 10 = all)
+        int             phase_launches[3] = {0, 0, 0};
     } gunzip;
+    uint64_t opt_gunzip_chunk = 0; // LX_OPT_GUNZIP_CHUNK (0 = default)
+    uint64_t opt_gunzip_from  = 0; // LX_OPT_GUNZIP_PARALLEL_FROM (0 = default)
+    uint64_t gunzip_wave      = 0; // kOptGunzipWaveTest: chunks per wave (0 = default), so that a test reaches a wave's edges with a megabyte
     // lx_seed_queries (lx_seed_host.cpp): a call's queries, reads, decline flags, counters, the two scoring matrices, subjects the
     // caller handed in; the match block of the last freed result, kept for the next call
     struct Seed
@@ -249,6 +259,9 @@ struct lx_handle
 
 namespace lxi
 {
+
+// not part of the ABI: lx_set_option takes it for the tests of lx_gunzip's waves (2..512 chunks per wave, 0 = default)
+constexpr int kOptGunzipWaveTest = 1017;
 
 int        fail(lx_handle * h, int code, char const * fmt, ...);
 hipEvent_t pool_event(lx_handle * h);
