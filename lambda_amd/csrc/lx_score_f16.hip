@@ -90,10 +90,17 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     using Geo = PairGeo<G, C>;
     extern __shared__ uint32_t lds[];
 
+    static_assert(G == 8 || G == 16, "lane groups of half a DPP row or a whole one");
+    // G = 8: the two lane groups of a 16-lane DPP row sit on its even and its odd lanes.  A strip's left neighbour is then
+    // row_shr:2, and the first lane of either group has no source lane in its row: with bound_ctrl off it keeps the DPP's
+    // `old` operand, so the left boundary needs no select (G = 16: row_shr:1 does the same).  kGs = lanes between two strips.
+    constexpr int kGs     = G == 8 ? 2 : 1;
+    constexpr int kDppShr = 0x110 + kGs; // row_shr:kGs
     int const  lane     = threadIdx.x;
-    int const  grp      = lane / G;
-    int const  g        = lane % G;
+    int const  g        = G == 8 ? (lane & 15) >> 1 : lane % G;
+    int const  grp      = G == 8 ? ((lane >> 4) << 1) | (lane & 1) : lane / G;
     bool const is_first = (g == 0);
+    auto lane_of = [](int group, int strip) { return G == 8 ? ((group >> 1) << 4) | (strip << 1) | (group & 1) : group * G + strip; };
 
     uint64_t const pair   = (uint64_t)blockIdx.x * Geo::kGroups + grp;
     uint64_t const eA     = 2 * pair, eB = 2 * pair + 1;
@@ -133,14 +140,18 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     // p.pair_share lane groups (0 = all of them) use one LDS profile: the extensions of such a block share the query
     int const share_g = (p.pair_share > 0 && p.pair_share < Geo::kGroups) ? p.pair_share : Geo::kGroups;
     int const blk     = grp / share_g;
+    uint64_t  q_blk;  // the block's query as its first lane has it: the profile below is built from these by all of its lanes
+    int       lq_blk;
     {
         // the caller promised one query per block: verify against the block's first lane, fail loudly otherwise
-        int const      leader = blk * share_g * G;
+        int const      leader = lane_of(blk * share_g, 0);
         uint64_t const q0     = ((uint64_t)(uint32_t)__shfl((int)(q_off >> 32), leader) << 32) | (uint32_t)__shfl((int)(uint32_t)q_off, leader);
         int const      l0     = __shfl(lq, leader);
         bool const     lead_in = __shfl(actA ? 1 : 0, leader) != 0;
         if (lead_in && ((actA && (q_off != q0 || lq != l0)) || (actB && (q_offB != q0 || lqB != l0))))
             atomicExch(p.err, 2);
+        q_blk  = q0;
+        lq_blk = l0;
     }
 
     int ls_max = max(lsA, lsB);
@@ -172,7 +183,7 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
         }
 #pragma unroll
         for (int off = G / 2; off >= 1; off >>= 1)
-            bound += __shfl_xor(bound, off);
+            bound += __shfl_xor(bound, off * kGs);
     }
     // (every group summed its own query; one block over the limit sends the whole wavefront to the fix-up launch)
     bool too_big = __ballot((lq > Geo::kPanel) || (bound + (-ge) * (steps + G + 2) + sc->smax + 2 > 2046)) != 0;
@@ -208,41 +219,42 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     }
 
     // ---- profile: prof[t][g][h] = (s(q_col, t) - ge) as half, lane-contiguous
+    // Built by every lane of the block that shares it.  A unit of work is one dword column d of one strip (two query columns)
+    // for eight letters: one 16-byte load from the matrix row of either column, eight permutes, eight LDS writes.  The units are
+    // dealt round robin; letters at or beyond nrows are not built (the small alphabets have one group of eight).
     int const slot_dw = blk * (nrows * Geo::kRowDw);
-    if (grp % share_g == 0)
     {
+        constexpr int  kStripDw = G * Geo::kUsedDw;           // (strip, dword column) pairs of the panel
+        int const      units    = ((nrows + 7) >> 3) * kStripDw;
+        int const      in_blk   = (grp - blk * share_g) * G + g; // this lane among the block's share_g * G
+        uint8_t const * qb      = p.q_res + q_blk;             // the block's query (every lane builds for every strip)
 #pragma unroll 1
-        for (int d = 0; d < Geo::kUsedDw; ++d)
+        for (int u = in_blk; u < units; u += share_g * G)
         {
-            uint32_t rows[2][16];
+            int const x  = u / kStripDw;                      // letters 8 x .. 8 x + 7
+            int const sd = u - x * kStripDw;
+            int const sg = sd / Geo::kUsedDw, d = sd - sg * Geo::kUsedDw;
+            uint4     rows[2];
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc)
             {
                 int const c  = 2 * d + cc;
-                int const j  = col0 + c;
+                int const j  = sg * C + c;
                 uint32_t  ql = kAlph - 1;
-                if (c < C && j < lq)
-                    ql = q[j] & (kAlph - 1);
-                uint4 const * mrow = reinterpret_cast<uint4 const *>(sc->mat_h + ql * kAlph);
-#pragma unroll
-                for (int x = 0; x < 4; ++x)
-                {
-                    uint4 const v      = mrow[x];
-                    rows[cc][4 * x + 0] = v.x;
-                    rows[cc][4 * x + 1] = v.y;
-                    rows[cc][4 * x + 2] = v.z;
-                    rows[cc][4 * x + 3] = v.w;
-                }
+                if (c < C && j < lq_blk)
+                    ql = qb[j] & (kAlph - 1);
+                rows[cc] = reinterpret_cast<uint4 const *>(sc->mat_h + ql * kAlph)[x];
             }
-            uint32_t * dst = lds + slot_dw + g * Geo::kLaneDw + d;
+            uint32_t const r0[4] = {rows[0].x, rows[0].y, rows[0].z, rows[0].w}, r1[4] = {rows[1].x, rows[1].y, rows[1].z, rows[1].w};
+            uint32_t *     dst   = lds + slot_dw + (8 * x) * Geo::kRowDw + sg * Geo::kLaneDw + d;
 #pragma unroll
-            for (int w = 0; w < 16; ++w)
+            for (int w = 0; w < 4; ++w)
             {
-                if (2 * w < nrows)
+                if (8 * x + 2 * w < nrows)
                 {
-                    // letters t = 2w (low halves) and 2w+1 (high halves) of both columns
-                    dst[(2 * w) * Geo::kRowDw]     = __builtin_amdgcn_perm(rows[1][w], rows[0][w], 0x05040100u);
-                    dst[(2 * w + 1) * Geo::kRowDw] = __builtin_amdgcn_perm(rows[1][w], rows[0][w], 0x07060302u);
+                    // letters t = 8x + 2w (low halves) and t + 1 (high halves) of both columns
+                    dst[(2 * w) * Geo::kRowDw]     = __builtin_amdgcn_perm(r1[w], r0[w], 0x05040100u);
+                    dst[(2 * w + 1) * Geo::kRowDw] = __builtin_amdgcn_perm(r1[w], r0[w], 0x07060302u);
                 }
             }
         }
@@ -265,6 +277,7 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     h2 diag0 = Z + GE;
     h2 sendH = Z + GE;
     h2 sendE = as_h2(kHalfNegInf2);
+    h2 recvE = as_h2(kHalfNegInf2); // E from the left: the shift's own `old`, so a group's first lane stays at -inf for good
     h2 best  = hsplat(0.f);
     // CKPT: first row that reached this strip's best value, "a later row reached it again" (bit 0 = A, bit 1 = B)
     int      rowA = 0, rowB = 0;
@@ -309,8 +322,9 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
         }
 
         // left boundary: H[i][-1] = 0 (skewed: z), E = -inf
-        h2 const recvH = as_h2((uint32_t)shift_from_left<G>((int)as_u32(sendH), (int)as_u32(Z), is_first));
-        h2       Ecur  = as_h2((uint32_t)shift_from_left<G>((int)as_u32(sendE), (int)kHalfNegInf2, is_first));
+        h2 const recvH = as_h2((uint32_t)__builtin_amdgcn_update_dpp((int)as_u32(Z), (int)as_u32(sendH), kDppShr, 0xf, 0xf, false));
+        recvE          = as_h2((uint32_t)__builtin_amdgcn_update_dpp((int)as_u32(recvE), (int)as_u32(sendE), kDppShr, 0xf, 0xf, false));
+        h2       Ecur  = recvE;
         h2       dg    = diag0;
         diag0          = recvH;
 
@@ -532,7 +546,7 @@ LX_UNROLL(LX_F16_UNROLL)
     {
 #pragma unroll
         for (int off = G / 2; off >= 1; off >>= 1)
-            best = hmax(best, as_h2((uint32_t)__shfl_xor((int)as_u32(best), off)));
+            best = hmax(best, as_h2((uint32_t)__shfl_xor((int)as_u32(best), off * kGs)));
 
         if (is_first)
         {
@@ -551,7 +565,7 @@ LX_UNROLL(LX_F16_UNROLL)
 #pragma unroll
             for (int off = 1; off < G; off <<= 1)
             {
-                int const  ob = __shfl_xor(gbest, off), os = __shfl_xor(gstrip, off), orow = __shfl_xor(grow, off), ot = __shfl_xor(gtie, off);
+                int const  ob = __shfl_xor(gbest, off * kGs), os = __shfl_xor(gstrip, off * kGs), orow = __shfl_xor(grow, off * kGs), ot = __shfl_xor(gtie, off * kGs);
                 bool const take = ob > gbest || (ob == gbest && os < gstrip);
                 gbest  = take ? ob : gbest;
                 gstrip = take ? os : gstrip;
@@ -585,8 +599,10 @@ static hipError_t launch_pair_cfg(ScoreParams const & p, hipStream_t stream)
     uint64_t const blocks   = (p.n + per_wave - 1) / per_wave;
     if (blocks > 0x7fffffffull)
         return hipErrorInvalidValue;
-    int const    slots = (p.pair_share > 0 && p.pair_share < Geo::kGroups) ? Geo::kGroups / p.pair_share : 1;
-    if (slots * p.pair_share != Geo::kGroups && slots != 1)
+    // (the kernel deals a profile's build over the share_g lane groups of its block: every block must have that many)
+    bool const   split = p.pair_share > 0 && p.pair_share < Geo::kGroups;
+    int const    slots = split ? Geo::kGroups / p.pair_share : 1;
+    if (split && slots * p.pair_share != Geo::kGroups)
         return hipErrorInvalidValue;
     size_t const lds = ((size_t)slots * (size_t)p.nrows * Geo::kRowDw + (CKPT ? 64 * 8 : 0)) * sizeof(uint32_t);
     hipLaunchKernelGGL((score_pair_kernel<G, C, CKPT>), dim3((unsigned)blocks), dim3(64), lds, stream, p);
