@@ -171,6 +171,9 @@ enum
                                          (0 = default, 8 MiB: above the measured crossover against the host thread; UINT64_MAX = never).  The input behind a
                                          header may be many small members, so the host tries the first 64 KiB (or this many bytes,
                                          if fewer) itself and keeps a member that ends inside them */
+    LX_OPT_BAM_RANGE_BYTES = 17, /* lx_render_bam_dev / lx_write_bam_dev: rendered bytes per range of records, i.e. what stands on the device
+                                    at once (0 = default, 256 MiB; accepted from 128 KiB to 2 GiB; a range is whole tiles of 2048 records,
+                                    at least one).  It changes where the cuts fall, never a byte of the output */
     LX_OPT_BAND            = 9  /* band mode -- NOT the reference's configuration (src/search_algo.hpp:1081 runs BandOff, :1102
                                    says why; _bandSize only pads the window, src/search_misc.hpp:46-50) and therefore not a
                                    parity mode: 0 (default) = full rectangle; b > 0 = only cells whose diagonal i - j (row i of
@@ -690,6 +693,25 @@ int lx_bgzf_compress(lx_handle * h, uint8_t const * in, uint64_t n, uint8_t * ou
 int lx_write_records_bgzf(lx_handle * h, char const * path, int format, char const * program, lx_blast_match const * m, uint64_t n,
                           uint8_t const * ops, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
                           lx_output_options const * opt, int64_t footer_records);
+/* LX_OUT_BAM of lx_render_records, the records made by kernels on h's device: the same bytes.  The record loop of myWriteRecord
+ * (src/search_output.hpp:463-733) runs as the kernels of lx_bam.hip -- query groups (FLAG, IH, --sam-bam-seq uniq), CIGAR, SEQ, POS,
+ * all fourteen tags -- over ranges of records whose bytes stay within LX_OPT_BAM_RANGE_BYTES; the header (magic, SAM text, reference
+ * list; myWriteHeader, :305-461) is made on the host.  `ops_bytes` is the extent of `ops` (the device copy must know it): a row whose
+ * ops_off + n_ops exceeds it is refused.  LX_EINVAL, before any device work and with lx_last_output_error()'s text, for what
+ * lx_render_records refuses (program, NULL arguments, unknown tag keys, n_qid >= n_q, n_sid >= n_s), for a NULL h, and for lists
+ * beyond the kernels' counters (2^31 - 16 rows, queries of 2^30 letters, ids of 2^20 characters).  *out is released with
+ * lx_bytes_free.  lx_last_phase_ms(h, 11, ...) = device time of the render kernels in the call. */
+int lx_render_bam_dev(lx_handle * h, int write_header, char const * program, lx_blast_match const * m, uint64_t n,
+                      uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
+                      uint64_t const * q_ascii_off, lx_output_options const * opt, lx_bytes ** out);
+/* lx_write_records_bgzf(LX_OUT_BAM) with the records rendered AND compressed on the device (myWriteRecord,
+ * src/search_output.hpp:463-733, then the BGZF encoder where the bytes stand): rows, ops and query letters go up, only members come
+ * down.  The file is byte-identical: the part of a range's stream that does not fill a 65 280-byte block is carried into the next
+ * range, so the members are cut where lx_bgzf_compress cuts them.  Refusals as lx_render_bam_dev; `path` is created or truncated once
+ * everything is made.  lx_last_phase_ms: 11 = the render kernels, 4 = the encoder's. */
+int lx_write_bam_dev(lx_handle * h, char const * path, char const * program, lx_blast_match const * m, uint64_t n,
+                     uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
+                     uint64_t const * q_ascii_off, lx_output_options const * opt);
 
 /* Decompresses a gzip stream of one or more members (RFC 1952): BGZF members on h's device, other members on the calling
  * thread; h may be NULL (every member on the host).  *out is released with lx_bytes_free.  Malformed input: LX_EINVAL.
@@ -918,7 +940,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*),
  * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top),
  * 8 = the word table's kernels (lx_index_build on a handle), 9 = the seeding kernel (lx_seed_queries on a handle),
- * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve). */
+ * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
+ * lx_write_bam_dev: groups, measure, scans, emit). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "lx_widen_and_preprocess", "lx_postprocess_records", "lx_postprocess_records_dev", "lx_iterate_matches_dev_top", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
-    "lx_write_records_bgzf", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
+    "lx_write_records_bgzf", "lx_render_bam_dev", "lx_write_bam_dev", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
     "lx_index_build", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
@@ -51,6 +51,7 @@ LX_OPT_HOST_THREADS = 14
 LX_OPT_ADAPT_PERMILLE = 12
 LX_OPT_GUNZIP_CHUNK = 15
 LX_OPT_GUNZIP_PARALLEL_FROM = 16
+LX_OPT_BAM_RANGE_BYTES = 17
 OPT_GUNZIP_WAVE_TEST = 1017  # not part of the ABI (lx_internal.h): chunks per wave, for the tests of lx_gunzip's waves
 LX_GUNZIP_NEVER = (1 << 64) - 1  # LX_OPT_GUNZIP_PARALLEL_FROM: no plain member takes the device path
 
@@ -318,6 +319,8 @@ def load():
     lib.lx_seed_result_free.restype = None
     lib.lx_write_records_bgzf.argtypes = [vp, C.c_char_p, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
                                           C.c_int64]
+    lib.lx_render_bam_dev.argtypes = [vp, i32, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions), C.POINTER(vp)]
+    lib.lx_write_bam_dev.argtypes = [vp, C.c_char_p, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions)]
     _lib = lib
     return lib
 
@@ -1070,6 +1073,24 @@ class Handle:
         """lx_write_records_bgzf: header, records and footer (footer_records >= 0) of `fmt`, BGZF-compressed into `path`."""
         args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
         self._check(self.lib.lx_write_records_bgzf(self.h, str(path).encode(), fmt, program.encode(), *args, footer_records))
+
+    def render_bam(self, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", write_header=True,
+                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None) -> bytes:
+        """lx_render_bam_dev: render_records(LX_OUT_BAM, ...) with the records made by kernels on this handle's device; the same bytes."""
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        out = C.c_void_p()
+        rc = self.lib.lx_render_bam_dev(self.h, 1 if write_header else 0, program.encode(), *args[:3], len(ops), *args[3:], C.byref(out))
+        self._check(rc)
+        try:
+            return C.string_at(self.lib.lx_bytes_data(out), self.lib.lx_bytes_size(out)) if self.lib.lx_bytes_size(out) else b""
+        finally:
+            self.lib.lx_bytes_free(out)
+
+    def write_bam(self, path, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",
+                  q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None):
+        """lx_write_bam_dev: write_records_bgzf(path, LX_OUT_BAM, ...) with the records rendered and compressed on the device; the same file."""
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        self._check(self.lib.lx_write_bam_dev(self.h, str(path).encode(), program.encode(), *args[:3], len(ops), *args[3:]))
 
     def last_gunzip_stats(self) -> GunzipStats:
         """lx_last_gunzip_stats: the counts of the last gunzip(handle, ...); .decline_text is the last decline reason in words."""

@@ -3,6 +3,12 @@
 //
 //   lambda3 searchp -q queries.fasta -d db.fasta -o out.m8 [-e 1e-2] [-n 25] [--seed-length 10] [--seed-offset 5]
 //                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--seeding gpu|host] [--records gpu|host|auto]
+//                   [--render gpu|host|auto]
+//
+// --render: where the alignment records of a .bam output are made.  host: lx_render_records on the host, the stream uploaded and
+// compressed by lx_bgzf_compress (what this front end always did; every other format takes this path whatever the option says).  gpu:
+// lx_write_bam_dev on the first device -- the records are kernels' work, compressed where they stand, only BGZF members come down; the
+// file is byte-identical.  auto = host until the measurement of DESIGN.md (4.13, "BAM records on the device") decides otherwise.
 //
 // --records: where _writeRecord's sort / unique / sort / cut to -n (src/search_algo.hpp:820-882) runs.  host: lx_postprocess_records
 // once, over the records of all workers (what this front end always did).  gpu: a worker's Level-2 call on a DEVICE match list
@@ -386,6 +392,7 @@ struct Options
     std::string table       = "auto"; // --table gpu | host | auto: where the word table is made (auto: search* on the GPU, mkindex* on the host)
     std::string seeding     = "gpu";  // --seeding gpu | host: where search() runs (lx_seed_queries on the worker's handle -- one lane per read, reads
                                       // the device declines are finished on the host threads inside the call --, or on the -t threads)
+    std::string render      = "auto"; // --render gpu | host | auto: where the records of a .bam output are made (the header comment)
     std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
     int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     // mkindex* (src/mkindex_options.hpp:96-262): -d the database (FASTA), -i the index file to write
@@ -601,6 +608,12 @@ Options parse(int argc, char ** argv)
             o.records = val();
             if (o.records != "gpu" && o.records != "host" && o.records != "auto")
                 throw std::runtime_error("--records takes gpu, host or auto");
+        }
+        else if (a == "--render")
+        {
+            o.render = val();
+            if (o.render != "gpu" && o.render != "host" && o.render != "auto")
+                throw std::runtime_error("--render takes gpu, host or auto");
         }
         else if (a == "--seeding")
         {
@@ -1692,6 +1705,8 @@ int main(int argc, char ** argv)
         lx_seq_names names{qid.data(), qs.orig_len.data(), sid.data(), db.orig_len.data(), qid.size(), sid.size()};
         int const    fmt = outFmt;
         double       msCompress = 0; // (.bam, *.gz: BGZF on the first handle's device)
+        double       msRenderDev = 0; // (--render gpu: the render kernels' device time)
+        bool         renderedOnGpu = false;
         {
             lx_output_options oo;
             lx_output_options_default(&oo);
@@ -1735,7 +1750,22 @@ int main(int argc, char ** argv)
                     oo.tax_names = taxNames.data();
                 }
             }
-            if (fmt == LX_OUT_BAM || outGz)
+            if (fmt == LX_OUT_BAM && !outGz && opt.render == "gpu")
+            {
+                // --render gpu: the records made and compressed on the first device, only the members come down
+                lx_handle * zh = nullptr;
+                if (lx_create(devices[0], &zh) != LX_OK)
+                    throw std::runtime_error(lx_last_error(nullptr));
+                std::unique_ptr<lx_handle, void (*)(lx_handle *)> keepH(zh, lx_destroy);
+                if (lx_write_bam_dev(zh, opt.output.c_str(), program, bms.data(), nOut, ops.data(), ops.size(), &names,
+                                     reinterpret_cast<uint8_t const *>(qs.ascii.data()), qs.ascii_off.data(), &oo) != LX_OK)
+                    throw std::runtime_error(std::string("BAM records on the GPU: ") + lx_last_error(zh));
+                float msK = 0;
+                (void)lx_last_phase_ms(zh, 11, &msK, nullptr);
+                msRenderDev = msK;
+                renderedOnGpu = true;
+            }
+            else if (fmt == LX_OUT_BAM || outGz)
             {
                 // records, footer and header rendered on the host threads, compressed on the device, written at once
                 lx_bytes * raw = nullptr;
@@ -1782,7 +1812,10 @@ int main(int argc, char ** argv)
                      "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records %.1f (%s), records + output %.0f%s, total %.0f\n",
                      msRead, gunzipNote.c_str(), fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
                      nPassesOnHost, msExtendMax, msRecords, recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msSince(tOut) - msCompress,
-                     (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str() : "", msSince(tStart));
+                     renderedOnGpu                  ? (", BAM records rendered and BGZF-compressed on the GPU (render kernels " + std::to_string((long)(msRenderDev + 0.5)) + ")").c_str()
+                     : (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str()
+                                                    : "",
+                     msSince(tStart));
         return 0;
     }
     catch (std::exception const & e)

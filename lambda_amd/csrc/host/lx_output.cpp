@@ -617,6 +617,45 @@ int lx_write_records(char const * path, int format, int write_header, char const
 
 } // extern "C"
 
+// The SAM header text (src/search_output.hpp:347-460): @HD, one @SQ per subject with --sam-with-refheader, @PG, the @CO lines
+static void samHeaderText(Sink & hs, lx_seq_names const * names, lx_output_options const & opt, bool const (&tags)[kNumSamTags])
+{
+    hs.print("@HD\tVN:1.4\tGO:query\n");
+    // --sam-with-refheader: seqan's writeHeader adds one @SQ per subject from the context ([UPSTREAM-RECALL] behind @HD)
+    if (opt.sam_with_ref_header)
+        for (uint64_t i = 0; i < names->n_s; ++i)
+            hs.print("@SQ\tSN:%s\tLN:%llu\n", firstWord(names->s_ids[i]).c_str(), (unsigned long long)names->s_lens[i]);
+    if (opt.version_to_output) // :391-399
+        hs.print("@PG\tID:lambda\tPN:lambda\tVN:%s\tCL:%s\n", opt.version ? opt.version : "", opt.command_line ? opt.command_line : "");
+    hs.print("@CO\tLambda is a high performance BLAST compatible local aligner, please see http://seqan.de/lambda "
+             "for more information.\n");
+    hs.print("@CO\tSAM/BAM dialect documentation is available here: https://github.com/seqan/lambda/wiki/Output-Formats\n");
+    hs.print("@CO\tIf you use any results found by Lambda, please cite Hauswedell et al. (2014) doi: "
+             "10.1093/bioinformatics/btu439\n");
+    std::string tagLine = "Optional tags as follow"; // :424-437
+    for (int t = 0; t < kNumSamTags; ++t)
+        if (tags[t])
+            tagLine += std::string("\t") + kSamTags[t].key + ":" + kSamTags[t].desc;
+    hs.print("@CO\t%s\n", tagLine.c_str());
+}
+
+// What stands in front of a BAM stream's records: the magic, the SAM header text, the reference list
+static std::string bamHeaderBytes(std::string const & headerText, lx_seq_names const * names)
+{
+    std::string h = "BAM\1";
+    putLe<int32_t>(h, (int32_t)headerText.size());
+    h += headerText;
+    putLe<int32_t>(h, (int32_t)names->n_s);
+    for (uint64_t i = 0; i < names->n_s; ++i)
+    {
+        std::string const sn = firstWord(names->s_ids[i]);
+        putLe<int32_t>(h, (int32_t)(sn.size() + 1));
+        h.append(sn.c_str(), sn.size() + 1);
+        putLe<int32_t>(h, (int32_t)names->s_lens[i]);
+    }
+    return h;
+}
+
 // The writers of myWriteHeader / myWriteRecord into a sink: the text formats, or BAM (format LX_OUT_BAM: the SAM records in
 // binary, the SAM header with its @SQ lines and the reference list in front).  `f` == nullptr: only the arguments are checked.
 static int renderRecords(Sink * f, int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n,
@@ -719,36 +758,10 @@ static int renderRecords(Sink * f, int format, int write_header, char const * pr
             opt.sam_with_ref_header = 1;
         if (write_header) // src/search_output.hpp:347-460
         {
-            hs.print("@HD\tVN:1.4\tGO:query\n");
-            // --sam-with-refheader: seqan's writeHeader adds one @SQ per subject from the context ([UPSTREAM-RECALL] behind @HD)
-            if (opt.sam_with_ref_header)
-                for (uint64_t i = 0; i < names->n_s; ++i)
-                    hs.print("@SQ\tSN:%s\tLN:%llu\n", firstWord(names->s_ids[i]).c_str(), (unsigned long long)names->s_lens[i]);
-            if (opt.version_to_output) // :391-399
-                hs.print("@PG\tID:lambda\tPN:lambda\tVN:%s\tCL:%s\n", opt.version ? opt.version : "", opt.command_line ? opt.command_line : "");
-            hs.print("@CO\tLambda is a high performance BLAST compatible local aligner, please see http://seqan.de/lambda "
-                            "for more information.\n");
-            hs.print("@CO\tSAM/BAM dialect documentation is available here: https://github.com/seqan/lambda/wiki/Output-Formats\n");
-            hs.print("@CO\tIf you use any results found by Lambda, please cite Hauswedell et al. (2014) doi: "
-                            "10.1093/bioinformatics/btu439\n");
-            std::string tagLine = "Optional tags as follow"; // :424-437
-            for (int t = 0; t < kNumSamTags; ++t)
-                if (tags[t])
-                    tagLine += std::string("\t") + kSamTags[t].key + ":" + kSamTags[t].desc;
-            hs.print("@CO\t%s\n", tagLine.c_str());
+            samHeaderText(hs, names, opt, tags);
             if (bam)
             {
-                std::string h = "BAM\1";
-                putLe<int32_t>(h, (int32_t)headerText.size());
-                h += headerText;
-                putLe<int32_t>(h, (int32_t)names->n_s);
-                for (uint64_t i = 0; i < names->n_s; ++i)
-                {
-                    std::string const sn = firstWord(names->s_ids[i]);
-                    putLe<int32_t>(h, (int32_t)(sn.size() + 1));
-                    h.append(sn.c_str(), sn.size() + 1);
-                    putLe<int32_t>(h, (int32_t)names->s_lens[i]);
-                }
+                std::string const h = bamHeaderBytes(headerText, names);
                 f->write(h.data(), h.size());
             }
         }
@@ -1144,3 +1157,41 @@ void lx_bytes_free(lx_bytes * b)
 }
 
 } // extern "C"
+
+// ---- for the device BAM writer (lx_bam_host.cpp): what renderRecords refuses, and its header, without a copy of either
+namespace lxi
+{
+int bam_check(char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names, lx_output_options const * opt_in,
+              uint32_t * tag_mask)
+{
+    int const rc = renderRecords(nullptr, LX_OUT_BAM, 1, program, m, n, nullptr, names, nullptr, nullptr, opt_in);
+    if (rc != LX_OK)
+        return rc;
+    bool tags[kNumSamTags] = {};
+    if (!resolveTags(opt_in ? opt_in->sam_tags : nullptr, tags))
+        return LX_EINVAL;
+    *tag_mask = 0;
+    for (int t = 0; t < kNumSamTags; ++t)
+        *tag_mask |= tags[t] ? 1u << t : 0u;
+    for (uint64_t k = 0; k < n; ++k) // (the record loop's refusal)
+        if (m[k].n_qid >= names->n_q || m[k].n_sid >= names->n_s)
+            return LX_EINVAL;
+    return LX_OK;
+}
+
+std::string bam_header(lx_seq_names const * names, lx_output_options const * opt_in, uint32_t tag_mask)
+{
+    lx_output_options opt;
+    lx_output_options_default(&opt);
+    if (opt_in)
+        opt = *opt_in;
+    opt.sam_with_ref_header = 1; // (BAM always carries the references)
+    bool tags[kNumSamTags];
+    for (int t = 0; t < kNumSamTags; ++t)
+        tags[t] = (tag_mask >> t) & 1u;
+    std::string headerText;
+    Sink        hs{nullptr, &headerText};
+    samHeaderText(hs, names, opt, tags);
+    return bamHeaderBytes(headerText, names);
+}
+} // namespace lxi

@@ -1206,6 +1206,11 @@ int lx_set_option(lx_handle * h, int option, uint64_t value)
             h->opt_gunzip_chunk = value;
             return LX_OK;
         case LX_OPT_GUNZIP_PARALLEL_FROM: h->opt_gunzip_from = value; return LX_OK;
+        case LX_OPT_BAM_RANGE_BYTES:
+            if (value && (value < (128u << 10) || value > (2ull << 30)))
+                return fail(h, LX_EINVAL, "LX_OPT_BAM_RANGE_BYTES: 0, or 128 KiB to 2 GiB");
+            h->opt_bam_range = value;
+            return LX_OK;
         case lxi::kOptGunzipWaveTest:
             if (value == 1 || value > 512)
                 return fail(h, LX_EINVAL, "chunks per wave: 0, or 2 to 512");
@@ -1242,6 +1247,7 @@ int lx_get_option(lx_handle const * h, int option, uint64_t * value)
         case LX_OPT_HOST_THREADS: *value = lxi::HostPool::instance().width(); return LX_OK;
         case LX_OPT_GUNZIP_CHUNK: *value = h->opt_gunzip_chunk; return LX_OK;
         case LX_OPT_GUNZIP_PARALLEL_FROM: *value = h->opt_gunzip_from; return LX_OK;
+        case LX_OPT_BAM_RANGE_BYTES: *value = h->opt_bam_range; return LX_OK;
         default: return LX_EINVAL;
     }
 }

@@ -1,0 +1,757 @@
+// lx_bam.hip -- BAM alignment records made on the device (gfx950): the record loop of renderRecords and bamRecord
+// (host/lx_output.cpp; myWriteRecord, /root/reference/src/search_output.hpp:463-733) restated as kernels, byte for byte.  The host
+// code is the specification: its quirks are kept (the CIGAR's runs and clips as cigarOf makes them, the truncated n_cigar_op /
+// l_read_name / bin, POS of a translated subject's minus strand taken from the QUERY length, the wrapping casts of the tags).
+//
+//   groups   a head flag per row (n_qid differs from the row before) and a sum scan (lx_scan.h): the row's group, the groups' first
+//            rows -- FLAG's secondary bit, tag IH, --sam-bam-seq uniq's "first of its group", the group's LCA.
+//   measure  one lane per record walks its ops: CIGAR elements, the length of OC's text, l_seq, the tags' bytes -> the record's size;
+//            64-bit totals per kBamTile records for the host's range cuts.
+//   emit     per range: an exclusive scan of the sizes (uint32), then one wavefront per record.  Lane 0 writes the fixed fields, the
+//            numeric tags, the CIGAR and the decimal texts (it walks the ops once more: a wavefront's latency hides behind the other
+//            wavefronts of the CU); qname, SEQ, QUAL and the Z strings qs / ls are strided over the 64 lanes.
+//
+// Stores: DIRECT BYTE STORES TO GLOBAL MEMORY, no LDS staging.  A record starts at an arbitrary byte and has an arbitrary length (36
+// bytes to more than a BGZF block for a long read with SEQ), so a staged copy could neither be bounded by an LDS budget nor written
+// back with aligned dword stores without a read-modify-write at both ends shared with the neighbouring records.  The strided parts
+// write 64 consecutive bytes per wavefront instruction, which the memory pipeline merges into whole-line writes; the serial parts are
+// a few dozen bytes per record in one or two lines that stay in L2 until the wavefront's other stores complete them.  Every byte of a
+// range is written exactly once: nothing is read back, no atomics, the stream is the same on every run.
+//
+// Bounds: a record's bytes lie in [off, off + size) of its range by construction (emit lays out with the function measure sized with,
+// and takes the two walked counts from measure); ops reads stay inside the host-checked [ops_off, ops_off + n_ops); reads of the
+// queries' letters beyond the uploaded extent are answered with 'N' and never made.
+#include <hip/hip_runtime.h>
+
+#include "lx_bam.h"
+#include "lx_level2.h"
+
+namespace lx
+{
+namespace
+{
+
+#include "lx_scan.h"
+
+static_assert(kBamTile == kL2ScanTile, "a size total per scan tile");
+
+__device__ __forceinline__ uint8_t up(uint8_t c)
+{
+    return c >= 'a' && c <= 'z' ? (uint8_t)(c - 32) : c;
+}
+__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
+{
+    uint32_t d = 1;
+    while (v >= 10)
+    {
+        v /= 10;
+        ++d;
+    }
+    return d;
+}
+__device__ __forceinline__ void put_dec(uint8_t * p, uint64_t v, uint32_t d)
+{
+    for (uint32_t i = d; i-- > 0;)
+    {
+        p[i] = (uint8_t)('0' + v % 10);
+        v /= 10;
+    }
+}
+// reverseComplementAscii's letter
+__device__ __forceinline__ uint8_t rc_letter(uint8_t c)
+{
+    switch (up(c))
+    {
+        case 'A': return 'T';
+        case 'C': return 'G';
+        case 'G': return 'C';
+        case 'T':
+        case 'U': return 'A';
+        default: return 'N';
+    }
+}
+// bamRecord's 4-bit code
+__device__ __forceinline__ uint32_t nt16(uint8_t c)
+{
+    constexpr char k[17] = "=ACMGRSVTWYHKDBN";
+    c                    = up(c);
+    uint32_t code        = 15;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (c == (uint8_t)k[i])
+            code = (uint32_t)i;
+    return code;
+}
+// frameProtein's nucleotide ranks and lx_translate_six_frames' complement
+__device__ __forceinline__ uint32_t nt5(uint8_t c)
+{
+    switch (up(c))
+    {
+        case 'A': return 0;
+        case 'C': return 1;
+        case 'G': return 2;
+        case 'T':
+        case 'U': return 4;
+        default: return 3;
+    }
+}
+__device__ __forceinline__ uint32_t comp5(uint32_t x)
+{
+    return x == 0 ? 4u : x == 1 ? 2u : x == 2 ? 1u : x == 3 ? 3u : 0u; // A <-> T (rank 4), C <-> G, N stays
+}
+__device__ __forceinline__ int reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14)
+        return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17)
+        return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20)
+        return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23)
+        return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26)
+        return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+__device__ __forceinline__ bool is_op(uint8_t o)
+{
+    return o == 'D' || o == 'I' || o == 'M';
+}
+
+__device__ __forceinline__ uint8_t letter(BamCtx const & c, uint64_t at)
+{
+    return at < c.q_ascii_bytes ? c.q_ascii[at] : (uint8_t)'N';
+}
+
+// what one record is made of besides its ops: the same values for measure and emit
+struct Rec
+{
+    lx_blast_match const * b;
+    uint64_t               qlen, base; // the untranslated query's length, where its letters begin
+    uint32_t               g, ih;      // group, its size
+    bool                   first, minus;
+    bool                   cig; // the program has a DNA cigar
+    uint64_t               trans, lfc, rfc, lclip, rclip, frame_len;
+    uint64_t               l_seq, seq_at; // letter i: seq_at + i (plus strand) / complement of seq_at - 1 - i (minus)
+    uint64_t               qs_len, qs_a;  // tag qs: 0 = "*"
+    int                    qs_mode;       // 1 = the query's letters, 2 / 3 = translated, plus / minus strand
+    uint64_t               qs_shift;
+    uint64_t               qn_at;
+    uint32_t               qn_len;
+    uint64_t               pos;
+    uint32_t               lca, name_off, name_len; // name_len 0xffffffff: "*"
+    uint64_t               st_lo, st_hi;            // the subject's taxa (st_lo == st_hi: "*")
+};
+
+__device__ __forceinline__ Rec rec_of(BamCtx const & c, uint64_t k)
+{
+    Rec                    r;
+    lx_blast_match const & b = c.rows[k];
+    r.b                      = &b;
+    r.qlen                   = c.q_lens[b.n_qid];
+    bool const ascii         = c.q_ascii != nullptr && c.q_ascii_off != nullptr;
+    r.base                   = ascii ? c.q_ascii_off[b.n_qid] : 0;
+    r.g                      = c.grp[k];
+    uint32_t const lo        = c.grp_first[r.g];
+    r.ih                     = c.grp_first[r.g + 1] - lo;
+    r.first                  = k == lo;
+    int const qf             = (int)b.q_frame;
+    int const aqf            = qf < 0 ? -qf : qf;
+    r.minus                  = qf < 0;
+    r.qn_at                  = c.qn_off[b.n_qid];
+    r.qn_len                 = (uint32_t)(c.qn_off[b.n_qid + 1] - r.qn_at);
+    // cigarOf's clips
+    r.cig       = c.is_n || c.q_trans;
+    r.trans     = c.q_trans ? 3 : 1;
+    r.lfc       = (uint64_t)aqf - (qf != 0 ? 1 : 0);
+    r.rfc       = c.q_trans ? (r.qlen - r.lfc) % 3 : 0;
+    r.frame_len = c.q_trans ? (r.qlen - r.lfc) / 3 : r.qlen;
+    r.lclip     = b.q_start * r.trans;
+    r.rclip     = (r.frame_len - b.q_end) * r.trans;
+    // --sam-bam-seq
+    bool write_seq = c.sam_seq >= LX_SAM_SEQ_ALWAYS;
+    if (c.sam_seq == LX_SAM_SEQ_UNIQ)
+    {
+        write_seq = r.first;
+        if (!r.first)
+        {
+            lx_blast_match const & p = c.rows[k - 1];
+            write_seq                = b.q_frame != p.q_frame || b.q_start != p.q_start || b.q_end != p.q_end;
+        }
+    }
+    // SEQ
+    r.l_seq  = 0;
+    r.seq_at = 0;
+    if (c.is_n && write_seq && ascii)
+    {
+        uint64_t a = 0, len = r.qlen;
+        if (c.hard)
+        {
+            bool const ok = b.q_end <= r.qlen && b.q_start <= b.q_end;
+            a             = ok ? b.q_start : 0;
+            len           = ok ? b.q_end - b.q_start : 0;
+        }
+        r.l_seq  = len;
+        r.seq_at = r.base + (r.minus ? r.qlen - a : a);
+    }
+    else if (c.q_trans && write_seq && ascii && qf != 0)
+    {
+        uint64_t const fc = (uint64_t)aqf - 1, L = (r.qlen - fc) / 3;
+        uint64_t const a = c.hard ? b.q_start : 0, e = c.hard ? b.q_end : L;
+        if (!(e > L || a > e))
+        {
+            r.l_seq  = 3 * (e - a);
+            r.seq_at = r.base + (r.minus ? (r.qlen - (3 * e + fc)) + r.l_seq : 3 * a + fc);
+        }
+    }
+    if (r.l_seq == 1 && !r.minus && letter(c, r.seq_at) == '*') // (a sequence that reads "*" is the absent one to bamRecord)
+        r.l_seq = 0;
+    // tag qs
+    r.qs_len   = 0;
+    r.qs_a     = 0;
+    r.qs_mode  = 0;
+    r.qs_shift = 0;
+    if ((c.tags & kBamTagQs) && !c.is_n && write_seq && ascii)
+    {
+        uint64_t fl = 0;
+        if (!c.q_trans)
+        {
+            fl        = r.qlen;
+            r.qs_mode = 1;
+        }
+        else if (qf != 0 && aqf <= 3 && c.codon)
+        {
+            r.qs_shift = (uint64_t)aqf - 1;
+            fl         = r.qlen >= r.qs_shift ? (r.qlen - r.qs_shift) / 3 : 0;
+            r.qs_mode  = r.minus ? 3 : 2;
+        }
+        if (fl > 0 && c.hard)
+        {
+            bool const ok = b.q_end <= fl && b.q_start <= b.q_end;
+            r.qs_a        = ok ? b.q_start : 0;
+            r.qs_len      = ok ? b.q_end - b.q_start : 0;
+        }
+        else
+            r.qs_len = fl;
+    }
+    // POS (the minus-strand branch subtracts from the QUERY length, as the host writer does)
+    r.pos = b.s_start;
+    if (c.s_trans)
+    {
+        int const sf = (int)b.s_frame;
+        r.pos        = b.s_start * 3 + (uint64_t)(sf < 0 ? -sf : sf) - (sf != 0 ? 1 : 0);
+        if (sf < 0)
+            r.pos = r.qlen - r.pos;
+    }
+    // taxonomy
+    r.lca      = c.grp_lca ? c.grp_lca[r.g] : 0u;
+    r.name_off = 0;
+    r.name_len = 0xffffffffu;
+    if (c.grp_name_len)
+    {
+        r.name_off = c.grp_name_off[r.g];
+        r.name_len = c.grp_name_len[r.g];
+    }
+    r.st_lo = r.st_hi = 0;
+    if (c.s_tax_off && b.n_sid < c.tax_n_s)
+    {
+        r.st_lo = c.s_tax_off[b.n_sid];
+        r.st_hi = c.s_tax_off[b.n_sid + 1];
+    }
+    return r;
+}
+
+// the runs of the ops (maximal runs of one code, which is what cigarOf's D / I / M loops and protCigarOf's loop both cut): run(op, count)
+// for each; false if a byte is no op code
+template <class F>
+__device__ __forceinline__ bool walk_runs(uint8_t const * o, uint32_t n, F && run)
+{
+    for (uint32_t i = 0; i < n;)
+    {
+        uint8_t const op = o[i];
+        if (!is_op(op))
+            return false;
+        uint32_t const i0 = i;
+        while (i < n && o[i] == op)
+            ++i;
+        run(op, i - i0);
+    }
+    return true;
+}
+__device__ __forceinline__ bool ops_valid(uint8_t const * o, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i)
+        if (!is_op(o[i]))
+            return false;
+    return true;
+}
+
+// bytes of the optional fields but the text of OC
+__device__ __forceinline__ uint64_t tag_bytes(BamCtx const & c, Rec const & r, uint32_t oc_len)
+{
+    uint32_t const t = c.tags;
+    uint64_t       s = 0;
+    s += (t & kBamTagAe) ? 7 : 0;
+    s += (t & kBamTagAS) ? 5 : 0;
+    s += (t & kBamTagAr) ? 4 : 0;
+    s += (t & kBamTagAi) ? 4 : 0;
+    s += (t & kBamTagAp) ? 5 : 0;
+    s += (t & kBamTagQf) ? 4 : 0;
+    s += (t & kBamTagSf) ? 4 : 0;
+    if (t & kBamTagSt)
+    {
+        uint64_t len = 0;
+        for (uint64_t x = r.st_lo; x < r.st_hi; ++x)
+            len += dec_digits(c.s_tax_ids[x]) + (x > r.st_lo ? 1 : 0);
+        s += 3 + (len ? len : 1) + 1;
+    }
+    if (t & kBamTagLs)
+        s += 3 + (r.name_len == 0xffffffffu ? 1u : r.name_len) + 1;
+    s += (t & kBamTagLt) ? 7 : 0;
+    if (t & kBamTagQs)
+        s += 3 + (r.qs_len ? r.qs_len : 1) + 1;
+    if (t & kBamTagOC)
+        s += 3 + (uint64_t)oc_len + 1;
+    s += (t & kBamTagNM) ? 7 : 0;
+    s += (t & kBamTagIH) ? 7 : 0;
+    return s;
+}
+
+struct HeadVal
+{
+    lx_blast_match const * rows;
+    __device__ uint32_t    operator()(uint64_t k) const { return k == 0 || rows[k].n_qid != rows[k - 1].n_qid ? 1u : 0u; }
+};
+struct HeadOut
+{
+    lx_blast_match const * rows;
+    uint64_t               n;
+    uint32_t *             grp, *grp_first;
+    __device__ void        operator()(uint64_t k, uint32_t incl, uint32_t excl) const
+    {
+        grp[k] = incl - 1;
+        if (incl != excl)
+            grp_first[incl - 1] = (uint32_t)k;
+        if (k == n - 1)
+            grp_first[incl] = (uint32_t)n;
+    }
+};
+struct SizeVal
+{
+    uint32_t const *    size;
+    __device__ uint32_t operator()(uint64_t j) const { return size[j]; }
+};
+struct OffOut
+{
+    uint32_t *      off;
+    __device__ void operator()(uint64_t j, uint32_t, uint32_t excl) const { off[j] = excl; }
+};
+
+__global__ __launch_bounds__(256) void bam_measure_kernel(BamCtx c, unsigned long long * tile_total)
+{
+    uint64_t const k    = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t       size = 0;
+    if (k < c.n)
+    {
+        Rec const              r = rec_of(c, k);
+        lx_blast_match const & b = *r.b;
+        uint8_t const * const  o = c.ops + b.ops_off;
+        uint32_t               runs = 0, oc = 0;
+        bool const             need_oc = (c.tags & kBamTagOC) && !c.is_n;
+        bool const             valid   = (r.cig || need_oc) ? walk_runs(o, b.n_ops,
+                                                                    [&](uint8_t, uint32_t cnt)
+                                                                    {
+                                                                        ++runs;
+                                                                        oc += dec_digits(cnt) + 1;
+                                                                    })
+                                                            : true;
+        uint32_t n_cigar = 0;
+        if (r.cig && valid)
+        {
+            n_cigar = runs;
+            if (c.hard)
+                n_cigar += (r.lfc + r.lclip > 0 ? 1 : 0) + (r.rfc + r.rclip > 0 ? 1 : 0);
+            else
+                n_cigar += (r.lfc > 0 ? 1 : 0) + (r.lclip > 0 ? 1 : 0) + (r.rclip > 0 ? 1 : 0) + (r.rfc > 0 ? 1 : 0);
+        }
+        uint32_t oc_len = 1; // "*"
+        if (need_oc && valid)
+        {
+            // protCigarOf: clips in protein space, never reversed
+            uint64_t const right = r.frame_len >= b.q_end ? r.frame_len - b.q_end : 0;
+            uint32_t const len   = (b.q_start ? dec_digits(b.q_start) + 1 : 0) + oc + (right ? dec_digits(right) + 1 : 0);
+            oc_len               = len ? len : 1;
+        }
+        c.aux[k] = BamAux{n_cigar, oc_len};
+        size     = 36 + (uint64_t)r.qn_len + 1 + 4 * (uint64_t)n_cigar + (r.l_seq + 1) / 2 + r.l_seq + tag_bytes(c, r, oc_len);
+        c.size[k] = (uint32_t)size;
+    }
+    // the tile's total: a wavefront lies in one tile (kBamTile is a multiple of 64)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        size += (uint64_t)__shfl_down((unsigned long long)size, off);
+    if ((threadIdx.x & 63) == 0 && k < c.n)
+        atomicAdd(&tile_total[k / kBamTile], (unsigned long long)size);
+}
+
+// one wavefront's cursor into its record: every lane keeps the same position, lane 0 writes the serial parts
+struct Cursor
+{
+    uint8_t * p;
+    int       lane;
+    template <class T>
+    __device__ __forceinline__ void le(T v, int bytes)
+    {
+        if (lane == 0)
+            for (int i = 0; i < bytes; ++i)
+                p[i] = (uint8_t)((uint64_t)v >> (8 * i));
+        p += bytes;
+    }
+    __device__ __forceinline__ void tag(char a, char b, char type)
+    {
+        if (lane == 0)
+        {
+            p[0] = (uint8_t)a;
+            p[1] = (uint8_t)b;
+            p[2] = (uint8_t)type;
+        }
+        p += 3;
+    }
+};
+
+// the double expression of tag ap, divided as IEEE does (no contraction, no reciprocal)
+__device__ __forceinline__ uint16_t ppos_u16(int32_t num_positives, int32_t alignment_length)
+{
+#pragma clang fp contract(off)
+    double const v = alignment_length ? 100.0 * num_positives / alignment_length : 0.0;
+    return (uint16_t)(int32_t)v;
+}
+
+__global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint64_t first, uint64_t count, uint32_t const * off, uint8_t * out)
+{
+    uint64_t const j    = (uint64_t)blockIdx.x * kBamEmitRecs + (threadIdx.x >> 6);
+    int const      lane = threadIdx.x & 63;
+    if (j >= count)
+        return;
+    uint64_t const         k = first + j;
+    Rec const              r = rec_of(c, k);
+    lx_blast_match const & b = *r.b;
+    BamAux const           a = c.aux[k];
+    uint8_t const * const  o = c.ops + b.ops_off;
+    uint8_t * const        rec = out + off[j];
+    uint32_t const         size = c.size[k];
+    Cursor                 w{rec, lane};
+
+    // span of the reference the CIGAR covers: its M and D runs
+    int64_t span = 0;
+    if (a.n_cigar) // (a "*" has none)
+    {
+        uint64_t md = 0;
+        for (uint32_t i = lane; i < b.n_ops; i += 64)
+            md += o[i] != 'I' ? 1 : 0;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+            md += (uint64_t)__shfl_xor((unsigned long long)md, s);
+        span = (int64_t)(md * r.trans);
+    }
+    int64_t const pos0 = (int64_t)r.pos;
+    int const     flag = (r.first ? 0 : 256) | (r.minus ? 16 : 0);
+    w.le<uint32_t>(size - 4, 4); // block_size
+    w.le<int32_t>((int32_t)b.n_sid, 4);
+    w.le<int32_t>((int32_t)pos0, 4);
+    w.le<uint8_t>((uint8_t)(r.qn_len + 1), 1);
+    w.le<uint8_t>(255, 1);
+    w.le<uint16_t>((uint16_t)reg2bin(pos0, pos0 + (span > 0 ? span : 1)), 2);
+    w.le<uint16_t>((uint16_t)a.n_cigar, 2);
+    w.le<uint16_t>((uint16_t)flag, 2);
+    w.le<int32_t>((int32_t)r.l_seq, 4);
+    w.le<int32_t>(-1, 4);
+    w.le<int32_t>(-1, 4);
+    w.le<int32_t>(0, 4);
+    // qname and its NUL
+    for (uint32_t i = lane; i < r.qn_len; i += 64)
+        w.p[i] = c.qn_blob[r.qn_at + i];
+    if (lane == 0)
+        w.p[r.qn_len] = 0;
+    w.p += r.qn_len + 1;
+    // CIGAR: cigarOf's elements, reversed on the minus strand
+    if (a.n_cigar && lane == 0)
+    {
+        uint32_t e   = 0;
+        auto     put = [&](uint32_t op, uint64_t len)
+        {
+            if (e < a.n_cigar)
+            {
+                uint32_t const  v = (uint32_t)len << 4 | op;
+                uint8_t * const q = w.p + 4 * (uint64_t)(r.minus ? a.n_cigar - 1 - e : e);
+                q[0]              = (uint8_t)v;
+                q[1]              = (uint8_t)(v >> 8);
+                q[2]              = (uint8_t)(v >> 16);
+                q[3]              = (uint8_t)(v >> 24);
+            }
+            ++e;
+        };
+        if (c.hard)
+        {
+            if (r.lfc + r.lclip > 0)
+                put(5, r.lfc + r.lclip);
+        }
+        else
+        {
+            if (r.lfc > 0)
+                put(5, r.lfc);
+            if (r.lclip > 0)
+                put(4, r.lclip);
+        }
+        (void)walk_runs(o, b.n_ops, [&](uint8_t op, uint32_t cnt) { put(op == 'M' ? 0u : op == 'I' ? 1u : 2u, (uint64_t)cnt * r.trans); });
+        if (c.hard)
+        {
+            if (r.rfc + r.rclip > 0)
+                put(5, r.rfc + r.rclip);
+        }
+        else
+        {
+            if (r.rclip > 0)
+                put(4, r.rclip);
+            if (r.rfc > 0)
+                put(5, r.rfc);
+        }
+    }
+    w.p += 4 * (uint64_t)a.n_cigar;
+    // SEQ: two letters a byte, the odd last nibble 0; QUAL: absent
+    uint64_t const seq_bytes = (r.l_seq + 1) / 2;
+    for (uint64_t i = lane; i < seq_bytes; i += 64)
+    {
+        uint32_t v = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+        {
+            uint64_t const x = 2 * i + h;
+            uint32_t       code = 0;
+            if (x < r.l_seq)
+                code = nt16(r.minus ? rc_letter(letter(c, r.seq_at - 1 - x)) : letter(c, r.seq_at + x));
+            v = v << 4 | code;
+        }
+        w.p[i] = (uint8_t)v;
+    }
+    w.p += seq_bytes;
+    for (uint64_t i = lane; i < r.l_seq; i += 64)
+        w.p[i] = 0xff;
+    w.p += r.l_seq;
+    // the optional fields, in myWriteRecord's order
+    uint32_t const t = c.tags;
+    if (t & kBamTagAe)
+    {
+        w.tag('a', 'e', 'f');
+        w.le<uint32_t>(__float_as_uint((float)b.e_value), 4);
+    }
+    if (t & kBamTagAS)
+    {
+        w.tag('A', 'S', 'S');
+        w.le<uint16_t>((uint16_t)(int32_t)b.bit_score, 2);
+    }
+    if (t & kBamTagAr)
+    {
+        w.tag('a', 'r', 'C');
+        w.le<uint8_t>((uint8_t)b.score, 1);
+    }
+    if (t & kBamTagAi)
+    {
+        w.tag('a', 'i', 'C');
+        w.le<uint8_t>((uint8_t)(int32_t)b.identity, 1);
+    }
+    if (t & kBamTagAp)
+    {
+        w.tag('a', 'p', 'S');
+        w.le<uint16_t>(ppos_u16(b.num_positives, b.alignment_length), 2);
+    }
+    if (t & kBamTagQf)
+    {
+        w.tag('q', 'f', 'c');
+        w.le<uint8_t>((uint8_t)(int8_t)b.q_frame, 1);
+    }
+    if (t & kBamTagSf)
+    {
+        w.tag('s', 'f', 'c');
+        w.le<uint8_t>((uint8_t)(int8_t)b.s_frame, 1);
+    }
+    if (t & kBamTagSt)
+    {
+        w.tag('s', 't', 'Z');
+        uint64_t len = 0;
+        for (uint64_t x = r.st_lo; x < r.st_hi; ++x)
+        {
+            uint32_t const id = c.s_tax_ids[x];
+            uint32_t const d  = dec_digits(id);
+            if (lane == 0)
+            {
+                if (x > r.st_lo)
+                    w.p[len] = ';';
+                put_dec(w.p + len + (x > r.st_lo ? 1 : 0), id, d);
+            }
+            len += d + (x > r.st_lo ? 1 : 0);
+        }
+        if (len == 0)
+        {
+            if (lane == 0)
+                w.p[0] = '*';
+            len = 1;
+        }
+        if (lane == 0)
+            w.p[len] = 0;
+        w.p += len + 1;
+    }
+    if (t & kBamTagLs)
+    {
+        w.tag('l', 's', 'Z');
+        uint32_t len = r.name_len;
+        if (len == 0xffffffffu)
+        {
+            if (lane == 0)
+                w.p[0] = '*';
+            len = 1;
+        }
+        else
+            for (uint32_t i = lane; i < len; i += 64)
+                w.p[i] = c.name_blob[r.name_off + i];
+        if (lane == 0)
+            w.p[len] = 0;
+        w.p += len + 1;
+    }
+    if (t & kBamTagLt)
+    {
+        w.tag('l', 't', 'I');
+        w.le<uint32_t>(r.lca, 4);
+    }
+    if (t & kBamTagQs)
+    {
+        w.tag('q', 's', 'Z');
+        uint64_t len = r.qs_len;
+        if (len == 0)
+        {
+            if (lane == 0)
+                w.p[0] = '*';
+            len = 1;
+        }
+        else if (r.qs_mode == 1)
+            for (uint64_t i = lane; i < len; i += 64)
+                w.p[i] = letter(c, r.base + r.qs_a + i);
+        else
+            for (uint64_t i = lane; i < len; i += 64)
+            {
+                // lx_translate_six_frames' codon of the frame's letter r.qs_a + i
+                uint64_t const p = r.qs_shift + 3 * (r.qs_a + i);
+                uint32_t       x0, x1, x2;
+                if (r.qs_mode == 2)
+                {
+                    x0 = nt5(letter(c, r.base + p));
+                    x1 = nt5(letter(c, r.base + p + 1));
+                    x2 = nt5(letter(c, r.base + p + 2));
+                }
+                else
+                {
+                    x0 = comp5(nt5(letter(c, r.base + r.qlen - 1 - p)));
+                    x1 = comp5(nt5(letter(c, r.base + r.qlen - 2 - p)));
+                    x2 = comp5(nt5(letter(c, r.base + r.qlen - 3 - p)));
+                }
+                w.p[i] = c.codon[25 * x0 + 5 * x1 + x2];
+            }
+        if (lane == 0)
+            w.p[len] = 0;
+        w.p += len + 1;
+    }
+    if (t & kBamTagOC)
+    {
+        w.tag('O', 'C', 'Z');
+        if (lane == 0)
+        {
+            bool const need_oc = !c.is_n;
+            uint32_t   at      = 0;
+            auto       add     = [&](uint8_t op, uint64_t cnt)
+            {
+                if (!cnt)
+                    return;
+                uint32_t const d = dec_digits(cnt);
+                if (at + d + 1 <= a.oc_len)
+                {
+                    put_dec(w.p + at, cnt, d);
+                    w.p[at + d] = op;
+                }
+                at += d + 1;
+            };
+            // (one op byte that is no code makes the whole text "*": measure saw it and left oc_len 1)
+            if (need_oc && ops_valid(o, b.n_ops))
+            {
+                uint8_t const  clip  = c.hard ? 'H' : 'S';
+                uint64_t const right = r.frame_len >= b.q_end ? r.frame_len - b.q_end : 0;
+                add(clip, b.q_start);
+                (void)walk_runs(o, b.n_ops, [&](uint8_t op, uint32_t cnt) { add(op, cnt); });
+                add(clip, right);
+            }
+            if (at == 0)
+                w.p[0] = '*';
+            w.p[a.oc_len] = 0;
+        }
+        w.p += (uint64_t)a.oc_len + 1;
+    }
+    if (t & kBamTagNM)
+    {
+        w.tag('N', 'M', 'I');
+        w.le<uint32_t>((uint32_t)(b.alignment_length - b.num_matches), 4);
+    }
+    if (t & kBamTagIH)
+    {
+        w.tag('I', 'H', 'I');
+        w.le<uint32_t>(r.ih, 4);
+    }
+}
+
+uint64_t scan_tiles(uint64_t n)
+{
+    return (n + kL2ScanTile - 1) / kL2ScanTile;
+}
+
+} // namespace
+
+hipError_t bam_launch_groups(BamCtx const & c, uint32_t * block_tot, hipStream_t stream)
+{
+    if (c.n == 0)
+        return hipSuccess;
+    uint64_t const tiles = scan_tiles(c.n);
+    dim3 const     grid((unsigned)tiles), block(kL2ScanBlock);
+    HeadVal const  hv{c.rows};
+    hipLaunchKernelGGL((l2_scan_reduce_kernel<kOpSum, false, HeadVal>), grid, block, 0, stream, hv, c.n, block_tot);
+    hipLaunchKernelGGL((l2_scan_tops_kernel<kOpSum>), dim3(1), block, 0, stream, block_tot, tiles);
+    hipLaunchKernelGGL((l2_scan_apply_kernel<kOpSum, false, HeadVal, HeadOut>), grid, block, 0, stream, hv, HeadOut{c.rows, c.n, c.grp, c.grp_first}, c.n,
+                       block_tot);
+    return hipGetLastError();
+}
+
+hipError_t bam_launch_measure(BamCtx const & c, uint64_t * tile_total, hipStream_t stream)
+{
+    if (c.n == 0)
+        return hipSuccess;
+    hipError_t const e = hipMemsetAsync(tile_total, 0, scan_tiles(c.n) * sizeof(uint64_t), stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(bam_measure_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, stream, c, reinterpret_cast<unsigned long long *>(tile_total));
+    return hipGetLastError();
+}
+
+hipError_t bam_launch_emit(BamCtx const & c, uint64_t first, uint64_t count, uint32_t * off, uint32_t * block_tot, uint8_t * out, hipStream_t stream)
+{
+    if (count == 0)
+        return hipSuccess;
+    uint64_t const tiles = scan_tiles(count);
+    dim3 const     grid((unsigned)tiles), block(kL2ScanBlock);
+    SizeVal const  sv{c.size + first};
+    hipLaunchKernelGGL((l2_scan_reduce_kernel<kOpSum, false, SizeVal>), grid, block, 0, stream, sv, count, block_tot);
+    hipLaunchKernelGGL((l2_scan_tops_kernel<kOpSum>), dim3(1), block, 0, stream, block_tot, tiles);
+    hipLaunchKernelGGL((l2_scan_apply_kernel<kOpSum, false, SizeVal, OffOut>), grid, block, 0, stream, sv, OffOut{off}, count, block_tot);
+    hipLaunchKernelGGL(bam_emit_kernel, dim3((unsigned)((count + kBamEmitRecs - 1) / kBamEmitRecs)), dim3(kBamEmitBlock), 0, stream, c, first, count,
+                       off, out);
+    return hipGetLastError();
+}
+
+} // namespace lx

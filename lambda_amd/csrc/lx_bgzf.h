@@ -11,6 +11,9 @@ constexpr uint32_t kBgzfBlock = 65280;  // input bytes per member at most (htsli
 constexpr uint32_t kBgzfSlot  = 65536;  // device bytes per member before the members are placed one after another
 constexpr uint32_t kBgzfMemberOverhead = 18 + 5 + 8; // header with the BC subfield, a stored block's header, CRC32 + ISIZE
 
+// the empty member that ends a BGZF file (SAM/BAM specification 4.1.2)
+constexpr uint8_t kEofMember[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
 struct BgzfParams
 {
     uint8_t const * in;    // the chunk, 16-byte aligned

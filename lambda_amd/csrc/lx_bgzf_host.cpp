@@ -1,4 +1,5 @@
-// lx_bgzf_host.cpp -- the host side of the BGZF encoder (lx_bgzf.hip): lx_bgzf_bound, lx_bgzf_compress, lx_write_records_bgzf.
+// lx_bgzf_host.cpp -- the host side of the BGZF encoder (lx_bgzf.hip): lx_bgzf_bound, lx_bgzf_compress, lx_write_records_bgzf, and the
+// same pipeline over bytes that stand on the device already (lxi::bgzf_compress_dev: the BAM records of lx_bam_host.cpp).
 //
 // lx_bgzf_compress streams its input through the device in chunks of kChunkBlocks blocks (33 MB), so that a large output never
 // needs all of its bytes on the device at once.  Per chunk, on the handle's stream: upload from a pinned lane, the two kernels,
@@ -15,10 +16,84 @@ namespace
 constexpr uint32_t kChunkBlocks = 512;
 constexpr uint64_t kChunkBytes  = (uint64_t)kChunkBlocks * lx::kBgzfBlock;
 
-// the empty member that ends a BGZF file (SAM/BAM specification 4.1.2)
-constexpr uint8_t kEofMember[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+using lx::kEofMember;
+
+// The chunk pipeline of lx_bgzf_compress over n bytes: from host memory (host_in: through the pinned lanes into the chunk's device
+// buffer) or where they stand on the device (dev_in, 16-byte aligned: every chunk begins at a multiple of kChunkBytes).  Each chunk's
+// members go to `sink` in order.
+int compress_chunks(lx_handle * h, uint8_t const * host_in, uint8_t const * dev_in, uint64_t n,
+                    std::function<int(uint8_t const *, uint64_t)> const & sink)
+{
+    int            rc     = LX_OK;
+    auto &         B      = h->bgzf;
+    uint64_t const first  = std::min(n, kChunkBytes);
+    uint64_t const blocks = (first + lx::kBgzfBlock - 1) / lx::kBgzfBlock;
+    if (n > 0 &&
+        ((host_in && (rc = ensure(h, B.d_in, blocks * lx::kBgzfBlock))) || (rc = ensure(h, B.d_slots, blocks * lx::kBgzfSlot)) ||
+         (rc = ensure(h, B.d_dist, blocks * lx::kBgzfBlock * 2)) || (rc = ensure(h, B.d_sym, blocks * lx::kBgzfBlock * 2)) ||
+         (rc = ensure(h, B.d_sizes, blocks * 4)) || (rc = ensure(h, B.d_out, blocks * lx::kBgzfSlot)) || (rc = ensure(h, B.d_total, 8)) ||
+         (host_in && ((rc = ensure_pinned(h, B.p_in[0], first, kExact)) || (rc = ensure_pinned(h, B.p_in[1], first, kExact)))) ||
+         (rc = ensure_pinned(h, B.p_out, blocks * lx::kBgzfSlot, kExact)) || (rc = ensure_pinned(h, B.p_total, 8, kExact))))
+        return rc;
+    hipStream_t const s     = h->stream;
+    uint64_t * const  total = static_cast<uint64_t *>(B.p_total.ptr);
+    // queues chunk c (its bytes already in its pinned lane, or on the device): upload, kernels, the size of its members
+    auto enqueue = [&](uint64_t c) -> int
+    {
+        uint64_t const at = c * kChunkBytes, len = std::min(kChunkBytes, n - at);
+        if (host_in)
+            LX_HIP(h, hipMemcpyAsync(B.d_in.ptr, B.p_in[c & 1].ptr, len, hipMemcpyHostToDevice, s));
+        lx::BgzfParams p{host_in ? static_cast<uint8_t const *>(B.d_in.ptr) : dev_in + at, len, (uint32_t)((len + lx::kBgzfBlock - 1) / lx::kBgzfBlock),
+                         static_cast<uint8_t *>(B.d_slots.ptr), static_cast<uint16_t *>(B.d_dist.ptr), static_cast<uint16_t *>(B.d_sym.ptr),
+                         static_cast<uint32_t *>(B.d_sizes.ptr), static_cast<uint8_t *>(B.d_out.ptr), static_cast<uint64_t *>(B.d_total.ptr)};
+        PhaseTimer t(h, s, 4);
+        LX_HIP(h, lx::launch_bgzf(p, s));
+        t.close();
+        LX_HIP(h, hipMemcpyAsync(total, B.d_total.ptr, 8, hipMemcpyDeviceToHost, s));
+        return LX_OK;
+    };
+    uint64_t const chunks = (n + kChunkBytes - 1) / kChunkBytes;
+    if (chunks > 0)
+    {
+        if (host_in)
+            std::memcpy(B.p_in[0].ptr, host_in, first);
+        if ((rc = enqueue(0)))
+            return rc;
+    }
+    for (uint64_t c = 0; c < chunks; ++c)
+    {
+        if (host_in && c + 1 < chunks) // the next chunk into the other lane (its last reader, the upload of chunk c - 1, is done)
+        {
+            uint64_t const at = (c + 1) * kChunkBytes;
+            std::memcpy(B.p_in[(c + 1) & 1].ptr, host_in + at, std::min(kChunkBytes, n - at));
+        }
+        LX_HIP(h, hipStreamSynchronize(s));
+        uint64_t const bytes = *total;
+        if (bytes > blocks * lx::kBgzfSlot)
+            return fail(h, LX_EHIP, "lx_bgzf_compress: the encoder reported %llu bytes for a chunk", (unsigned long long)bytes);
+        LX_HIP(h, hipMemcpyAsync(B.p_out.ptr, B.d_out.ptr, bytes, hipMemcpyDeviceToHost, s));
+        hipEvent_t const down = pool_event(h);
+        if (!down)
+            return fail(h, LX_EHIP, "lx_bgzf_compress: no event");
+        LX_HIP(h, hipEventRecord(down, s));
+        if (c + 1 < chunks && (rc = enqueue(c + 1)))
+            return rc;
+        LX_HIP(h, hipEventSynchronize(down));
+        if ((rc = sink(static_cast<uint8_t const *>(B.p_out.ptr), bytes)))
+            return rc;
+    }
+    return LX_OK;
+}
 
 } // namespace
+
+namespace lxi
+{
+int bgzf_compress_dev(lx_handle * h, uint8_t const * d_in, uint64_t n, std::function<int(uint8_t const *, uint64_t)> const & sink)
+{
+    return compress_chunks(h, nullptr, d_in, n, sink);
+}
+} // namespace lxi
 
 extern "C" {
 
@@ -42,62 +117,18 @@ int lx_bgzf_compress(lx_handle * h, uint8_t const * in, uint64_t n, uint8_t * ou
         return rc;
     h->phase_ev.clear();
     h->ev_pool_used = 0;
-    auto &         B      = h->bgzf;
-    uint64_t const first  = std::min(n, kChunkBytes);
-    uint64_t const blocks = (first + lx::kBgzfBlock - 1) / lx::kBgzfBlock;
-    if (n > 0 &&
-        ((rc = ensure(h, B.d_in, blocks * lx::kBgzfBlock)) || (rc = ensure(h, B.d_slots, blocks * lx::kBgzfSlot)) ||
-         (rc = ensure(h, B.d_dist, blocks * lx::kBgzfBlock * 2)) || (rc = ensure(h, B.d_sym, blocks * lx::kBgzfBlock * 2)) ||
-         (rc = ensure(h, B.d_sizes, blocks * 4)) || (rc = ensure(h, B.d_out, blocks * lx::kBgzfSlot)) || (rc = ensure(h, B.d_total, 8)) ||
-         (rc = ensure_pinned(h, B.p_in[0], first, kExact)) || (rc = ensure_pinned(h, B.p_in[1], first, kExact)) ||
-         (rc = ensure_pinned(h, B.p_out, blocks * lx::kBgzfSlot, kExact)) || (rc = ensure_pinned(h, B.p_total, 8, kExact))))
+    uint64_t w      = 0;
+    rc              = compress_chunks(h, in, nullptr, n,
+                                      [&](uint8_t const * members, uint64_t bytes) -> int
+                                      {
+                                          if (w + bytes > cap)
+                                              return fail(h, LX_EHIP, "lx_bgzf_compress: the encoder reported %llu bytes for a chunk", (unsigned long long)bytes);
+                                          std::memcpy(out + w, members, bytes);
+                                          w += bytes;
+                                          return LX_OK;
+                                      });
+    if (rc)
         return rc;
-    hipStream_t const s     = h->stream;
-    uint64_t * const  total = static_cast<uint64_t *>(B.p_total.ptr);
-    uint64_t          w     = 0;
-    // queues chunk c (its bytes already in its pinned lane): upload, kernels, the size of its members
-    auto enqueue = [&](uint64_t c) -> int
-    {
-        uint64_t const at = c * kChunkBytes, len = std::min(kChunkBytes, n - at);
-        LX_HIP(h, hipMemcpyAsync(B.d_in.ptr, B.p_in[c & 1].ptr, len, hipMemcpyHostToDevice, s));
-        lx::BgzfParams p{static_cast<uint8_t const *>(B.d_in.ptr), len, (uint32_t)((len + lx::kBgzfBlock - 1) / lx::kBgzfBlock),
-                         static_cast<uint8_t *>(B.d_slots.ptr), static_cast<uint16_t *>(B.d_dist.ptr), static_cast<uint16_t *>(B.d_sym.ptr),
-                         static_cast<uint32_t *>(B.d_sizes.ptr), static_cast<uint8_t *>(B.d_out.ptr), static_cast<uint64_t *>(B.d_total.ptr)};
-        PhaseTimer t(h, s, 4);
-        LX_HIP(h, lx::launch_bgzf(p, s));
-        t.close();
-        LX_HIP(h, hipMemcpyAsync(total, B.d_total.ptr, 8, hipMemcpyDeviceToHost, s));
-        return LX_OK;
-    };
-    uint64_t const chunks = (n + kChunkBytes - 1) / kChunkBytes;
-    if (chunks > 0)
-    {
-        std::memcpy(B.p_in[0].ptr, in, first);
-        if ((rc = enqueue(0)))
-            return rc;
-    }
-    for (uint64_t c = 0; c < chunks; ++c)
-    {
-        if (c + 1 < chunks) // the next chunk into the other lane (its last reader, the upload of chunk c - 1, is done)
-        {
-            uint64_t const at = (c + 1) * kChunkBytes;
-            std::memcpy(B.p_in[(c + 1) & 1].ptr, in + at, std::min(kChunkBytes, n - at));
-        }
-        LX_HIP(h, hipStreamSynchronize(s));
-        uint64_t const bytes = *total;
-        if (bytes > blocks * lx::kBgzfSlot || w + bytes > cap)
-            return fail(h, LX_EHIP, "lx_bgzf_compress: the encoder reported %llu bytes for a chunk", (unsigned long long)bytes);
-        LX_HIP(h, hipMemcpyAsync(B.p_out.ptr, B.d_out.ptr, bytes, hipMemcpyDeviceToHost, s));
-        hipEvent_t const down = pool_event(h);
-        if (!down)
-            return fail(h, LX_EHIP, "lx_bgzf_compress: no event");
-        LX_HIP(h, hipEventRecord(down, s));
-        if (c + 1 < chunks && (rc = enqueue(c + 1)))
-            return rc;
-        LX_HIP(h, hipEventSynchronize(down));
-        std::memcpy(out + w, B.p_out.ptr, bytes);
-        w += bytes;
-    }
     if (flags & LX_BGZF_EOF)
     {
         std::memcpy(out + w, kEofMember, sizeof(kEofMember));

@@ -246,6 +246,15 @@ struct lx_handle
         float           phase_ms[3] = {0, 0, 0};      // ... its find, decode and resolve kernels (lx_last_phase_ms 101..103, 10 = all)
         int             phase_launches[3] = {0, 0, 0};
     } gunzip;
+    // lx_render_bam_dev / lx_write_bam_dev (lx_bam_host.cpp): the call's inputs flattened on the device, what the kernels leave per
+    // record, a range's stream (the carried part of a BGZF block in front), the tile totals on their way up
+    struct Bam
+    {
+        DevBuf d_rows, d_ops, d_ascii, d_ascii_off, d_qlens, d_qn_blob, d_qn_off, d_tax_off, d_tax_ids, d_grp_tab, d_name_blob, d_codon;
+        DevBuf d_grp, d_grp_first, d_aux, d_size, d_off, d_scan, d_tiles, d_stream;
+        Pinned p_tiles;
+    } bam;
+    uint64_t opt_bam_range = 0; // LX_OPT_BAM_RANGE_BYTES (0 = default)
     uint64_t opt_gunzip_chunk = 0; // LX_OPT_GUNZIP_CHUNK (0 = default)
     uint64_t opt_gunzip_from  = 0; // LX_OPT_GUNZIP_PARALLEL_FROM (0 = default)
     uint64_t gunzip_wave      = 0; // kOptGunzipWaveTest: chunks per wave (0 = default), so that a test reaches a wave's edges with a megabyte
@@ -335,6 +344,16 @@ int    bind(lx_handle * h);
 // (host/lx_output.cpp) an lx_bytes that takes over s; the message lx_last_output_error() returns
 lx_bytes * bytes_adopt(std::string && s);
 void       set_output_error(std::string const & msg);
+// (host/lx_output.cpp) for the device BAM writer: renderRecords' refusals for LX_OUT_BAM (program, NULL arguments, tag keys, the rows'
+// ids; lx_last_output_error() has its text) and the resolved tags as bits in kSamTags' order; the bytes in front of the records
+// (magic, SAM header text, reference list)
+int         bam_check(char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names, lx_output_options const * opt,
+                      uint32_t * tag_mask);
+std::string bam_header(lx_seq_names const * names, lx_output_options const * opt, uint32_t tag_mask);
+// (lx_bgzf_host.cpp) lx_bgzf_compress's members of n bytes that stand on the device already (16-byte aligned): the same chunks of 512
+// blocks, the same member bytes, the same download pipeline; `sink` takes each chunk's members in order.  The phase events of the
+// call so far stay.
+int bgzf_compress_dev(lx_handle * h, uint8_t const * d_in, uint64_t n, std::function<int(uint8_t const *, uint64_t)> const & sink);
 size_t pair_lds_limit();
 int    pick_cfg(uint32_t qlen, bool shared);
 int    ckpt_cfg_for(uint64_t max_q, bool packed16 = false);
