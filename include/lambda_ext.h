@@ -171,8 +171,8 @@ enum
                                          (0 = default, 8 MiB: above the measured crossover against the host thread; UINT64_MAX = never).  The input behind a
                                          header may be many small members, so the host tries the first 64 KiB (or this many bytes,
                                          if fewer) itself and keeps a member that ends inside them */
-    LX_OPT_BAM_RANGE_BYTES = 17, /* lx_render_bam_dev / lx_write_bam_dev: rendered bytes per range of records, i.e. what stands on the device
-                                    at once (0 = default, 256 MiB; accepted from 128 KiB to 2 GiB; a range is whole tiles of 2048 records,
+    LX_OPT_BAM_RANGE_BYTES = 17, /* lx_render_bam_dev / lx_write_bam_dev and lx_render_text_dev / lx_write_text_dev: rendered bytes per
+                                    range of records, i.e. what stands on the device at once (0 = default, 256 MiB; accepted from 128 KiB to 2 GiB; a range is whole tiles of 2048 records,
                                     at least one).  It changes where the cuts fall, never a byte of the output */
     LX_OPT_BAND            = 9  /* band mode -- NOT the reference's configuration (src/search_algo.hpp:1081 runs BandOff, :1102
                                    says why; _bandSize only pads the window, src/search_misc.hpp:46-50) and therefore not a
@@ -713,6 +713,47 @@ int lx_write_bam_dev(lx_handle * h, char const * path, char const * program, lx_
                      uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
                      uint64_t const * q_ascii_off, lx_output_options const * opt);
 
+/* The characters glibc's printf writes for a number, made with integer arithmetic alone (no printf, no double operation beyond
+ * taking the bits apart): what the device text writers below print, and what the host writer's snprintf calls print
+ * (host/lx_output.cpp: "%.1e" of the e-value, "%.1f" of the bit score, "%.2f" of pident and ppos, "%g" of SAM's ae -- seqan's
+ * BlastTabular writeRecord behind myWriteRecord, src/search_output.hpp:463-733).  Rounding is to nearest, an exact tie to even.
+ * LX_NUM_E1: "%.1e" of any double (subnormals, +-0, inf, -inf, nan, -nan).  LX_NUM_G_FLOAT: "%g" of v, which the callers have
+ * narrowed to float and widened again.  LX_NUM_F1 / LX_NUM_F2: "%.1f" / "%.2f" of a finite v with |v| < 1e15.  Writes the text and a
+ * terminating NUL into out[0 .. cap) and returns its length (at most 24); LX_EINVAL for a cap that is too short, an unknown kind, a
+ * NULL out, or an F value outside the domain. */
+enum
+{
+    LX_NUM_E1      = 0,
+    LX_NUM_F1      = 1,
+    LX_NUM_F2      = 2,
+    LX_NUM_G_FLOAT = 3
+};
+int lx_format_number(int kind, double v, char * out, uint64_t cap);
+
+/* lx_render_records for LX_OUT_BLAST_TAB, LX_OUT_BLAST_TAB_COMMENTS and LX_OUT_SAM with the records made by kernels on h's device:
+ * the same bytes.  The tabular record of seqan's writeRecord (behind myWriteRecord, src/search_output.hpp:463-733; every column of
+ * --output-columns, in any order and as often as named, src/search_options.hpp:716-760) and the SAM record with its tags (:463-733)
+ * run as the kernels of lx_text.hip over query groups (the comment lines and hit count of .m9, FLAG, IH, --sam-bam-seq uniq) in
+ * ranges of records whose bytes stay within LX_OPT_BAM_RANGE_BYTES; numbers are printed by lx_format_number's formatter.  The SAM
+ * header (myWriteHeader, :347-460) and the .m9 footer (myWriteFooter, :739-750; footer_records >= 0) are made on the host.  Only the
+ * first words of the subject ids the rows name go up.  `ops` is read for LX_OUT_SAM only (the tabular formats have no column made of
+ * them, as in lx_write_records_ex: there they may be NULL, and the rows' ops_off / n_ops are not looked at).  LX_EINVAL, before any device work and with lx_last_output_error()'s text,
+ * for what lx_render_bam_dev refuses, for an unknown column specifier, for LX_OUT_BAM (lx_render_bam_dev makes it), and for a row
+ * whose bit_score or identity is not finite or not below 1e15 in magnitude (the host writer's own buffer is no yardstick there).
+ * *out is released with lx_bytes_free.  lx_last_phase_ms(h, 12, ...) = device time of the text record kernels in the call. */
+int lx_render_text_dev(lx_handle * h, int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n,
+                       uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
+                       uint64_t const * q_ascii_off, lx_output_options const * opt, int64_t footer_records, lx_bytes ** out);
+/* The file of a text format with the records rendered on the device (myWriteHeader, myWriteRecord, myWriteFooter,
+ * src/search_output.hpp:305-750).  bgzf = 0: the plain file lx_write_records_ex(write_header = 1) + lx_write_footer write.  bgzf = 1:
+ * the file lx_write_records_bgzf writes, byte for byte, compressed where the stream stands as in lx_write_bam_dev: less than a block
+ * is carried into the next range, the footer goes behind the last range, then the EOF member; only members come down.  Refusals
+ * as lx_render_text_dev; `path` is created or truncated once everything is made.  lx_last_phase_ms: 12 = the text record kernels,
+ * 4 = the encoder's. */
+int lx_write_text_dev(lx_handle * h, char const * path, int format, int bgzf, char const * program, lx_blast_match const * m, uint64_t n,
+                      uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
+                      uint64_t const * q_ascii_off, lx_output_options const * opt, int64_t footer_records);
+
 /* Decompresses a gzip stream of one or more members (RFC 1952): BGZF members on h's device, other members on the calling
  * thread; h may be NULL (every member on the host).  *out is released with lx_bytes_free.  Malformed input: LX_EINVAL.
  * A member with the BGZF subfield (BC, BSIZE) whose DEFLATE bytes and ISIZE are at most 64 KiB is decoded on the device, one
@@ -941,7 +982,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top),
  * 8 = the word table's kernels (lx_index_build on a handle), 9 = the seeding kernel (lx_seed_queries on a handle),
  * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
- * lx_write_bam_dev: groups, measure, scans, emit). */
+ * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,
+ * numbers, measure, scans, emit). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

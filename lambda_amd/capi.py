@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "lx_widen_and_preprocess", "lx_postprocess_records", "lx_postprocess_records_dev", "lx_iterate_matches_dev_top", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
-    "lx_write_records_bgzf", "lx_render_bam_dev", "lx_write_bam_dev", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
+    "lx_write_records_bgzf", "lx_render_bam_dev", "lx_write_bam_dev", "lx_format_number", "lx_render_text_dev", "lx_write_text_dev", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
     "lx_index_build", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
@@ -321,6 +321,11 @@ def load():
                                           C.c_int64]
     lib.lx_render_bam_dev.argtypes = [vp, i32, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions), C.POINTER(vp)]
     lib.lx_write_bam_dev.argtypes = [vp, C.c_char_p, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions)]
+    lib.lx_format_number.argtypes = [i32, C.c_double, C.c_char_p, u64]
+    lib.lx_render_text_dev.argtypes = [vp, i32, i32, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions), C.c_int64,
+                                       C.POINTER(vp)]
+    lib.lx_write_text_dev.argtypes = [vp, C.c_char_p, i32, i32, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
+                                      C.c_int64]
     _lib = lib
     return lib
 
@@ -419,6 +424,20 @@ def render_records(fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, 
         return C.string_at(lib.lx_bytes_data(out), lib.lx_bytes_size(out)) if lib.lx_bytes_size(out) else b""
     finally:
         lib.lx_bytes_free(out)
+
+
+LX_NUM_E1, LX_NUM_F1, LX_NUM_F2, LX_NUM_G_FLOAT = 0, 1, 2, 3
+
+
+def format_number(kind: int, v: float, cap: int = 32) -> str:
+    """lx_format_number: the text printf makes of v ("%.1e", "%.1f", "%.2f", or "%g" of a float widened to double), by the integer
+    formatter the device text writers print with.  LambdaExtError(LX_EINVAL) for a short cap, an unknown kind, an F value outside
+    |v| < 1e15."""
+    buf = C.create_string_buffer(max(cap, 1))
+    n = load().lx_format_number(kind, C.c_double(v), buf, cap)
+    if n < 0:
+        raise LambdaExtError(n, "lx_format_number")
+    return buf.raw[:n].decode("ascii")
 
 
 def bgzf_bound(n: int) -> int:
@@ -1091,6 +1110,28 @@ class Handle:
         """lx_write_bam_dev: write_records_bgzf(path, LX_OUT_BAM, ...) with the records rendered and compressed on the device; the same file."""
         args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
         self._check(self.lib.lx_write_bam_dev(self.h, str(path).encode(), program.encode(), *args[:3], len(ops), *args[3:]))
+
+    def render_text(self, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", write_header=True,
+                    q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1) -> bytes:
+        """lx_render_text_dev: render_records(fmt, ...) for LX_OUT_BLAST_TAB, LX_OUT_BLAST_TAB_COMMENTS and LX_OUT_SAM with the records made
+        by kernels on this handle's device; the same bytes."""
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        out = C.c_void_p()
+        rc = self.lib.lx_render_text_dev(self.h, fmt, 1 if write_header else 0, program.encode(), *args[:3], len(ops), *args[3:], footer_records,
+                                         C.byref(out))
+        self._check(rc)
+        try:
+            return C.string_at(self.lib.lx_bytes_data(out), self.lib.lx_bytes_size(out)) if self.lib.lx_bytes_size(out) else b""
+        finally:
+            self.lib.lx_bytes_free(out)
+
+    def write_text(self, path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", bgzf=False,
+                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1):
+        """lx_write_text_dev: the file write_records + write_footer (bgzf False) or write_records_bgzf (bgzf True) write for a text format,
+        with the records rendered (and compressed) on the device; the same file."""
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        self._check(self.lib.lx_write_text_dev(self.h, str(path).encode(), fmt, 1 if bgzf else 0, program.encode(), *args[:3], len(ops), *args[3:],
+                                               footer_records))
 
     def last_gunzip_stats(self) -> GunzipStats:
         """lx_last_gunzip_stats: the counts of the last gunzip(handle, ...); .decline_text is the last decline reason in words."""

@@ -5,10 +5,11 @@
 //                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--seeding gpu|host] [--records gpu|host|auto]
 //                   [--render gpu|host|auto]
 //
-// --render: where the alignment records of a .bam output are made.  host: lx_render_records on the host, the stream uploaded and
-// compressed by lx_bgzf_compress (what this front end always did; every other format takes this path whatever the option says).  gpu:
-// lx_write_bam_dev on the first device -- the records are kernels' work, compressed where they stand, only BGZF members come down; the
-// file is byte-identical.  auto = host until the measurement of DESIGN.md (4.13, "BAM records on the device") decides otherwise.
+// --render: where the records of the output are made, for every format.  host: the host writer (lx_write_records_ex for a plain
+// text file; lx_render_records, the stream uploaded and compressed by lx_bgzf_compress, for .bam and *.gz: what this front end always
+// did).  gpu: the records are kernels' work on the first device -- lx_write_bam_dev for .bam, lx_write_text_dev for .m8, .m9 and .sam;
+// with .bam and *.gz they are compressed where they stand and only BGZF members come down; the file is byte-identical.  auto = host
+// until the measurements of DESIGN.md (4.13, "BAM records on the device"; 4.14, "Text records on the device") decide otherwise.
 //
 // --records: where _writeRecord's sort / unique / sort / cut to -n (src/search_algo.hpp:820-882) runs.  host: lx_postprocess_records
 // once, over the records of all workers (what this front end always did).  gpu: a worker's Level-2 call on a DEVICE match list
@@ -392,7 +393,7 @@ struct Options
     std::string table       = "auto"; // --table gpu | host | auto: where the word table is made (auto: search* on the GPU, mkindex* on the host)
     std::string seeding     = "gpu";  // --seeding gpu | host: where search() runs (lx_seed_queries on the worker's handle -- one lane per read, reads
                                       // the device declines are finished on the host threads inside the call --, or on the -t threads)
-    std::string render      = "auto"; // --render gpu | host | auto: where the records of a .bam output are made (the header comment)
+    std::string render      = "auto"; // --render gpu | host | auto: where the records of the output are made (the header comment)
     std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
     int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     // mkindex* (src/mkindex_options.hpp:96-262): -d the database (FASTA), -i the index file to write
@@ -1765,6 +1766,22 @@ int main(int argc, char ** argv)
                 msRenderDev = msK;
                 renderedOnGpu = true;
             }
+            else if (opt.render == "gpu")
+            {
+                // --render gpu, a text format: the records made on the first device; *.gz compressed there, too
+                lx_handle * zh = nullptr;
+                if (lx_create(devices[0], &zh) != LX_OK)
+                    throw std::runtime_error(lx_last_error(nullptr));
+                std::unique_ptr<lx_handle, void (*)(lx_handle *)> keepH(zh, lx_destroy);
+                if (lx_write_text_dev(zh, opt.output.c_str(), fmt, outGz ? 1 : 0, program, bms.data(), nOut, ops.data(), ops.size(), &names,
+                                      reinterpret_cast<uint8_t const *>(qs.ascii.data()), qs.ascii_off.data(), &oo,
+                                      (int64_t)rst.qrys_with_hit) != LX_OK)
+                    throw std::runtime_error(std::string("text records on the GPU: ") + lx_last_error(zh));
+                float msK = 0;
+                (void)lx_last_phase_ms(zh, 12, &msK, nullptr);
+                msRenderDev   = msK;
+                renderedOnGpu = true;
+            }
             else if (fmt == LX_OUT_BAM || outGz)
             {
                 // records, footer and header rendered on the host threads, compressed on the device, written at once
@@ -1812,7 +1829,9 @@ int main(int argc, char ** argv)
                      "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records %.1f (%s), records + output %.0f%s, total %.0f\n",
                      msRead, gunzipNote.c_str(), fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
                      nPassesOnHost, msExtendMax, msRecords, recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msSince(tOut) - msCompress,
-                     renderedOnGpu                  ? (", BAM records rendered and BGZF-compressed on the GPU (render kernels " + std::to_string((long)(msRenderDev + 0.5)) + ")").c_str()
+                     renderedOnGpu                  ? (std::string(", ") + (fmt == LX_OUT_BAM ? "BAM" : fmt == LX_OUT_SAM ? "SAM" : "tabular") + " records rendered" +
+                                                       (fmt == LX_OUT_BAM || outGz ? " and BGZF-compressed" : "") + " on the GPU (render kernels " +
+                                                       std::to_string((long)(msRenderDev + 0.5)) + ")").c_str()
                      : (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str()
                                                     : "",
                      msSince(tStart));

@@ -1194,4 +1194,70 @@ std::string bam_header(lx_seq_names const * names, lx_output_options const * opt
     samHeaderText(hs, names, opt, tags);
     return bamHeaderBytes(headerText, names);
 }
+
+// ---- for the device text writer (lx_text_host.cpp): renderRecords' refusals for a text format, what it resolved (the columns as
+// indices into kColumns / the tags as bits in kSamTags' order), and the texts the host makes: the SAM header, the three constant
+// parts of a group's .m9 comment lines (in front of the query's id, between it and the hit count, behind the count)
+int text_check(int format, char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names,
+               lx_output_options const * opt_in, std::vector<int> & cols, uint32_t * tag_mask)
+{
+    int const rc = renderRecords(nullptr, format, 1, program, m, n, nullptr, names, nullptr, nullptr, opt_in);
+    if (rc != LX_OK)
+        return rc;
+    cols.clear();
+    *tag_mask = 0;
+    if (format == LX_OUT_SAM)
+    {
+        bool tags[kNumSamTags] = {};
+        if (!resolveTags(opt_in ? opt_in->sam_tags : nullptr, tags))
+            return LX_EINVAL;
+        for (int t = 0; t < kNumSamTags; ++t)
+            *tag_mask |= tags[t] ? 1u << t : 0u;
+    }
+    else if (!resolveColumns(opt_in ? opt_in->columns : nullptr, cols))
+        return LX_EINVAL;
+    for (uint64_t k = 0; k < n; ++k) // (the record loop's refusal)
+        if (m[k].n_qid >= names->n_q || m[k].n_sid >= names->n_s)
+        {
+            g_output_error = "a record names a query or a subject the name lists do not have";
+            return LX_EINVAL;
+        }
+    return LX_OK;
+}
+
+std::string sam_header(lx_seq_names const * names, lx_output_options const * opt_in, uint32_t tag_mask)
+{
+    lx_output_options opt;
+    lx_output_options_default(&opt);
+    if (opt_in)
+        opt = *opt_in;
+    bool tags[kNumSamTags];
+    for (int t = 0; t < kNumSamTags; ++t)
+        tags[t] = (tag_mask >> t) & 1u;
+    std::string headerText;
+    Sink        hs{nullptr, &headerText};
+    samHeaderText(hs, names, opt, tags);
+    return headerText;
+}
+
+void m9_comment_parts(char const * program, lx_output_options const * opt_in, std::vector<int> const & cols, std::string (&parts)[3])
+{
+    lx_output_options opt;
+    lx_output_options_default(&opt);
+    if (opt_in)
+        opt = *opt_in;
+    std::string upper(program);
+    for (char & c : upper)
+        c = (char)std::toupper((unsigned char)c);
+    std::string versionLine = upper + " 2.2.26+";
+    if (opt.version_to_output)
+        versionLine += std::string(" [created by LAMBDA") + (opt.version ? std::string("-") + opt.version : std::string()) +
+                       ", see http://seqan.de/lambda and please cite correctly in your academic work]";
+    std::string fields;
+    for (int c : cols)
+        fields += (fields.empty() ? "" : ", ") + std::string(kColumns[c].desc);
+    parts[0] = "# " + versionLine + "\n# Query: ";
+    parts[1] = std::string("\n# Database: ") + (opt.db_name ? opt.db_name : "lambda_ext") + "\n# Fields: " + fields + "\n# ";
+    parts[2] = " hits found\n";
+}
 } // namespace lxi

@@ -6,6 +6,7 @@
 // No DP arithmetic happens on the host and there is no CPU fallback: without a usable gfx950 device every entry point
 // returns an error.
 #include "lx_internal.h"
+#include "lx_numfmt.h"
 
 static_assert(sizeof(lx_extension) == sizeof(lx::Extension), "ABI mismatch");
 static_assert(sizeof(lx_hsp) == sizeof(lx::Hsp), "ABI mismatch");
@@ -1441,6 +1442,24 @@ char const * lx_last_kernel_name(lx_handle const * h)
 char const * lx_last_trace_kernel_name(lx_handle const * h)
 {
     return h ? h->last_trace_kernel.c_str() : "";
+}
+
+static_assert(LX_NUM_E1 == lx::kNumE1 && LX_NUM_F1 == lx::kNumF1 && LX_NUM_F2 == lx::kNumF2 && LX_NUM_G_FLOAT == lx::kNumGFloat,
+              "the ABI's kinds are the formatter's");
+
+int lx_format_number(int kind, double v, char * out, uint64_t cap)
+{
+    if (!out || kind < LX_NUM_E1 || kind > LX_NUM_G_FLOAT)
+        return LX_EINVAL;
+    uint64_t bits;
+    std::memcpy(&bits, &v, 8);
+    char      text[lx::kNumMaxText];
+    int const n = lx::num_format(kind, bits, text);
+    if (n == 0 || (uint64_t)n + 1 > cap) // (0: an F value outside the domain)
+        return LX_EINVAL;
+    std::memcpy(out, text, (size_t)n);
+    out[n] = 0;
+    return n;
 }
 
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches)

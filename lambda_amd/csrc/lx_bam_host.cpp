@@ -11,12 +11,14 @@
 // so the members are cut exactly where lx_bgzf_compress cuts them on the whole stream: the file is the one lx_write_records_bgzf
 // writes.  Only members come down.
 //
+// The steps the text writer (lx_text_host.cpp) shares -- the checks beyond the writer's own, flattening and upload, the groups, the
+// range cuts -- are lxi::rec_inputs and lxi::rec_ranges (lx_rec_host.h), defined here.
+//
 // lx_last_phase_ms: phase 11 = the render kernels (groups, measure, scans, emit), phase 4 = the encoder's, as for lx_bgzf_compress.
 #include <unordered_map>
 
-#include "lx_bam.h"
 #include "lx_bgzf.h"
-#include "lx_internal.h"
+#include "lx_rec_host.h"
 
 using namespace lxi;
 
@@ -27,49 +29,42 @@ constexpr uint64_t kDefaultRange = 256ull << 20;
 constexpr uint64_t kMaxRows      = (1ull << 31) - 16;
 constexpr uint64_t kMaxQlen      = 1ull << 30; // a record's bytes are counted in 32 bits
 constexpr uint32_t kMaxOps       = 1u << 26;
-constexpr uint64_t kMaxName      = 1ull << 20;
+constexpr uint64_t kMaxName      = kRecMaxName;
 
-struct Range
+using Range = RecRange;
+using Job   = RecJob;
+
+} // namespace
+
+namespace lxi
 {
-    uint64_t first, count, bytes;
-};
 
-struct Job
-{
-    lx::BamCtx         c{};
-    std::string        header;
-    std::vector<Range> ranges;
-    uint64_t           max_range = 0, total = 0;
-};
-
-int refuse(lx_handle * h, char const * who, int rc)
+int rec_refuse(lx_handle * h, char const * who, int rc)
 {
     return fail(h, rc, "%s: %s", who, *lx_last_output_error() ? lx_last_output_error() : "bad arguments");
 }
 
-template <class T>
-int upload(lx_handle * h, DevBuf & b, T const * src, uint64_t count, T const *& dev)
+int rec_begin(lx_handle * h)
 {
-    uint64_t const bytes = count * sizeof(T);
-    int const      rc    = ensure(h, b, std::max<uint64_t>(bytes, 16));
+    int const rc = bind(h);
     if (rc)
         return rc;
-    if (bytes)
-        LX_HIP(h, hipMemcpyAsync(b.ptr, src, bytes, hipMemcpyHostToDevice, h->stream));
-    dev = static_cast<T const *>(b.ptr);
+    h->phase_ev.clear();
+    h->ev_pool_used = 0;
     return LX_OK;
 }
 
-// checks, flattening, upload, groups + measure, the ranges
-int prepare(lx_handle * h, char const * who, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
-            uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, lx_output_options const * opt_in,
-            Job & job)
+int rec_inputs(lx_handle * h, char const * who, int phase, uint32_t tags, bool with_ops, char const * program, lx_blast_match const * m, uint64_t n,
+               uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+               lx_output_options const * opt_in, RecJob & job)
 {
-    // ---- refusals, before any device work
-    uint32_t tags = 0;
-    int      rc   = bam_check(program, m, n, names, opt_in, &tags);
-    if (rc != LX_OK)
-        return refuse(h, who, rc);
+    auto refuse = rec_refuse;
+    int  rc     = LX_OK;
+    if (!with_ops)
+    {
+        ops       = nullptr;
+        ops_bytes = 0;
+    }
     if ((!ops && ops_bytes) || (names->n_q && (!names->q_ids || !names->q_lens)))
         return refuse(h, who, LX_EINVAL);
     if (n > kMaxRows)
@@ -77,7 +72,7 @@ int prepare(lx_handle * h, char const * who, int write_header, char const * prog
         set_output_error("more records than the device writer takes in one call (2^31 - 16)");
         return refuse(h, who, LX_EINVAL);
     }
-    for (uint64_t k = 0; k < n; ++k)
+    for (uint64_t k = 0; with_ops && k < n; ++k)
         if (!lx_slice_ok(m[k].ops_off, m[k].n_ops, ops_bytes) || m[k].n_ops > kMaxOps)
         {
             set_output_error("a record's ops lie outside the ops buffer");
@@ -108,8 +103,6 @@ int prepare(lx_handle * h, char const * who, int write_header, char const * prog
     c.q_trans      = std::strcmp(program, "blastx") == 0 || std::strcmp(program, "tblastx") == 0;
     c.s_trans      = std::strcmp(program, "tblastn") == 0 || std::strcmp(program, "tblastx") == 0;
     c.n            = n;
-    if (write_header)
-        job.header = bam_header(names, opt_in, tags);
     if (n == 0)
         return LX_OK;
 
@@ -208,35 +201,35 @@ int prepare(lx_handle * h, char const * who, int write_header, char const * prog
 
     // ---- upload
     auto & B = h->bam;
-    if ((rc = upload(h, B.d_rows, m, n, c.rows)) || (rc = upload(h, B.d_ops, ops, ops_bytes, c.ops)) ||
-        (rc = upload(h, B.d_qlens, names->q_lens, n_q, c.q_lens)) || (rc = upload(h, B.d_qn_off, qn_off.data(), n_q + 1, c.qn_off)) ||
-        (rc = upload(h, B.d_qn_blob, qn_blob.data(), qn_blob.size(), c.qn_blob)))
+    if ((rc = rec_upload(h, B.d_rows, m, n, c.rows)) || (rc = rec_upload(h, B.d_ops, ops, ops_bytes, c.ops)) ||
+        (rc = rec_upload(h, B.d_qlens, names->q_lens, n_q, c.q_lens)) || (rc = rec_upload(h, B.d_qn_off, qn_off.data(), n_q + 1, c.qn_off)) ||
+        (rc = rec_upload(h, B.d_qn_blob, qn_blob.data(), qn_blob.size(), c.qn_blob)))
         return rc;
-    if (ascii && ((rc = upload(h, B.d_ascii, q_res_ascii, extent, c.q_ascii)) || (rc = upload(h, B.d_ascii_off, q_ascii_off, n_q, c.q_ascii_off))))
+    if (ascii && ((rc = rec_upload(h, B.d_ascii, q_res_ascii, extent, c.q_ascii)) || (rc = rec_upload(h, B.d_ascii_off, q_ascii_off, n_q, c.q_ascii_off))))
         return rc;
     c.q_ascii_bytes = ascii ? extent : 0;
     if ((tags & lx::kBamTagSt) && opt.tax && opt.tax->s_tax_off && (opt.tax->s_tax_ids || opt.tax->s_tax_off[opt.tax->n_s] == 0))
     {
         c.tax_n_s = opt.tax->n_s;
-        if ((rc = upload(h, B.d_tax_off, opt.tax->s_tax_off, c.tax_n_s + 1, c.s_tax_off)) ||
-            (rc = upload(h, B.d_tax_ids, opt.tax->s_tax_ids, opt.tax->s_tax_off[c.tax_n_s], c.s_tax_ids)))
+        if ((rc = rec_upload(h, B.d_tax_off, opt.tax->s_tax_off, c.tax_n_s + 1, c.s_tax_off)) ||
+            (rc = rec_upload(h, B.d_tax_ids, opt.tax->s_tax_ids, opt.tax->s_tax_off[c.tax_n_s], c.s_tax_ids)))
             return rc;
     }
     if (want_lca)
     {
         uint32_t const * tab = nullptr;
-        if ((rc = upload(h, B.d_grp_tab, grp_tab.data(), grp_tab.size(), tab)))
+        if ((rc = rec_upload(h, B.d_grp_tab, grp_tab.data(), grp_tab.size(), tab)))
             return rc;
         c.grp_lca = tab;
         if (tags & lx::kBamTagLs)
         {
             c.grp_name_off = tab + groups;
             c.grp_name_len = tab + 2 * groups;
-            if ((rc = upload(h, B.d_name_blob, name_blob.data(), name_blob.size(), c.name_blob)))
+            if ((rc = rec_upload(h, B.d_name_blob, name_blob.data(), name_blob.size(), c.name_blob)))
                 return rc;
         }
     }
-    if (have_codon && (rc = upload(h, B.d_codon, codon, (uint64_t)125, c.codon)))
+    if (have_codon && (rc = rec_upload(h, B.d_codon, codon, (uint64_t)125, c.codon)))
         return rc;
     uint64_t const tiles = (n + lx::kBamTile - 1) / lx::kBamTile;
     if ((rc = ensure(h, B.d_grp, n * 4)) || (rc = ensure(h, B.d_grp_first, (n + 1) * 4)) || (rc = ensure(h, B.d_aux, n * sizeof(lx::BamAux))) ||
@@ -248,16 +241,23 @@ int prepare(lx_handle * h, char const * who, int write_header, char const * prog
     c.aux       = static_cast<lx::BamAux *>(B.d_aux.ptr);
     c.size      = static_cast<uint32_t *>(B.d_size.ptr);
 
-    // ---- groups, sizes, and the tiles' totals for the cuts
-    hipStream_t const s = h->stream;
-    {
-        PhaseTimer t(h, s, 11);
-        LX_HIP(h, lx::bam_launch_groups(c, static_cast<uint32_t *>(B.d_scan.ptr), s));
-        LX_HIP(h, lx::bam_launch_measure(c, static_cast<uint64_t *>(B.d_tiles.ptr), s));
-        t.close();
-    }
+    // ---- groups
+    PhaseTimer t(h, h->stream, phase);
+    LX_HIP(h, lx::bam_launch_groups(c, static_cast<uint32_t *>(B.d_scan.ptr), h->stream));
+    t.close();
+    LX_HIP(h, hipStreamSynchronize(h->stream)); // (the uploads' host arrays go with this frame)
+    return LX_OK;
+}
+
+int rec_ranges(lx_handle * h, char const * who, RecJob & job)
+{
+    auto &            B     = h->bam;
+    uint64_t const    n     = job.c.n;
+    uint64_t const    tiles = (n + lx::kBamTile - 1) / lx::kBamTile;
+    hipStream_t const s     = h->stream;
+    // ---- the tiles' totals for the cuts
     LX_HIP(h, hipMemcpyAsync(B.p_tiles.ptr, B.d_tiles.ptr, tiles * 8, hipMemcpyDeviceToHost, s));
-    LX_HIP(h, hipStreamSynchronize(s)); // (the uploads' host arrays may go now, too)
+    LX_HIP(h, hipStreamSynchronize(s));
     uint64_t const * const tot    = static_cast<uint64_t const *>(B.p_tiles.ptr);
     uint64_t const         budget = h->opt_bam_range ? h->opt_bam_range : kDefaultRange;
     for (uint64_t t = 0; t < tiles;)
@@ -279,6 +279,36 @@ int prepare(lx_handle * h, char const * who, int write_header, char const * prog
     return LX_OK;
 }
 
+} // namespace lxi
+
+namespace
+{
+
+// checks, flattening, upload, groups + measure, the ranges
+int prepare(lx_handle * h, char const * who, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+            uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, lx_output_options const * opt_in,
+            Job & job)
+{
+    // ---- refusals, before any device work
+    uint32_t tags = 0;
+    int      rc   = bam_check(program, m, n, names, opt_in, &tags);
+    if (rc != LX_OK)
+        return rec_refuse(h, who, rc);
+    if ((rc = rec_inputs(h, who, 11, tags, true, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt_in, job)))
+        return rc;
+    if (write_header)
+        job.header = bam_header(names, opt_in, tags);
+    if (n == 0)
+        return LX_OK;
+    // ---- sizes, and the tiles' totals for the cuts
+    {
+        PhaseTimer t(h, h->stream, 11);
+        LX_HIP(h, lx::bam_launch_measure(job.c, static_cast<uint64_t *>(h->bam.d_tiles.ptr), h->stream));
+        t.close();
+    }
+    return rec_ranges(h, who, job);
+}
+
 // one range's records into `out` (device)
 int emit_range(lx_handle * h, Job const & job, Range const & r, uint8_t * out)
 {
@@ -286,16 +316,6 @@ int emit_range(lx_handle * h, Job const & job, Range const & r, uint8_t * out)
     PhaseTimer t(h, h->stream, 11);
     LX_HIP(h, lx::bam_launch_emit(job.c, r.first, r.count, static_cast<uint32_t *>(B.d_off.ptr), static_cast<uint32_t *>(B.d_scan.ptr), out, h->stream));
     t.close();
-    return LX_OK;
-}
-
-int begin(lx_handle * h)
-{
-    int const rc = bind(h);
-    if (rc)
-        return rc;
-    h->phase_ev.clear();
-    h->ev_pool_used = 0;
     return LX_OK;
 }
 
@@ -312,7 +332,7 @@ int lx_render_bam_dev(lx_handle * h, int write_header, char const * program, lx_
     if (!out)
         return fail(h, LX_EINVAL, "lx_render_bam_dev: out is NULL");
     *out   = nullptr;
-    int rc = begin(h);
+    int rc = rec_begin(h);
     if (rc)
         return rc;
     HostPool::Call in_call;
@@ -353,7 +373,7 @@ int lx_write_bam_dev(lx_handle * h, char const * path, char const * program, lx_
         return LX_EINVAL;
     if (!path)
         return fail(h, LX_EINVAL, "lx_write_bam_dev: path is NULL");
-    int rc = begin(h);
+    int rc = rec_begin(h);
     if (rc)
         return rc;
     HostPool::Call       in_call;

@@ -254,6 +254,13 @@ struct lx_handle
         DevBuf d_grp, d_grp_first, d_aux, d_size, d_off, d_scan, d_tiles, d_stream;
         Pinned p_tiles;
     } bam;
+    // lx_render_text_dev / lx_write_text_dev (lx_text_host.cpp) use `bam` for what both writers read, and beside it: the columns, the
+    // first words and lengths of the subjects the rows name and each row's index among them, the whole query ids and the constant
+    // parts of the comment lines (.m9), the number texts of every record
+    struct Text
+    {
+        DevBuf d_cols, d_row_s, d_slens, d_sn_off, d_sn_blob, d_qid_off, d_qid_blob, d_comment, d_nums;
+    } text;
     uint64_t opt_bam_range = 0; // LX_OPT_BAM_RANGE_BYTES (0 = default)
     uint64_t opt_gunzip_chunk = 0; // LX_OPT_GUNZIP_CHUNK (0 = default)
     uint64_t opt_gunzip_from  = 0; // LX_OPT_GUNZIP_PARALLEL_FROM (0 = default)
@@ -350,6 +357,13 @@ void       set_output_error(std::string const & msg);
 int         bam_check(char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names, lx_output_options const * opt,
                       uint32_t * tag_mask);
 std::string bam_header(lx_seq_names const * names, lx_output_options const * opt, uint32_t tag_mask);
+// (host/lx_output.cpp) for the device text writer: renderRecords' refusals for LX_OUT_BLAST_TAB / _COMMENTS / LX_OUT_SAM, with the
+// columns it resolved (indices into kColumns = lx_text.h's kTextCol*) or the tags as bits; the SAM header text; the three constant
+// parts of a query group's .m9 comment lines (in front of the query's id, between the id and the hit count, behind the count)
+int         text_check(int format, char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names,
+                       lx_output_options const * opt, std::vector<int> & cols, uint32_t * tag_mask);
+std::string sam_header(lx_seq_names const * names, lx_output_options const * opt, uint32_t tag_mask);
+void        m9_comment_parts(char const * program, lx_output_options const * opt, std::vector<int> const & cols, std::string (&parts)[3]);
 // (lx_bgzf_host.cpp) lx_bgzf_compress's members of n bytes that stand on the device already (16-byte aligned): the same chunks of 512
 // blocks, the same member bytes, the same download pipeline; `sink` takes each chunk's members in order.  The phase events of the
 // call so far stay.
