@@ -754,6 +754,43 @@ int lx_write_text_dev(lx_handle * h, char const * path, int format, int bgzf, ch
                       uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
                       uint64_t const * q_ascii_off, lx_output_options const * opt, int64_t footer_records);
 
+/* An output file written piece by piece.  After lx_out_close the file is byte for byte the file the one-shot writers make from
+ * the concatenated list -- lx_write_records_ex + lx_write_footer (plain text), lx_write_records_bgzf (bgzf, LX_OUT_BAM),
+ * lx_write_text_dev / lx_write_bam_dev (which agree with those) --, wherever the pieces were rendered and however the list was cut.
+ *
+ * lx_out_open writes the header: the SAM header, or the BAM magic with header text and reference list, from `subjects` (only s_ids,
+ * s_lens and n_s are read; they, opt->tax and opt->tax_names must stay valid until lx_out_close; the texts of opt are copied; its
+ * lca_* are not read).  bgzf = 1, and LX_OUT_BAM always: the stream is BGZF-compressed on h's device, cut into 65 280-byte blocks
+ * exactly as lx_bgzf_compress cuts the whole stream.  Refusals are those of the one-shot writers -- an unknown format, program,
+ * column or tag -- and bgzf or LX_OUT_BAM without a handle; all before `path` is created or truncated.  A failure behind them
+ * (the encoder, the disk) removes the file again.  h may be NULL for a plain
+ * file rendered on the host; the texts are then in lx_last_output_error(), else in lx_last_error(h).
+ *
+ * lx_out_append renders n records: where = LX_RENDER_HOST by the code of lx_render_records, LX_RENDER_DEV by the kernels of
+ * lx_render_text_dev / lx_render_bam_dev (it needs a handle).  A piece holds WHOLE query groups: everything that is decided per
+ * query (the comment lines of .m9, FLAG, IH, --sam-bam-seq uniq, the LCA) is then decided inside the piece.  `names` describes this
+ * piece's queries (q_ids, q_lens, n_q; m[].n_qid, q_ascii_off and lca_qid count within the piece); m[].n_sid counts within the
+ * subjects given at open.  Of a compressed stream, the bytes that do not fill a block (always fewer than 65 280) stay in the
+ * object -- on the device when the piece was rendered there, where the records are compressed as they stand and only members come
+ * down -- and go in front of the next piece.  n = 0 is a no-op whatever the other arguments are.  A refused piece (LX_EINVAL from
+ * the checks of the one-shot writers, made before any kernel runs) leaves the file as it was; after any other failure every later
+ * append is refused.  lx_last_phase_ms(h, 4 / 11 / 12, ...) report the last append.
+ *
+ * lx_out_close writes the footer of .m9 (footer_records >= 0: "# BLAST processed N queries"), the last partial block and the
+ * EOF member, closes the file and frees o -- also when it fails. */
+typedef struct lx_out lx_out;
+enum
+{
+    LX_RENDER_HOST = 0,
+    LX_RENDER_DEV  = 1
+};
+int lx_out_open(lx_handle * h, char const * path, int format, int bgzf, char const * program, lx_seq_names const * subjects,
+                lx_output_options const * opt, lx_out ** out);
+int lx_out_append(lx_out * o, int where, lx_blast_match const * m, uint64_t n, uint8_t const * ops, uint64_t ops_bytes,
+                  lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, uint64_t const * lca_qid,
+                  uint32_t const * lca_tax, uint64_t n_lca);
+int lx_out_close(lx_out * o, int64_t footer_records);
+
 /* Decompresses a gzip stream of one or more members (RFC 1952): BGZF members on h's device, other members on the calling
  * thread; h may be NULL (every member on the host).  *out is released with lx_bytes_free.  Malformed input: LX_EINVAL.
  * A member with the BGZF subfield (BC, BSIZE) whose DEFLATE bytes and ISIZE are at most 64 KiB is decoded on the device, one
@@ -807,6 +844,26 @@ typedef struct lx_gunzip_stats
 int lx_last_gunzip_stats(lx_handle const * h, lx_gunzip_stats * stats);
 /* A decline reason in words ("no boundary", "room", ...). */
 char const * lx_gunzip_decline_text(int reason);
+
+/* lx_gunzip over a FILE, piece by piece, in bounded memory.  The pieces, concatenated, are exactly what lx_gunzip(h, the file's
+ * bytes) returns; for a file that does not begin with the gzip magic they are the file's own bytes.  Every piece but the last has
+ * at least one byte and at most piece_bytes + 65536 (piece_bytes = 0: 64 MiB).  The stream walks the members as lx_gunzip does:
+ * BGZF members (BC subfield, at most 64 KiB of DEFLATE bytes and of text) are gathered, whole, until their ISIZE sum fills the
+ * piece, and the group is decoded by the BGZF path -- on h's device, or member by member on the calling thread when h is NULL --;
+ * only that group's compressed bytes are read from the file.  Every other member is decoded on the calling thread by the same
+ * DEFLATE code, which stops between two symbols once the piece is full and keeps the last 32 KiB of text as the window; CRC32 and
+ * ISIZE are checked at the trailer.  The parallel plain-member device path of lx_gunzip is NOT used here: it needs the member's
+ * whole text on the device.  The file is mapped (a file that cannot be mapped is read whole, compressed); between calls the stream
+ * holds O(piece_bytes) of text.  A corrupt stream fails in the call that reaches the damage, with lx_gunzip's message for the
+ * whole file: member number, and byte offset from the start of the file; every later call fails.  A plain member's CRC32 is
+ * known at its trailer only, so pieces handed out before the failing call may hold text of the member that failed.  NULL arguments and a file
+ * that cannot be opened: LX_EINVAL with a text (lx_last_error(h), or lx_last_output_error() when h is NULL).  While the stream is
+ * open, h serves no other call between lx_gunzip_stream_next and the reading of its phase time (5) or stats. */
+typedef struct lx_gunzip_stream lx_gunzip_stream;
+int  lx_gunzip_stream_open(lx_handle * h, char const * path, uint64_t piece_bytes, lx_gunzip_stream ** out);
+/* The next piece (released with lx_bytes_free); LX_OK with *piece == NULL at the end. */
+int  lx_gunzip_stream_next(lx_gunzip_stream * s, lx_bytes ** piece);
+void lx_gunzip_stream_close(lx_gunzip_stream * s);
 
 /* ---- taxonomy of an index (mkindex -m / -x: src/mkindex_algo.hpp:68-107, :277-598, src/mkindex_misc.hpp:69-144) ----------- */
 /* Every non-overlapping match of the reference's accession regex in text[0, n) (UniProt, NCBI nucleotide / protein / WGS / MGA,

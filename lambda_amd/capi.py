@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
     "lx_index_build", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
+    "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_close",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -290,6 +291,10 @@ def load():
     lib.lx_last_gunzip_stats.argtypes = [vp, C.POINTER(GunzipStats)]
     lib.lx_gunzip_decline_text.argtypes = [i32]
     lib.lx_gunzip_decline_text.restype = C.c_char_p
+    lib.lx_gunzip_stream_open.argtypes = [vp, C.c_char_p, u64, C.POINTER(vp)]
+    lib.lx_gunzip_stream_next.argtypes = [vp, C.POINTER(vp)]
+    lib.lx_gunzip_stream_close.argtypes = [vp]
+    lib.lx_gunzip_stream_close.restype = None
     lib.lx_find_accessions.argtypes = [vp, u64, vp, vp, u64, C.POINTER(u64)]
     lib.lx_taxmap_create.argtypes = [vp, i32, vp, vp, u64, u64, C.c_uint32, C.POINTER(vp)]
     lib.lx_taxmap_feed.argtypes = [vp, vp, u64]
@@ -326,6 +331,9 @@ def load():
                                        C.POINTER(vp)]
     lib.lx_write_text_dev.argtypes = [vp, C.c_char_p, i32, i32, C.c_char_p, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions),
                                       C.c_int64]
+    lib.lx_out_open.argtypes = [vp, C.c_char_p, i32, i32, C.c_char_p, C.POINTER(SeqNames), C.POINTER(OutputOptions), C.POINTER(vp)]
+    lib.lx_out_append.argtypes = [vp, i32, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, vp, vp, u64]
+    lib.lx_out_close.argtypes = [vp, C.c_int64]
     _lib = lib
     return lib
 
@@ -426,6 +434,49 @@ def render_records(fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, 
         lib.lx_bytes_free(out)
 
 
+LX_RENDER_HOST, LX_RENDER_DEV = 0, 1
+
+
+class Out:
+    """lx_out_*: an output file written piece by piece; after close() it is byte for byte the file the one-shot writers make from the
+    concatenated list.  handle None: a plain text file rendered on the host.  bgzf (always for LX_OUT_BAM): BGZF-compressed on the
+    handle's device.  append() takes whole query groups; its query ids, lengths, letters and LCA pairs are those of the piece, the
+    records' n_qid count within it."""
+
+    def __init__(self, handle: "Handle | None", path, fmt: int, s_ids, s_lens, program="blastp", bgzf=False,
+                 options: OutputOptions | None = None):
+        self.lib, self.handle, self.o = load(), handle, C.c_void_p()
+        sa = (C.c_char_p * len(s_ids))(*[x.encode() for x in s_ids])
+        sl = np.ascontiguousarray(s_lens, dtype=np.uint64)
+        self._keep = (sa, sl, options)  # (the library reads the subjects until close)
+        subjects = SeqNames(None, None, sa, sl.ctypes.data, 0, len(s_ids))
+        self._check(self.lib.lx_out_open(handle.h if handle is not None else None, os.fsencode(path), fmt, 1 if bgzf else 0, program.encode(),
+                                         C.byref(subjects), C.byref(options) if options is not None else None, C.byref(self.o)))
+
+    def _check(self, rc):
+        if rc != LX_OK:
+            raise LambdaExtError(rc, self.lib.lx_last_error(self.handle.h).decode() if self.handle is not None else last_output_error())
+
+    def append(self, where: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, q_ascii: bytes | None = None, q_ascii_off=None,
+               lca_qid=None, lca_tax=None):
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, [], [], q_ascii, q_ascii_off, None)
+        lq = np.ascontiguousarray(lca_qid, dtype=np.uint64) if lca_qid is not None else None
+        lt = np.ascontiguousarray(lca_tax, dtype=np.uint32) if lca_tax is not None else None
+        self._check(self.lib.lx_out_append(self.o, where, *args[:3], len(ops), *args[3:6], _ptr(lq) if lq is not None and len(lq) else None,
+                                           _ptr(lt) if lt is not None and len(lt) else None, len(lq) if lq is not None else 0))
+
+    def close(self, footer_records: int = -1):
+        o, self.o = self.o, C.c_void_p()
+        if o:
+            self._check(self.lib.lx_out_close(o, footer_records))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 LX_NUM_E1, LX_NUM_F1, LX_NUM_F2, LX_NUM_G_FLOAT = 0, 1, 2, 3
 
 
@@ -460,6 +511,38 @@ def gunzip(handle: "Handle | None", data: bytes) -> bytes:
         return C.string_at(lib.lx_bytes_data(out), lib.lx_bytes_size(out)) if lib.lx_bytes_size(out) else b""
     finally:
         lib.lx_bytes_free(out)
+
+
+def gunzip_stream(handle: "Handle | None", path, piece_bytes: int = 0):
+    """lx_gunzip_stream_*: yields the pieces of the file's decompressed text (of the file's own bytes when it is not gzip), each of
+    at most piece_bytes + 65536 bytes (0 = 64 MiB); concatenated they are gunzip(handle, the file's bytes).  BGZF members are decoded
+    in groups on the handle's device (handle None: on this thread), every other member on this thread with a 32 KiB window.  A
+    corrupt stream raises LambdaExtError(LX_EINVAL) from the piece that reaches the damage, with gunzip's message."""
+    lib = load()
+    h = handle.h if handle is not None else None
+
+    def error(rc):
+        return LambdaExtError(rc, lib.lx_last_error(h).decode() if h is not None else last_output_error())
+
+    s = C.c_void_p()
+    rc = lib.lx_gunzip_stream_open(h, os.fsencode(path) if path is not None else None, piece_bytes, C.byref(s))
+    if rc != LX_OK:
+        raise error(rc)
+    try:
+        while True:
+            out = C.c_void_p()
+            rc = lib.lx_gunzip_stream_next(s, C.byref(out))
+            if rc != LX_OK:
+                raise error(rc)
+            if not out:
+                return
+            try:
+                piece = C.string_at(lib.lx_bytes_data(out), lib.lx_bytes_size(out))
+            finally:
+                lib.lx_bytes_free(out)
+            yield piece
+    finally:
+        lib.lx_gunzip_stream_close(s)
 
 
 def find_accessions(text: bytes):

@@ -22,6 +22,21 @@
 // pass searches the queries WITHOUT records).  auto: see DESIGN.md ("_writeRecord on the device") for the measurement behind it.
 // LCA and the writers stay on the host, fed with the kept records; the output is byte-identical either way.
 //
+// --lazy-query 1 [--query-block N]: the query file block by block, in bounded memory -- the reference's batch loop with its reader
+// thread behind a bounded queue (src/search.cpp:389-459, src/search_algo.hpp:374-413).  One reader takes the file as a stream
+// (lx_gunzip_stream: BGZF groups on the first device, other members on its thread), parses it piece by piece
+// (lx_query_blocks.hpp) and makes blocks of at most N reads (default 2^20, NOT measured yet: tools/query_blocks_bench.py; a block
+// also closes at 2^30 letters): ranks, frames, reduction.  One worker per entry of --devices takes the next block and searches all of
+// it as the eager path searches a worker's range -- lx_set_queries and lx_reserve for the block, the --search0 pre-pass and the
+// second pass for its reads without a record, _writeRecord's cut (--records gpu | host: every record of a read comes out of its
+// block), the LCA.  The main thread appends the finished blocks in their order through lx_out (--render gpu: rendered, and for
+// .bam / *.gz compressed, on the first device).  At most workers + 2 blocks exist at a time; a full pipeline makes the reader wait.
+// The output is byte-identical to the eager run's; the two summary lines keep their wording with counts summed over the blocks and a
+// worker's times accumulated, and a third line names the blocks, the reads of the largest and the most blocks alive at once.  An
+// error in block k (a malformed record) ends the run non-zero with the eager run's message; the output file then holds the blocks
+// in front of k (the eager path fails before it writes).  --query-block N alone implies --lazy-query 1; --lazy-query 0 and
+// --query-block 0 are the eager path.  A query file that cannot be mapped (a pipe) is held whole in memory, compressed.
+//
 // Inputs (-q, -d of search* and mkindex*) are FASTA or FASTQ, plain or gzip-compressed, as the reference's (fa, fq, fasta, fastq,
 // fna, faa, each optionally .gz: src/search_options.hpp:157-167, src/mkindex_options.hpp:96-105); the format comes from the bytes
 // (gzip magic, then ">" or "@"), not the name.  lx_gunzip decompresses: BGZF members on the first device of --devices for search*
@@ -68,9 +83,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <fstream>
+#include <functional>
 #include <iostream>
+#include <condition_variable>
+#include <deque>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -79,6 +100,7 @@
 
 #include "blast_stats.hpp"
 #include "lambda_ext.hpp"
+#include "lx_query_blocks.hpp"
 #include "lx_seeding.hpp"
 #include "scoring_tables.hpp"
 
@@ -188,102 +210,18 @@ InputText readInput(std::string const & path, int device)
     return r;
 }
 
-// calls f(id, letters) per record of a FASTA (">") or FASTQ ("@") text, until f returns false.  FASTQ: the "@" line, sequence
-// lines up to a line starting with "+", then quality lines until there are as many quality characters as letters; the qualities
-// are dropped, as the reference drops them (src/search_algo.hpp:342).
-template <class F>
-void forEachRecord(std::string const & text, std::string const & path, F && f)
-{
-    size_t       p = 0;
-    size_t const n = text.size();
-    auto         nextLine = [&](char const *& a, size_t & len) -> bool
-    {
-        if (p >= n)
-            return false;
-        size_t e = text.find('\n', p);
-        if (e == std::string::npos)
-            e = n;
-        a   = text.data() + p;
-        len = e - p;
-        p   = e + 1;
-        if (len && a[len - 1] == '\r')
-            --len;
-        return true;
-    };
-    auto append = [](std::string & cur, char const * a, size_t len)
-    {
-        for (size_t i = 0; i < len; ++i)
-            if (!std::isspace((unsigned char)a[i]))
-                cur.push_back(a[i]);
-    };
-    size_t const first = text.find_first_not_of(" \t\r\n");
-    char const * a     = nullptr;
-    size_t       len   = 0;
-    std::string  id, cur;
-    if (first != std::string::npos && text[first] == '@')
-    {
-        while (nextLine(a, len))
-        {
-            if (len == 0)
-                continue;
-            if (a[0] != '@')
-                throw std::runtime_error(path + ": FASTQ record expected, found a line starting with '" + std::string(1, a[0]) + "'");
-            id.assign(a + 1, len - 1);
-            cur.clear();
-            bool plus = false;
-            while (nextLine(a, len))
-            {
-                if (len && a[0] == '+')
-                {
-                    plus = true;
-                    break;
-                }
-                append(cur, a, len);
-            }
-            if (!plus)
-                throw std::runtime_error(path + ": FASTQ record '" + id + "' has no '+' line");
-            size_t quals = 0;
-            while (quals < cur.size() && nextLine(a, len))
-                quals += len;
-            if (quals != cur.size())
-                throw std::runtime_error(path + ": FASTQ record '" + id + "' has " + std::to_string(quals) + " quality characters for " +
-                                         std::to_string(cur.size()) + " letters");
-            if (!f(id, cur))
-                return;
-        }
-        return;
-    }
-    bool have = false;
-    while (nextLine(a, len))
-    {
-        if (len == 0)
-            continue;
-        if (a[0] == '>')
-        {
-            if (have && !f(id, cur))
-                return;
-            id.assign(a + 1, len - 1);
-            cur.clear();
-            have = true;
-        }
-        else if (have)
-            append(cur, a, len);
-    }
-    if (have)
-        f(id, cur);
-}
+// f(id, letters) per record of a FASTA (">") or FASTQ ("@") text, until f returns false: the rules are lx_query_blocks.hpp's, an
+// incremental parser that is fed the whole text here.
+using lx_query_blocks::forEachRecord;
 
 // translate = six protein frames per nucleotide sequence (BLASTX queries: qryNumFrames = 6, translate_join)
 // bsFrames: 0 = none; 1 = bisulfite subjects (every sequence twice: views::duplicate, src/shared_definitions.hpp:249-250);
 // 2 = bisulfite queries (strand, strand, reverse complement, reverse complement: add_reverse_complement | duplicate, :260-261)
-void readFasta(std::string const & text, std::string const & path, bool protein, bool addRevComp, SeqSet & out, bool translate = false,
-               int geneticCode = 1, int bsFrames = 0)
+// one record into the set: its letters, ranks and frames (`cur` is used up)
+void addRecord(SeqSet & out, std::string const & id, std::string & cur, bool protein, bool addRevComp, bool translate, int geneticCode, int bsFrames)
 {
-    std::string cur;
-    auto flush = [&]()
     {
-        if (out.ids.size() == out.orig_len.size())
-            return;
+        out.ids.push_back(id);
         out.ascii_off.push_back(out.ascii.size());
         out.orig_len.push_back(cur.size());
         out.ascii += cur;
@@ -354,13 +292,16 @@ void readFasta(std::string const & text, std::string const & path, bool protein,
                 out.res[at + k] = comp[out.res[at - 1 - k]];
         }
         cur.clear();
-    };
+    }
+}
+
+void readFasta(std::string const & text, std::string const & path, bool protein, bool addRevComp, SeqSet & out, bool translate = false,
+               int geneticCode = 1, int bsFrames = 0)
+{
     forEachRecord(text, path,
                   [&](std::string const & id, std::string & letters)
                   {
-                      out.ids.push_back(id);
-                      cur.swap(letters);
-                      flush();
+                      addRecord(out, id, letters, protein, addRevComp, translate, geneticCode, bsFrames);
                       return true;
                   });
 }
@@ -396,6 +337,9 @@ struct Options
     std::string render      = "auto"; // --render gpu | host | auto: where the records of the output are made (the header comment)
     std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
     int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
+    bool        lazyQuery   = false; // --lazy-query 1: the query file block by block (the header comment)
+    uint64_t    queryBlock  = 0;     // --query-block N: at most N reads per block; given and > 0, it implies --lazy-query 1
+    bool        queryBlockGiven = false;
     // mkindex* (src/mkindex_options.hpp:96-262): -d the database (FASTA), -i the index file to write
     std::string index;                // -i of mkindex* (default: DATABASE.lba, :132, :249-250)
     std::string dbIndexType = "fm";   // --db-index-type fm | bifm (:157-165; recorded, the word table answers both)
@@ -422,6 +366,143 @@ bool looksLikeDna(std::string const & text, std::string const & path)
     return all > 0 && nuc * 10 >= all * 9;
 }
 
+// ---- --lazy-query: the query file as a stream of pieces (lx_gunzip_stream: decompressed where needed, BGZF groups on `device`)
+// and of records (lx_query_blocks::RecordParser).  The first two pieces are taken at once: the bzip2 refusal and the alphabet come
+// from the first, and whether it is the whole file from the second.
+struct QueryStream
+{
+    std::string                                       path;
+    std::unique_ptr<lx_handle, void (*)(lx_handle *)> h{nullptr, lx_destroy};
+    lx_gunzip_stream *                                s = nullptr;
+    std::vector<lx_bytes *>                           ahead; // pieces taken and not parsed yet
+    bool                                              ended = false;
+    lx_query_blocks::RecordParser                     parser;
+
+    QueryStream(std::string const & path_, int device) : path(path_), parser(path_)
+    {
+        lx_handle * raw = nullptr;
+        if (device >= 0 && lx_create(device, &raw) != LX_OK)
+            throw std::runtime_error(lx_last_error(nullptr));
+        h.reset(raw);
+        if (lx_gunzip_stream_open(raw, path.c_str(), kPiece, &s) != LX_OK)
+        {
+            std::string const why = raw ? lx_last_error(raw) : lx_last_output_error();
+            throw std::runtime_error(why.find("cannot open") != std::string::npos ? "cannot open " + path : path + ": " + why);
+        }
+        take();
+        take();
+        if (!ahead.empty() && lx_bytes_size(ahead[0]) >= 3 && std::memcmp(lx_bytes_data(ahead[0]), "BZh", 3) == 0)
+            throw std::runtime_error(path + ": bzip2-compressed input is not supported (decompress it, or recompress it with gzip or bgzip)");
+    }
+    QueryStream(QueryStream const &) = delete;
+    ~QueryStream()
+    {
+        for (lx_bytes * b : ahead)
+            lx_bytes_free(b);
+        lx_gunzip_stream_close(s);
+    }
+    void take() // one more piece into `ahead`, or the end
+    {
+        if (ended)
+            return;
+        lx_bytes * piece = nullptr;
+        if (lx_gunzip_stream_next(s, &piece) != LX_OK)
+            throw std::runtime_error(path + ": " + (h ? lx_last_error(h.get()) : lx_last_output_error()));
+        if (piece)
+            ahead.push_back(piece);
+        else
+            ended = true;
+    }
+    // looksLikeDna over the first piece (all of the file a small file has)
+    bool looksLikeDna() const
+    {
+        uint64_t nuc = 0, all = 0;
+        auto     f   = [&](std::string const &, std::string const & letters)
+        {
+            for (char c : letters)
+                nuc += std::strchr("ACGTUNacgtun", c) != nullptr;
+            all += letters.size();
+            return all < 100000;
+        };
+        lx_query_blocks::RecordParser p(path);
+        try
+        {
+            if (!ahead.empty() && p.feed(reinterpret_cast<char const *>(lx_bytes_data(ahead[0])), lx_bytes_size(ahead[0]), f) && ahead.size() == 1)
+                p.finish(f);
+        }
+        catch (std::runtime_error const &)
+        {
+            // (a malformed record: the letters in front of it decide; the block that holds it reports it)
+        }
+        return all > 0 && nuc * 10 >= all * 9;
+    }
+    // f(id, letters) per record from where the last call stopped, until f returns false (true: more may follow) or the file ends
+    // (false).  A piece is parsed whole, so records f has not asked for wait in `kept`.
+    template <class F>
+    bool records(F && f)
+    {
+        for (;;)
+        {
+            while (keptAt < kept.size())
+            {
+                auto & r = kept[keptAt++];
+                if (!f(r.first, r.second))
+                    return true;
+            }
+            kept.clear();
+            keptAt = 0;
+            if (malformed) // (the records in front of it have been handed out)
+                std::rethrow_exception(malformed);
+            auto keep = [&](std::string const & id, std::string & letters)
+            {
+                kept.emplace_back(id, std::string());
+                kept.back().second.swap(letters);
+                return true;
+            };
+            if (!ahead.empty()) // (a slice of the piece at a time: `kept` stays small)
+            {
+                lx_bytes * const b = ahead.front();
+                uint64_t const   n = std::min<uint64_t>(kSlice, lx_bytes_size(b) - pieceAt);
+                try
+                {
+                    parser.feed(reinterpret_cast<char const *>(lx_bytes_data(b)) + pieceAt, n, keep);
+                }
+                catch (std::runtime_error const &)
+                {
+                    malformed = std::current_exception();
+                }
+                if ((pieceAt += n) == lx_bytes_size(b))
+                {
+                    lx_bytes_free(b);
+                    ahead.erase(ahead.begin());
+                    pieceAt = 0;
+                    take();
+                }
+            }
+            else if (!finished)
+            {
+                finished = true;
+                try
+                {
+                    parser.finish(keep);
+                }
+                catch (std::runtime_error const &)
+                {
+                    malformed = std::current_exception();
+                }
+            }
+            else
+                return false;
+        }
+    }
+    std::vector<std::pair<std::string, std::string>> kept;
+    size_t                                           keptAt = 0;
+    uint64_t                                         pieceAt = 0; // bytes of ahead[0] the parser has
+    bool                                             finished = false;
+    std::exception_ptr                               malformed; // the parser's error, kept until the records in front of it are out
+    static constexpr uint64_t kPiece = 8ull << 20, kSlice = 1ull << 20; // text per piece of the stream; per call of the parser
+};
+
 static int outputFormat(std::string const & path, bool & gz);
 
 Options parse(int argc, char ** argv)
@@ -429,7 +510,8 @@ Options parse(int argc, char ** argv)
     Options o;
     if (argc < 2)
         throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.{fa,fq,fasta,fastq,fna,faa}[.gz] (-i DB.lba | -d DB.fasta[.gz]) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
-                                 "[--devices 0,1,...] [-t THREADS]\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
+                                 "[--devices 0,1,...] [-t THREADS]\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
+                                 "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
     if (o.cmd != "searchp" && o.cmd != "searchn" && o.cmd != "searchbs" && !mk)
@@ -635,7 +717,17 @@ Options parse(int argc, char ** argv)
             if (which != "auto" && which != "dna5" && which != "aminoacid")
                 throw std::runtime_error("--input-alphabet takes auto, dna5 or aminoacid");
         }
-        else if (a == "-v" || a == "--verbosity" || a == "--lazy-query")
+        else if (a == "--lazy-query") // (the reference's switch: the query file in blocks, src/search.cpp:389-459)
+            o.lazyQuery = onOff(val());
+        else if (a == "--query-block") // (this front end's: reads per block; giving it implies lazy loading, 0 = the eager path)
+        {
+            long long const v = std::stoll(val());
+            if (v < 0)
+                throw std::runtime_error("--query-block takes a number of reads (0 = read the whole file at once)");
+            o.queryBlock      = (uint64_t)v;
+            o.queryBlockGiven = true;
+        }
+        else if (a == "-v" || a == "--verbosity")
             (void)val(); // accepted for command-line compatibility, no effect here
         else
             throw std::runtime_error("unknown option " + a);
@@ -1074,6 +1166,9 @@ int main(int argc, char ** argv)
         bool const    prot = opt.cmd == "searchp" || opt.cmd == "mkindexp", bs = opt.cmd == "searchbs" || opt.cmd == "mkindexbs";
         // -i / -d names an index made by `lambda3 mkindex*`, or the database as FASTA (the table is then made in memory)
         bool const    fromIndex = !mk && isIndexFile(opt.db);
+        // --lazy-query 1 / --query-block N: the query file block by block (the header comment); --query-block 0 = the eager path
+        bool const     lazy       = !mk && (opt.queryBlockGiven ? opt.queryBlock > 0 : opt.lazyQuery);
+        uint64_t const blockReads = opt.queryBlock ? opt.queryBlock : (1ull << 20); // (the default is not measured yet: DESIGN.md 5.1)
         SeqSet           qs, db;
         IndexFileOptions ifo;
         struct FileCloser
@@ -1107,6 +1202,9 @@ int main(int argc, char ** argv)
         int const   gunzipDevice = (!mk || opt.table == "gpu") ? (opt.devices.empty() ? 0 : opt.devices[0]) : -1;
         InputText   qIn, dIn;
         std::string loadError;
+        std::unique_ptr<QueryStream> qStream; // --lazy-query: the query file stays a stream (its first pieces are here: format, alphabet)
+        if (lazy)
+            qStream.reset(new QueryStream(opt.query, gunzipDevice));
         {
             std::thread qLoader;
             auto        loadQueries = [&]()
@@ -1129,9 +1227,9 @@ int main(int argc, char ** argv)
                         t.join();
                 }
             } loadJoiner{qLoader};
-            if (!mk && opt.threads != 1)
+            if (!mk && !lazy && opt.threads != 1)
                 qLoader = std::thread(loadQueries);
-            else if (!mk)
+            else if (!mk && !lazy)
                 loadQueries();
             if (!fromIndex)
                 dIn = readInput(opt.db, gunzipDevice);
@@ -1143,7 +1241,7 @@ int main(int argc, char ** argv)
         uint64_t const plainMembers = qIn.plainMembers + dIn.plainMembers, plainChunks = qIn.plainChunks + dIn.plainChunks;
         std::string const reduction = !fromIndex ? opt.reduction : ifo.redAlph == kAlphLi10 ? "li10" : ifo.redAlph == kAlphMurphy10 ? "murphy10" : "none";
         // searchp with nucleotide queries is BLASTX: six translated frames per query against the protein database
-        bool const    blastx = !mk && prot && (opt.qryAlphabet == "dna5" || (opt.qryAlphabet == "auto" && looksLikeDna(qIn.text, opt.query)));
+        bool const    blastx = !mk && prot && (opt.qryAlphabet == "dna5" || (opt.qryAlphabet == "auto" && (lazy ? qStream->looksLikeDna() : looksLikeDna(qIn.text, opt.query))));
         // searchp against a nucleotide database translates the subjects instead (TBLASTN), or both sides (TBLASTX)
         bool const    sTrans  = fromIndex ? (prot && ifo.origAlph != ifo.transAlph)
                                           : prot && (opt.dbAlphabet == "dna5" || (opt.dbAlphabet == "auto" && looksLikeDna(dIn.text, opt.db)));
@@ -1182,9 +1280,9 @@ int main(int argc, char ** argv)
                     t.join();
             }
         } joiner{qryReader};
-        if (!mk && opt.threads != 1)
+        if (!mk && !lazy && opt.threads != 1)
             qryReader = std::thread(readQueries);
-        else if (!mk)
+        else if (!mk && !lazy)
             readQueries();
         if (!fromIndex)
         {
@@ -1198,7 +1296,7 @@ int main(int argc, char ** argv)
             qryReader.join();
         if (!qryError.empty())
             throw std::runtime_error(qryError);
-        if ((!mk && qs.ids.empty()) || db.ids.empty())
+        if ((!mk && !lazy && qs.ids.empty()) || db.ids.empty())
             throw std::runtime_error("empty query or database file");
         if (fromIndex && db.off.size() != db.ids.size() * (size_t)sFrames)
             throw std::runtime_error("index file " + opt.db + ": the frames of its sequences do not fit its alphabets");
@@ -1412,7 +1510,7 @@ int main(int argc, char ** argv)
         // one worker = one handle per entry of --devices (a device may be listed twice); -t host threads in all, shared out among
         // the workers for the seeding of their reads (the reference: -t OpenMP threads, each with its own LocalDataHolder; a GPU
         // wants few, large extension batches, the seeding wants every core)
-        size_t const   nWorkers = std::max<size_t>(1, std::min<size_t>(devices.size(), qs.ids.size()));
+        size_t const   nWorkers = lazy ? devices.size() : std::max<size_t>(1, std::min<size_t>(devices.size(), qs.ids.size()));
         unsigned const seedThreads = std::max(1u, nThreads / (unsigned)nWorkers);
 
         // ---- seeding (search(), src/search_algo.hpp:611-762) over the sorted table of reduced words
@@ -1471,15 +1569,22 @@ int main(int argc, char ** argv)
         uint64_t const    nReads = qs.ids.size();
         // --records (the header comment): auto = host -- the measured rule of DESIGN.md ("_writeRecord on the device")
         bool const recordsOnGpu = opt.records == "gpu" && opt.maxMatches > 0;
-        auto worker = [&](size_t w)
+        // what a worker searches in one go: a range of the reads of a sequence set, its records into `bms` / `ops` (the eager path: one
+        // range of all reads per worker; --lazy-query: one block after the other, all of its reads)
+        struct Job
+        {
+            SeqSet const *                q   = nullptr;
+            std::vector<uint8_t> const *  red = nullptr;
+            uint64_t                      rLo = 0, rHi = 0;
+            std::vector<lx_blast_match> * bms = nullptr;
+            std::vector<uint8_t> *        ops = nullptr;
+            void *                        block = nullptr;
+        };
+        auto worker = [&](size_t w, std::function<bool(Job &)> const & nextJob, std::function<void(Job &)> const & jobDone)
         {
             Part & pt = parts[w];
             try
             {
-                // contiguous range of reads, as `omp for schedule(dynamic)` over whole batches would hand a thread (:384-385)
-                uint64_t const rLo = nReads * w / nWorkers, rHi = nReads * (w + 1) / nWorkers;
-                if (rLo == rHi)
-                    return;
                 // worker 0 works with the handle the table is resident on; the others make their own and attach the table to it
                 bool const         borrow = w == 0 && firstHandle;
                 lambda_amd::Engine eng(borrow ? firstHandle.get() : nullptr, devices[w % devices.size()]);
@@ -1509,8 +1614,15 @@ int main(int argc, char ** argv)
                 // (LAMBDA3_HOST_LIST=1: the matches come down and go through lx_iterate_matches, the A/B switch of the tests)
                 bool const deviceList = gpuIndex && !std::getenv("LAMBDA3_HOST_LIST");
                 if (deviceList)
-                {
                     eng.check(lx_set_subject_seqs(eng.raw(), db.off.data(), db.len.data(), db.off.size()));
+                Job job;
+                // the job's queries for the Level-2 kernels, and room for its one call per seeding pass
+                auto beginJob = [&]()
+                {
+                    SeqSet const & qs  = *job.q;
+                    uint64_t const rLo = job.rLo, rHi = job.rHi;
+                    if (!deviceList)
+                        return;
                     eng.check(lx_set_queries(eng.raw(), qs.res.data(), qs.res.size(), qs.off.data(), qs.len.data(), qs.off.size(), qs.orig_len.data(), qFrames));
                     // this worker makes ONE Level-2 call per seeding pass: what that call would allocate and touch inside itself is asked
                     // for here, before the seeding (a dozen promising seeds per read, a window per seven of them, a record per twelve --
@@ -1521,13 +1633,17 @@ int main(int argc, char ** argv)
                         len = std::max<uint64_t>(len, qs.len[i]);
                     if (est >= 100000)
                         eng.check(lx_reserve(eng.raw(), est, est / 7, est / 12, wantOps ? est / 12 * (len + len / 16) : 0));
-                }
+                };
                 lx_seed_params spar{};
                 spar.half_exact = sin.halfExact ? 1 : 0, spar.adaptive = sin.adaptive ? 1 : 0, spar.pre_scoring = sin.preScoring;
                 spar.pre_scoring_thresh = sin.preScoringThresh, spar.max_matches = sin.maxMatches, spar.q_num_frames = sin.qNumFrames;
                 spar.unknown_rank = sin.unknownRank, spar.matrix = sin.matrix, spar.matrix_rev = sin.matrixRev, spar.host_threads = seedThreads;
                 auto pass = [&](lambda_amd::SeedParams const & so, std::vector<uint64_t> const & which)
                 {
+                    SeqSet const &               qs   = *job.q;
+                    std::vector<uint8_t> const & qRed = *job.red;
+                    std::vector<lx_blast_match> & outBms = *job.bms;
+                    std::vector<uint8_t> &        outOps = *job.ops;
                     if (std::getenv("LAMBDA3_TRACE"))
                         std::fprintf(stderr, "[worker %zu] seeding %zu frame sequences (seed %d/%d, delta %d)\n", w, which.size(), so.seedLength, so.seedOffset, so.maxSeedDist);
                     auto const            tSeed = std::chrono::steady_clock::now();
@@ -1598,30 +1714,33 @@ int main(int argc, char ** argv)
                     }
                     pt.rst.qrys_with_hit += passRst.qrys_with_hit, pt.rst.hits_duplicate2 += passRst.hits_duplicate2, pt.rst.hits_abundant += passRst.hits_abundant;
                     pt.rst.hits_final += passRst.hits_final, pt.rst.pairs += passRst.pairs;
-                    uint64_t const         ob = pt.ops.size();
+                    uint64_t const         ob = outOps.size();
                     uint64_t opsEnd = 0; // (the records are ordered by query, their ops as the passes produced them: bisulfite runs two)
                     for (uint64_t k = 0; k < n && wantOps; ++k)
                         opsEnd = std::max<uint64_t>(opsEnd, bm[k].ops_off + bm[k].n_ops);
                     if (opsEnd)
-                        pt.ops.insert(pt.ops.end(), lx_iterate_result_ops(res), lx_iterate_result_ops(res) + opsEnd);
+                        outOps.insert(outOps.end(), lx_iterate_result_ops(res), lx_iterate_result_ops(res) + opsEnd);
                     for (uint64_t k = 0; k < n; ++k)
                     {
-                        pt.bms.push_back(bm[k]);
-                        pt.bms.back().ops_off += ob;
+                        outBms.push_back(bm[k]);
+                        outBms.back().ops_off += ob;
                     }
                     lx_iterate_stats const st = lx_iterate_result_stats(res);
                     pt.ist.hits_duplicate += st.hits_duplicate, pt.ist.failed_bitscore += st.failed_bitscore, pt.ist.failed_evalue += st.failed_evalue;
                     pt.ist.failed_identity += st.failed_identity, pt.ist.num_ext_score += st.num_ext_score, pt.ist.num_ext_ali += st.num_ext_ali;
                     lx_iterate_result_free(res);
                 };
+                while (nextJob(job))
+                {
+                beginJob();
                 std::vector<uint64_t> all;
-                for (uint64_t i = rLo * (uint64_t)qFrames; i < rHi * (uint64_t)qFrames; ++i)
+                for (uint64_t i = job.rLo * (uint64_t)qFrames; i < job.rHi * (uint64_t)qFrames; ++i)
                     all.push_back(i);
                 if (opt.search0) // iterativeSearch (:1391-1457): the exact pre-search first, the default parameters for reads without a result
                 {
                     pass(so0, all);
-                    std::vector<uint8_t> successful(nReads, 0);
-                    for (auto const & bm : pt.bms)
+                    std::vector<uint8_t> successful(job.q->ids.size(), 0);
+                    for (auto const & bm : *job.bms)
                         successful[bm.n_qid] = 1;
                     std::vector<uint64_t> rest;
                     for (uint64_t i : all)
@@ -1631,24 +1750,327 @@ int main(int argc, char ** argv)
                         pass(so1, rest);
                     // (the reference writes phase 1's records of a batch before phase 2's; here both lists are written together:
                     // order by read, as one batch holding every read would give)
-                    std::stable_sort(pt.bms.begin(), pt.bms.end(), [](lx_blast_match const & a, lx_blast_match const & b) { return a.n_qid < b.n_qid; });
+                    std::stable_sort(job.bms->begin(), job.bms->end(), [](lx_blast_match const & a, lx_blast_match const & b) { return a.n_qid < b.n_qid; });
                 }
                 else
                     pass(so1, all);
+                jobDone(job);
+                }
             }
             catch (std::exception const & e)
             {
                 pt.error = e.what();
             }
         };
-        auto const tSearch = std::chrono::steady_clock::now();
+        // ---- what the writers are told, on both paths (the LCA pairs are added per list)
+        lx_tax_tree               tree{};
+        std::vector<char const *> taxNames;
+        if (indexTax.has)
         {
+            tree.parents   = indexTax.parents.data();
+            tree.heights   = indexTax.heights.data();
+            tree.n_taxa    = indexTax.parents.size();
+            tree.s_tax_off = indexTax.off.data();
+            tree.s_tax_ids = indexTax.ids.data();
+            tree.n_s       = indexTax.off.size() - 1;
+            if (wantLca && indexTax.hasTree)
+                for (std::string const & n : indexTax.names)
+                    taxNames.push_back(n.c_str());
+        }
+        auto outputOptions = [&](lx_output_options & oo)
+        {
+            lx_output_options_default(&oo);
+            oo.columns             = opt.outputColumns.c_str();
+            oo.sam_tags            = opt.samTags.c_str();
+            oo.sam_seq             = opt.samSeq == "never" ? LX_SAM_SEQ_NEVER : opt.samSeq == "uniq" ? LX_SAM_SEQ_UNIQ : LX_SAM_SEQ_ALWAYS;
+            oo.sam_hard_clip       = opt.samClip == "hard";
+            oo.sam_with_ref_header = opt.samWithRefHeader;
+            oo.version_to_output   = opt.versionToOutput;
+            oo.version             = "3.0.0-lx"; // (the reference release this front end follows, src/CMakeLists.txt:14-19)
+            oo.command_line        = opt.commandLine.c_str();
+            oo.db_name             = opt.db.c_str(); // the index path there (src/search_algo.hpp:320)
+            oo.genetic_code        = geneticCodeQry;
+            if (indexTax.has)
+            {
+                oo.tax = &tree;
+                if (wantLca && indexTax.hasTree)
+                    oo.tax_names = taxNames.data();
+            }
+        };
+        int const fmt = outFmt;
+        double    msCompress = 0;  // (.bam, *.gz: BGZF on the first handle's device)
+        double    msRenderDev = 0; // (--render gpu: the render kernels' device time)
+        bool      renderedOnGpu = false;
+        // --lazy-query: what the blocks came to
+        struct LazyTotals
+        {
+            uint64_t        blocks = 0, largest = 0, maxAlive = 0, reads = 0, hsps = 0, written = 0;
+            lx_record_stats rst{};
+        } lazyTotals;
+        auto const tSearch = std::chrono::steady_clock::now();
+        if (!lazy)
+        {
+            // contiguous ranges of reads, as `omp for schedule(dynamic)` over whole batches would hand a thread (:384-385)
+            auto run = [&](size_t w)
+            {
+                bool given = false;
+                worker(w,
+                       [&](Job & job)
+                       {
+                           if (given)
+                               return false;
+                           given = true;
+                           job   = Job{&qs, &qRed, nReads * w / nWorkers, nReads * (w + 1) / nWorkers, &parts[w].bms, &parts[w].ops, nullptr};
+                           return job.rLo != job.rHi;
+                       },
+                       [](Job &) {});
+            };
             std::vector<std::thread> pool;
             for (size_t w = 1; w < nWorkers; ++w)
-                pool.emplace_back(worker, w);
-            worker(0);
+                pool.emplace_back(run, w);
+            run(0);
             for (auto & t : pool)
                 t.join();
+        }
+        else
+        {
+            // ---- the block pipeline (the reference's batch loop, src/search.cpp:389-459, with its reader thread behind a bounded
+            // queue, src/search_algo.hpp:374-413): one reader makes blocks of at most blockReads reads (stream -> parser -> SeqSet:
+            // ranks, frames, reduction), one worker per entry of --devices takes the next block and searches all of it as the eager
+            // path searches a worker's range (then _writeRecord's cut and the LCA, both per query and so per block), and this thread
+            // appends the finished blocks in their order through lx_out.  At most nWorkers + 2 blocks exist at any time: the reader
+            // waits for a free place before it begins one.  An error in block k (a malformed record, a failed call) ends the run with
+            // its message; the blocks in front of k are written and the file is closed behind them.
+            struct Block
+            {
+                uint64_t                    index = 0;
+                SeqSet                      qs;
+                std::vector<uint8_t>        red;
+                std::vector<lx_blast_match> bms;
+                std::vector<uint8_t>        ops;
+                uint64_t                    found = 0, kept = 0; // records before and after _writeRecord's cut
+                lx_record_stats             rst{};               // (--records host: this block's step)
+                std::vector<uint64_t>       lcaQid;
+                std::vector<uint32_t>       lcaTax;
+                uint64_t                    nLca = 0;
+            };
+            std::mutex                                   mu;
+            std::condition_variable                      cv;
+            std::deque<std::unique_ptr<Block>>           toSearch;
+            std::map<uint64_t, std::unique_ptr<Block>>   done;
+            uint64_t                                     alive = 0, made = 0;
+            bool                                         readerDone = false, stop = false;
+            std::string                                  pipeError;
+            uint64_t const                               cap = nWorkers + 2;
+            // the run's error; hard: nothing more is searched (a block failed), else the blocks made so far go through (the reader failed)
+            auto fail = [&](std::string const & why, bool hard) // (under no lock)
+            {
+                std::lock_guard<std::mutex> lock(mu);
+                if (pipeError.empty())
+                    pipeError = why;
+                stop = stop || hard;
+                cv.notify_all();
+            };
+            auto reader = [&]()
+            {
+                bool holding = false; // a place taken for a block that is not in the queue yet
+                try
+                {
+                    lx_query_blocks::BlockCutter cut(blockReads);
+                    for (bool more = true; more;)
+                    {
+                        {
+                            std::unique_lock<std::mutex> lock(mu);
+                            cv.wait(lock, [&] { return alive < cap || stop; });
+                            if (stop)
+                                break;
+                            ++alive;
+                            holding = true;
+                            lazyTotals.maxAlive = std::max(lazyTotals.maxAlive, alive);
+                        }
+                        std::unique_ptr<Block> b(new Block);
+                        more = qStream->records(
+                            [&](std::string const & id, std::string & letters)
+                            {
+                                uint64_t const n = letters.size();
+                                addRecord(b->qs, id, letters, prot, !prot, blastx, geneticCodeQry, bs ? 2 : 0);
+                                return !cut.add(n);
+                            });
+                        if (!b->qs.ids.empty())
+                            b->red = reduce(b->qs);
+                        std::lock_guard<std::mutex> lock(mu);
+                        holding = false;
+                        if (b->qs.ids.empty()) // (the file ended where the last block closed)
+                        {
+                            --alive;
+                            break;
+                        }
+                        b->index = made++;
+                        lazyTotals.blocks  = made;
+                        lazyTotals.largest = std::max<uint64_t>(lazyTotals.largest, b->qs.ids.size());
+                        lazyTotals.reads += b->qs.ids.size();
+                        toSearch.push_back(std::move(b));
+                        cv.notify_all();
+                    }
+                }
+                catch (std::exception const & e)
+                {
+                    fail(e.what(), false);
+                }
+                std::lock_guard<std::mutex> lock(mu);
+                if (holding)
+                    --alive;
+                readerDone = true;
+                cv.notify_all();
+            };
+            auto run = [&](size_t w)
+            {
+                std::unique_ptr<Block> current; // the block this worker searches
+                worker(w,
+                       [&](Job & job)
+                       {
+                           std::unique_lock<std::mutex> lock(mu);
+                           cv.wait(lock, [&] { return !toSearch.empty() || readerDone || stop; });
+                           if (stop || toSearch.empty())
+                               return false;
+                           current = std::move(toSearch.front());
+                           toSearch.pop_front();
+                           Block * const b = current.get();
+                           job = Job{&b->qs, &b->red, 0, b->qs.ids.size(), &b->bms, &b->ops, b};
+                           return true;
+                       },
+                       [&](Job & job)
+                       {
+                           std::unique_ptr<Block> b = std::move(current);
+                           b->found = b->kept = b->bms.size();
+                           if (!recordsOnGpu) // _writeRecord's cut: every record of a read is in its block
+                           {
+                               auto const tRec = std::chrono::steady_clock::now();
+                               b->kept         = lx_postprocess_records(b->bms.data(), b->bms.size(), opt.maxMatches, &b->rst);
+                               parts[w].msRecords += msSince(tRec);
+                           }
+                           if (indexTax.has && wantLca && indexTax.hasTree)
+                           {
+                               b->lcaQid.resize(std::max<uint64_t>(b->kept, 1));
+                               b->lcaTax.resize(std::max<uint64_t>(b->kept, 1));
+                               if (lx_compute_lca(b->bms.data(), b->kept, &tree, b->lcaQid.data(), b->lcaTax.data(), &b->nLca) != LX_OK)
+                                   throw std::runtime_error("LCA-computation error: One of the paths didn't lead to root.");
+                           }
+                           std::lock_guard<std::mutex> lock(mu);
+                           uint64_t const              at = b->index;
+                           done[at] = std::move(b);
+                           cv.notify_all();
+                       });
+                if (!parts[w].error.empty())
+                    fail(parts[w].error, true);
+            };
+            std::thread              readerThread(reader);
+            std::vector<std::thread> pool;
+            for (size_t w = 0; w < nWorkers; ++w)
+                pool.emplace_back(run, w);
+            struct JoinAll // (joined on every way out; an error first tells the others to stop)
+            {
+                std::thread &              r;
+                std::vector<std::thread> & p;
+                std::function<void()>      halt;
+                ~JoinAll()
+                {
+                    halt();
+                    r.join();
+                    for (auto & t : p)
+                        t.join();
+                }
+            } joinAll{readerThread, pool, [&] {
+                          std::lock_guard<std::mutex> lock(mu);
+                          if (!readerDone || !toSearch.empty())
+                              stop = true;
+                          cv.notify_all();
+                      }};
+            // ---- the writer: this thread
+            bool const  dev = opt.render == "gpu";
+            lx_handle * zh  = nullptr;
+            if ((dev || outGz || fmt == LX_OUT_BAM) && lx_create(devices[0], &zh) != LX_OK)
+                throw std::runtime_error(lx_last_error(nullptr));
+            std::unique_ptr<lx_handle, void (*)(lx_handle *)> keepH(zh, lx_destroy);
+            auto outError = [&]() { return std::string(zh ? lx_last_error(zh) : lx_last_output_error()); };
+            std::vector<char const *> sidL;
+            for (auto const & s : db.ids)
+                sidL.push_back(s.c_str());
+            lx_seq_names const subjects{nullptr, nullptr, sidL.data(), db.orig_len.data(), 0, sidL.size()};
+            lx_output_options  oo;
+            outputOptions(oo);
+            lx_out * out = nullptr;
+            struct CloseOut // (an error on the way: the file is closed behind the blocks it holds)
+            {
+                lx_out *& o;
+                ~CloseOut()
+                {
+                    if (o)
+                        (void)lx_out_close(o, -1);
+                }
+            } closeOut{out};
+            renderedOnGpu = dev;
+            for (uint64_t next = 0;; ++next)
+            {
+                std::unique_ptr<Block> b;
+                {
+                    std::unique_lock<std::mutex> lock(mu);
+                    cv.wait(lock, [&] { return done.count(next) || stop || (readerDone && next == made); });
+                    auto it = done.find(next);
+                    if (it == done.end())
+                        break; // (every block is written, or the one that comes next never will be)
+                    b = std::move(it->second);
+                    done.erase(it);
+                }
+                if (!out && lx_out_open(zh, opt.output.c_str(), fmt, outGz ? 1 : 0, program, &subjects, &oo, &out) != LX_OK)
+                {
+                    std::string const why = outError();
+                    throw std::runtime_error(!why.empty() ? why : "cannot write " + opt.output);
+                }
+                std::vector<char const *> qidB;
+                for (auto const & s : b->qs.ids)
+                    qidB.push_back(s.c_str());
+                lx_seq_names const nm{qidB.data(), b->qs.orig_len.data(), nullptr, nullptr, qidB.size(), 0};
+                if (lx_out_append(out, dev ? LX_RENDER_DEV : LX_RENDER_HOST, b->bms.data(), b->kept, b->ops.data(), b->ops.size(), &nm,
+                                  reinterpret_cast<uint8_t const *>(b->qs.ascii.data()), b->qs.ascii_off.data(), b->lcaQid.data(), b->lcaTax.data(),
+                                  b->nLca) != LX_OK)
+                {
+                    std::string const why = outError();
+                    throw std::runtime_error((dev ? "records on the GPU: " : "") + (!why.empty() ? why : "cannot write " + opt.output));
+                }
+                float msK = 0;
+                if (dev && b->kept && lx_last_phase_ms(zh, fmt == LX_OUT_BAM ? 11 : 12, &msK, nullptr) == LX_OK)
+                    msRenderDev += msK;
+                if (!dev && zh && b->kept && lx_last_phase_ms(zh, 4, &msK, nullptr) == LX_OK)
+                    msCompress += msK;
+                lazyTotals.hsps += b->found;
+                lazyTotals.written += b->kept;
+                lazyTotals.rst.qrys_with_hit += b->rst.qrys_with_hit, lazyTotals.rst.hits_duplicate2 += b->rst.hits_duplicate2;
+                lazyTotals.rst.hits_abundant += b->rst.hits_abundant, lazyTotals.rst.hits_final += b->rst.hits_final, lazyTotals.rst.pairs += b->rst.pairs;
+                b.reset();
+                std::lock_guard<std::mutex> lock(mu);
+                --alive;
+                cv.notify_all();
+            }
+            std::string error;
+            {
+                std::lock_guard<std::mutex> lock(mu);
+                error = pipeError;
+            }
+            if (error.empty() && lazyTotals.reads == 0)
+                error = "empty query or database file";
+            uint64_t withHit = lazyTotals.rst.qrys_with_hit; // (--records gpu: counted in the workers' passes, which are over)
+            for (Part const & pt : parts)
+                withHit += error.empty() ? pt.rst.qrys_with_hit : 0;
+            if (out)
+            {
+                lx_out * const o = out;
+                out              = nullptr;
+                if (lx_out_close(o, (int64_t)withHit) != LX_OK && error.empty())
+                    error = "cannot write " + opt.output;
+            }
+            if (!error.empty())
+                throw std::runtime_error(error);
         }
         double const msSearch = msSince(tSearch);
         auto const   tOut     = std::chrono::steady_clock::now();
@@ -1687,12 +2109,17 @@ int main(int argc, char ** argv)
             rst.hits_final += pt.rst.hits_final, rst.pairs += pt.rst.pairs;
         }
         nHspParts = rst.hits_final + rst.hits_duplicate2 + rst.hits_abundant;
-        uint64_t const nHsp   = recordsOnGpu ? nHspParts : bms.size();
+        uint64_t const nHsp   = recordsOnGpu ? nHspParts : lazy ? lazyTotals.hsps : bms.size();
+        if (lazy) // (the blocks' host steps; --records gpu counted in the passes above)
+        {
+            rst.qrys_with_hit += lazyTotals.rst.qrys_with_hit, rst.hits_duplicate2 += lazyTotals.rst.hits_duplicate2, rst.hits_abundant += lazyTotals.rst.hits_abundant;
+            rst.hits_final += lazyTotals.rst.hits_final, rst.pairs += lazyTotals.rst.pairs;
+        }
         size_t const   nSeeds = (size_t)sst.hitsAfterSeeding;
 
         // ---- _writeRecord + writer
-        uint64_t nOut = bms.size(); // (--records gpu: every pass's records are cut already)
-        if (!recordsOnGpu)
+        uint64_t nOut = lazy ? lazyTotals.written : bms.size(); // (--records gpu: every pass's records are cut already)
+        if (!recordsOnGpu && !lazy)
         {
             auto const tRec = std::chrono::steady_clock::now();
             nOut      = lx_postprocess_records(bms.data(), bms.size(), opt.maxMatches, &rst);
@@ -1704,38 +2131,15 @@ int main(int argc, char ** argv)
         for (auto const & s : db.ids)
             sid.push_back(s.c_str());
         lx_seq_names names{qid.data(), qs.orig_len.data(), sid.data(), db.orig_len.data(), qid.size(), sid.size()};
-        int const    fmt = outFmt;
-        double       msCompress = 0; // (.bam, *.gz: BGZF on the first handle's device)
-        double       msRenderDev = 0; // (--render gpu: the render kernels' device time)
-        bool         renderedOnGpu = false;
+        if (!lazy)
         {
             lx_output_options oo;
-            lx_output_options_default(&oo);
-            oo.columns             = opt.outputColumns.c_str();
-            oo.sam_tags            = opt.samTags.c_str();
-            oo.sam_seq             = opt.samSeq == "never" ? LX_SAM_SEQ_NEVER : opt.samSeq == "uniq" ? LX_SAM_SEQ_UNIQ : LX_SAM_SEQ_ALWAYS;
-            oo.sam_hard_clip       = opt.samClip == "hard";
-            oo.sam_with_ref_header = opt.samWithRefHeader;
-            oo.version_to_output   = opt.versionToOutput;
-            oo.version             = "3.0.0-lx"; // (the reference release this front end follows, src/CMakeLists.txt:14-19)
-            oo.command_line        = opt.commandLine.c_str();
-            oo.db_name             = opt.db.c_str(); // the index path there (src/search_algo.hpp:320)
-            oo.genetic_code        = geneticCodeQry;
-            // the index's taxonomy (the reference's _writeRecord, src/search_algo.hpp:884-908): the LCA per query, over the records
-            // of every worker together
-            lx_tax_tree               tree{};
-            std::vector<uint64_t>     lcaQid;
-            std::vector<uint32_t>     lcaTax;
-            std::vector<char const *> taxNames;
+            outputOptions(oo);
+            // the LCA per query (the reference's _writeRecord, src/search_algo.hpp:884-908), over the records of every worker together
+            std::vector<uint64_t> lcaQid;
+            std::vector<uint32_t> lcaTax;
             if (indexTax.has)
             {
-                tree.parents   = indexTax.parents.data();
-                tree.heights   = indexTax.heights.data();
-                tree.n_taxa    = indexTax.parents.size();
-                tree.s_tax_off = indexTax.off.data();
-                tree.s_tax_ids = indexTax.ids.data();
-                tree.n_s       = indexTax.off.size() - 1;
-                oo.tax         = &tree;
                 if (wantLca && indexTax.hasTree)
                 {
                     lcaQid.resize(std::max<uint64_t>(nOut, 1));
@@ -1746,9 +2150,6 @@ int main(int argc, char ** argv)
                     oo.lca_qid = lcaQid.data();
                     oo.lca_tax = lcaTax.data();
                     oo.n_lca   = nLca;
-                    for (std::string const & n : indexTax.names)
-                        taxNames.push_back(n.c_str());
-                    oo.tax_names = taxNames.data();
                 }
             }
             if (fmt == LX_OUT_BAM && !outGz && opt.render == "gpu")
@@ -1820,7 +2221,7 @@ int main(int argc, char ** argv)
         std::fprintf(stderr,
                      "lambda3 %s (%s, %u host thread(s), %zu handle(s) on %zu device(s)): %zu queries, %zu subjects (%llu residues); seeds %zu -> promising %zu -> "
                      "windows %llu -> traced %llu -> HSPs %llu -> written %llu (queries with hit: %llu)\n",
-                     opt.cmd.c_str(), program, nThreads, nWorkers, devices.size(), qs.ids.size(), db.ids.size(), (unsigned long long)dbTotal, nSeeds, nPromising,
+                     opt.cmd.c_str(), program, nThreads, nWorkers, devices.size(), lazy ? (size_t)lazyTotals.reads : qs.ids.size(), db.ids.size(), (unsigned long long)dbTotal, nSeeds, nPromising,
                      (unsigned long long)(ist.num_ext_score - ist.hits_duplicate), (unsigned long long)ist.num_ext_ali,
                      (unsigned long long)nHsp, (unsigned long long)nOut, (unsigned long long)rst.qrys_with_hit);
         // where the wall clock went (the reference prints its own at verbosity 2, src/search.cpp): per worker the slowest counts
@@ -1835,6 +2236,10 @@ int main(int argc, char ** argv)
                      : (fmt == LX_OUT_BAM || outGz) ? (", BGZF compression on the GPU " + std::to_string((long)(msCompress + 0.5))).c_str()
                                                     : "",
                      msSince(tStart));
+        if (lazy)
+            std::fprintf(stderr, "lambda3 query blocks: %llu block(s) of at most %llu read(s), %llu read(s) in the largest, at most %llu block(s) alive at once\n",
+                         (unsigned long long)lazyTotals.blocks, (unsigned long long)blockReads, (unsigned long long)lazyTotals.largest,
+                         (unsigned long long)lazyTotals.maxAlive);
         return 0;
     }
     catch (std::exception const & e)

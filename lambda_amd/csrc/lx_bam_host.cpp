@@ -321,6 +321,64 @@ int emit_range(lx_handle * h, Job const & job, Range const & r, uint8_t * out)
 
 } // namespace
 
+namespace lxi
+{
+
+int rec_append_ranges(lx_handle * h, RecJob const & job, std::function<int(RecRange const &, uint8_t *)> const & emit, uint8_t * d_carry,
+                      uint64_t * carry, MemberSink const & sink)
+{
+    // the stream buffer: what is carried (less than a block) + a range
+    int rc = ensure(h, h->bam.d_stream, lx::kBgzfBlock + job.max_range + 16);
+    if (rc)
+        return rc;
+    uint8_t * const   d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
+    hipStream_t const s = h->stream;
+    uint64_t          c = *carry;
+    if (c >= lx::kBgzfBlock)
+        return fail(h, LX_EINVAL, "lx_out_append: a carry of a block or more");
+    if (c)
+        LX_HIP(h, hipMemcpyAsync(d, d_carry, c, hipMemcpyDeviceToDevice, s));
+    for (RecRange const & r : job.ranges)
+    {
+        if ((rc = emit(r, d + c)))
+            return rc;
+        uint64_t const have = c + r.bytes, whole = have / lx::kBgzfBlock * lx::kBgzfBlock;
+        if (whole && (rc = bgzf_compress_dev(h, d, whole, sink)))
+            return rc;
+        c = have - whole;
+        if (c && whole) // (whole is at least a block, the rest less: the two do not overlap)
+            LX_HIP(h, hipMemcpyAsync(d, d + whole, c, hipMemcpyDeviceToDevice, s));
+    }
+    if (c)
+        LX_HIP(h, hipMemcpyAsync(d_carry, d, c, hipMemcpyDeviceToDevice, s));
+    LX_HIP(h, hipStreamSynchronize(s));
+    *carry = c;
+    return LX_OK;
+}
+
+int bam_append_dev(lx_handle * h, char const * who, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+                   uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                   lx_output_options const * opt, uint8_t * d_carry, uint64_t * carry, MemberSink const & sink)
+{
+    int rc = rec_begin(h);
+    if (rc)
+        return rc;
+    HostPool::Call in_call;
+    try
+    {
+        Job job;
+        if ((rc = prepare(h, who, 0, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, job)))
+            return rc;
+        return rec_append_ranges(h, job, [&](Range const & r, uint8_t * out) { return emit_range(h, job, r, out); }, d_carry, carry, sink);
+    }
+    catch (std::bad_alloc const &)
+    {
+        return fail(h, LX_ENOMEM, "%s: out of host memory", who);
+    }
+}
+
+} // namespace lxi
+
 extern "C" {
 
 int lx_render_bam_dev(lx_handle * h, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,

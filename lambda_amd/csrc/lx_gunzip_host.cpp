@@ -12,12 +12,23 @@
 // bytes in waves of chunks -- find, decode with markers, chain check here, resolve -- and its bytes down into the result.  Nothing
 // of it counts before the trailer's CRC32 and ISIZE agree; in every other case the member is declined, the result is where it was,
 // and host_member decodes it from its first byte: today's bytes or today's error text.
+//
+// lx_gunzip_stream_* is the same walk over a mapped file, handing the text out in pieces: BGZF members in groups whose text fills a
+// piece, each group a Walk of its own over its slice of the file (so the device path and the error texts are lx_gunzip's); every
+// other member through StepInflater, which stops between two symbols when the piece is full and keeps a 32 KiB window.  It never
+// takes the parallel path: that one wants the whole member's text on the device at once.
 #include "lx_crc32.h"
 #include "lx_gunzip.h"
 #include "lx_inflate.h"
 #include "lx_internal.h"
 #include "lx_pgunzip.h"
 
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -154,22 +165,26 @@ char const * parse_header(uint8_t const * in, uint64_t n, uint64_t at, Header & 
     return nullptr;
 }
 
+// what is wrong with member k, which begins at byte `at` of the file
+int member_error(lx_handle * h, uint64_t k, uint64_t at, char const * why)
+{
+    char buf[320];
+    snprintf(buf, sizeof(buf), "lx_gunzip: member %llu at byte %llu: %s", (unsigned long long)k, (unsigned long long)at, why);
+    if (h)
+        return fail(h, LX_EINVAL, "%s", buf);
+    set_output_error(buf);
+    return LX_EINVAL;
+}
+
 struct Walk
 {
     lx_handle *     h;
     uint8_t const * in;
     uint64_t        n;
     Result &        res;
+    uint64_t        k_base = 0, at_base = 0; // in[0, n) is a slice of a file (lx_gunzip_stream): the members and bytes in front of it
 
-    int error(uint64_t k, uint64_t at, char const * why)
-    {
-        char buf[320];
-        snprintf(buf, sizeof(buf), "lx_gunzip: member %llu at byte %llu: %s", (unsigned long long)k, (unsigned long long)at, why);
-        if (h)
-            return fail(h, LX_EINVAL, "%s", buf);
-        set_output_error(buf);
-        return LX_EINVAL;
-    }
+    int error(uint64_t k, uint64_t at, char const * why) { return member_error(h, k_base + k, at_base + at, why); }
 
     // a member decoded here; *next = the byte after its trailer.  With a limit (the probe in front of the parallel path) the decoder
     // sees that many DEFLATE bytes only, and a stream that does not end inside them leaves the result where it was: *small = false
@@ -554,9 +569,405 @@ struct Walk
     }
 };
 
+// ---- lx_gunzip_stream: the same walk, piece by piece
+//
+// The text not handed out yet: buf[keep, keep + fill), behind the last `keep` (<= 32 KiB) bytes of what was handed out -- the window
+// a plain member's back-references still reach.
+struct StreamBuf
+{
+    std::string buf;
+    uint64_t    keep = 0, fill = 0;
+    uint8_t *   room(uint64_t need) // room for `need` more bytes behind the text
+    {
+        uint64_t const at = keep + fill;
+        if (at + need > buf.size())
+            buf.resize(std::max<uint64_t>(at + need, std::max<uint64_t>(2 * buf.size(), 1u << 16)));
+        return reinterpret_cast<uint8_t *>(&buf[0]) + at;
+    }
+    // the text leaves; its last 32 KiB stay in front of what comes next
+    std::string take()
+    {
+        std::string    piece(buf.data() + keep, fill);
+        uint64_t const all = keep + fill, w = std::min<uint64_t>(all, 32768);
+        std::memmove(&buf[0], buf.data() + (all - w), w);
+        keep = w;
+        fill = 0;
+        return piece;
+    }
+};
+
+struct StreamSink
+{
+    StreamBuf & b;
+    uint64_t    member = 0; // bytes of the current member so far
+    bool put(uint8_t v)
+    {
+        *b.room(1) = v;
+        ++b.fill;
+        ++member;
+        return true;
+    }
+    bool dist_ok(uint32_t d) const { return d <= member; }
+    bool copy(uint32_t d, uint32_t len)
+    {
+        if (!dist_ok(d))
+            return false;
+        uint8_t * const dst = b.room(len); // (d <= min(member, 32768) <= keep + fill: the source is in the buffer)
+        for (uint32_t i = 0; i < len; ++i)
+            dst[i] = dst[(int64_t)i - (int64_t)d];
+        b.fill += len;
+        member += len;
+        return true;
+    }
+};
+
+// the Inflater, stopping between two symbols or two blocks once the sink holds `limit` bytes: at most 257 bytes (a copy) or
+// 65 535 (a stored block) beyond it.  codes() is restated here with that one check; everything else is the Inflater's own.
+struct StepInflater : lx::inflate::Inflater<StreamSink, uint64_t>
+{
+    using Base = lx::inflate::Inflater<StreamSink, uint64_t>;
+    using Base::Base;
+    bool     in_codes = false, done = false;
+    uint32_t last = 0;
+
+    // kOk with done = false: the limit was reached
+    uint32_t step(uint64_t limit)
+    {
+        namespace fl = lx::inflate;
+        for (;;)
+        {
+            if (!in_codes)
+            {
+                if (out.b.fill >= limit)
+                    return fl::kOk;
+                uint32_t type, rc = fl::kOk;
+                if (!take(1, last) || !take(2, type))
+                    return fl::kTruncated;
+                if (type == 0)
+                {
+                    if ((rc = stored()))
+                        return rc;
+                    if ((done = last != 0))
+                        return fl::kOk;
+                    continue;
+                }
+                if (type == 1)
+                    fixed_tables();
+                else if (type == 2)
+                    rc = dynamic_tables();
+                else
+                    rc = fl::kBadBlockType;
+                if (rc)
+                    return rc;
+                in_codes = true;
+            }
+            for (;;)
+            {
+                if (out.b.fill >= limit)
+                    return fl::kOk;
+                uint32_t sym, rc;
+                if ((rc = decode(T.lit, sym)))
+                    return rc;
+                if (sym < 256)
+                {
+                    out.put((uint8_t)sym);
+                    continue;
+                }
+                if (sym == 256)
+                    break;
+                sym -= 257;
+                if (sym >= 29)
+                    return fl::kBadSymbol;
+                uint32_t const le = sym < 8 || sym == 28 ? 0 : (sym >> 2) - 1;
+                uint32_t const lb = sym < 8 ? 3 + sym : sym == 28 ? 258 : ((4 | (sym & 3)) << le) + 3;
+                uint32_t       x, dsym;
+                if (!take(le, x))
+                    return fl::kTruncated;
+                uint32_t const len = lb + x;
+                if ((rc = decode(T.dist, dsym)))
+                    return rc;
+                if (dsym >= 30)
+                    return fl::kBadSymbol;
+                uint32_t const de = dsym < 4 ? 0 : (dsym >> 1) - 1;
+                if (!take(de, x))
+                    return fl::kTruncated;
+                uint32_t const dist = (dsym < 4 ? 1 + dsym : ((2 | (dsym & 1)) << de) + 1) + x;
+                if (!out.copy(dist, len))
+                    return fl::kDistTooFar;
+            }
+            in_codes = false;
+            if ((done = last != 0))
+                return fl::kOk;
+        }
+    }
+};
+
 } // namespace
 
+struct lx_gunzip_stream
+{
+    lx_handle *     h = nullptr;
+    uint8_t const * in = nullptr;
+    uint64_t        n = 0;
+    void *          map = nullptr; // the file, mapped; or, where it cannot be mapped (a pipe), read into `held`
+    std::string     held;
+    uint64_t        piece = 0;
+    bool            gz = false, failed = false;
+    uint64_t        at = 0, k = 0; // the next member: its first byte, its number
+    uint64_t        released = 0;  // pages of the mapping in front of this byte were given back
+    StreamBuf       sb;
+    // the plain member being decoded
+    lx::inflate::Tables           T;
+    StreamSink                    sink{sb};
+    std::unique_ptr<StepInflater> inf;
+    Header                        hd;
+    uint64_t                      crc_from = 0; // sb.buf[crc_from, keep + fill) is the member's text not in `crc` yet
+    uint32_t                      crc = 0;
+
+    ~lx_gunzip_stream()
+    {
+        if (map)
+            munmap(map, n);
+    }
+    int say(int code, char const * text)
+    {
+        failed = true;
+        if (h)
+            return fail(h, code, "%s", text);
+        set_output_error(text);
+        return code;
+    }
+    int error(char const * why) { return member_error(h, k, at, why); }
+    void crc_up()
+    {
+        uint64_t const end = sb.keep + sb.fill;
+        crc      = crc32(reinterpret_cast<uint8_t const *>(sb.buf.data()) + crc_from, end - crc_from, crc);
+        crc_from = end;
+    }
+    // the compressed bytes in front of `upto` are done with: their pages need not stay resident
+    void release(uint64_t upto)
+    {
+        uint64_t const page = 4096, lo = (released + page - 1) / page * page, hi = upto / page * page;
+        if (map && hi > lo)
+        {
+            madvise(static_cast<uint8_t *>(map) + lo, hi - lo, MADV_DONTNEED);
+            released = hi;
+        }
+    }
+    int emit(lx_bytes ** out)
+    {
+        if (inf)
+            crc_up();
+        *out = bytes_adopt(sb.take());
+        crc_from = sb.keep;
+        release(inf ? hd.end + inf->pos - std::min<uint64_t>(inf->pos, 8) : at);
+        return LX_OK;
+    }
+    // true: the member at `at` goes into a group for the BGZF path (`end` = the byte after it, `isize` its text)
+    bool bgzf_member(Header const & hd_, uint64_t a, uint64_t * end, uint32_t * isize) const
+    {
+        if (hd_.bsize < 0 || (uint64_t)hd_.bsize + 1 > n - a)
+            return false;
+        uint64_t const e = a + (uint64_t)hd_.bsize + 1;
+        if (e < hd_.end + 8 || e - 8 - hd_.end > lx::kGunzipMaxPayload || le32(in + e - 4) > lx::kGunzipMaxIsize)
+            return false;
+        *end   = e;
+        *isize = le32(in + e - 4);
+        return true;
+    }
+    int next(lx_bytes ** out)
+    {
+        if (!gz) // the file's own bytes
+        {
+            uint64_t const len = std::min(piece, n - at);
+            if (len)
+                *out = bytes_adopt(std::string(reinterpret_cast<char const *>(in) + at, len));
+            at += len;
+            release(at);
+            return LX_OK;
+        }
+        for (;;)
+        {
+            if (sb.fill >= piece)
+                return emit(out);
+            if (inf)
+            {
+                uint32_t const st = inf->step(piece);
+                if (st != lx::inflate::kOk)
+                    return failed = true, error(lx::inflate::status_text(st));
+                if (!inf->done)
+                    continue; // (the limit: the piece leaves at the loop's head)
+                uint64_t const t = hd.end + inf->consumed();
+                crc_up();
+                char const * bad = n - t < 8                                                ? "truncated gzip trailer"
+                                   : crc != le32(in + t)                                    ? "CRC32 mismatch"
+                                   : (uint32_t)sink.member != le32(in + t + 4)              ? "ISIZE mismatch"
+                                   : hd.bsize >= 0 && t + 8 != at + (uint64_t)hd.bsize + 1 ? "BSIZE does not match the member's DEFLATE stream"
+                                                                                            : nullptr;
+                if (bad)
+                    return failed = true, error(bad);
+                inf.reset();
+                if (h)
+                    ++h->gunzip.stats.plain_host;
+                at = t + 8;
+                ++k;
+                continue;
+            }
+            if (at >= n)
+                return sb.fill ? emit(out) : LX_OK;
+            hd = Header{};
+            if (char const * bad = parse_header(in, n, at, hd))
+                return failed = true, error(bad);
+            if (hd.bsize >= 0 && (uint64_t)hd.bsize + 1 > n - at)
+                return failed = true, error("BSIZE points past the end of the data");
+            uint64_t end   = 0;
+            uint32_t isize = 0;
+            if (bgzf_member(hd, at, &end, &isize))
+            {
+                // whole members until the piece is full, through the walk of lx_gunzip: on h's device, or one by one on this thread
+                uint64_t sum = isize, members = 1;
+                for (Header g; sb.fill + sum < piece && end < n; ++members)
+                {
+                    g = Header{};
+                    uint64_t e2 = 0;
+                    if (parse_header(in, n, end, g) || !bgzf_member(g, end, &e2, &isize))
+                        break;
+                    sum += isize;
+                    end = e2;
+                }
+                if (h)
+                {
+                    h->phase_ev.clear();
+                    h->ev_pool_used = 0;
+                }
+                Result    r;
+                int const rc = Walk{h, in + at, end - at, r, k, at}.run();
+                if (rc)
+                    return failed = true, rc;
+                if (sb.fill == 0 && r.size >= piece) // (nothing waits in front of it: the group's text is the piece)
+                {
+                    r.out.resize(r.size);
+                    *out    = bytes_adopt(std::move(r.out));
+                    sb.keep = 0;
+                }
+                else
+                {
+                    std::memcpy(sb.room(r.size), r.out.data(), r.size);
+                    sb.fill += r.size;
+                }
+                at = end;
+                k += members;
+                release(at);
+                if (*out)
+                    return LX_OK;
+                continue;
+            }
+            if (h && hd.bsize >= 0 && at + (uint64_t)hd.bsize + 1 < hd.end + 8)
+                return failed = true, error("BSIZE is smaller than the member's header and trailer");
+            sink.member = 0;
+            crc         = 0;
+            crc_from    = sb.keep + sb.fill;
+            inf.reset(new StepInflater(in + hd.end, n - hd.end, sink, T));
+        }
+    }
+};
+
 extern "C" {
+
+int lx_gunzip_stream_open(lx_handle * h, char const * path, uint64_t piece_bytes, lx_gunzip_stream ** out)
+{
+    auto refuse = [&](std::string const & text)
+    {
+        if (h)
+            return fail(h, LX_EINVAL, "%s", text.c_str());
+        set_output_error(text);
+        return (int)LX_EINVAL;
+    };
+    if (!h)
+        set_output_error("");
+    if (!path || !out)
+        return refuse("lx_gunzip_stream_open: NULL argument");
+    *out = nullptr;
+    int const fd = ::open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0)
+        return refuse(std::string("lx_gunzip_stream_open: cannot open ") + path);
+    try
+    {
+        std::unique_ptr<lx_gunzip_stream> s(new lx_gunzip_stream);
+        s->h     = h;
+        s->piece = piece_bytes ? piece_bytes : 64ull << 20;
+        struct stat st;
+        void *      m = MAP_FAILED;
+        if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0)
+            m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m != MAP_FAILED)
+        {
+            s->map = m;
+            s->n   = (uint64_t)st.st_size;
+            s->in  = static_cast<uint8_t const *>(m);
+            madvise(m, s->n, MADV_SEQUENTIAL);
+        }
+        else // (an empty file, a pipe: read to its end; its bytes are held whole, compressed)
+        {
+            char    buf[1 << 16];
+            ssize_t got;
+            while ((got = ::read(fd, buf, sizeof(buf))) > 0)
+                s->held.append(buf, (size_t)got);
+            if (got < 0)
+            {
+                ::close(fd);
+                return refuse(std::string("lx_gunzip_stream_open: error while reading ") + path);
+            }
+            s->n  = s->held.size();
+            s->in = reinterpret_cast<uint8_t const *>(s->held.data());
+        }
+        ::close(fd);
+        s->gz = s->n >= 2 && s->in[0] == 0x1f && s->in[1] == 0x8b;
+        if (h)
+        {
+            h->gunzip.stats = lx_gunzip_stats{};
+            for (int i = 0; i < 3; ++i)
+                h->gunzip.phase_ms[i] = 0.f, h->gunzip.phase_launches[i] = 0;
+        }
+        *out = s.release();
+        return LX_OK;
+    }
+    catch (std::bad_alloc const &)
+    {
+        ::close(fd);
+        if (h)
+            return fail(h, LX_ENOMEM, "lx_gunzip_stream_open: out of host memory");
+        set_output_error("lx_gunzip_stream_open: out of host memory");
+        return LX_ENOMEM;
+    }
+}
+
+int lx_gunzip_stream_next(lx_gunzip_stream * s, lx_bytes ** piece)
+{
+    if (!s || !piece)
+    {
+        set_output_error("lx_gunzip_stream_next: NULL argument");
+        return s && s->h ? fail(s->h, LX_EINVAL, "lx_gunzip_stream_next: NULL argument") : (int)LX_EINVAL;
+    }
+    *piece = nullptr;
+    if (!s->h)
+        set_output_error("");
+    if (s->failed)
+        return s->say(LX_EINVAL, "lx_gunzip_stream_next: the stream has failed");
+    try
+    {
+        return s->next(piece);
+    }
+    catch (std::bad_alloc const &)
+    {
+        return s->say(LX_ENOMEM, "lx_gunzip_stream_next: out of host memory");
+    }
+}
+
+void lx_gunzip_stream_close(lx_gunzip_stream * s)
+{
+    delete s;
+}
 
 int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out)
 {

@@ -2,6 +2,7 @@
 // of the ABI.  A call checks and flattens its inputs and uploads them (rec_inputs, which also runs the groups kernels), runs its own
 // measure kernel, and cuts the list into ranges of whole tiles from the tiles' size totals (rec_ranges); per range it runs its emit.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -54,5 +55,20 @@ int rec_inputs(lx_handle * h, char const * who, int phase, uint32_t tags, bool w
                lx_output_options const * opt_in, RecJob & job);
 // after the measure kernel: the tiles' totals come down, job.ranges / max_range / total are made (LX_OPT_BAM_RANGE_BYTES)
 int rec_ranges(lx_handle * h, char const * who, RecJob & job);
+
+// ---- one append of lx_out (lx_out_host.cpp) whose records are made on the device and compressed where they stand.  m[0, n) is
+// rendered without header and footer behind the *carry (< 65 280) bytes of d_carry; the whole blocks of carry + records go through
+// the BGZF encoder, their members to `sink`; what does not fill a block is back in d_carry (room for a block), its size in *carry.
+// The refusals are those of the one-shot device writers, before any device work.
+using MemberSink = std::function<int(uint8_t const *, uint64_t)>;
+// the part both writers share: the job's ranges through `emit` (a range's records to a device address) and the encoder
+int rec_append_ranges(lx_handle * h, RecJob const & job, std::function<int(RecRange const &, uint8_t *)> const & emit, uint8_t * d_carry,
+                      uint64_t * carry, MemberSink const & sink);
+int bam_append_dev(lx_handle * h, char const * who, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+                   uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                   lx_output_options const * opt, uint8_t * d_carry, uint64_t * carry, MemberSink const & sink);
+int text_append_dev(lx_handle * h, char const * who, int format, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+                    uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                    lx_output_options const * opt, uint8_t * d_carry, uint64_t * carry, MemberSink const & sink);
 
 } // namespace lxi

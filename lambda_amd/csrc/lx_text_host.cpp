@@ -240,6 +240,35 @@ int emit_range(lx_handle * h, TextJob const & job, RecRange const & r, uint8_t *
 
 } // namespace
 
+namespace lxi
+{
+
+int text_append_dev(lx_handle * h, char const * who, int format, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+                    uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
+                    lx_output_options const * opt, uint8_t * d_carry, uint64_t * carry, MemberSink const & sink)
+{
+    Checked ck;
+    int     rc = check_args(h, who, format, program, m, n, names, opt, ck);
+    if (rc)
+        return rc;
+    if ((rc = rec_begin(h)))
+        return rc;
+    HostPool::Call in_call;
+    try
+    {
+        TextJob job;
+        if ((rc = prepare(h, who, ck, format, 0, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, -1, job)))
+            return rc;
+        return rec_append_ranges(h, job.rec, [&](RecRange const & r, uint8_t * out) { return emit_range(h, job, r, out); }, d_carry, carry, sink);
+    }
+    catch (std::bad_alloc const &)
+    {
+        return fail(h, LX_ENOMEM, "%s: out of host memory", who);
+    }
+}
+
+} // namespace lxi
+
 extern "C" {
 
 int lx_render_text_dev(lx_handle * h, int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n,
