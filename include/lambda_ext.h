@@ -174,6 +174,10 @@ enum
     LX_OPT_BAM_RANGE_BYTES = 17, /* lx_render_bam_dev / lx_write_bam_dev and lx_render_text_dev / lx_write_text_dev: rendered bytes per
                                     range of records, i.e. what stands on the device at once (0 = default, 256 MiB; accepted from 128 KiB to 2 GiB; a range is whole tiles of 2048 records,
                                     at least one).  It changes where the cuts fall, never a byte of the output */
+    LX_OPT_INDEX_SLICE_WORDS = 18, /* lx_index_build on a handle: 0 (default) = one radix sort over all words (fewer than 2^31 of them, about
+                                      72 bytes of device memory per word at once); N >= 1 = the build in slices of the key space of at most
+                                      N words each (lx_index_plan_slices), for sets of fewer than 2^32 - 1 words: 16 bytes per word for the
+                                      entries and 32 per word of the largest slice.  The same table entry for entry either way */
     LX_OPT_BAND            = 9  /* band mode -- NOT the reference's configuration (src/search_algo.hpp:1081 runs BandOff, :1102
                                    says why; _bandSize only pads the window, src/search_misc.hpp:46-50) and therefore not a
                                    parity mode: 0 (default) = full rectangle; b > 0 = only cells whose diagonal i - j (row i of
@@ -952,16 +956,30 @@ typedef struct lx_index_entry /* one row of the table */
 
 /* The table the reference's mkindex step would put into its index (src/mkindex_algo.hpp generateIndexAndDump; the FM-index's place).
  * h != NULL: keys, the library's radix sort, entries and prefix table as kernels on h's device and stream (lx_last_phase_ms phase 8),
- * and the table and the reduced subjects stay resident there for lx_seed_queries on h.  That needs fewer than 2^31 words in all and
- * fewer than 2^32 - 1 sequences: beyond, LX_EINVAL with a text (LX_ENOMEM: the device has no room for the build) -- build with h ==
- * NULL then.  h == NULL: on host_threads host threads (0 = the library's share of the CPUs), no device is touched.  The same table
- * entry for entry either way.  Needs every sequence shorter than 2^32 - 1 letters and at most 2^32 - 1 sequences. */
+ * and the table and the reduced subjects stay resident there for lx_seed_queries on h.  That needs fewer than 2^31 words in all (the
+ * sort ranks with 32 bits) and fewer than 2^32 - 1 sequences: beyond, LX_EINVAL with a text (LX_ENOMEM: the device has no room for
+ * the build) -- build with h == NULL then, or in slices: with LX_OPT_INDEX_SLICE_WORDS = N >= 1 on h the words are counted by their
+ * first prefix_len letters (the counts' scan is the prefix table), the buckets are cut into slices (lx_index_plan_slices) and every
+ * slice is compacted, sorted and written on its own.  That takes fewer than 2^32 - 1 words (a cursor on the device is a 32-bit range)
+ * with no bucket beyond 2^31 - 1; phase 8 then reports the slices as its launches.  h == NULL: on host_threads host threads (0 = the
+ * library's share of the CPUs), no device is touched.  The same table entry for entry every way.  Needs every sequence shorter than
+ * 2^32 - 1 letters and at most 2^32 - 1 sequences. */
 int lx_index_build(lx_handle * h, uint8_t const * s_red, uint64_t const * s_off, uint64_t const * s_len, uint64_t n_sseq, int32_t alph,
                    uint32_t host_threads, lx_index ** out);
+/* How the sliced build cuts a prefix table (pre[w] = first entry whose word is >= w, n_prefix values; bucket w holds pre[w + 1] - pre[w]
+ * words) into slices of at most slice_words words; no device is touched.  The buckets are walked in order with one running slice: a
+ * bucket joins it if the slice still has no words or if its words plus the bucket's do not exceed slice_words, otherwise the slice
+ * closes and the bucket opens the next one -- a bucket larger than slice_words is a slice of its own --; a last slice without words
+ * (empty buckets behind a slice that is full) is joined to the one before it, so that every slice of a table with words has some.
+ * first_word[s] = the first bucket of slice s (slice s ends where s + 1 begins, the last at bucket n_prefix - 1).  *n_slices is always
+ * written, first_word only when cap >= *n_slices.  LX_EINVAL for NULL pre / n_slices (or first_word with cap > 0), slice_words == 0,
+ * n_prefix < 2, a pre that does not ascend, a bucket of more than 2^31 - 1 words (beyond the sort). */
+int lx_index_plan_slices(uint64_t const * pre, uint64_t n_prefix, uint64_t slice_words, uint64_t * first_word, uint64_t cap, uint64_t * n_slices);
 /* An index file's table: exactly the bytes lx_index_save writes -- int32 {alph, key_len, prefix_len, 0}, uint64 {n_entries,
  * n_prefix}, the entries (16 bytes each), the prefix table --, over the sequences they were made from.  LX_EINVAL for truncated
  * bytes, bytes that are left over, a geometry or counts that do not fit the sequences, a prefix table that does not ascend, an entry
- * outside its sequence.  h != NULL: the table becomes resident on h's device as after lx_index_build. */
+ * outside its sequence.  h != NULL: the table becomes resident on h's device as after lx_index_build; no sort runs, so the only
+ * limit is the device cursor's: fewer than 2^32 - 1 entries (and the device's memory). */
 int lx_index_load(lx_handle * h, uint8_t const * bytes, uint64_t n, uint8_t const * s_red, uint64_t const * s_off, uint64_t const * s_len,
                   uint64_t n_sseq, lx_index ** out);
 int lx_index_save(lx_index const * ix, lx_bytes ** out);
@@ -1037,7 +1055,7 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
  * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*),
  * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top),
- * 8 = the word table's kernels (lx_index_build on a handle), 9 = the seeding kernel (lx_seed_queries on a handle),
+ * 8 = the word table's kernels (lx_index_build on a handle; in slices: launches = the number of slices), 9 = the seeding kernel (lx_seed_queries on a handle),
  * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
  * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,
  * numbers, measure, scans, emit). */

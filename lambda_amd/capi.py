@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
     "lx_write_records_bgzf", "lx_render_bam_dev", "lx_write_bam_dev", "lx_format_number", "lx_render_text_dev", "lx_write_text_dev", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
-    "lx_index_build", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
+    "lx_index_build", "lx_index_plan_slices", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
     "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_close",
 ]
@@ -53,6 +53,7 @@ LX_OPT_ADAPT_PERMILLE = 12
 LX_OPT_GUNZIP_CHUNK = 15
 LX_OPT_GUNZIP_PARALLEL_FROM = 16
 LX_OPT_BAM_RANGE_BYTES = 17
+LX_OPT_INDEX_SLICE_WORDS = 18  # lx_index_build on a handle: 0 = one sort, N >= 1 = in slices of at most N words
 OPT_GUNZIP_WAVE_TEST = 1017  # not part of the ABI (lx_internal.h): chunks per wave, for the tests of lx_gunzip's waves
 LX_GUNZIP_NEVER = (1 << 64) - 1  # LX_OPT_GUNZIP_PARALLEL_FROM: no plain member takes the device path
 
@@ -306,6 +307,7 @@ def load():
     lib.lx_taxonomy_free.argtypes = [vp]
     lib.lx_taxonomy_free.restype = None
     lib.lx_index_build.argtypes = [vp, vp, vp, vp, u64, i32, C.c_uint32, C.POINTER(vp)]
+    lib.lx_index_plan_slices.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64)]
     lib.lx_index_load.argtypes = [vp, vp, u64, vp, vp, vp, u64, C.POINTER(vp)]
     lib.lx_index_save.argtypes = [vp, C.POINTER(vp)]
     lib.lx_index_attach.argtypes = [vp, vp, C.POINTER(vp)]
@@ -612,6 +614,22 @@ class TaxMap:
 
 def _raise(lib, h, rc):
     raise LambdaExtError(rc, lib.lx_last_error(h).decode() if h is not None else last_output_error())
+
+
+def index_plan_slices(pre, slice_words: int) -> np.ndarray:
+    """lx_index_plan_slices: the first bucket of every slice the sliced build (LX_OPT_INDEX_SLICE_WORDS) cuts the prefix table
+    `pre` into; no device is touched."""
+    lib = load()
+    pre = np.ascontiguousarray(pre, dtype=np.uint64)
+    n = C.c_uint64()
+    rc = lib.lx_index_plan_slices(_ptr(pre) if pre.size else None, pre.size, slice_words, None, 0, C.byref(n))
+    if rc != LX_OK:
+        _raise(lib, None, rc)
+    first = np.zeros(n.value, np.uint64)
+    rc = lib.lx_index_plan_slices(_ptr(pre), pre.size, slice_words, _ptr(first), first.size, C.byref(n))
+    if rc != LX_OK:
+        _raise(lib, None, rc)
+    return first
 
 
 class Index:

@@ -2,7 +2,7 @@
 // section 8f rows N2/N3): plumbing for BASELINE.json configs[0], not a port of the reference's driver.
 //
 //   lambda3 searchp -q queries.fasta -d db.fasta -o out.m8 [-e 1e-2] [-n 25] [--seed-length 10] [--seed-offset 5]
-//                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--seeding gpu|host] [--records gpu|host|auto]
+//                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--table-slice WORDS] [--seeding gpu|host] [--records gpu|host|auto]
 //                   [--render gpu|host|auto]
 //
 // --render: where the records of the output are made, for every format.  host: the host writer (lx_write_records_ex for a plain
@@ -332,6 +332,7 @@ struct Options
     std::string commandLine;
     std::vector<int> devices;         // --devices (default: every visible device)
     std::string table       = "auto"; // --table gpu | host | auto: where the word table is made (auto: search* on the GPU, mkindex* on the host)
+    uint64_t    tableSlice  = 0;      // --table-slice N: the GPU makes the table in slices of at most N words (0: one sort where it can, slices of 2^30 where it cannot)
     std::string seeding     = "gpu";  // --seeding gpu | host: where search() runs (lx_seed_queries on the worker's handle -- one lane per read, reads
                                       // the device declines are finished on the host threads inside the call --, or on the -t threads)
     std::string render      = "auto"; // --render gpu | host | auto: where the records of the output are made (the header comment)
@@ -685,6 +686,14 @@ Options parse(int argc, char ** argv)
             o.table = val();
             if (o.table != "gpu" && o.table != "host" && o.table != "auto")
                 throw std::runtime_error("--table takes gpu, host or auto");
+        }
+        else if (a == "--table-slice") // (LX_OPT_INDEX_SLICE_WORDS: the device build in slices of the key space)
+        {
+            std::string const v = val();
+            bool              ok = !v.empty() && v.size() <= 18 && std::all_of(v.begin(), v.end(), [](char c) { return c >= '0' && c <= '9'; });
+            o.tableSlice         = ok ? std::stoull(v) : 0;
+            if (o.tableSlice == 0)
+                throw std::runtime_error("--table-slice takes a number of words (at least 1): the most one slice of the GPU's word table build may hold");
         }
         else if (a == "--records")
         {
@@ -1366,6 +1375,7 @@ int main(int argc, char ** argv)
         std::unique_ptr<lx_handle, void (*)(lx_handle *)> firstHandle(nullptr, lx_destroy);
         IndexOwner                                        ix(nullptr, lx_index_destroy);
         bool                                              tableOnGpu = false;
+        int                                               tableSlices = 0; // (> 0: the GPU made the table in that many slices)
         bool const gpuSeedingWanted = !mk && opt.seeding == "gpu";
         auto       makeFirstHandle  = [&]()
         {
@@ -1397,7 +1407,7 @@ int main(int argc, char ** argv)
             if (ok && gpuSeedingWanted && lx_device_count() > 0)
                 makeFirstHandle();
             if (ok && firstHandle && lx_index_load(firstHandle.get(), bytes.data(), bytes.size(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), &raw) != LX_OK)
-                firstHandle.reset(); // (no room on the device, ...: the host copy alone; a table that is wrong fails again below)
+                firstHandle.reset(); // (no room on the device, 2^32 - 1 entries or more, ...: the host copy alone; a table that is wrong fails again below)
             ok = ok && (raw || lx_index_load(nullptr, bytes.data(), bytes.size(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), &raw) == LX_OK);
             ix.reset(raw);
             lx_index_info info{};
@@ -1413,14 +1423,34 @@ int main(int argc, char ** argv)
         else
         {
             // on the GPU (keys, one radix sort, prefix table: lx_seed.hip) where there is one to take it, else on the -t host threads;
-            // the same table either way
+            // the same table either way.  The GPU makes it in slices of the key space where --table-slice says so, where the set has
+            // 2^31 words or more (beyond one sort) and, once, where one sort's memory is more than the device has left.
             bool const wantGpu = opt.table == "gpu" || (opt.table == "auto" && !mk);
             lx_index * raw     = nullptr;
             if (wantGpu && lx_device_count() > 0)
             {
                 makeFirstHandle();
-                int const rc = lx_index_build(firstHandle.get(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), alph, nThreads, &raw);
-                tableOnGpu   = rc == LX_OK;
+                uint64_t const kAutoSlice = 1ull << 30;
+                uint64_t       dbLetters  = 0;
+                for (uint64_t l : db.len)
+                    dbLetters += l;
+                uint64_t slice = opt.tableSlice ? opt.tableSlice : dbLetters >= (1ull << 31) ? kAutoSlice : 0;
+                auto     build = [&]()
+                {
+                    if (slice && lx_set_option(firstHandle.get(), LX_OPT_INDEX_SLICE_WORDS, slice) != LX_OK)
+                        throw std::runtime_error(std::string("lambda_ext: ") + lx_last_error(firstHandle.get()));
+                    return lx_index_build(firstHandle.get(), dbRed.data(), db.off.data(), db.len.data(), db.off.size(), alph, nThreads, &raw);
+                };
+                int rc = build();
+                if (rc == LX_ENOMEM && !slice)
+                {
+                    slice = kAutoSlice;
+                    rc    = build();
+                }
+                tableOnGpu = rc == LX_OK;
+                float msTable = 0;
+                if (tableOnGpu && slice && lx_last_phase_ms(firstHandle.get(), 8, &msTable, &tableSlices) != LX_OK)
+                    tableSlices = 0;
                 if (rc != LX_OK && rc != LX_EINVAL && rc != LX_ENOMEM) // (too large for the device build or for its memory: the host threads make it)
                 {
                     if (opt.table == "gpu")
@@ -1450,7 +1480,8 @@ int main(int argc, char ** argv)
             }
             ix.reset(raw);
         }
-        double const msIndex = msSince(tIndex);
+        double const      msIndex = msSince(tIndex);
+        std::string const onGpu   = tableSlices > 0 ? "on the GPU in " + std::to_string(tableSlices) + " slices" : "on the GPU";
         if (mk)
         {
             // mkindexp | mkindexn | mkindexbs (src/mkindex.cpp): the options that fix the types, ids, sequences, table -> one file
@@ -1483,7 +1514,7 @@ int main(int argc, char ** argv)
                          "lambda3 %s: %zu sequences (%llu residues in %d frame(s); original alphabet %s, translated %s, reduced %s, genetic code %d) -> %s\n"
                          "lambda3 times [ms]: read %.0f%s, reduce + word table %.0f (%s), write %.0f, total %.0f\n",
                          opt.cmd.c_str(), db.ids.size(), (unsigned long long)residues, sFrames, alphName(out.origAlph), alphName(out.transAlph),
-                         alphName(out.redAlph), (int)out.geneticCode, opt.index.c_str(), msRead, gunzipNote.c_str(), msIndex, tableOnGpu ? "on the GPU" : (std::to_string(nThreads) + " host thread(s)").c_str(),
+                         alphName(out.redAlph), (int)out.geneticCode, opt.index.c_str(), msRead, gunzipNote.c_str(), msIndex, tableOnGpu ? onGpu.c_str() : (std::to_string(nThreads) + " host thread(s)").c_str(),
                          msSince(tWrite), msSince(tStart));
             return 0;
         }
@@ -2228,7 +2259,7 @@ int main(int argc, char ** argv)
         std::fprintf(stderr,
                      "lambda3 times [ms]: read %.0f%s, reduce + word table %s%.0f, search %.0f (seeding on the %s %.0f [%zu read(s) and %zu launch(es) left to "
                      "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records %.1f (%s), records + output %.0f%s, total %.0f\n",
-                     msRead, gunzipNote.c_str(), fromIndex ? "(read from the index) " : tableOnGpu ? "(on the GPU) " : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
+                     msRead, gunzipNote.c_str(), fromIndex ? "(read from the index) " : tableOnGpu ? ("(" + onGpu + ") ").c_str() : "", msIndex, msSearch, anyGpuSeeding ? "GPU" : "host", msSeedMax, nDeclined,
                      nPassesOnHost, msExtendMax, msRecords, recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msSince(tOut) - msCompress,
                      renderedOnGpu                  ? (std::string(", ") + (fmt == LX_OUT_BAM ? "BAM" : fmt == LX_OUT_SAM ? "SAM" : "tabular") + " records rendered" +
                                                        (fmt == LX_OUT_BAM || outGz ? " and BGZF-compressed" : "") + " on the GPU (render kernels " +

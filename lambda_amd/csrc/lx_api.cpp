@@ -1207,8 +1207,9 @@ int lx_set_option(lx_handle * h, int option, uint64_t value)
             h->opt_gunzip_chunk = value;
             return LX_OK;
         case LX_OPT_GUNZIP_PARALLEL_FROM: h->opt_gunzip_from = value; return LX_OK;
+        case LX_OPT_INDEX_SLICE_WORDS: h->opt_index_slice = value; return LX_OK;
         case LX_OPT_BAM_RANGE_BYTES:
-            if (value && (value < (128u << 10) || value > (2ull << 30)))
+            if (value &&(value < (128u << 10) || value > (2ull << 30)))
                 return fail(h, LX_EINVAL, "LX_OPT_BAM_RANGE_BYTES: 0, or 128 KiB to 2 GiB");
             h->opt_bam_range = value;
             return LX_OK;
@@ -1248,6 +1249,7 @@ int lx_get_option(lx_handle const * h, int option, uint64_t * value)
         case LX_OPT_HOST_THREADS: *value = lxi::HostPool::instance().width(); return LX_OK;
         case LX_OPT_GUNZIP_CHUNK: *value = h->opt_gunzip_chunk; return LX_OK;
         case LX_OPT_GUNZIP_PARALLEL_FROM: *value = h->opt_gunzip_from; return LX_OK;
+        case LX_OPT_INDEX_SLICE_WORDS: *value = h->opt_index_slice; return LX_OK;
         case LX_OPT_BAM_RANGE_BYTES: *value = h->opt_bam_range; return LX_OK;
         default: return LX_EINVAL;
     }
@@ -1472,13 +1474,13 @@ int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches)
     float total = 0.f;
     int   cnt   = 0;
     for (auto const & pe : h->phase_ev)
-        if (pe.phase == phase)
+        if (pe.phase == phase || pe.phase == phase + lxi::kPhaseTimeOnly)
         {
             float t = 0.f;
             LX_HIP(h, hipEventSynchronize(pe.b));
             LX_HIP(h, hipEventElapsedTime(&t, pe.a, pe.b));
             total += t;
-            ++cnt;
+            cnt += pe.phase == phase ? 1 : 0;
         }
     for (int i = 0; i < 3; ++i) // (lx_gunzip's plain-member kernels: summed per wave by the call itself)
         if (phase == 10 || phase == 101 + i)

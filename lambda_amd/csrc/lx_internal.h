@@ -264,6 +264,7 @@ struct lx_handle
     uint64_t opt_bam_range = 0; // LX_OPT_BAM_RANGE_BYTES (0 = default)
     uint64_t opt_gunzip_chunk = 0; // LX_OPT_GUNZIP_CHUNK (0 = default)
     uint64_t opt_gunzip_from  = 0; // LX_OPT_GUNZIP_PARALLEL_FROM (0 = default)
+    uint64_t opt_index_slice  = 0; // LX_OPT_INDEX_SLICE_WORDS (0 = the single sort)
     uint64_t gunzip_wave      = 0; // kOptGunzipWaveTest: chunks per wave (0 = default), so that a test reaches a wave's edges with a megabyte
     // lx_seed_queries (lx_seed_host.cpp): a call's queries, reads, decline flags, counters, the two scoring matrices, subjects the
     // caller handed in; the match block of the last freed result, kept for the next call
@@ -310,6 +311,10 @@ struct HostMarks
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
 };
+
+// a bracket of phase p + kPhaseTimeOnly adds its time to phase p but is no launch of it (the sliced word table's counting pass: its
+// launches are its slices)
+constexpr int kPhaseTimeOnly = 1000;
 
 // RAII-less phase bracket: records a start event now, the end event on close()
 struct PhaseTimer

@@ -56,4 +56,29 @@ hipError_t seed_launch_table_keys(uint8_t const * red, uint64_t const * off, uin
 hipError_t seed_launch_table_entries(uint64_t const * keys, uint64_t const * vals, uint64_t total, lambda_amd::ReducedIndex::Entry * out, hipStream_t stream);
 hipError_t seed_launch_table_prefix(uint64_t const * keys, uint64_t total, uint64_t preDiv, uint64_t nPre, uint64_t * pre, hipStream_t stream);
 
+// The word table in slices of the key space (lx_seed_host.cpp: build_in_slices).  One workgroup of kTabBlock threads per kTabBlock
+// positions; the 64-bit scan works on tiles of kTabScanTile values.
+constexpr int kTabBlock = 256, kTabScanItems = 8, kTabScanTile = kTabBlock * kTabScanItems;
+inline uint64_t tab_blocks(uint64_t total)
+{
+    return (total + kTabBlock - 1) / kTabBlock;
+}
+inline uint64_t tab_scan_tiles(uint64_t n)
+{
+    return (n + kTabScanTile - 1) / kTabScanTile;
+}
+// hist[w] += the positions whose first preLen letters are the word w (hist: nPre zeroed values; words are < nPre)
+hipError_t seed_launch_table_counts(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first, uint64_t nSeq, uint64_t total,
+                                    int preLen, uint64_t base, int alph, uint64_t nPre, uint64_t * hist, hipStream_t stream);
+// a[0 .. n) becomes its exclusive sum scan, in place; tile_tot: tab_scan_tiles(n) values of workspace
+hipError_t seed_launch_scan64(uint64_t * a, uint64_t n, uint64_t * tile_tot, hipStream_t stream);
+// block_cnt[b] = how many of positions [b * kTabBlock, (b + 1) * kTabBlock) have their first preLen letters in [wLo, wHi) (tab_blocks(total) values) ...
+hipError_t seed_launch_table_slice_counts(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first, uint64_t nSeq, uint64_t total,
+                                          int preLen, uint64_t base, int alph, uint64_t wLo, uint64_t wHi, uint64_t * block_cnt, hipStream_t stream);
+// ... and, block_before = their exclusive scan, those positions' keys / vals (as seed_launch_table_keys makes them) side by side in
+// (sequence, position) order; cap = how many there are (nothing is written at or behind it)
+hipError_t seed_launch_table_slice_keys(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first, uint64_t nSeq, uint64_t total,
+                                        int preLen, int keyLen, uint64_t base, int alph, uint64_t wLo, uint64_t wHi, uint64_t const * block_before, uint64_t cap,
+                                        uint64_t * keys, uint64_t * vals, hipStream_t stream);
+
 } // namespace lx

@@ -352,6 +352,257 @@ __global__ void table_prefix_kernel(uint64_t const * keys, uint64_t total, uint6
     pre[w] = a;
 }
 
+// ---- the word table in slices of the key space (lx_seed_host.cpp: build_in_slices), for sets whose keys do not fit the device, or the
+// sort's 32-bit ranks, all at once.  The words' first preLen letters are counted into a 64-bit histogram whose exclusive scan IS the
+// prefix table; the host cuts it into runs of buckets (lx_index_plan_slices); per slice the positions whose prefix lies in the run are
+// compacted in (sequence, position) order -- flag counts per block, a scan, the write --, sorted by the same radix sort and written as
+// entries where the prefix table says the run begins.  Every pass reads the reduced subjects again: bandwidth next to a sort.
+
+// the sequence that holds entry e and e's position in it (first[s] = entry of sequence s's first position; as table_keys_kernel)
+__device__ __forceinline__ uint64_t place_of(uint64_t const * first, uint64_t nSeq, uint64_t e, uint64_t & pos)
+{
+    uint64_t a = 0, b = nSeq;
+    while (b - a > 1)
+    {
+        uint64_t const mid = a + (b - a) / 2;
+        if (first[mid] <= e)
+            a = mid;
+        else
+            b = mid;
+    }
+    while (a + 1 < nSeq && first[a + 1] <= e) // (skip empty sequences that start where the next one does)
+        ++a;
+    pos = e - first[a];
+    return a;
+}
+
+// letters [from, to) behind position pos appended to `word` (the pad digit behind the sequence's end)
+__device__ __forceinline__ uint64_t word_more(uint64_t word, uint8_t const * r, uint64_t pos, uint64_t L, int from, int to, uint64_t base, int alph)
+{
+    for (int i = from; i < to; ++i)
+        word = word * base + (pos + (uint64_t)i < L ? (uint64_t)r[i] : (uint64_t)alph);
+    return word;
+}
+
+constexpr uint64_t kNoWord = ~0ull; // a lane behind the last position
+
+// (a) hist[w] += the positions whose first preLen letters are the word w.  Real sets hold long runs of one word (poly-A, masked
+// stretches, the pads): neighbouring lanes with the same word are combined, the run's first lane adds its length -- one atomic per
+// run of a wavefront, not one per position.
+__global__ __launch_bounds__(kTabBlock) void table_counts_kernel(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first,
+                                                                 uint64_t nSeq, uint64_t total, int preLen, uint64_t base, int alph, uint64_t nPre,
+                                                                 unsigned long long * hist)
+{
+    uint64_t const e = (uint64_t)blockIdx.x * kTabBlock + threadIdx.x;
+    uint64_t       w = kNoWord;
+    if (e < total)
+    {
+        uint64_t       pos;
+        uint64_t const a = place_of(first, nSeq, e, pos);
+        w                = word_more(0, red + off[a] + pos, pos, len[a], 0, preLen, base, alph);
+    }
+    int const      lane  = threadIdx.x & 63;
+    uint64_t const left  = (uint64_t)__shfl_up((unsigned long long)w, 1);
+    bool const     head  = lane == 0 || left != w;
+    uint64_t const heads = __ballot(head);
+    if (head && w < nPre)
+    {
+        uint64_t const above = lane == 63 ? 0ull : heads >> (lane + 1); // (bit k: lane + 1 + k begins the next run)
+        int const      run   = above ? __ffsll((unsigned long long)above) : 64 - lane;
+        atomicAdd(hist + w, (unsigned long long)run);
+    }
+}
+
+// ---- an exclusive 64-bit sum scan in place (lx_scan.h's tiled scans carry uint32_t): the tiles' sums, one workgroup that turns them
+// into what precedes each tile, the pass over the elements
+
+__device__ __forceinline__ uint64_t block_inclusive64(uint64_t v, uint64_t * wave_tot, uint64_t & total)
+{
+    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t  incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+        uint64_t const up = (uint64_t)__shfl_up((unsigned long long)incl, o);
+        if (lane >= o)
+            incl += up;
+    }
+    if (lane == 63)
+        wave_tot[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < kTabBlock / 64; ++k)
+    {
+        uint64_t const x = wave_tot[k];
+        if (k < wave)
+            before += x;
+        tot += x;
+    }
+    total = tot;
+    __syncthreads();
+    return before + incl;
+}
+
+__global__ __launch_bounds__(kTabBlock) void scan64_sums_kernel(uint64_t const * a, uint64_t n, uint64_t * tile_tot)
+{
+    __shared__ uint64_t wave_tot[kTabBlock / 64];
+    uint64_t const      j0  = (uint64_t)blockIdx.x * kTabScanTile + threadIdx.x;
+    uint64_t            acc = 0;
+#pragma unroll
+    for (int k = 0; k < kTabScanItems; ++k)
+    {
+        uint64_t const j = j0 + (uint64_t)k * kTabBlock;
+        if (j < n)
+            acc += a[j];
+    }
+    uint64_t total;
+    (void)block_inclusive64(acc, wave_tot, total);
+    if (threadIdx.x == 0)
+        tile_tot[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kTabBlock) void scan64_tops_kernel(uint64_t * tile_tot, uint64_t tiles)
+{
+    __shared__ uint64_t wave_tot[kTabBlock / 64];
+    uint64_t            carry = 0;
+    for (uint64_t b0 = 0; b0 < tiles; b0 += kTabBlock)
+    {
+        uint64_t const b = b0 + threadIdx.x;
+        uint64_t const v = b < tiles ? tile_tot[b] : 0;
+        uint64_t       total;
+        uint64_t const incl = block_inclusive64(v, wave_tot, total);
+        if (b < tiles)
+            tile_tot[b] = carry + incl - v;
+        carry += total;
+    }
+}
+
+// (a thread reads its kTabScanItems consecutive values before it writes them: in place)
+__global__ __launch_bounds__(kTabBlock) void scan64_apply_kernel(uint64_t * a, uint64_t n, uint64_t const * tile_before)
+{
+    __shared__ uint64_t wave_tot[kTabBlock / 64];
+    uint64_t const      j0 = (uint64_t)blockIdx.x * kTabScanTile + (uint64_t)threadIdx.x * kTabScanItems;
+    uint64_t            v[kTabScanItems], acc = 0;
+#pragma unroll
+    for (int k = 0; k < kTabScanItems; ++k)
+    {
+        v[k] = j0 + (uint64_t)k < n ? a[j0 + (uint64_t)k] : 0;
+        acc += v[k];
+    }
+    uint64_t       total;
+    uint64_t const incl = block_inclusive64(acc, wave_tot, total);
+    uint64_t       run  = tile_before[blockIdx.x] + incl - acc;
+#pragma unroll
+    for (int k = 0; k < kTabScanItems; ++k)
+    {
+        if (j0 + (uint64_t)k < n)
+            a[j0 + (uint64_t)k] = run;
+        run += v[k];
+    }
+}
+
+// (d) a slice = the buckets [wLo, wHi).  block_cnt[b] = how many of block b's positions belong to it ...
+__global__ __launch_bounds__(kTabBlock) void table_slice_counts_kernel(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first,
+                                                                       uint64_t nSeq, uint64_t total, int preLen, uint64_t base, int alph, uint64_t wLo,
+                                                                       uint64_t wHi, uint64_t * block_cnt)
+{
+    __shared__ uint32_t wave_cnt[kTabBlock / 64];
+    uint64_t const      e  = (uint64_t)blockIdx.x * kTabBlock + threadIdx.x;
+    bool                in = false;
+    if (e < total)
+    {
+        uint64_t       pos;
+        uint64_t const a = place_of(first, nSeq, e, pos);
+        uint64_t const w = word_more(0, red + off[a] + pos, pos, len[a], 0, preLen, base, alph);
+        in               = w >= wLo && w < wHi;
+    }
+    uint64_t const mine = __ballot(in);
+    if ((threadIdx.x & 63) == 0)
+        wave_cnt[threadIdx.x >> 6] = (uint32_t)__popcll((unsigned long long)mine);
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        uint32_t sum = 0;
+        for (int k = 0; k < kTabBlock / 64; ++k)
+            sum += wave_cnt[k];
+        block_cnt[blockIdx.x] = sum;
+    }
+}
+
+// ... and, block_before = the exclusive scan of those counts, its keys and values at block_before[b] + the position's rank among the
+// block's: the slice's pairs in (sequence, position) order, as the stable sort wants them.  cap = the slice's words.
+__global__ __launch_bounds__(kTabBlock) void table_slice_keys_kernel(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first,
+                                                                     uint64_t nSeq, uint64_t total, int preLen, int keyLen, uint64_t base, int alph, uint64_t wLo,
+                                                                     uint64_t wHi, uint64_t const * block_before, uint64_t cap, uint64_t * keys, uint64_t * vals)
+{
+    __shared__ uint32_t wave_cnt[kTabBlock / 64];
+    uint64_t const      e = (uint64_t)blockIdx.x * kTabBlock + threadIdx.x;
+    int const           lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool                in = false;
+    uint64_t            a = 0, pos = 0, w = 0;
+    if (e < total)
+    {
+        a  = place_of(first, nSeq, e, pos);
+        w  = word_more(0, red + off[a] + pos, pos, len[a], 0, preLen, base, alph);
+        in = w >= wLo && w < wHi;
+    }
+    uint64_t const mine = __ballot(in);
+    if (lane == 0)
+        wave_cnt[wave] = (uint32_t)__popcll((unsigned long long)mine);
+    __syncthreads();
+    if (!in)
+        return;
+    uint64_t at = block_before[blockIdx.x] + (uint64_t)__popcll((unsigned long long)(mine & ((1ull << lane) - 1ull)));
+    for (int k = 0; k < wave; ++k)
+        at += wave_cnt[k];
+    if (at >= cap)
+        return;
+    keys[at] = word_more(w, red + off[a] + pos, pos, len[a], preLen, keyLen, base, alph);
+    vals[at] = (a << 32) | pos;
+}
+
+hipError_t seed_launch_table_counts(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first, uint64_t nSeq, uint64_t total,
+                                    int preLen, uint64_t base, int alph, uint64_t nPre, uint64_t * hist, hipStream_t stream)
+{
+    if (total == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(table_counts_kernel, dim3((unsigned)tab_blocks(total)), dim3(kTabBlock), 0, stream, red, off, len, first, nSeq, total, preLen, base, alph, nPre, reinterpret_cast<unsigned long long *>(hist));
+    return hipGetLastError();
+}
+
+hipError_t seed_launch_scan64(uint64_t * a, uint64_t n, uint64_t * tile_tot, hipStream_t stream)
+{
+    if (n == 0)
+        return hipSuccess;
+    unsigned const tiles = (unsigned)tab_scan_tiles(n);
+    hipLaunchKernelGGL(scan64_sums_kernel, dim3(tiles), dim3(kTabBlock), 0, stream, a, n, tile_tot);
+    hipLaunchKernelGGL(scan64_tops_kernel, dim3(1), dim3(kTabBlock), 0, stream, tile_tot, (uint64_t)tiles);
+    hipLaunchKernelGGL(scan64_apply_kernel, dim3(tiles), dim3(kTabBlock), 0, stream, a, n, tile_tot);
+    return hipGetLastError();
+}
+
+hipError_t seed_launch_table_slice_counts(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first, uint64_t nSeq, uint64_t total,
+                                          int preLen, uint64_t base, int alph, uint64_t wLo, uint64_t wHi, uint64_t * block_cnt, hipStream_t stream)
+{
+    if (total == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(table_slice_counts_kernel, dim3((unsigned)tab_blocks(total)), dim3(kTabBlock), 0, stream, red, off, len, first, nSeq, total, preLen, base,
+                       alph, wLo, wHi, block_cnt);
+    return hipGetLastError();
+}
+
+hipError_t seed_launch_table_slice_keys(uint8_t const * red, uint64_t const * off, uint64_t const * len, uint64_t const * first, uint64_t nSeq, uint64_t total,
+                                        int preLen, int keyLen, uint64_t base, int alph, uint64_t wLo, uint64_t wHi, uint64_t const * block_before, uint64_t cap,
+                                        uint64_t * keys, uint64_t * vals, hipStream_t stream)
+{
+    if (total == 0 || cap == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(table_slice_keys_kernel, dim3((unsigned)tab_blocks(total)), dim3(kTabBlock), 0, stream, red, off, len, first, nSeq, total, preLen, keyLen,
+                       base, alph, wLo, wHi, block_before, cap, keys, vals);
+    return hipGetLastError();
+}
+
 hipError_t seed_launch_reads(SeedDev const & p, hipStream_t stream)
 {
     if (p.nReads == 0)

@@ -88,9 +88,16 @@ bool extent_of(uint64_t const * off, uint64_t const * len, uint64_t n, uint64_t 
     return true;
 }
 
+enum DeviceBuild // which builder's limits take_subjects applies
+{
+    kNoDeviceBuild = 0, // h == NULL, or a load (no sort runs; upload_table has the resident table's limit)
+    kSingleSort,
+    kInSlices
+};
+
 // the index's own copy of the subjects, checked: what every later step relies on
 int take_subjects(lx_handle * h, char const * who, uint8_t const * s_red, uint64_t const * s_off, uint64_t const * s_len, uint64_t n_sseq, int alph,
-                  unsigned threads, HostTable & t)
+                  unsigned threads, DeviceBuild build, HostTable & t)
 {
     if (n_sseq && (!s_off || !s_len))
         return say(h, LX_EINVAL, "%s: NULL sequence table", who);
@@ -102,9 +109,14 @@ int take_subjects(lx_handle * h, char const * who, uint8_t const * s_red, uint64
     if (!extent_of(s_off, s_len, n_sseq, extent, t.total))
         return say(h, LX_EINVAL, "%s: a sequence lies outside the address range", who);
     // (what the lengths alone say comes before the letters are read and copied)
-    if (h && (t.total > 0x7fffffffull || n_sseq >= 0xffffffffull))
+    if (build == kSingleSort && (t.total > 0x7fffffffull || n_sseq >= 0xffffffffull))
         return fail(h, LX_EINVAL, "%s: %llu words in %llu sequences are beyond the device (fewer than 2^31 words, fewer than 2^32 - 1 sequences): build with h == NULL", who,
                     (unsigned long long)t.total, (unsigned long long)n_sseq);
+    if (build == kInSlices && (t.total >= 0xffffffffull || n_sseq >= 0xffffffffull))
+        return fail(h, LX_EINVAL,
+                    "%s: %llu words in %llu sequences are beyond the device (a cursor on the device is a 32-bit range: fewer than 2^32 - 1 words, fewer than 2^32 - 1 "
+                    "sequences): build with h == NULL",
+                    who, (unsigned long long)t.total, (unsigned long long)n_sseq);
     for (uint64_t i = 0; i < n_sseq; ++i)
         if (s_len[i] >= 0xffffffffull)
             return say(h, LX_EINVAL, "%s: sequence %llu has %llu letters (an entry names its position with 32 bits)", who, (unsigned long long)i,
@@ -235,6 +247,122 @@ int build_on_device(lx_handle * h, lx_index & ix, int alph)
     return LX_OK;
 }
 
+// The walk of lx_index_plan_slices (include/lambda_ext.h has the rule): begin(w) for every bucket that opens a slice but the first;
+// the number of slices, or 0 for a prefix table that descends or a bucket beyond the sort.
+template <class Begin>
+uint64_t walk_slices(uint64_t const * pre, uint64_t n_prefix, uint64_t slice_words, Begin && begin)
+{
+    uint64_t n = 1, words = 0; // (words + c <= pre[w + 1]: no overflow)
+    for (uint64_t w = 0; w + 1 < n_prefix; ++w)
+    {
+        if (pre[w + 1] < pre[w] || pre[w + 1] - pre[w] > 0x7fffffffull)
+            return 0;
+        uint64_t const c = pre[w + 1] - pre[w];
+        if (words != 0 && words + c > slice_words)
+        {
+            begin(w);
+            ++n, words = 0;
+        }
+        words += c;
+    }
+    return n > 1 && words == 0 ? n - 1 : n; // (empty buckets behind a full slice are that slice's)
+}
+
+// The table made slice by slice (lx_seed.hip), for sets beyond the single sort: the words counted by their first prefix_len letters,
+// the counts' scan = the prefix table, which comes down and is cut (lx_index_plan_slices); per slice its positions' keys compacted in
+// (sequence, position) order, the radix sort, the entries written where the prefix table says the slice begins, and brought down.
+// On the device at once: the entries (16 bytes a word), keys and values twice for the largest slice (32 bytes a word of it), the
+// prefix table, the blocks' counts (8 bytes per 256 words), the subjects, the sort's digit counts.
+int build_in_slices(lx_handle * h, lx_index & ix, int alph, uint64_t slice_words)
+{
+    HostTable &    t     = *ix.t;
+    uint64_t const total = t.total, n_max = std::min<uint64_t>(slice_words, 0x7fffffffull); // (a slice is one sort)
+    size_t const   nSeq  = t.off.size();
+    int            rc    = bind(h);
+    if (rc)
+        return rc;
+    t.ix.prepareExternal(t.red, t.off, t.len, alph);
+    int const      keyLen = t.ix.keyLen(), preLen = t.ix.prefixLen();
+    uint64_t const nPre = t.ix.prefixCount(), blocks = lx::tab_blocks(total);
+    uint64_t const tiles = std::max(lx::tab_scan_tiles(blocks), lx::tab_scan_tiles(nPre));
+    auto const     no_room = [&](uint64_t largest) // what a build with slices of `largest` words still has to take from the device
+    {
+        size_t freeB = 0, totalB = 0;
+        if (hipMemGetInfo(&freeB, &totalB) != hipSuccess)
+            return true;
+        return (double)largest * 32.5 + (double)(64 << 20) > (double)freeB; // keys + values twice, the sort's digit counts
+    };
+    {
+        size_t freeB = 0, totalB = 0;
+        LXS_HIP(h, hipMemGetInfo(&freeB, &totalB));
+        double const fixed = (double)total * 16.0 + (double)nPre * 8.0 + (double)(blocks + tiles) * 8.0 + (double)t.red.size() + (double)nSeq * 24.0;
+        if (fixed + (double)std::min(total, n_max) * 32.5 + (double)(64 << 20) > (double)freeB)
+            return fail(h, LX_ENOMEM, "lx_index_build: the device has no room for a table of %llu words in slices of %llu: build with h == NULL",
+                        (unsigned long long)total, (unsigned long long)n_max);
+    }
+    std::vector<uint64_t> first(nSeq + 1, 0);
+    for (size_t s = 0; s < nSeq; ++s)
+        first[s + 1] = first[s] + t.len[s];
+    if ((rc = upload_subjects(h, ix)))
+        return rc;
+    lxi::DevBlock<uint64_t> dFirst, dBlocks, dTiles, k0, k1, v0, v1;
+    if ((rc = dev_block(h, dFirst, nSeq + 1)) || (rc = dev_block(h, ix.d_entries, total)) || (rc = dev_block(h, ix.d_pre, nPre)) || (rc = dev_block(h, dBlocks, blocks)) ||
+        (rc = dev_block(h, dTiles, tiles)))
+        return rc;
+    LXS_HIP(h, hipMemcpy(dFirst, first.data(), (nSeq + 1) * 8, hipMemcpyHostToDevice));
+    uint64_t const    base = (uint64_t)alph + 1;
+    hipStream_t const st   = h->stream;
+    h->phase_ev.clear();
+    h->ev_pool_used = 0;
+    // the counts and their scan: the prefix table itself (pre[w] = first entry whose word is >= w, pre[nPre - 1] = total)
+    lxi::PhaseTimer pc(h, st, 8 + lxi::kPhaseTimeOnly);
+    LXS_HIP(h, hipMemsetAsync(ix.d_pre, 0, nPre * 8, st));
+    LXS_HIP(h, lx::seed_launch_table_counts(ix.d_sred, ix.d_soff, ix.d_slen, dFirst, (uint64_t)nSeq, total, preLen, base, alph, nPre, ix.d_pre, st));
+    LXS_HIP(h, lx::seed_launch_scan64(ix.d_pre, nPre, dTiles, st));
+    pc.close();
+    LXS_HIP(h, hipStreamSynchronize(st));
+    uint64_t * const pre = t.ix.prefixForFill();
+    LXS_HIP(h, hipMemcpy(pre, ix.d_pre, nPre * 8, hipMemcpyDeviceToHost));
+    if (pre[0] != 0 || pre[nPre - 1] != total)
+        return fail(h, LX_EHIP, "lx_index_build: the word counts do not add up to the %llu words of the set", (unsigned long long)total);
+    uint64_t n_slices = 0;
+    if (lx_index_plan_slices(pre, nPre, n_max, nullptr, 0, &n_slices) != LX_OK)
+        return fail(h, LX_EINVAL, "lx_index_build: one prefix of %d letters begins more than 2^31 - 1 words, which is beyond the device's sort: build with h == NULL", preLen);
+    std::vector<uint64_t> cut(n_slices + 1, nPre - 1);
+    (void)lx_index_plan_slices(pre, nPre, n_max, cut.data(), n_slices, &n_slices);
+    uint64_t largest = 0;
+    for (uint64_t s = 0; s < n_slices; ++s)
+        largest = std::max(largest, pre[cut[s + 1]] - pre[cut[s]]);
+    if (no_room(largest))
+        return fail(h, LX_ENOMEM, "lx_index_build: the device has no room for a slice of %llu words of the table: build with h == NULL", (unsigned long long)largest);
+    if ((rc = dev_block(h, k0, largest)) || (rc = dev_block(h, k1, largest)) || (rc = dev_block(h, v0, largest)) || (rc = dev_block(h, v1, largest)))
+        return rc;
+    int bits = 1;
+    while (bits < 64 && (t.ix.power(keyLen) - 1) >> bits)
+        ++bits;
+    for (uint64_t s = 0; s < n_slices; ++s)
+    {
+        uint64_t const  at = pre[cut[s]], n = pre[cut[s + 1]] - at;
+        lxi::PhaseTimer pt(h, st, 8);
+        LXS_HIP(h, lx::seed_launch_table_slice_counts(ix.d_sred, ix.d_soff, ix.d_slen, dFirst, (uint64_t)nSeq, total, preLen, base, alph, cut[s], cut[s + 1], dBlocks, st));
+        LXS_HIP(h, lx::seed_launch_scan64(dBlocks, blocks, dTiles, st));
+        LXS_HIP(h, lx::seed_launch_table_slice_keys(ix.d_sred, ix.d_soff, ix.d_slen, dFirst, (uint64_t)nSeq, total, preLen, keyLen, base, alph, cut[s], cut[s + 1], dBlocks,
+                                                    n, k0, v0, st));
+        uint64_t * kk[2] = {k0, k1}, * vv[2] = {v0, v1};
+        int        where = 0;
+        if ((rc = lx_sort_words_dev(h->device, kk, vv, n, bits >= 64 ? ~0ull : ((1ull << bits) - 1), st, &where)) != LX_OK)
+            return fail(h, rc, "lx_index_build: the sort of slice %llu of the word table failed", (unsigned long long)s);
+        LXS_HIP(h, lx::seed_launch_table_entries(kk[where], vv[where], n, ix.d_entries.raw + at, st));
+        pt.close();
+        LXS_HIP(h, hipStreamSynchronize(st));
+        if (n)
+            LXS_HIP(h, hipMemcpy(t.ix.entriesForFill() + at, ix.d_entries.raw + at, n * sizeof(ReducedIndex::Entry), hipMemcpyDeviceToHost));
+    }
+    t.built_on_device = true;
+    ix.h = h, ix.device = h->device;
+    return LX_OK;
+}
+
 int finish_index(int rc, std::unique_ptr<lx_index> & ix, lx_index ** out)
 {
     if (rc == LX_OK)
@@ -259,13 +387,14 @@ int lx_index_build(lx_handle * h, uint8_t const * s_red, uint64_t const * s_off,
         unsigned const            threads = threads_or_share(host_threads);
         std::unique_ptr<lx_index> ix(new lx_index());
         ix->t  = std::make_shared<HostTable>();
-        int rc = take_subjects(h, "lx_index_build", s_red, s_off, s_len, n_sseq, alph, threads, *ix->t);
+        uint64_t const slice_words = h ? h->opt_index_slice : 0;
+        int rc = take_subjects(h, "lx_index_build", s_red, s_off, s_len, n_sseq, alph, threads, !h ? kNoDeviceBuild : slice_words ? kInSlices : kSingleSort, *ix->t);
         if (rc)
             return rc;
         if (h && ix->t->total > 0)
         {
             ix->device = h->device; // (blocks that were taken before a failure go back on this device)
-            return finish_index(build_on_device(h, *ix, alph), ix, out);
+            return finish_index(slice_words ? build_in_slices(h, *ix, alph, slice_words) : build_on_device(h, *ix, alph), ix, out);
         }
         ix->t->ix.build(ix->t->red, ix->t->off, ix->t->len, alph, threads);
         if (h) // (nothing to sort: the empty table, resident)
@@ -282,6 +411,36 @@ int lx_index_build(lx_handle * h, uint8_t const * s_red, uint64_t const * s_off,
     }
 }
 
+int lx_index_plan_slices(uint64_t const * pre, uint64_t n_prefix, uint64_t slice_words, uint64_t * first_word, uint64_t cap, uint64_t * n_slices)
+{
+    if (n_slices)
+        *n_slices = 0;
+    if (!pre || !n_slices || (cap && !first_word) || slice_words == 0 || n_prefix < 2)
+    {
+        lxi::set_output_error("lx_index_plan_slices: NULL argument, slices of no words or a prefix table of fewer than two values");
+        return LX_EINVAL;
+    }
+    uint64_t const n = walk_slices(pre, n_prefix, slice_words, [](uint64_t) {});
+    if (n == 0)
+    {
+        lxi::set_output_error("lx_index_plan_slices: the prefix table does not ascend, or one of its buckets holds more than 2^31 - 1 words (beyond the sort: build with h == NULL)");
+        return LX_EINVAL;
+    }
+    *n_slices = n;
+    if (cap >= n)
+    {
+        uint64_t s    = 0;
+        first_word[0] = 0;
+        (void)walk_slices(pre, n_prefix, slice_words,
+                          [&](uint64_t w)
+                          {
+                              if (++s < n)
+                                  first_word[s] = w;
+                          });
+    }
+    return LX_OK;
+}
+
 int lx_index_load(lx_handle * h, uint8_t const * bytes, uint64_t n, uint8_t const * s_red, uint64_t const * s_off, uint64_t const * s_len, uint64_t n_sseq,
                   lx_index ** out)
 {
@@ -294,11 +453,17 @@ int lx_index_load(lx_handle * h, uint8_t const * bytes, uint64_t n, uint8_t cons
         return say(h, LX_EINVAL, bytes ? "lx_index_load: truncated (no header)" : "lx_index_load: NULL buffer");
     try
     {
-        int32_t geo[4];
+        int32_t  geo[4];
+        uint64_t cnt[2];
         std::memcpy(geo, bytes, sizeof(geo));
+        std::memcpy(cnt, bytes + sizeof(geo), sizeof(cnt));
+        // (what the header alone says comes before the letters are read and copied: the bytes its counts ask for)
+        if (cnt[0] > (~0ull >> 5) || cnt[1] > (~0ull >> 5) || n != 32 + cnt[0] * sizeof(ReducedIndex::Entry) + cnt[1] * 8)
+            return say(h, LX_EINVAL, "lx_index_load: the word table is truncated or has bytes left over (its header counts %llu entries and %llu prefixes)",
+                       (unsigned long long)cnt[0], (unsigned long long)cnt[1]);
         std::unique_ptr<lx_index> ix(new lx_index());
         ix->t  = std::make_shared<HostTable>();
-        int rc = take_subjects(h, "lx_index_load", s_red, s_off, s_len, n_sseq, geo[0], threads_or_share(0), *ix->t);
+        int rc = take_subjects(h, "lx_index_load", s_red, s_off, s_len, n_sseq, geo[0], threads_or_share(0), kNoDeviceBuild, *ix->t);
         if (rc)
             return rc;
         uint64_t at   = 0;
