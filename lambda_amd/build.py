@@ -111,7 +111,7 @@ CLI = CSRC / "lambda3"
 def build_cli(force: bool = False) -> Path:
     """The minimal `lambda3 searchp|searchn` front end (plumbing for BASELINE.json configs[0])."""
     src = CSRC / "host" / "lambda3_main.cpp"
-    if not force and _newer(CLI, [src, LIB] + list((CSRC / "host").glob("*.hpp"))):
+    if not force and _newer(CLI, [src, LIB] + list((CSRC / "host").glob("*.hpp")) + list((CSRC / "host" / "cli").glob("*.hpp"))):
         return CLI
     cmd = [_hipcc(), "-O2", "-std=c++17", "-x", "hip", "--offload-arch=gfx950", f"-I{ROOT / 'include'}", str(src), "-o", str(CLI),
            f"-L{CSRC}", "-llambda_ext", f"-Wl,-rpath,$ORIGIN"]
