@@ -344,7 +344,10 @@ int lx_extend_batch_list(lx_handle * h, int slot, uint8_t const * q_res, uint64_
 int lx_last_extend_stats(lx_handle const * h, uint64_t * out4);
 
 /* ---- pre-extension filter (seedLooksPromising, src/search_algo.hpp:426-481) ------------------ */
-/* One diagonal per item; out_keep[i] = 1 if the ungapped max-segment score reaches the threshold. */
+/* One diagonal per item; out_keep[i] = 1 if the ungapped max-segment score reaches the threshold.  LX_EINVAL, before any kernel runs
+ * and with the handle as usable as before: a seed with qry_end < qry_start, qry_end > q_len or subj_start + (qry_end - qry_start) >
+ * s_len, a sequence that does not lie inside q_bytes / s_bytes, and -- unlike the other batch calls, which say LX_ESTATE -- a scoring
+ * slot that is not set. */
 typedef struct lx_seed
 {
     uint64_t q_off, s_off; /* start of the whole (frame) query / subject sequence */
@@ -515,9 +518,12 @@ int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint
 uint64_t lx_plan_free_packing_bound(uint64_t n, uint64_t n_qseq, uint32_t nranges);
 int      lx_plan_free_packing_dev(lx_handle * h, void const * d_ext, uint64_t n, uint64_t n_qseq, int32_t strip_cols, uint32_t nranges, uint64_t const * cut,
                                   uint32_t * out_plan, uint32_t * out_pan, uint32_t * out_maxs, uint32_t * out_report);
-/* The library's own radix sort (least significant digit first, 8 bits per pass, only the digits set in key_bits; stable) for n (key, value)
- * word pairs in device memory: key[0] / value[0] hold the input, key[1] / value[1] are scratch of the same size; *sorted_in says which of
- * the two holds the sorted words afterwards.  Synchronises `stream`; the caller's current device is left as it was.  n < 2^31.  (lx_index_build sorts its word table with it;
+/* The library's own radix sort (least significant digit first, 8 bits per pass; stable) for n (key, value) word pairs in device memory.
+ * key_bits is a bit MASK, not a number of bits: there is one pass for every 8-bit digit (bits 8k .. 8k+7) in which key_bits has any bit
+ * set, and that pass sorts by the WHOLE digit, so the words end up ordered by key & (the 0xff bytes key_bits touches), equal ones in
+ * their input order; key_bits == 0 sorts nothing.  key[0] / value[0] hold the input, key[1] / value[1] are scratch of the same size;
+ * *sorted_in says which of the two holds the sorted words afterwards (the number of passes modulo 2).  Synchronises `stream`; the
+ * caller's current device is left as it was.  n < 2^31.  (lx_index_build sorts its word table with it;
  * the Level-2 driver sorts matches and survivors with the same kernels.) */
 int lx_sort_words_dev(int device, uint64_t * key[2], uint64_t * value[2], uint64_t n, uint64_t key_bits, void * stream, int * sorted_in);
 /* Ahead of a handle's first lx_iterate_matches_dev (or large lx_iterate_matches) call: allocates -- and, on the host side, touches -- the

@@ -257,6 +257,7 @@ def load():
     lib.lx_reserve.restype = i32
     lib.lx_reserve.argtypes = [vp, u64, u64, u64, u64]
     lib.lx_widen_and_preprocess_dev.argtypes = [vp, vp, u64, i32, vp, C.POINTER(u64)]
+    lib.lx_sort_words_dev.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), u64, u64, vp, C.POINTER(i32)]
     lib.lx_iterate_result_count.argtypes = [vp]
     lib.lx_iterate_result_count.restype = u64
     lib.lx_iterate_result_matches.argtypes = [vp]
@@ -896,6 +897,22 @@ def builtin_scoring(method: int, match: int = 2, mismatch: int = -3, gap_open: i
     if rc != LX_OK:
         raise LambdaExtError(rc, "lx_builtin_scoring")
     return sc
+
+
+def sort_words_dev(key0, key1, val0, val1, n: int, key_bits: int, device: int = 0, stream=None) -> int:
+    """lx_sort_words_dev: the library's radix sort of n (key, value) uint64 pairs in device memory.  key0 / val0 hold the input, key1 /
+    val1 are scratch of the same size: device pointers (integers, None for NULL) or objects with data_ptr().  key_bits is a bit mask:
+    every 8-bit digit it touches is sorted by in full.  Returns sorted_in, the index of the buffer pair that holds the result."""
+    def dptr(a):
+        return a.data_ptr() if hasattr(a, "data_ptr") else a
+
+    key = (C.c_void_p * 2)(dptr(key0), dptr(key1))
+    val = (C.c_void_p * 2)(dptr(val0), dptr(val1))
+    where = C.c_int(-1)
+    rc = load().lx_sort_words_dev(device, key, val, n, key_bits & 0xFFFFFFFFFFFFFFFF, stream, C.byref(where))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, "lx_sort_words_dev")
+    return int(where.value)
 
 
 def _sptr(a):

@@ -610,8 +610,8 @@ int lx_prefilter_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t 
 {
     if (!h)
         return LX_EINVAL;
-    if (slot < 0 || slot > 1 || !h->have_sc[slot])
-        return fail(h, LX_ESTATE, "scoring slot %d not set", slot);
+    if (slot < 0 || slot > 1 || !h->have_sc[slot]) // (every refusal of this call is LX_EINVAL, this one too: tests/test_gpu_prefilter.py)
+        return fail(h, LX_EINVAL, "scoring slot %d not set", slot);
     if (n == 0)
         return LX_OK;
     if (!seeds || !out_keep || !q_res)

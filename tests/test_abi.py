@@ -114,6 +114,38 @@ def test_widen_and_preprocess_large_lists_in_any_order(oracle):
             assert (got[f] == want[f]).all(), f
 
 
+def test_sort_words_argument_checks(lx_lib):
+    """lx_sort_words_dev's argument checks and its n < 2 exits come before any HIP call (lx_level2_host.cpp), so they hold without a
+    device -- and with host addresses for buffers, which are never dereferenced on these paths."""
+    host = np.zeros(4, np.uint64).ctypes.data
+    p4 = (host, host, host, host)
+
+    def code(*a, **kw):
+        try:
+            return capi.LX_OK, capi.sort_words_dev(*a, **kw)
+        except capi.LambdaExtError as e:
+            return e.code, None
+
+    assert code(None, None, None, None, 0, ~0) == (capi.LX_OK, 0)                 # n == 0: NULL buffers are fine
+    for k in range(4):                                                            # n == 1: each of the four buffers is checked
+        assert code(*[None if j == k else host for j in range(4)], 1, ~0) == (capi.LX_EINVAL, None), k
+    assert code(*p4, 1 << 31, ~0) == (capi.LX_EINVAL, None)                       # n < 2^31
+    assert code(*p4, (1 << 31) - 1, ~0, device=-1) == (capi.LX_EINVAL, None)
+    for device in (-1, 64):                                                       # 0 <= device < 64
+        assert code(*p4, 1, ~0, device=device) == (capi.LX_EINVAL, None), device
+    for bits in (~0, 0, 0x10):
+        assert code(*p4, 1, bits) == (capi.LX_OK, 0)                              # n == 1: sorted as it stands, in buffer 0
+    assert code(*p4, 1, ~0, device=63) == (capi.LX_OK, 0)                         # (the device is not touched either)
+    # a NULL sorted_in, and NULL key / value arrays
+    key, val = (C.c_void_p * 2)(host, host), (C.c_void_p * 2)(host, host)
+    where = C.c_int(-1)
+    assert lx_lib.lx_sort_words_dev(0, key, val, 1, ~0 & 0xFFFFFFFFFFFFFFFF, None, None) == capi.LX_EINVAL
+    assert lx_lib.lx_sort_words_dev(0, None, val, 1, 0xFF, None, C.byref(where)) == capi.LX_EINVAL
+    assert lx_lib.lx_sort_words_dev(0, key, None, 1, 0xFF, None, C.byref(where)) == capi.LX_EINVAL
+    assert where.value == -1                                                      # a refused call writes nothing
+    assert lx_lib.lx_sort_words_dev(0, key, val, 1, 0xFF, None, C.byref(where)) == capi.LX_OK and where.value == 0
+
+
 def test_rank_bridge():
     """lx_convert_ranks = seqan2_to_rank_inner (src/seqan2_to_biocpp.hpp:352-395): aa27 moves X behind Z, bisulfite
     dna5 moves N behind T, match/mismatch alphabets pass through; out-of-alphabet ranks are an error."""

@@ -11,8 +11,8 @@ import pytest
 
 from lambda_amd import build, capi
 from tests import bam_decode
-from tests.test_taxonomy import (join_error_cases, model_join, model_lca, model_tree, run_join, same_join, synthetic, taxdump,
-                                 world)
+from tests.test_taxonomy import (edge_join_cases, edge_join_error_cases, fit_chunk, join_error_cases, model_join, model_lca, model_tree,
+                                 run_join, same_join, synthetic, taxdump, world)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,6 +46,29 @@ def test_device_join_errors(handle):
             assert str(ed.value) == str(eh.value), name
     text = b"accession\taccession.version\ttaxid\tgi\nQ00001\tx\tnope\t1\nXP_77\tX\t4294967295\t2\nP12345\tP\t007\t3\n"
     same_join(run_join(ids, capi.LX_TAXMAP_NCBI, text, chunk=32, piece=7, handle=handle), model_join(ids, capi.LX_TAXMAP_NCBI, text))
+
+
+@pytest.mark.parametrize("case", range(12))
+def test_device_join_edge_texts(handle, case):
+    """tests/test_taxonomy.py's texts around join_parse_kernel's bounds: as one chunk (chunk_bytes = 0, so the text's tiles are the
+    chunk's) and in chunks of 8192 bytes, against the host join, which the CPU tests hold against the model."""
+    name, fmt, ids, text = edge_join_cases()[case]
+    host = run_join(ids, fmt, text, chunk=0)
+    same_join(host, model_join(ids, fmt, text))
+    same_join(run_join(ids, fmt, text, chunk=0, handle=handle), host)  # (a tile that overflows is an error here: counters->overflow)
+    assert handle.last_phase_ms(6)[1] >= 1
+    chunk = fit_chunk(8192, text)
+    same_join(run_join(ids, fmt, text, chunk=chunk, piece=4096, handle=handle), host)
+
+
+def test_device_join_first_bad_taxon_in_line_order(handle):
+    for name, fmt, ids, text in edge_join_error_cases():
+        for chunk, piece in ((0, None), (8192, 4096)):
+            with pytest.raises(capi.LambdaExtError) as eh:
+                run_join(ids, fmt, text, chunk=chunk, piece=piece)
+            with pytest.raises(capi.LambdaExtError) as ed:
+                run_join(ids, fmt, text, chunk=chunk, piece=piece, handle=handle)
+            assert "first-bad" in str(eh.value) and str(ed.value) == str(eh.value), (name, str(ed.value), str(eh.value))
 
 
 def big_map(n_lines, n_subjects, seed):

@@ -257,10 +257,34 @@ def test_seed_looks_promising(oracle):
     # same coordinates on a random diagonal
     assert not oracle.seed_looks_promising(q, s, 40, 50, 100, 10, 2, 2.0, sc)
     # seed at the very start: the region is shifted, not truncated below zero (search_algo.hpp:440-452)
-    assert oracle.seed_looks_promising(q, s, 30, 40, 200, 10, 2, 2.0, sc) in (True, False)
+    from tests import prefilter_cases
+
+    mat = SCHEMES["blosum62"].matrix_np()
+    assert oracle.seed_looks_promising(q, s, 30, 40, 200, 10, 2, 2.0, sc) == prefilter_cases.model(q, s, 30, 40, 200, 10, 2, 2.0, mat)
     s2 = s.copy()
     s2[0:40] = q[0:40]
     assert oracle.seed_looks_promising(q, s2, 0, 10, 0, 10, 2, 2.0, sc)
+    # the same three, and seeds within 5 of either start (both begins shift, the region shrinks), against the independent model
+    for qs, ss in ((40, 210), (40, 100), (30, 200), (0, 0), (2, 0), (0, 4), (3, 203), (110, 390)):
+        for s_ in (s, s2):
+            assert oracle.seed_looks_promising(q, s_, qs, qs + 10, ss, 10, 2, 2.0, sc) == prefilter_cases.model(q, s_, qs, qs + 10, ss, 10, 2, 2.0, mat), (qs, ss)
+
+
+def test_seed_looks_promising_equals_the_model_on_the_case_table(oracle):
+    """The oracle's lxo_seed_looks_promising is the same code as the kernel; tests/prefilter_cases.py restates the reference
+    independently.  Every case of the table, every group with both answers, and the hand-derived answers where the table has them."""
+    from tests import prefilter_cases as pc
+
+    cs = pc.cases()
+    seen = {}
+    for c in cs:
+        want = pc.expected(c)
+        assert c.expect is None or want == c.expect, (c.group, c.name)
+        got = oracle.seed_looks_promising(c.q, c.s, c.qry_start, c.qry_end, c.subj_start, c.seed_length, c.pre_scoring, c.thresh,
+                                          oracle_lib.scoring_from(SCHEMES[c.scheme]))
+        assert got == want, (c.group, c.name)
+        seen.setdefault(c.group, set()).add(want)
+    assert len(seen) == 8 and all(v == {True, False} for v in seen.values()), seen
 
 
 def test_blast_statistics(oracle):

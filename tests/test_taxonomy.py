@@ -275,6 +275,194 @@ def test_host_join_errors():
     assert got["s_tax_ids"].tolist() == [4294967295, 7] and got["s_tax_off"].tolist() == [0, 0, 1, 2]
 
 
+# ---- texts built around the device join's structural bounds (join_parse_kernel, lx_taxmap.hip) ---------------------------------------
+# The kernel sees a chunk of whole lines -- for the NCBI form, what follows the header line -- in tiles of JOIN_TILE bytes, 16 bytes per
+# lane; with chunk_bytes = 0 the whole text is one chunk, so an offset below is an offset in that chunk.
+JOIN_TILE = 4096            # kJoinTile
+JOIN_TILE_CAP = 512         # kJoinTileCap = kJoinTile / 8
+EDGE_IDS = ["ref|NC_1| the shortest accession", "sp|P12345|B_X", "ref|XP_77.1| C", "sp|P12345|D later"]
+
+
+class _Chunk:
+    """the lines of one chunk, with the offset the next line starts at"""
+
+    def __init__(self, fmt, seed):
+        self.fmt, self.rng, self.parts, self.pos = fmt, np.random.default_rng(seed), [], 0
+
+    def add(self, line: bytes):
+        self.parts.append(line)
+        self.pos += len(line)
+
+    def match(self, acc: str, tax, tail: str = "77"):
+        """a line whose accession is in the table"""
+        self.add((f"{acc}\t{acc}.1\t{tax}\t{tail}\n" if self.fmt == capi.LX_TAXMAP_NCBI else f"{acc}\tNCBI_TaxID\t{tax}\n").encode())
+
+    def ordinary(self):
+        """a line as the other texts have them: 20 to 38 bytes, most of them matching"""
+        k = int(self.rng.integers(0, 1000))
+        acc = ("P12345", "XP_77", "NC_1")[k % 3] if k % 10 < 7 else f"QQQ{k:05d}"
+        if self.fmt == capi.LX_TAXMAP_UNIPROT and k % 4 == 0:
+            self.add(f"{acc}\tGeneID\t{k}\n".encode())
+        else:
+            self.match(acc, 100 + k, tail=str(k))
+
+    def pad_to(self, target: int):
+        """ordinary lines, then one line that matches nothing and ends just before `target`"""
+        assert target >= self.pos
+        while target - self.pos > 120:
+            self.ordinary()
+        gap = target - self.pos
+        if gap:
+            self.add(b"Z" * (gap - 1) + b"\n")
+        assert self.pos == target
+
+    def text(self, final_newline=True) -> bytes:
+        body = b"".join(self.parts)
+        if not final_newline:
+            assert body.endswith(b"\n")
+            body = body[:-1]
+        return (NCBI_HEADER + b"\n" if self.fmt == capi.LX_TAXMAP_NCBI else b"") + body
+
+
+def edge_join_cases():
+    """(name, fmt, ids, text) texts whose join succeeds"""
+    out = []
+    N, U = capi.LX_TAXMAP_NCBI, capi.LX_TAXMAP_UNIPROT
+    # densest tile: "NC_1\t\t1\n" is the shortest line that yields a pair (8 bytes: kJoinTileCap's bound).  From offset 0 every tile
+    # holds 512 of them, two per lane (`a` and `b`, cnt == 2 without the overflow flag; excl + 1 == 511 in the last lane)
+    c = _Chunk(N, 1)
+    for i in range(3000):
+        c.add(f"NC_1\t\t{1 + i % 9}\n".encode())
+    assert c.pos == 3000 * 8 and c.pos > 5 * JOIN_TILE
+    out.append(("densest tile: 512 pairs, two per lane", N, EDGE_IDS, c.text()))
+    # the same shifted by 1 .. 7 bytes (an empty line before each run of 700): the lane's two line starts sit at s and s + 8 of its 16
+    # bytes; the tile an empty line falls in has room for 511 or 512 lines, and three lines name an accession that is not in
+    # the table (their lanes have cnt == 1), so tiles hold 511 or 512 pairs
+    c = _Chunk(N, 2)
+    for shift in range(1, 8):
+        c.add(b"\n")
+        assert c.pos % 8 == shift
+        for i in range(700):
+            c.add(f"NC_{2 if (shift, i) in ((2, 300), (4, 350), (7, 600)) else 1}\t\t{1 + (i + shift) % 9}\n".encode())
+    out.append(("densest tile shifted by 1 .. 7 bytes: 511 or 512 pairs", N, EDGE_IDS, c.text()))
+    # a matching line that starts d bytes before a tile's edge, d = 0 .. 24.  d = 0 is a line start on a tile's first byte (`prev` is
+    # text[t0 - 1]); the others split field 0, "NCBI_TaxID" or the taxon's digits across the tiles (get()'s `q < n ? text[q]` path)
+    for fmt in (N, U):
+        c = _Chunk(fmt, 3 + fmt)
+        for d in range(25):
+            c.pad_to(JOIN_TILE * (d + 1) - d)
+            c.match("XP_77" if fmt == N else "P12345", 10000 + d)
+            c.match("NC_1", 20000 + d)
+        c.ordinary()
+        out.append((f"a line start 0 .. 24 bytes before a tile's edge, format {fmt}", fmt, EDGE_IDS, c.text()))
+    # long lines: field 0 of 9999 bytes (beyond max_len: lookup() refuses it by its length) and a matching line whose fourth field is
+    # 9000 bytes, so that at least one whole tile has no line start (lines == 0, cnt == 0 in all of its lanes, tile_cnt == 0 in the scan)
+    for fmt in (N, U):
+        c = _Chunk(fmt, 5 + fmt)
+        c.pad_to(1000)
+        c.match("P12345", 31)
+        c.add(b"A" * 9999 + b"\n")
+        c.match("XP_77", 32)
+        c.ordinary()
+        c.match("NC_1", 33)
+        c.add((b"NC_1\tNC_1.1\t34\t" if fmt == N else b"NC_1\tNCBI_TaxID\t34\t") + b"9" * 9000 + b"\n")
+        c.match("P12345", 35)
+        c.ordinary()
+        out.append((f"lines of 10 000 and 9 000 bytes, format {fmt}", fmt, EDGE_IDS, c.text()))
+    # empty lines: 100 '\n' in a row are 100 lines, 16 line starts in a lane and no pair
+    for fmt in (N, U):
+        c = _Chunk(fmt, 7 + fmt)
+        c.pad_to(JOIN_TILE - 40)
+        c.match("XP_77", 41)
+        for _ in range(100):
+            c.add(b"\n")
+        c.match("P12345", 42)
+        c.ordinary()
+        out.append((f"a run of 100 empty lines, format {fmt}", fmt, EDGE_IDS, c.text()))
+    # no final newline at a tile's end: the chunk is 4096 k or 4096 k + 1 bytes before lx_taxmap_finish appends the '\n', and the last
+    # line matches (tn == 1 in the last tile: the staging loop for a partial tile)
+    for fmt in (N, U):
+        for extra in (0, 1):
+            c = _Chunk(fmt, 9 + fmt)
+            last = (b"XP_77\tXP_77.1\t51\t1\n" if fmt == N else b"XP_77\tNCBI_TaxID\t51\n")
+            c.pad_to(2 * JOIN_TILE + extra - (len(last) - 1))
+            c.add(last)
+            t = c.text(final_newline=False)
+            assert c.pos - 1 == 2 * JOIN_TILE + extra and not t.endswith(b"\n")
+            out.append((f"no final newline, {2 * JOIN_TILE + extra} bytes, format {fmt}", fmt, EDGE_IDS, t))
+    return out
+
+
+def edge_join_error_cases():
+    """(name, fmt, ids, text): two matched lines whose taxa do not parse, in tiles 1 and 3 of the one chunk; the error names the one in
+    tile 1, whichever workgroup runs first (atomicMin on bad_off) and whichever host thread's part it falls in"""
+    out = []
+    for fmt in (capi.LX_TAXMAP_NCBI, capi.LX_TAXMAP_UNIPROT):
+        c = _Chunk(fmt, 11 + fmt)
+        c.pad_to(JOIN_TILE + 100)
+        c.match("XP_77", "first-bad")
+        c.pad_to(3 * JOIN_TILE + 100)
+        c.match("P12345", "second-bad")
+        c.ordinary()
+        out.append((f"bad taxa in tiles 1 and 3, format {fmt}", fmt, EDGE_IDS, c.text()))
+    return out
+
+
+def fit_chunk(chunk: int, text: bytes) -> int:
+    """chunk_bytes for a text: a line longer than the chunk is refused by design, so the chunk is doubled until the longest line fits"""
+    longest = max(len(l) for l in text.split(b"\n")) + 1
+    while 0 < chunk < longest:
+        chunk *= 2
+    return chunk
+
+
+@pytest.mark.parametrize("case", range(12))
+def test_host_join_edge_texts_match_model(case):
+    name, fmt, ids, text = edge_join_cases()[case]
+    want = model_join(ids, fmt, text)
+    assert want["matched"] >= 2, name
+    if name.startswith("densest tile:"):
+        assert want["matched"] == 3000 and want["s_tax_ids"].tolist() == [1 + i % 9 for i in range(3000)]
+    for chunk in (0, 4096, 1024):
+        for piece in (None, 37, 4096):
+            same_join(run_join(ids, fmt, text, chunk=fit_chunk(chunk, text), piece=piece), want)
+
+
+def test_edge_join_cases_are_what_they_claim():
+    cases = edge_join_cases()
+    assert len(cases) == 12
+    for name, fmt, ids, text in cases:
+        body = text[len(NCBI_HEADER) + 1:] if fmt == capi.LX_TAXMAP_NCBI else text
+        nl = np.nonzero(np.frombuffer(body, np.uint8) == 10)[0]
+        starts = [0] + [int(i) + 1 for i in nl if i + 1 < len(body)]
+        acc = (b"NC_1\t", b"P12345\t", b"XP_77\t")
+        per_tile = np.bincount([p // JOIN_TILE for p in starts if body.startswith(acc, p) and b"GeneID" not in body[p:p + 16]])
+        if name.startswith("densest tile:"):
+            assert (per_tile[:5] == JOIN_TILE_CAP).all()
+        elif name.startswith("densest tile shifted"):
+            assert set(per_tile[:-1].tolist()) == {JOIN_TILE_CAP - 1, JOIN_TILE_CAP} and {p % 8 for p in starts} == set(range(8))
+        elif name.startswith("a line start"):
+            assert all(JOIN_TILE * (d + 1) - d in starts for d in range(25))
+        elif name.startswith("lines of"):
+            tiles_with_start = {p // JOIN_TILE for p in starts}
+            assert len(set(range(len(body) // JOIN_TILE)) - tiles_with_start) >= 2
+        elif name.startswith("a run of 100"):
+            assert b"\n" * 101 in body
+        else:
+            assert len(body) in (2 * JOIN_TILE, 2 * JOIN_TILE + 1) and not body.endswith(b"\n")
+
+
+def test_host_join_first_bad_taxon_in_line_order():
+    for name, fmt, ids, text in edge_join_error_cases():
+        with pytest.raises(ModelError) as me:
+            model_join(ids, fmt, text)
+        assert "first-bad" in str(me.value)
+        for chunk, piece in ((0, None), (4096, 37), (1024, 4096)):
+            with pytest.raises(capi.LambdaExtError) as e:
+                run_join(ids, fmt, text, chunk=chunk, piece=piece)
+            assert e.value.code == capi.LX_EINVAL and str(me.value) in str(e.value), (name, str(e.value), str(me.value))
+
+
 def test_tree_matches_model():
     nodes, names = taxdump()
     for present in ([5, 6], [9, 12, 5], [3, 9], [11], [5, 30], [12, 10, 8]):
