@@ -178,7 +178,9 @@ enum
                                       72 bytes of device memory per word at once); N >= 1 = the build in slices of the key space of at most
                                       N words each (lx_index_plan_slices), for sets of fewer than 2^32 - 1 words: 16 bytes per word for the
                                       entries and 32 per word of the largest slice.  The same table entry for entry either way */
-    LX_OPT_BAND            = 9  /* band mode -- NOT the reference's configuration (src/search_algo.hpp:1081 runs BandOff, :1102
+    LX_OPT_LCA_RANGE_ROWS  = 19, /* lx_compute_lca_dev: rows per range of whole queries, i.e. what stands on the device at once (0 = default,
+                                    2^24; a query with more rows is a range of its own).  It changes where the cuts fall, never a result */
+    LX_OPT_BAND            = 9 /* band mode -- NOT the reference's configuration (src/search_algo.hpp:1081 runs BandOff, :1102
                                    says why; _bandSize only pads the window, src/search_misc.hpp:46-50) and therefore not a
                                    parity mode: 0 (default) = full rectangle; b > 0 = only cells whose diagonal i - j (row i of
                                    the subject slice, column j of the query slice, 0-based) lies within b of the extension's
@@ -593,6 +595,49 @@ typedef struct lx_tax_tree
  * (the reference throws "LCA-computation error"). */
 int lx_compute_lca(lx_blast_match const * m, uint64_t n, lx_tax_tree const * tree, uint64_t * out_qid, uint32_t * out_lca,
                    uint64_t * out_n);
+/* Which records of a query enter its LCA.  top_percent = 100 is the reference's rule (src/search_algo.hpp:884-907: every record of
+ * the query); below 100 only the records whose bit score lies within top_percent percent of the query's best one (what MEGAN calls
+ * "top percent" and DIAMOND --top): with best = the largest bit_score of the query and f = 1.0 - top_percent / 100.0 (computed once,
+ * in double), a record is kept iff bit_score >= best * f || bit_score == best.  0 keeps the best records only. */
+typedef struct lx_lca_options
+{
+    double   top_percent; /* 0 .. 100; 100 = the reference's rule */
+    uint64_t reserved;
+} lx_lca_options;
+void lx_lca_options_default(lx_lca_options * o); /* top_percent = 100 */
+/* lx_compute_lca (src/search_algo.hpp:884-907, computeLCA: src/search_misc.hpp:86-112) over the records lx_lca_options keeps: a
+ * query is a maximal run of equal n_qid; the fold starts from the first KEPT record whose subject has a first taxon with a parent and
+ * takes in every assigned taxon of every KEPT record, in list order; one pair per query as there (0 = nothing started the fold).
+ * opt == NULL or top_percent == 100: exactly lx_compute_lca, for every input (bit scores are not looked at).  LX_EINVAL for what
+ * lx_compute_lca refuses, for a top_percent outside [0, 100] or not a number, and below 100 for a bit_score that is not finite.
+ * This function is the specification of lx_compute_lca_dev. */
+int lx_compute_lca_ex(lx_blast_match const * m, uint64_t n, lx_tax_tree const * tree, lx_lca_options const * opt, uint64_t * out_qid,
+                      uint32_t * out_lca, uint64_t * out_n);
+/* Whether `tree` is one on which every climb of computeLCA (src/search_misc.hpp:86-112) ends, as the trees of lx_taxonomy_build are
+ * (their heights are counted from the final parents): the pointers lx_compute_lca needs are there; s_tax_off starts at 0 and
+ * ascends; every s_tax_ids[x] < n_taxa; for every t < n_taxa parents[t] < n_taxa, parents[t] > 1 implies heights[t] ==
+ * heights[parents[t]] + 1, and parents[t] <= 1 implies heights[t] == 0.  A climb then ends after at most max height + 2 steps.
+ * Trees with two roots or with disconnected taxa pass (a query that mixes them is the fold's LX_EINVAL, src/search_algo.hpp:884-907).
+ * No device is touched.  LX_OK, or LX_EINVAL with the broken rule in lx_last_output_error(). */
+int lx_check_tax_tree(lx_tax_tree const * tree);
+
+/* The LCA step (src/search_algo.hpp:884-907, src/search_misc.hpp:86-112) on h's device.  lx_tax_dev is a tree resident there:
+ * lx_tax_dev_create runs lx_check_tax_tree (a failure is LX_EINVAL before any device work, the text in lx_last_error(h)) and uploads
+ * parents and heights side by side, the subjects' taxon lists and the largest height; destroy it before its handle.
+ * lx_compute_lca_dev gives what lx_compute_lca_ex gives for n rows in HOST memory: the same pairs in the same order, the same count.
+ * Only n_qid, n_sid (as 32 bits) and, below top_percent 100, bit_score go up, through pinned staging, in ranges of whole queries of
+ * at most LX_OPT_LCA_RANGE_ROWS rows (a longer query is a range of its own); a range's upload overlaps the kernels of the range
+ * before it.  One lane folds one query, its rows in list order; every loop of the kernel ends after max height + 2 steps.  One
+ * uint32 per query and one error word per range come down: an error word that is set (two taxa of a query without a common ancestor)
+ * makes the call LX_EINVAL with the reference's text, "LCA-computation error: One of the paths didn't lead to root.", and nothing of
+ * the out arrays is then promised.  LX_EINVAL with a text, before any device work: NULL arguments, a handle that is not the tree's,
+ * n >= 2^31 - 16, a row with n_sid >= n_s, the option errors of lx_compute_lca_ex.  lx_last_phase_ms(h, 13, ...) = device time of
+ * the kernels in the call. */
+typedef struct lx_tax_dev lx_tax_dev;
+int  lx_tax_dev_create(lx_handle * h, lx_tax_tree const * tree, lx_tax_dev ** out);
+void lx_tax_dev_destroy(lx_tax_dev * t);
+int  lx_compute_lca_dev(lx_handle * h, lx_tax_dev const * t, lx_blast_match const * m, uint64_t n, lx_lca_options const * opt,
+                        uint64_t * out_qid, uint32_t * out_lca, uint64_t * out_n);
 
 /* What the writers need to know about the sequences (the reference reads these from lH.qryIds / indexFile.ids). */
 typedef struct lx_seq_names
@@ -1064,7 +1109,7 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * 8 = the word table's kernels (lx_index_build on a handle; in slices: launches = the number of slices), 9 = the seeding kernel (lx_seed_queries on a handle),
  * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
  * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,
- * numbers, measure, scans, emit). */
+ * numbers, measure, scans, emit), 13 = the LCA kernels (lx_compute_lca_dev: query heads, fold; launches = the number of ranges). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

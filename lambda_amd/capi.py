@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "lx_index_build", "lx_index_plan_slices", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
     "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_close",
+    "lx_lca_options_default", "lx_compute_lca_ex", "lx_check_tax_tree", "lx_tax_dev_create", "lx_tax_dev_destroy", "lx_compute_lca_dev",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -54,6 +55,7 @@ LX_OPT_GUNZIP_CHUNK = 15
 LX_OPT_GUNZIP_PARALLEL_FROM = 16
 LX_OPT_BAM_RANGE_BYTES = 17
 LX_OPT_INDEX_SLICE_WORDS = 18  # lx_index_build on a handle: 0 = one sort, N >= 1 = in slices of at most N words
+LX_OPT_LCA_RANGE_ROWS = 19  # lx_compute_lca_dev: rows per range of whole queries (0 = default, 2^24)
 OPT_GUNZIP_WAVE_TEST = 1017  # not part of the ABI (lx_internal.h): chunks per wave, for the tests of lx_gunzip's waves
 LX_GUNZIP_NEVER = (1 << 64) - 1  # LX_OPT_GUNZIP_PARALLEL_FROM: no plain member takes the device path
 
@@ -99,6 +101,11 @@ class GunzipStats(C.Structure):
 class TaxTree(C.Structure):
     _fields_ = [("parents", C.c_void_p), ("heights", C.c_void_p), ("n_taxa", C.c_uint64), ("s_tax_off", C.c_void_p),
                 ("s_tax_ids", C.c_void_p), ("n_s", C.c_uint64)]
+
+
+class LcaOptions(C.Structure):
+    """lx_lca_options: top_percent 100 = the reference's rule, below it only the records within that share of the query's best bit score."""
+    _fields_ = [("top_percent", C.c_double), ("reserved", C.c_uint64)]
 
 
 class TaxmapResult(C.Structure):
@@ -279,6 +286,14 @@ def load():
     lib.lx_output_options_default.restype = None
     lib.lx_last_output_error.restype = C.c_char_p
     lib.lx_compute_lca.argtypes = [vp, u64, C.POINTER(TaxTree), vp, vp, C.POINTER(u64)]
+    lib.lx_lca_options_default.argtypes = [C.POINTER(LcaOptions)]
+    lib.lx_lca_options_default.restype = None
+    lib.lx_compute_lca_ex.argtypes = [vp, u64, C.POINTER(TaxTree), C.POINTER(LcaOptions), vp, vp, C.POINTER(u64)]
+    lib.lx_check_tax_tree.argtypes = [C.POINTER(TaxTree)]
+    lib.lx_tax_dev_create.argtypes = [vp, C.POINTER(TaxTree), C.POINTER(vp)]
+    lib.lx_tax_dev_destroy.argtypes = [vp]
+    lib.lx_tax_dev_destroy.restype = None
+    lib.lx_compute_lca_dev.argtypes = [vp, vp, vp, u64, C.POINTER(LcaOptions), vp, vp, C.POINTER(u64)]
     lib.lx_render_records.argtypes = [i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions), C.c_int64, C.POINTER(vp)]
     lib.lx_bytes_data.argtypes = [vp]
     lib.lx_bytes_data.restype = vp
@@ -356,6 +371,73 @@ def compute_lca(bms: np.ndarray, parents, heights, s_tax_off, s_tax_ids):
     if rc != 0:
         raise LambdaExtError(rc, "lx_compute_lca: ids outside the taxonomy, or a path that does not lead to the root")
     return qid[: cnt.value].copy(), lca[: cnt.value].copy()
+
+
+def _tax_tree(parents, heights, s_tax_off, s_tax_ids):
+    """An lx_tax_tree over the four arrays (returned too: they must outlive the calls that read the tree)."""
+    par = np.ascontiguousarray(parents, dtype=np.uint32)
+    hgt = np.ascontiguousarray(heights, dtype=np.uint32)
+    off = np.ascontiguousarray(s_tax_off, dtype=np.uint64)
+    ids = np.ascontiguousarray(s_tax_ids, dtype=np.uint32)
+    tree = TaxTree(par.ctypes.data if len(par) else None, hgt.ctypes.data if len(hgt) else None, len(par), off.ctypes.data,
+                   ids.ctypes.data if len(ids) else None, len(off) - 1)
+    return tree, (par, hgt, off, ids)
+
+
+def lca_options(top_percent: float = 100.0) -> LcaOptions:
+    o = LcaOptions()
+    load().lx_lca_options_default(C.byref(o))
+    o.top_percent = top_percent
+    return o
+
+
+def compute_lca_ex(bms: np.ndarray, parents, heights, s_tax_off, s_tax_ids, top_percent: float = 100.0):
+    """lx_compute_lca_ex: compute_lca over the records whose bit score lies within top_percent percent of their query's best
+    (100 = all of them, the reference's rule): (n_qid, lcaTaxId) arrays."""
+    m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE)
+    tree, keep = _tax_tree(parents, heights, s_tax_off, s_tax_ids)
+    qid = np.zeros(max(len(m), 1), dtype=np.uint64)
+    lca = np.zeros(max(len(m), 1), dtype=np.uint32)
+    cnt = C.c_uint64(0)
+    opt = lca_options(top_percent)
+    rc = load().lx_compute_lca_ex(_ptr(m) if len(m) else None, len(m), C.byref(tree), C.byref(opt), _ptr(qid), _ptr(lca), C.byref(cnt))
+    if rc != 0:
+        raise LambdaExtError(rc, "lx_compute_lca_ex: " + (last_output_error() or "ids outside the taxonomy, or a path that does not lead to the root"))
+    return qid[: cnt.value].copy(), lca[: cnt.value].copy()
+
+
+def check_tax_tree(parents, heights, s_tax_off, s_tax_ids):
+    """lx_check_tax_tree: raises LambdaExtError with the broken rule unless every climb on the tree ends."""
+    tree, keep = _tax_tree(parents, heights, s_tax_off, s_tax_ids)
+    rc = load().lx_check_tax_tree(C.byref(tree))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, last_output_error())
+
+
+class TaxDev:
+    """lx_tax_dev: a taxonomic tree resident on a handle's device (checked by lx_check_tax_tree first).  Close it before its handle."""
+
+    def __init__(self, handle: "Handle", parents, heights, s_tax_off, s_tax_ids):
+        self.lib = load()
+        self.handle = handle
+        tree, keep = _tax_tree(parents, heights, s_tax_off, s_tax_ids)
+        t = C.c_void_p()
+        handle._check(self.lib.lx_tax_dev_create(handle.h, C.byref(tree), C.byref(t)))
+        self.t = t
+
+    def close(self):
+        if getattr(self, "t", None):
+            self.lib.lx_tax_dev_destroy(self.t)
+            self.t = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 def postprocess_records(bms: np.ndarray, max_matches: int = 25):
@@ -1263,6 +1345,17 @@ class Handle:
 
     def last_trace_kernel_name(self) -> str:
         return self.lib.lx_last_trace_kernel_name(self.h).decode()
+
+    def compute_lca_dev(self, tax_dev: "TaxDev", bms: np.ndarray, top_percent: float = 100.0):
+        """lx_compute_lca_dev: compute_lca_ex with the fold as kernels on this handle's device, over `tax_dev`'s resident tree."""
+        m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE)
+        qid = np.zeros(max(len(m), 1), dtype=np.uint64)
+        lca = np.zeros(max(len(m), 1), dtype=np.uint32)
+        cnt = C.c_uint64(0)
+        opt = lca_options(top_percent)
+        self._check(self.lib.lx_compute_lca_dev(self.h, tax_dev.t if tax_dev is not None else None, _ptr(m) if len(m) else None, len(m),
+                                                C.byref(opt), _ptr(qid), _ptr(lca), C.byref(cnt)))
+        return qid[: cnt.value].copy(), lca[: cnt.value].copy()
 
     def last_phase_ms(self, phase: int):
         ms, cnt = C.c_float(), C.c_int()

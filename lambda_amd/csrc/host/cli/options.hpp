@@ -38,6 +38,9 @@ struct Options
                                       // the device declines are finished on the host threads inside the call --, or on the -t threads)
     std::string render      = "auto"; // --render gpu | host | auto: where the records of the output are made (the header comment)
     std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
+    std::string lca         = "auto"; // --lca gpu | host | auto: where the LCA per query is folded (the header comment)
+    double      lcaTopPercent = 100;  // --lca-top-percent P: only the records within P percent of a query's best bit score enter its LCA (100: all)
+    bool        lcaTopGiven = false;
     int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     bool        lazyQuery   = false; // --lazy-query 1: the query file block by block (the header comment)
     uint64_t    queryBlock  = 0;     // --query-block N: at most N reads per block; given and > 0, it implies --lazy-query 1
@@ -76,7 +79,8 @@ Options parse(int argc, char ** argv)
     Options o;
     if (argc < 2)
         throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.{fa,fq,fasta,fastq,fna,faa}[.gz] (-i DB.lba | -d DB.fasta[.gz]) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
-                                 "[--devices 0,1,...] [-t THREADS]\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
+                                 "[--devices 0,1,...] [-t THREADS]\n                 [--lca-top-percent P] [--lca gpu|host|auto]   the LCA per query (lcataxid, lt, ls) over the records within P percent of the query's best\n"
+                                 "                 bit score (0 .. 100, default 100: all records, the reference's rule), folded on the GPU or on the host (auto: the GPU)\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
                                  "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
@@ -108,7 +112,7 @@ Options parse(int argc, char ** argv)
     };
     auto inRange = [](std::string const & name, double v, double lo, double hi)
     {
-        if (v < lo || v > hi)
+        if (!(v >= lo && v <= hi)) // (not a number is outside, too)
             throw std::runtime_error("Value " + std::to_string(v) + " of option " + name + " is not in range [" + std::to_string(lo) + "," + std::to_string(hi) + "].");
     };
     auto oneOf = [](std::string const & v, std::initializer_list<char const *> allowed, char const * message) // v, if it is one of them
@@ -246,6 +250,14 @@ Options parse(int argc, char ** argv)
         }
         else if (a == "--records")
             o.records = oneOf(val(), {"gpu", "host", "auto"}, "--records takes gpu, host or auto");
+        else if (a == "--lca")
+            o.lca = oneOf(val(), {"gpu", "host", "auto"}, "--lca takes gpu, host or auto");
+        else if (a == "--lca-top-percent")
+        {
+            o.lcaTopPercent = std::stod(val());
+            inRange(a, o.lcaTopPercent, 0, 100);
+            o.lcaTopGiven = true;
+        }
         else if (a == "--render")
             o.render = oneOf(val(), {"gpu", "host", "auto"}, "--render takes gpu, host or auto");
         else if (a == "--seeding")

@@ -3,7 +3,16 @@
 //
 //   lambda3 searchp -q queries.fasta -d db.fasta -o out.m8 [-e 1e-2] [-n 25] [--seed-length 10] [--seed-offset 5]
 //                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--table-slice WORDS] [--seeding gpu|host] [--records gpu|host|auto]
-//                   [--render gpu|host|auto]
+//                   [--render gpu|host|auto] [--lca-top-percent P] [--lca gpu|host|auto]
+//
+// --lca-top-percent P (0 .. 100, default 100): which records of a query enter its LCA (lcataxid, lt, ls).  100 is the reference's
+// rule, every record (src/search_algo.hpp:884-907); below it only the records whose bit score lies within P percent of the query's
+// best one (MEGAN's "top percent", DIAMOND's --top), 0 the best ones alone: lx_compute_lca_ex has the rule.  --lca: where the fold
+// runs.  host: lx_compute_lca_ex on the thread that has the records.  gpu: lx_compute_lca_dev -- the tree resident on the device, one
+// lane per query -- on a handle on the first device (the eager path) or on the handle of the worker that searched the block
+// (--lazy-query; one resident tree per worker, made at its first block).  The output is byte-identical either way.  auto = gpu:
+// DESIGN.md (4.12.1, "The LCA on the device") has the measurement and the rule.  Where --lca gpu or --lca-top-percent was given, a
+// line of its own on stderr names the rule, the place and the time.
 //
 // --render: where the records of the output are made, for every format.  host: the host writer (lx_write_records_ex for a plain
 // text file; lx_render_records, the stream uploaded and compressed by lx_bgzf_compress, for .bam and *.gz: what this front end always
@@ -20,7 +29,7 @@
 // appends their matches to its device list) keeps
 // the host step, applied to that pass's records alone; the statistics of the parts are summed; -n 0 keeps the host step (the second
 // pass searches the queries WITHOUT records).  auto: see DESIGN.md ("_writeRecord on the device") for the measurement behind it.
-// LCA and the writers stay on the host, fed with the kept records; the output is byte-identical either way.
+// The LCA (--lca) and the writers (--render) are fed with the kept records; the output is byte-identical either way.
 //
 // --lazy-query 1 [--query-block N]: the query file block by block, in bounded memory -- the reference's batch loop with its reader
 // thread behind a bounded queue (src/search.cpp:389-459, src/search_algo.hpp:374-413).  One reader takes the file as a stream
@@ -514,6 +523,7 @@ struct Part
     lambda_amd::SeedingStats    sst{};
     size_t                      nPromising = 0;
     double                      msSeed = 0, msExtend = 0, msRecords = 0;
+    double                      msLca = 0; // (--lazy-query: the LCA of this worker's blocks)
     lx_record_stats             rst{}; // --records gpu: _writeRecord's statistics of this worker's passes
     bool                        gpuSeeding = false; // the seeding stage of this worker ran on its device
     size_t                      nDeclined = 0, nPassesOnHost = 0; // reads the GPU seeding stage left to the host; passes whose match buffer was full
@@ -600,6 +610,8 @@ public:
         // order by read, as one batch holding every read would give)
         std::stable_sort(job.bms->begin(), job.bms->end(), [](lx_blast_match const & a, lx_blast_match const & b) { return a.n_qid < b.n_qid; });
     }
+
+    lx_handle * handle() { return eng_.raw(); }
 
 private:
     // the job's queries for the Level-2 kernels, and room for its one call per seeding pass
@@ -726,18 +738,23 @@ private:
     lx_seed_params        spar_{};
 };
 
-// worker w's thread: its set-up, then the jobs nextJob hands it (false: no more), each reported to jobDone; an error ends it and
-// stays in its part
-template <class Next, class Done>
-void runWorker(size_t w, SearchContext const & c, Part & part, Next && nextJob, Done && jobDone)
+// worker w's thread: its set-up, then the jobs nextJob hands it (false: no more), each reported to jobDone with the worker's handle
+// (for what follows a search on the same device); an error ends it and stays in its part.  `leave` runs before the handle goes.
+template <class Next, class Done, class Leave>
+void runWorker(size_t w, SearchContext const & c, Part & part, Next && nextJob, Done && jobDone, Leave && leave)
 {
     try
     {
         Worker worker(w, c, part);
+        struct AtExit
+        {
+            Leave & f;
+            ~AtExit() { f(); }
+        } const atExit{leave};
         for (Job job; nextJob(job);)
         {
             worker.search(job);
-            jobDone(job);
+            jobDone(job, worker.handle());
         }
     }
     catch (std::exception const & e)
@@ -765,7 +782,7 @@ void runEager(SearchContext const & c, SeqSet const & qs, std::vector<uint8_t> c
                 job   = Job{&qs, &qRed, nReads * w / nWorkers, nReads * (w + 1) / nWorkers, &parts[w].bms, &parts[w].ops};
                 return job.rLo != job.rHi;
             },
-            [](Job &) {});
+            [](Job &, lx_handle *) {}, [] {});
     };
     {
         std::vector<std::thread> pool;
@@ -785,11 +802,16 @@ struct OutputSetup
     lx_tax_tree               tree{};
     std::vector<char const *> taxNames;
     bool                      lca = false; // the LCA per query is asked for and the index has the tree for it
+    bool                      lcaOnGpu = false; // --lca gpu | auto
+    lx_lca_options            lcaOptions;       // --lca-top-percent
     lx_output_options         options;
 
     OutputSetup(Options const & opt, Run const & run, IndexTaxonomy const & tax)
     {
-        lca = tax.has && run.wantLca && tax.hasTree;
+        lca      = tax.has && run.wantLca && tax.hasTree;
+        lcaOnGpu = opt.lca != "host"; // (auto = gpu: DESIGN.md 4.12.1, profiles/lca_bench.txt)
+        lx_lca_options_default(&lcaOptions);
+        lcaOptions.top_percent = opt.lcaTopPercent;
         if (tax.has)
         {
             tree.parents   = tax.parents.data();
@@ -823,12 +845,30 @@ struct OutputSetup
     OutputSetup(OutputSetup const &) = delete; // (`options` points into it)
 };
 
-// the LCA per query (the reference's _writeRecord, src/search_algo.hpp:884-908) over the n records of a list
-void computeLca(OutputSetup const & out, lx_blast_match const * bms, uint64_t n, std::vector<uint64_t> & lcaQid, std::vector<uint32_t> & lcaTax, uint64_t & nLca)
+using TaxDevOwner = std::unique_ptr<lx_tax_dev, FreeWith<lx_tax_dev_destroy>>;
+
+// the index's tree resident on h's device (--lca gpu); destroyed before h
+TaxDevOwner makeTaxDev(lx_handle * h, OutputSetup const & out)
+{
+    lx_tax_dev * t = nullptr;
+    if (lx_tax_dev_create(h, &out.tree, &t) != LX_OK)
+        throw std::runtime_error(std::string("the taxonomic tree on the GPU: ") + lx_last_error(h));
+    return TaxDevOwner(t);
+}
+
+// the LCA per query (the reference's _writeRecord, src/search_algo.hpp:884-908) over the n records of a list, of the records
+// --lca-top-percent keeps: on the host, or (--lca gpu: h and its resident tree) as kernels
+void computeLca(OutputSetup const & out, lx_handle * h, lx_tax_dev const * dev, lx_blast_match const * bms, uint64_t n, std::vector<uint64_t> & lcaQid,
+                std::vector<uint32_t> & lcaTax, uint64_t & nLca)
 {
     lcaQid.resize(std::max<uint64_t>(n, 1));
     lcaTax.resize(std::max<uint64_t>(n, 1));
-    if (lx_compute_lca(bms, n, &out.tree, lcaQid.data(), lcaTax.data(), &nLca) != LX_OK)
+    if (dev)
+    {
+        if (lx_compute_lca_dev(h, dev, bms, n, &out.lcaOptions, lcaQid.data(), lcaTax.data(), &nLca) != LX_OK)
+            throw std::runtime_error(lx_last_error(h)); // ("LCA-computation error: ..." where the fold failed)
+    }
+    else if (lx_compute_lca_ex(bms, n, &out.tree, &out.lcaOptions, lcaQid.data(), lcaTax.data(), &nLca) != LX_OK)
         throw std::runtime_error("LCA-computation error: One of the paths didn't lead to root.");
 }
 
@@ -837,6 +877,7 @@ struct RenderTimes
 {
     double msCompress  = 0; // (.bam, *.gz: BGZF on the first handle's device)
     double msRenderDev = 0; // (--render gpu: the render kernels' device time)
+    double msLca       = 0; // (the eager path: the LCA over all records, the resident tree's upload included)
     bool   onGpu       = false;
 };
 
@@ -1018,6 +1059,7 @@ void readBlocks(Run const & run, QueryStream & stream, BlockPipeline & pipe)
 void searchBlocks(size_t w, SearchContext const & c, OutputSetup const & out, BlockPipeline & pipe, Part & part)
 {
     std::unique_ptr<Block> current; // the block this worker searches
+    TaxDevOwner            taxDev;  // --lca gpu: the tree on this worker's handle, made at its first block
     runWorker(
         w, c, part,
         [&](Job & job)
@@ -1028,7 +1070,7 @@ void searchBlocks(size_t w, SearchContext const & c, OutputSetup const & out, Bl
             job = Job{&current->qs, &current->red, 0, current->qs.ids.size(), &current->bms, &current->ops};
             return true;
         },
-        [&](Job &)
+        [&](Job &, lx_handle * h)
         {
             std::unique_ptr<Block> b = std::move(current);
             b->found = b->kept = b->bms.size();
@@ -1039,9 +1081,16 @@ void searchBlocks(size_t w, SearchContext const & c, OutputSetup const & out, Bl
                 part.msRecords += msSince(tRec);
             }
             if (out.lca)
-                computeLca(out, b->bms.data(), b->kept, b->lcaQid, b->lcaTax, b->nLca);
+            {
+                auto const tLca = Clock::now();
+                if (out.lcaOnGpu && !taxDev)
+                    taxDev = makeTaxDev(h, out);
+                computeLca(out, h, taxDev.get(), b->bms.data(), b->kept, b->lcaQid, b->lcaTax, b->nLca);
+                part.msLca += msSince(tLca);
+            }
             pipe.finish(std::move(b));
-        });
+        },
+        [&] { taxDev.reset(); });
     if (!part.error.empty())
         pipe.fail(part.error, true);
 }
@@ -1155,6 +1204,7 @@ struct Totals : Part
         msSeed     = std::max(msSeed, pt.msSeed);
         msExtend   = std::max(msExtend, pt.msExtend);
         msRecords  = std::max(msRecords, pt.msRecords);
+        msLca      = std::max(msLca, pt.msLca);
         rst += pt.rst;
     }
 };
@@ -1246,17 +1296,21 @@ RenderTimes writeEager(Options const & opt, Run const & run, int device, OutputS
     lx_output_options     oo = output.options;
     std::vector<uint64_t> lcaQid;
     std::vector<uint32_t> lcaTax;
+    RenderTimes           times;
     if (output.lca)
     {
-        uint64_t nLca = 0;
-        computeLca(output, t.bms.data(), t.nOut, lcaQid, lcaTax, nLca);
-        oo.lca_qid = lcaQid.data();
-        oo.lca_tax = lcaTax.data();
-        oo.n_lca   = nLca;
+        uint64_t          nLca = 0;
+        auto const        tLca = Clock::now();
+        HandleOwner const lh   = output.lcaOnGpu ? makeHandle(device) : HandleOwner();
+        TaxDevOwner const dev  = output.lcaOnGpu ? makeTaxDev(lh.get(), output) : TaxDevOwner();
+        computeLca(output, lh.get(), dev.get(), t.bms.data(), t.nOut, lcaQid, lcaTax, nLca);
+        times.msLca = msSince(tLca);
+        oo.lca_qid  = lcaQid.data();
+        oo.lca_tax  = lcaTax.data();
+        oo.n_lca    = nLca;
     }
     EagerRecords const r{run.program, t.bms.data(), t.nOut, t.ops, &names, reinterpret_cast<uint8_t const *>(in.qs.ascii.data()), in.qs.ascii_off.data(),
                          &oo,         (int64_t)t.rst.qrys_with_hit};
-    RenderTimes        times;
     if (opt.render == "gpu")
     {
         bool const        bam = run.outFmt == LX_OUT_BAM;
@@ -1303,6 +1357,9 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
                  in.msRead, in.gunzipNote.c_str(), tableNote.c_str(), table.msIndex, msSearch, t.gpuSeeding ? "GPU" : "host", t.msSeed, t.nDeclined,
                  t.nPassesOnHost, t.msExtend, t.msRecords, run.recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msOutput - times.msCompress,
                  outputNote.c_str(), msSince(run.tStart));
+    if (run.wantLca && (opt.lca == "gpu" || opt.lcaTopGiven))
+        std::fprintf(stderr, "lambda3 LCA: records within %g percent of a query's best bit score, folded on the %s: %.1f ms%s\n", opt.lcaTopPercent,
+                     opt.lca != "host" ? "GPU" : "host", run.lazy ? t.msLca : times.msLca, run.lazy ? " on the slowest worker" : "");
     if (run.lazy)
         std::fprintf(stderr, "lambda3 query blocks: %llu block(s) of at most %llu read(s), %llu read(s) in the largest, at most %llu block(s) alive at once\n",
                      (unsigned long long)lazy.counts.blocks, (unsigned long long)run.blockReads, (unsigned long long)lazy.counts.largest,

@@ -557,6 +557,130 @@ int lx_compute_lca(lx_blast_match const * m, uint64_t n, lx_tax_tree const * tre
     return LX_OK;
 }
 
+void lx_lca_options_default(lx_lca_options * o)
+{
+    if (!o)
+        return;
+    *o             = lx_lca_options{};
+    o->top_percent = 100.0;
+}
+
+// lx_compute_lca (src/search_algo.hpp:884-907, src/search_misc.hpp:86-112) over the records within top_percent of the query's best
+// bit score: the same two loops, both over the kept records only
+int lx_compute_lca_ex(lx_blast_match const * m, uint64_t n, lx_tax_tree const * tree, lx_lca_options const * opt, uint64_t * out_qid,
+                      uint32_t * out_lca, uint64_t * out_n)
+{
+    double const top = opt ? opt->top_percent : 100.0;
+    g_output_error.clear();
+    if (!(top >= 0.0 && top <= 100.0)) // (a NaN fails both)
+    {
+        g_output_error = "lx_compute_lca_ex: top_percent must be in [0, 100]";
+        return LX_EINVAL;
+    }
+    if (top == 100.0)
+        return lx_compute_lca(m, n, tree, out_qid, out_lca, out_n);
+    if ((!m && n) || !tree || !out_qid || !out_lca || !out_n || !tree->parents || !tree->heights || !tree->s_tax_off ||
+        (!tree->s_tax_ids && tree->n_s && tree->s_tax_off[tree->n_s]))
+        return LX_EINVAL;
+    lx_tax_tree const & t = *tree;
+    double const        f = 1.0 - top / 100.0;
+    uint64_t            w = 0;
+    for (uint64_t lo = 0; lo < n;)
+    {
+        uint64_t hi = lo + 1;
+        while (hi < n && m[hi].n_qid == m[lo].n_qid)
+            ++hi;
+        for (uint64_t k = lo; k < hi; ++k)
+        {
+            if (m[k].n_sid >= t.n_s)
+                return LX_EINVAL;
+            if (!std::isfinite(m[k].bit_score))
+            {
+                g_output_error = "lx_compute_lca_ex: a bit score that is not finite (row " + std::to_string(k) + ")";
+                return LX_EINVAL;
+            }
+        }
+        double best = m[lo].bit_score;
+        for (uint64_t k = lo + 1; k < hi; ++k)
+            best = m[k].bit_score > best ? m[k].bit_score : best;
+        double const cut  = best * f; // (one multiplication: the device's is the same)
+        auto const   kept = [&](uint64_t k) { return m[k].bit_score >= cut || m[k].bit_score == best; };
+        uint32_t     lca  = 0;
+        for (uint64_t k = lo; k < hi && lca == 0; ++k) // :887-896, over the kept records
+        {
+            if (!kept(k))
+                continue;
+            uint64_t const a = t.s_tax_off[m[k].n_sid], b = t.s_tax_off[m[k].n_sid + 1];
+            if (b > a)
+            {
+                uint32_t const first = t.s_tax_ids[a];
+                if (first >= t.n_taxa)
+                    return LX_EINVAL;
+                if (t.parents[first] != 0)
+                    lca = first;
+            }
+        }
+        if (lca != 0) // :898-906, over the kept records
+            for (uint64_t k = lo; k < hi; ++k)
+            {
+                if (!kept(k))
+                    continue;
+                for (uint64_t x = t.s_tax_off[m[k].n_sid]; x < t.s_tax_off[m[k].n_sid + 1]; ++x)
+                {
+                    uint32_t const tax = t.s_tax_ids[x];
+                    if (tax >= t.n_taxa)
+                        return LX_EINVAL;
+                    if (t.parents[tax] != 0 && !lca_of(t, tax, lca, lca))
+                    {
+                        g_output_error = "LCA-computation error: One of the paths didn't lead to root.";
+                        return LX_EINVAL;
+                    }
+                }
+            }
+        out_qid[w] = m[lo].n_qid;
+        out_lca[w] = lca;
+        ++w;
+        lo = hi;
+    }
+    *out_n = w;
+    return LX_OK;
+}
+
+// the invariants of lx_taxonomy_build's trees (host/lx_taxonomy.cpp, step 4) that make every climb of lca_of end
+int lx_check_tax_tree(lx_tax_tree const * tree)
+{
+    auto const refuse = [](std::string const & why)
+    {
+        g_output_error = "lx_check_tax_tree: " + why;
+        return LX_EINVAL;
+    };
+    if (!tree || !tree->parents || !tree->heights || !tree->s_tax_off)
+        return refuse("NULL tree, parents, heights or s_tax_off");
+    lx_tax_tree const & t = *tree;
+    if (t.s_tax_off[0] != 0)
+        return refuse("s_tax_off does not start at 0");
+    for (uint64_t s = 0; s < t.n_s; ++s)
+        if (t.s_tax_off[s + 1] < t.s_tax_off[s])
+            return refuse("s_tax_off descends at subject " + std::to_string(s));
+    uint64_t const n_ids = t.s_tax_off[t.n_s];
+    if (n_ids && !t.s_tax_ids)
+        return refuse("NULL s_tax_ids");
+    for (uint64_t x = 0; x < n_ids; ++x)
+        if (t.s_tax_ids[x] >= t.n_taxa)
+            return refuse("taxon " + std::to_string(t.s_tax_ids[x]) + " of a subject is not in the tree (" + std::to_string(t.n_taxa) + " taxa)");
+    for (uint64_t x = 0; x < t.n_taxa; ++x)
+    {
+        uint32_t const p = t.parents[x];
+        if (p >= t.n_taxa)
+            return refuse("the parent of taxon " + std::to_string(x) + " is not in the tree");
+        if (p > 1 && t.heights[x] != (uint64_t)t.heights[p] + 1)
+            return refuse("the height of taxon " + std::to_string(x) + " is not its parent's plus one");
+        if (p <= 1 && t.heights[x] != 0)
+            return refuse("taxon " + std::to_string(x) + " has no parent below the root and a height that is not 0");
+    }
+    return LX_OK;
+}
+
 void lx_output_options_default(lx_output_options * o)
 {
     if (!o)

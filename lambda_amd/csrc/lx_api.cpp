@@ -1208,6 +1208,7 @@ int lx_set_option(lx_handle * h, int option, uint64_t value)
             return LX_OK;
         case LX_OPT_GUNZIP_PARALLEL_FROM: h->opt_gunzip_from = value; return LX_OK;
         case LX_OPT_INDEX_SLICE_WORDS: h->opt_index_slice = value; return LX_OK;
+        case LX_OPT_LCA_RANGE_ROWS: h->opt_lca_range = value; return LX_OK;
         case LX_OPT_BAM_RANGE_BYTES:
             if (value &&(value < (128u << 10) || value > (2ull << 30)))
                 return fail(h, LX_EINVAL, "LX_OPT_BAM_RANGE_BYTES: 0, or 128 KiB to 2 GiB");
@@ -1250,6 +1251,7 @@ int lx_get_option(lx_handle const * h, int option, uint64_t * value)
         case LX_OPT_GUNZIP_CHUNK: *value = h->opt_gunzip_chunk; return LX_OK;
         case LX_OPT_GUNZIP_PARALLEL_FROM: *value = h->opt_gunzip_from; return LX_OK;
         case LX_OPT_INDEX_SLICE_WORDS: *value = h->opt_index_slice; return LX_OK;
+        case LX_OPT_LCA_RANGE_ROWS: *value = h->opt_lca_range; return LX_OK;
         case LX_OPT_BAM_RANGE_BYTES: *value = h->opt_bam_range; return LX_OK;
         default: return LX_EINVAL;
     }

@@ -265,6 +265,15 @@ struct lx_handle
     uint64_t opt_gunzip_chunk = 0; // LX_OPT_GUNZIP_CHUNK (0 = default)
     uint64_t opt_gunzip_from  = 0; // LX_OPT_GUNZIP_PARALLEL_FROM (0 = default)
     uint64_t opt_index_slice  = 0; // LX_OPT_INDEX_SLICE_WORDS (0 = the single sort)
+    uint64_t opt_lca_range    = 0; // LX_OPT_LCA_RANGE_ROWS (0 = default)
+    // lx_compute_lca_dev (lx_lca_host.cpp): a range's columns in two lanes (pinned and on the device), the query heads, the scan's
+    // tile values, the LCA words and the error word of a range on their way down
+    struct Lca
+    {
+        Pinned     p_in[2], p_out[2];
+        DevBuf     d_in[2], d_out[2], d_first, d_tot;
+        lxi::Event ev_up[2], ev_k[2];
+    } lca;
     uint64_t gunzip_wave      = 0; // kOptGunzipWaveTest: chunks per wave (0 = default), so that a test reaches a wave's edges with a megabyte
     // lx_seed_queries (lx_seed_host.cpp): a call's queries, reads, decline flags, counters, the two scoring matrices, subjects the
     // caller handed in; the match block of the last freed result, kept for the next call
