@@ -859,14 +859,15 @@ int lx_out_close(lx_out * o, int64_t footer_records);
  * its header, and not ending inside the first 64 KiB of them, is decoded on h's device in parallel: its DEFLATE bytes are cut into chunks of LX_OPT_GUNZIP_CHUNK bytes and handled in
  * waves of at most 512 chunks.  Per wave a finder kernel looks in every chunk but the first for the first bit where a
  * non-final dynamic-Huffman block begins; a decode kernel runs one decoder per found chunk up to the next found bit, writing 16-bit
- * symbols in which a back-reference into the unknown 32 KiB in front of the chunk is a marker; the host keeps the chunks that
- * begin on the very bit their predecessor ended on and starts the next wave where the last of them ended; a window pass and a byte
- * pass turn the symbols into bytes at their final offsets and take the CRC32.  Only bytes that passed the trailer's CRC32 and
+ * symbols in which a back-reference into the unknown 32 KiB in front of the chunk is a marker; a chain kernel keeps the chunks that
+ * begin on the very bit their predecessor ended on, and the next wave starts where the last of them ended; a window pass and a byte
+ * pass turn the symbols into bytes at their final offsets and take the CRC32.  The four steps of a wave are one submission with
+ * one stream synchronisation (lx_gunzip_stats.waits) behind it; the wave's bytes then come down in one blocking copy.  Only bytes that passed the trailer's CRC32 and
  * ISIZE are returned: in every other case (no block boundary in four chunks on end, a chunk that ends in a decode status or runs out of room --
  * ten symbols per compressed byte --, a chain that keeps breaking, a CRC32, ISIZE, BSIZE or trailer difference) the member is
  * DECLINED and decoded on the calling thread from its first byte, which gives the bytes or the error text that path gives.  The
  * options move work between the device and the host and never change a byte or a verdict.  lx_last_phase_ms(h, 10, ...) = device
- * time of the plain-member kernels in the last call (101, 102, 103 = its find, decode and resolve kernels alone). */
+ * time of the plain-member kernels in the last call (101, 102, 103 = its find, its decode, and its chain and resolve kernels alone). */
 int lx_gunzip(lx_handle * h, uint8_t const * in, uint64_t n, lx_bytes ** out);
 
 /* Why the parallel path declined a plain member. */
@@ -893,9 +894,10 @@ typedef struct lx_gunzip_stats
     uint64_t bytes_up;       /* bytes the plain path moved to the device ... */
     uint64_t bytes_down;     /* ... and from it */
     int32_t  last_decline;   /* LX_GUNZIP_DECLINE_* of the last declined member */
-    int32_t  reserved;
+    int32_t  waits;          /* stream synchronisations of the plain path: one per wave (its bytes then come down in one blocking copy) */
 } lx_gunzip_stats;
-/* The counts of h's last lx_gunzip call. */
+/* The counts of h's last lx_gunzip call, or of its last lx_gunzip_stream_next call: of that call alone where it returned a piece,
+ * of the whole file (every call of the stream summed) where it reported the end. */
 int lx_last_gunzip_stats(lx_handle const * h, lx_gunzip_stats * stats);
 /* A decline reason in words ("no boundary", "room", ...). */
 char const * lx_gunzip_decline_text(int reason);
@@ -905,15 +907,27 @@ char const * lx_gunzip_decline_text(int reason);
  * at least one byte and at most piece_bytes + 65536 (piece_bytes = 0: 64 MiB).  The stream walks the members as lx_gunzip does:
  * BGZF members (BC subfield, at most 64 KiB of DEFLATE bytes and of text) are gathered, whole, until their ISIZE sum fills the
  * piece, and the group is decoded by the BGZF path -- on h's device, or member by member on the calling thread when h is NULL --;
- * only that group's compressed bytes are read from the file.  Every other member is decoded on the calling thread by the same
+ * only that group's compressed bytes are read from the file.  A plain member that lx_gunzip would decode on h's device -- at least
+ * LX_OPT_GUNZIP_PARALLEL_FROM bytes of the file behind its header, and not ending inside the first 64 KiB of them; with a threshold
+ * of fewer than 10 bytes a stream keeps to the calling thread, as it did before it had this path -- is decoded
+ * there wave by wave, by the kernels and under the options of lx_gunzip: a call runs a wave when less than a piece of text is
+ * left from the last one, and across calls the stream keeps the bit where the next wave starts, the CRC register and the length so
+ * far, and the text not handed out yet, whose last 32 KiB are the window the next wave is given (h keeps nothing of the stream
+ * between two calls).  A wave has at most max(2, piece_bytes / chunk) chunks, so that its text is at most 10 x max(piece_bytes,
+ * 2 chunks) bytes -- ten symbols of room per compressed byte -- and never more than 320 MiB with the default chunk; only the wave's
+ * compressed bytes are read from the file.  Where lx_gunzip would decline (no block boundary in four chunks on end, a decode
+ * status, a chunk out of room, a chain that keeps breaking) the stream does not fail: pieces handed out cannot be taken back, so the
+ * calling thread goes on where the last verified chunk ended, with the window, CRC and length so far, and finishes the member
+ * (stats: declined, last_decline, plain_host).  Every other member is decoded on the calling thread by the same
  * DEFLATE code, which stops between two symbols once the piece is full and keeps the last 32 KiB of text as the window; CRC32 and
- * ISIZE are checked at the trailer.  The parallel plain-member device path of lx_gunzip is NOT used here: it needs the member's
- * whole text on the device.  The file is mapped (a file that cannot be mapped is read whole, compressed); between calls the stream
- * holds O(piece_bytes) of text.  A corrupt stream fails in the call that reaches the damage, with lx_gunzip's message for the
- * whole file: member number, and byte offset from the start of the file; every later call fails.  A plain member's CRC32 is
+ * ISIZE are checked at the trailer, for a member from the device in the call that hands out its last bytes.  The file is mapped (a
+ * file that cannot be mapped is read whole, compressed); between calls the stream holds O(piece_bytes) of text and, inside such a
+ * plain member, what is left of one wave's text.  A corrupt stream fails in the call that reaches the damage, with lx_gunzip's
+ * message for the whole file: member number, and byte offset from the start of the file; every later call fails.  A plain member's CRC32 is
  * known at its trailer only, so pieces handed out before the failing call may hold text of the member that failed.  NULL arguments and a file
  * that cannot be opened: LX_EINVAL with a text (lx_last_error(h), or lx_last_output_error() when h is NULL).  While the stream is
- * open, h serves no other call between lx_gunzip_stream_next and the reading of its phase time (5) or stats. */
+ * open, h serves no other call between lx_gunzip_stream_next and the reading of its phase times (5; 10 and 101 to 103 for the
+ * waves) or stats, which are those of that call alone; behind the call that reports the end the stats are the whole file's. */
 typedef struct lx_gunzip_stream lx_gunzip_stream;
 int  lx_gunzip_stream_open(lx_handle * h, char const * path, uint64_t piece_bytes, lx_gunzip_stream ** out);
 /* The next piece (released with lx_bytes_free); LX_OK with *piece == NULL at the end. */

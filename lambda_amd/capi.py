@@ -93,9 +93,9 @@ class RecordStats(C.Structure):
 
 
 class GunzipStats(C.Structure):
-    """lx_gunzip_stats: where the members of the last lx_gunzip call were decoded."""
+    """lx_gunzip_stats: where the members of the last lx_gunzip or lx_gunzip_stream_next call were decoded."""
     _fields_ = [(n, C.c_uint64) for n in ("bgzf_members", "plain_parallel", "plain_host", "chunks", "chunks_dropped", "waves", "declined",
-                                          "bytes_up", "bytes_down")] + [("last_decline", C.c_int32), ("reserved", C.c_int32)]
+                                          "bytes_up", "bytes_down")] + [("last_decline", C.c_int32), ("waits", C.c_int32)]
 
 
 class TaxTree(C.Structure):
@@ -601,8 +601,10 @@ def gunzip(handle: "Handle | None", data: bytes) -> bytes:
 def gunzip_stream(handle: "Handle | None", path, piece_bytes: int = 0):
     """lx_gunzip_stream_*: yields the pieces of the file's decompressed text (of the file's own bytes when it is not gzip), each of
     at most piece_bytes + 65536 bytes (0 = 64 MiB); concatenated they are gunzip(handle, the file's bytes).  BGZF members are decoded
-    in groups on the handle's device (handle None: on this thread), every other member on this thread with a 32 KiB window.  A
-    corrupt stream raises LambdaExtError(LX_EINVAL) from the piece that reaches the damage, with gunzip's message."""
+    in groups on the handle's device (handle None: on this thread), plain members of LX_OPT_GUNZIP_PARALLEL_FROM bytes or more wave by
+    wave on it, every other member on this thread with a 32 KiB window.  Handle.last_gunzip_stats() and last_phase_ms(10) after a piece
+    are those of the call that made it; once the generator has ended the stats are those of the whole file.  A corrupt stream raises LambdaExtError(LX_EINVAL) from the piece that reaches the damage,
+    with gunzip's message."""
     lib = load()
     h = handle.h if handle is not None else None
 
@@ -1334,7 +1336,9 @@ class Handle:
                                                footer_records))
 
     def last_gunzip_stats(self) -> GunzipStats:
-        """lx_last_gunzip_stats: the counts of the last gunzip(handle, ...); .decline_text is the last decline reason in words."""
+        """lx_last_gunzip_stats: the counts of the last gunzip(handle, ...), of the last piece of gunzip_stream(handle, ...), or, once
+        that stream has ended, of its whole file;
+        .decline_text is the last decline reason in words."""
         st = GunzipStats()
         self._check(self.lib.lx_last_gunzip_stats(self.h, C.byref(st)))
         st.decline_text = self.lib.lx_gunzip_decline_text(st.last_decline).decode()

@@ -224,7 +224,8 @@ bool looksLikeDna(std::string const & text, std::string const & path)
     return vote.dna();
 }
 
-// ---- --lazy-query: the query file as a stream of pieces (lx_gunzip_stream: decompressed where needed, BGZF groups on `device`)
+// ---- --lazy-query: the query file as a stream of pieces (lx_gunzip_stream: decompressed where needed, BGZF groups and large plain
+// members on `device`)
 // and of records (lx_query_blocks::RecordParser).  The first two pieces are taken at once: the bzip2 refusal and the alphabet come
 // from the first, and whether it is the whole file from the second.
 struct QueryStream
@@ -268,6 +269,21 @@ struct QueryStream
             ahead.push_back(piece);
         else
             ended = true;
+        lx_gunzip_stats st; // (of the whole file, behind the call that reports its end)
+        if (ended && h && lx_last_gunzip_stats(h.get(), &st) == LX_OK)
+        {
+            plainMembers  = st.plain_parallel;
+            plainChunks   = st.chunks;
+            plainDeclined = st.declined;
+        }
+    }
+    // for the stage-time line, what readInput says of the eager path: the plain members the stream decoded on the device
+    std::string gunzipNote() const
+    {
+        if (!plainMembers && !plainDeclined)
+            return std::string();
+        return " (query stream: " + std::to_string(plainMembers) + " plain member(s) in " + std::to_string(plainChunks) + " chunks on the GPU" +
+               (plainDeclined ? ", " + std::to_string(plainDeclined) + " finished on the host after a decline" : std::string()) + ")";
     }
     // looksLikeDna over the first piece (all of the file a small file has)
     bool looksLikeDna() const
@@ -350,7 +366,12 @@ struct QueryStream
     uint64_t                                         pieceAt = 0; // bytes of ahead[0] the parser has
     bool                                             finished = false;
     std::exception_ptr                               malformed; // the parser's error, kept until the records in front of it are out
-    static constexpr uint64_t kPiece = 8ull << 20, kSlice = 1ull << 20; // text per piece of the stream; per call of the parser
+    uint64_t                                         plainMembers = 0, plainChunks = 0, plainDeclined = 0; // of the whole file, once the stream has ended
+    // text per piece of the stream; per call of the parser.  A wave of a plain member has a piece's worth of input at most, so 32 MiB
+    // are 512 chunks of 64 KiB, one per decoder the device runs at a time (lx_gunzip's own wave).  Not measured: no run at size yet.
+    // The cost is memory, for every kind of input: the reader holds up to two pieces of 32 MiB, inside a plain member up to
+    // 320 MiB of a wave's text on top (a third of that is typical), and the stream's handle about 1 GiB of device buffers.
+    static constexpr uint64_t kPiece = 32ull << 20, kSlice = 1ull << 20;
 };
 
 // ---- the reduced alphabet of the seeding stage (the word table is made over the reduced subjects, the seeds from the reduced queries)

@@ -33,7 +33,7 @@
 //
 // --lazy-query 1 [--query-block N]: the query file block by block, in bounded memory -- the reference's batch loop with its reader
 // thread behind a bounded queue (src/search.cpp:389-459, src/search_algo.hpp:374-413).  One reader takes the file as a stream
-// (lx_gunzip_stream: BGZF groups on the first device, other members on its thread), parses it piece by piece
+// (lx_gunzip_stream: BGZF groups and plain members of 8 MiB and more on the first device, other members on its thread), parses it piece by piece
 // (lx_query_blocks.hpp) and makes blocks of at most N reads (default 2^20, NOT measured yet: tools/query_blocks_bench.py; a block
 // also closes at 2^30 letters): ranks, frames, reduction.  One worker per entry of --devices takes the next block and searches all of
 // it as the eager path searches a worker's range -- lx_set_queries and lx_reserve for the block, the --search0 pre-pass and the
@@ -1344,6 +1344,8 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
                  in.db.ids.size(), (unsigned long long)setup.sp.db_total_length, (size_t)t.sst.hitsAfterSeeding, t.nPromising,
                  (unsigned long long)(t.ist.num_ext_score - t.ist.hits_duplicate), (unsigned long long)t.ist.num_ext_ali, (unsigned long long)t.nHsp,
                  (unsigned long long)t.nOut, (unsigned long long)t.rst.qrys_with_hit);
+    // (--lazy-query: the query file was decompressed while the blocks were searched; its stream has the counts)
+    std::string const gunzipNote = in.gunzipNote + (in.qStream ? in.qStream->gunzipNote() : std::string());
     std::string const tableNote = run.fromIndex ? "(read from the index) " : table.tableOnGpu ? "(" + table.onGpu() + ") " : "";
     std::string       outputNote;
     if (times.onGpu)
@@ -1354,7 +1356,7 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
     std::fprintf(stderr,
                  "lambda3 times [ms]: read %.0f%s, reduce + word table %s%.0f, search %.0f (seeding on the %s %.0f [%zu read(s) and %zu launch(es) left to "
                  "the host] + extension on the GPU incl. widen / merge / statistics %.0f on the slowest worker), records %.1f (%s), records + output %.0f%s, total %.0f\n",
-                 in.msRead, in.gunzipNote.c_str(), tableNote.c_str(), table.msIndex, msSearch, t.gpuSeeding ? "GPU" : "host", t.msSeed, t.nDeclined,
+                 in.msRead, gunzipNote.c_str(), tableNote.c_str(), table.msIndex, msSearch, t.gpuSeeding ? "GPU" : "host", t.msSeed, t.nDeclined,
                  t.nPassesOnHost, t.msExtend, t.msRecords, run.recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msOutput - times.msCompress,
                  outputNote.c_str(), msSince(run.tStart));
     if (run.wantLca && (opt.lca == "gpu" || opt.lcaTopGiven))

@@ -239,11 +239,11 @@ struct lx_handle
         DevBuf d_in, d_mem, d_status, d_out;
         Pinned p_in[2], p_mem[2], p_status[2];
         // a plain member in parallel (lx_pgunzip.hip): one wave's input, found bits + chunk results, symbol pool, windows, verified
-        // chunks, bytes, CRC words; what the host reads of a wave in a pinned block
+        // chunks, bytes, the WaveResult (d_crc); slot 0's bit on its way up and the WaveResult on its way down in pinned blocks
         DevBuf d_pin, d_slots, d_sym, d_win, d_ver, d_bytes, d_crc;
-        Pinned p_slots, p_ver, p_crc;
-        lx_gunzip_stats stats{}; // of the last lx_gunzip call (lx_last_gunzip_stats)
-        float           phase_ms[3] = {0, 0, 0};      // ... its find, decode and resolve kernels (lx_last_phase_ms 101..103, 10 = all)
+        Pinned p_slots, p_crc;
+        lx_gunzip_stats stats{}; // of the last lx_gunzip or lx_gunzip_stream_next call (lx_last_gunzip_stats)
+        float           phase_ms[3] = {0, 0, 0};      // ... its find, decode and chain + resolve kernels (lx_last_phase_ms 101..103, 10 = all)
         int             phase_launches[3] = {0, 0, 0};
     } gunzip;
     // lx_render_bam_dev / lx_write_bam_dev (lx_bam_host.cpp): the call's inputs flattened on the device, what the kernels leave per

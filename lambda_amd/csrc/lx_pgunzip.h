@@ -9,7 +9,8 @@
 //            only, so a boundary it misses costs a merge of two chunks and never a byte.
 //   decode   decode_chunk(): Inflater over a MarkerSink from bit b0 until a block ends at or beyond bit b1 or the final block ends.
 //            The output is 16-bit symbols: 0..255 a byte, kMarker | w = byte w of the 32 KiB window in front of the chunk.
-//   chain    chain(): chunk j is verified when chunk j - 1 is and ended on the very bit chunk j was found at.
+//   chain    chain(): chunk j is verified when chunk j - 1 is and ended on the very bit chunk j was found at.  chain_wave() is the
+//            whole step as chain_kernel runs it: chain(), the verified chunks' places, and the WaveResult the host reads.
 //   resolve  next_window_at() makes the window behind a chunk from the window in front of it and the chunk's last 32 Ki symbols;
 //            resolve() turns a symbol into its byte.
 // Bounds: the input reads are inside in[0, n) (Inflater and Bits check every one), the symbol writes inside the sink's room, the
@@ -349,7 +350,7 @@ struct Chain
 };
 
 // found[0] is a true boundary; every later chunk must begin on the bit where its verified predecessor ended
-inline Chain chain(uint64_t const * found, ChunkResult const * r, uint32_t nslots, uint32_t * ver)
+__host__ __device__ inline Chain chain(uint64_t const * found, ChunkResult const * r, uint32_t nslots, uint32_t * ver)
 {
     Chain c{0, 0, 0, 0};
     if (nslots == 0 || r[0].status)
@@ -440,20 +441,77 @@ struct WaveParams
     uint16_t *      sym;        // [nslots * room]
 };
 
+constexpr uint32_t kMaxWaveSlots = 512; // slots of a wave at most (chain_kernel keeps their numbers in LDS)
+
+// what a wave came to: written by the chain step, its crc and bad words completed by the resolve step; all the host reads of a
+// wave besides its bytes
+struct WaveResult
+{
+    uint64_t end_bit;  // where the last verified chunk ended: the next wave's start
+    uint64_t wave_len; // bytes of the verified chunks
+    uint32_t nver;     // verified chunks; 0: the wave's first chunk failed, with status0
+    uint32_t dropped;  // found chunks the chain check threw out
+    uint32_t final;    // the last verified chunk ended with the final block
+    uint32_t status0;  // the first chunk's status (the decline reason when nver == 0)
+    uint32_t crc;      // the wave's CRC register (no initial value, no final complement)
+    uint32_t bad;      // 1: a marker before the start of the member's output, 2: a chunk outside the wave's bytes
+    uint32_t longest;  // symbols of the longest verified chunk
+    uint32_t pad;
+};
+
+// the chain step of a wave: chain(), then the verified chunks' places in the symbol pool and in the wave's bytes and the part of
+// the window in front of each that exists (`before` = bytes of the member's text in front of the wave, kWindow at most).
+// idx[nslots] is scratch; a count beyond the chunk's room (MarkerSink allows none) ends the chain in front of that chunk
+__host__ __device__ inline void chain_wave(uint64_t const * found, ChunkResult const * r, uint32_t nslots, uint32_t room, uint32_t before,
+                                           uint32_t * idx, Verified * ver, WaveResult & o)
+{
+    Chain const c = chain(found, r, nslots, idx);
+    o             = WaveResult{c.end_bit, 0, c.nver, c.dropped, c.final, nslots ? r[0].status : (uint32_t)kChunkSkipped, 0, 0, 0, 0};
+    for (uint32_t v = 0; v < c.nver; ++v)
+    {
+        uint32_t const j = idx[v], cnt = r[j].count;
+        if (cnt > (uint64_t)(nslots - j) * room)
+        {
+            o.nver    = v;
+            o.final   = 0;
+            o.end_bit = v ? r[idx[v - 1]].end_bit : 0;
+            o.bad |= 2;
+            break;
+        }
+        uint64_t const seen = (uint64_t)before + o.wave_len;
+        ver[v]              = Verified{(uint64_t)j * room, o.wave_len, cnt, (uint32_t)(seen < kWindow ? seen : kWindow)};
+        o.wave_len += cnt;
+        if (cnt > o.longest)
+            o.longest = cnt;
+    }
+}
+
+struct ChainParams
+{
+    uint64_t const *    found;  // [nslots]
+    ChunkResult const * res;    // [nslots]
+    uint32_t            nslots; // <= kMaxWaveSlots
+    uint32_t            room;
+    uint32_t            before; // bytes of the member's text in front of the wave, kWindow at most
+    Verified *          ver;    // [nslots]
+    WaveResult *        out;
+};
+
 struct ResolveParams
 {
-    uint16_t const * sym;
-    Verified const * ver;
-    uint32_t         nver;
-    uint32_t         segs;     // 32 Ki-symbol segments of the longest chunk
-    uint8_t *        win;      // [(nver + 1) * kWindow]: window v lies in front of verified chunk v
-    uint8_t *        out;      // the wave's bytes
-    uint32_t         wave_len; // ... their number
-    uint32_t *       crc;      // [0] ^= the wave's CRC register (no initial value, no final complement), [1] |= a bad marker
+    uint16_t const *   sym;
+    Verified const *   ver;     // [wr->nver], made by the chain step
+    WaveResult *       wr;      // nver and wave_len are read on the device; crc ^= the wave's CRC register, bad |= 1 or 2
+    uint32_t           nslots;  // the grid: workgroups beyond wr->nver exit
+    uint32_t           max_seg; // 32 Ki-symbol segments of the longest chunk there can be
+    uint8_t *          win;     // [(nslots + 1) * kWindow]: window v lies in front of verified chunk v
+    uint8_t *          out;     // the wave's bytes
+    uint64_t           out_cap; // ... the room for them
 };
 
 hipError_t launch_find(WaveParams const & p, hipStream_t stream);
 hipError_t launch_decode(WaveParams const & p, hipStream_t stream);
+hipError_t launch_chain(ChainParams const & p, hipStream_t stream);
 hipError_t launch_resolve(ResolveParams const & p, hipStream_t stream);
 
 } // namespace pgunzip
