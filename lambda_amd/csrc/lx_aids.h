@@ -1,6 +1,6 @@
 // lx_aids.h -- development aids: the environment switches of the library, read ONCE per process (first use) in one place
 // (lx::dev_aids() in lx_api.cpp).  None of them is part of the ABI and none changes results: they steer measurements of the
-// committed tools (tools/, tests/test_gpu_two_calls.py) or print host timings.  Options a caller is meant to set go through
+// committed tools (tools/, tests/test_gpu_two_calls.py, tests/test_gpu_level2_ranges.py) or print host timings.  Options a caller is meant to set go through
 // lx_set_option (include/lambda_ext.h).
 #pragma once
 #include <cstddef>
@@ -20,8 +20,9 @@ struct DevAids
                                 //                       list's size
     int      bt_tile_at;        // LX_BT_TILE_AT         backtrace: lanes waiting for a tile that start the tile phase (0 = default) 0         tools/dev/bt_sweep.sh
     int      bt_refill_at;      // LX_BT_REFILL_AT       backtrace: retired lanes that trigger a queue refill (0 = default)          0         tools/dev/bt_sweep.sh
-    uint64_t l2_ranges;         // LX_L2_RANGES          Level-2 driver: ranges of the window list whose records are made chunk by   0         tools/dev/pmc_prot.sh
-                                //                       chunk (0 = by size: 2 from 300 000 windows, one more per four million, at most 4)
+    uint64_t l2_ranges;         // LX_L2_RANGES          Level-2 driver: ranges of the window list whose records are made chunk by   0         tools/dev/pmc_prot.sh,
+                                //                       chunk (0 = by the rule of lx_level2_plan.h: by size and by what the          tests/test_gpu_level2_ranges.py
+                                //                       ranges' checkpoint slots take)
     bool     host_timing;       // LX_HOST_TIMING        print where the host-buffer entry points spend their time                   off       tools/profile_round.sh, tests
 };
 

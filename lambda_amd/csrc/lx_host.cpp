@@ -147,6 +147,11 @@ public:
         return LX_OK;
     }
 
+    // where run() left the survivors (ResidentInput::keep_on_device: on the device where the multi-query plan served the list)
+    ResidentSurvivors::Where survivors_where() const
+    {
+        return !dev_list ? ResidentSurvivors::kOnHost : by_range ? ResidentSurvivors::kOnDeviceByRange : ResidentSurvivors::kOnDevice;
+    }
 
 private:
     lx_handle * const           h;
@@ -663,11 +668,10 @@ private:
         if ((rc = ensure(h, l2.d_surv_hsp, cap * sizeof(lx_hsp))) || (rc = ensure(h, l2.d_surv_src, cap * sizeof(uint32_t))) ||
             (rc = ensure(h, l2.d_surv_codes, cap * sizeof(uint64_t))))
             return rc;
-        l2.surv_cap       = cap;
-        l2.surv_total     = 0;
-        l2.surv_on_device = true;
-        dev_list          = true;
-        want_codes        = ri->want_codes;
+        l2.surv_cap   = cap;
+        l2.surv_total = 0;
+        dev_list      = true;
+        want_codes    = ri->want_codes;
         // records chunk by chunk where every range of the plan is a chunk the budgets admit (else: the call's list, one chain at the end)
         if (ri->chunk_records && ri->chunk_records->n_ranges >= 1 && preplanned)
         {
@@ -688,7 +692,6 @@ private:
                 by_range = a < b && b - a <= 4 * per_chunk && (b - a) * kWave * std::max(slot_b, slot_w) <= h->opt_trace_bytes &&
                            (b - a) * kWave * (pm * 8 + sm) <= (8ull << 30);
             }
-            l2.surv_by_range = by_range;
         }
         return LX_OK;
     }
@@ -1261,13 +1264,13 @@ private:
 static int extend_pipeline(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_bytes, uint8_t const * s_res, uint64_t s_bytes,
                            lx_extension const * ext, uint64_t n, int32_t const * min_score, int32_t min_score_all, int32_t * out_score,
                            lx_hsp * out_hsp, uint64_t * out_ops_off, uint8_t const ** out_ops, uint64_t * out_ops_bytes, int mode,
-                           lxi::ResidentInput const * ri = nullptr)
+                           lxi::ResidentInput const * ri = nullptr, lxi::ResidentSurvivors * where = nullptr)
 {
     bool const                 as_list = mode == 2;
     HostPool::Call const       in_flight_call; // (the host threads look for this call's next loop instead of going to sleep between two)
-    h->res_count         = 0;
-    h->l2.surv_on_device = false;
-    h->l2.surv_by_range  = false;
+    h->res_count = 0;
+    if (where)
+        *where = lxi::ResidentSurvivors{};
     int rc = bind(h);
     if (rc)
         return rc;
@@ -1318,7 +1321,10 @@ static int extend_pipeline(lx_handle * h, int slot, uint8_t const * q_res, uint6
     // (measured in round 3 and removed again: two chunks' kernels side by side on two streams -- ragged list 28.5 against 24.4 ms,
     // headline batch 40.0 against 31.3 ms -- and a chunk's backtrace on a second stream beside the next chunk's sweep -- no gain on
     // the ragged list, 34.9 against 29.0 ms on the headline: kernels side by side cost more than their tails and latencies save)
-    return pipe.run(ri ? ri->d_q : h->d_q.ptr, sref.dev);
+    rc = pipe.run(ri ? ri->d_q : h->d_q.ptr, sref.dev);
+    if (where && pipe.survivors_where() != lxi::ResidentSurvivors::kOnHost)
+        *where = lxi::ResidentSurvivors{pipe.survivors_where(), h->l2.surv_total};
+    return rc;
 }
 
 // the handle's survivor list of the last call, handed out
@@ -1392,16 +1398,17 @@ int lx_extend_batch_list(lx_handle * h, int slot, uint8_t const * q_res, uint64_
 
 // lx_extend_batch_list for the Level-2 driver on the device (lx_level2_host.cpp): query residues, window list and cut-offs are resident
 int lxi::extend_list_resident(lx_handle * h, int slot, ResidentInput const & ri, lx_extension const * ext, uint64_t n, int32_t const * min_score,
-                              int32_t * out_score, lx_survivor_list * out)
+                              int32_t * out_score, lx_survivor_list * out, ResidentSurvivors * where)
 {
-    *out = lx_survivor_list{};
+    *out   = lx_survivor_list{};
+    *where = ResidentSurvivors{};
     if (n == 0)
         return LX_OK;
     if (slot < 0 || slot > 1 || !h->have_sc[slot])
         return fail(h, LX_ESTATE, "scoring slot %d not set", slot);
     if (n > 0xfffffff0ull / 2)
         return fail(h, LX_EINVAL, "at most 2^31 extensions per call");
-    int const rc = extend_pipeline(h, slot, nullptr, ri.q_bytes, nullptr, 0, ext, n, min_score, 0, out_score, nullptr, nullptr, nullptr, nullptr, 2, &ri);
+    int const rc = extend_pipeline(h, slot, nullptr, ri.q_bytes, nullptr, 0, ext, n, min_score, 0, out_score, nullptr, nullptr, nullptr, nullptr, 2, &ri, where);
     if (rc == LX_OK)
         hand_out_list(h, out);
     return rc;

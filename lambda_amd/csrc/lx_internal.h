@@ -196,30 +196,25 @@ struct lx_handle
     {
         std::vector<uint64_t> q_off, s_off, s_len;
         std::vector<uint32_t> q_len, q_evlen, evlens; // evlens: the distinct e-value lengths of the query set
-        uint64_t              q_hash = 0, s_hash = 0, dup_before = 0; // content hashes of the sets lx_iterate_matches made resident; hits_duplicate before the last list
+        uint64_t              q_hash = 0, s_hash = 0; // content hashes of the sets lx_iterate_matches made resident
         uint64_t              q_bytes = 0, max_slen = 0, s_extent = 0; // s_extent: where the last subject ends in the residue buffer
         uint32_t              max_evlen = 0;
         int                   q_frames  = 1;
         DevBuf                d_qres, d_qoff, d_qlen, d_qband, d_qevlen, d_soff, d_slen;
-        DevBuf                d_pair[2], d_s0[2], d_hist, d_head, d_tail, d_tot, d_win, d_cut, d_cnt, d_up, d_plan, d_wf, d_fp; // (d_fp: workspace of the free-packing plan)
+        DevBuf                d_pair[2], d_s0[2], d_hist, d_head, d_tot, d_win, d_cut, d_cnt, d_up, d_plan, d_wf, d_fp; // (d_fp: workspace of the free-packing plan)
         Pinned                p_cnt, p_win, p_up;
         std::vector<lx_extension> ext;   // host copies of the window list, its cut-offs and scores
         std::vector<int32_t>      min, score;
-        std::vector<uint32_t>     wf_pan, wf_maxs; // a device plan's wavefronts
         lxi::Event                ev_win;    // the window list has arrived on the host
         lxi::Event                ev_rank[2]; // the window list is complete / the rank kernel (second stream) is through
         // records on the device (lx_records.hip): the call's survivors as the pipeline's chunks left them (alignment, window, where the
         // codes begin), the key / scan / record buffers, the host-made tables of the e-value
         uint32_t              max_qlen = 0;
         DevBuf                d_qevidx, d_surv_hsp, d_surv_src, d_surv_codes, d_listat, d_rec, d_reccodes, d_reccnt, d_tilekeep, d_tileops, d_pre, d_exp, d_rank;
-        uint32_t              rank_too_long = 0; // (lx_records.hip: rec_launch_rank's flag, downloaded with the plan)
-        Pinned                p_reccnt, p_reccodes, p_rows; // p_rows: a range's finished rows on their way into the result
+        Pinned                p_reccnt, p_rows; // p_rows: a range's finished rows on their way into the result
         Pinned                p_plan; // what the host reads of a device plan: [rank flag + probe windows][columns per lane][longest window] per wavefront
         std::vector<uint64_t> rec_codes;              // where the records' run-length codes begin (host copy)
-        uint64_t              surv_total = 0, surv_cap = 0;
-        bool                  surv_on_device = false; // the last pipeline call kept its survivors on the device
-        bool                  surv_by_range  = false; // ... and handed them over range by range (ResidentInput::ChunkRecords)
-        std::vector<uint64_t> cut_wf;                 // the ranges' first wavefronts
+        uint64_t              surv_total = 0, surv_cap = 0; // entries of d_surv_* that the pipeline's chunks have filled, and their room
         double                exp_lambda = 0;         // the scheme d_exp was made for
         uint32_t              exp_n      = 0;
         // _writeRecord's sort / unique / sort / cut on the device (lx_toprec.hip): the rows that stay and their code words, the step's
@@ -524,7 +519,7 @@ struct ResidentInput
     int              mq_cfg  = 0;
     bool             free_packing = false; // the device plan is the free packing (pairs of one query, at most four queries per wavefront), not the solo one
     uint64_t         cells   = 0;
-    // the survivors stay on the device (lx_handle::Level2::d_surv_*; taken where the plan above is served: surv_on_device says so),
+    // the survivors stay on the device (lx_handle::Level2::d_surv_*; taken where the plan above is served: ResidentSurvivors says so),
     // the scores too (h->d_score_all); want_codes: their run-length codes come down into the handle's code bytes
     bool keep_on_device = false, want_codes = true;
     // Records chunk by chunk (lx_level2_host.cpp): the plan's chunks are RANGES of the query-sorted window list (cut_wf: the wavefront
@@ -547,8 +542,20 @@ int  host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, uint6
                  lx_hsp * out_hsp, uint8_t * caller_ops, uint64_t const * caller_ops_off, uint64_t * out_ops_off, uint8_t const ** out_ops, uint64_t * out_ops_bytes);
 bool solo_plan_applies(lx_handle const * h, int slot);
 bool free_plan_applies(lx_handle const * h, int slot);
+// where extend_list_resident left the call's survivors: in `out` on the host, or in lx_handle::Level2::d_surv_* as one list of
+// `total` entries, or -- handed to ResidentInput::ChunkRecords range by range -- with their records made already
+struct ResidentSurvivors
+{
+    enum Where
+    {
+        kOnHost,
+        kOnDevice,
+        kOnDeviceByRange
+    } where = kOnHost;
+    uint64_t total = 0;
+};
 int  extend_list_resident(lx_handle * h, int slot, ResidentInput const & ri, lx_extension const * ext, uint64_t n, int32_t const * min_score,
-                         int32_t * out_score, lx_survivor_list * out);
+                         int32_t * out_score, lx_survivor_list * out, ResidentSurvivors * where);
 
 // [off, off + len) inside a buffer of `bytes`, written so that offsets near 2^64 cannot wrap past the test
 inline bool lx_slice_ok(uint64_t off, uint64_t len, uint64_t bytes)

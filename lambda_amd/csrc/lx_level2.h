@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "lx_device.h"
+#include "lx_level2_plan.h"
 
 namespace lx
 {
@@ -34,14 +35,7 @@ struct Match
     uint64_t qryId, subjId, qryStart, qryEnd, subjStart, subjEnd;
 };
 
-// One DP window after widen + merge + unique: what the reference's span holds when _widenAndPreprocessMatches returns
-// (qryStart = 0 and qryEnd = the query's length are implied).
-struct L2Window
-{
-    uint32_t q, s;     // frame-expanded ids
-    uint64_t beg, end; // subjStart, subjEnd
-};
-static_assert(sizeof(L2Window) == 24, "L2Window layout");
+// (L2Window, one DP window after widen + merge + unique, and kFpMaxRanges: lx_level2_plan.h -- the range plan reads them without HIP)
 
 // the two sequence sets, resident on the handle's device (lx_set_queries, lx_set_subject_seqs)
 struct L2Sets
@@ -88,7 +82,6 @@ uint64_t   l2_plan_key_bits(uint64_t max_qlen, uint64_t max_wlen);
 // the query changes).  plan: [cap_wf * 16] slots (position in ext[], bit 31 = filler), wf_pan / wf_maxs: [cap_wf]; report: [16]
 // uint32 in device memory -- [0] wavefronts, [1] non-zero = the bound was broken (a bug: the plan is not to be used), [2] runs,
 // [3] quads, [4 + r] first wavefront of range r (r <= nranges).
-constexpr uint32_t kFpMaxRanges = 8;
 struct FpArgs
 {
     Extension const * ext;
