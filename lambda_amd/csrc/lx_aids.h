@@ -1,5 +1,5 @@
 // lx_aids.h -- development aids: the environment switches of the library, read ONCE per process (first use) in one place
-// (lx::dev_aids() in lx_api.cpp).  None of them is part of the ABI and none changes results: they steer measurements of the
+// (lx::dev_aids() in lx_handle.cpp).  None of them is part of the ABI and none changes results: they steer measurements of the
 // committed tools (tools/, tests/test_gpu_two_calls.py, tests/test_gpu_level2_ranges.py) or print host timings.  Options a caller is meant to set go through
 // lx_set_option (include/lambda_ext.h).
 #pragma once

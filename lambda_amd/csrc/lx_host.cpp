@@ -3,7 +3,7 @@
 // pipeline of chunks (pinned staging, two chunks in flight, run-length coded ops on the wire), and the same pipeline over a list
 // that is resident on the device already (lxi::extend_list_resident, what the Level-2 driver calls).  Ragged lists are planned for
 // the multi-query sweep here (lx_plan_free.hip plans device lists).  The entry points of the single passes are lx_host_batch.cpp;
-// the device entry points all of them drive live in lx_api.cpp; no DP arithmetic here.
+// the fused step all of them drive lives in lx_step.cpp; no DP arithmetic here.
 #include "lx_internal.h"
 #include "lx_level2.h"
 using namespace lxi;
@@ -296,7 +296,7 @@ private:
         // back with the counts and is checked in collect()
         uint64_t * const d_cnt = static_cast<uint64_t *>(ln.d_cnt.ptr);
         hipStream_t const ke = ks;
-        LX_HIP(h, hipMemcpyAsync(d_cnt + 3, h->d_ws_top, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, ke));
+        LX_HIP(h, hipMemcpyAsync(d_cnt + 3, ws_word(h, kWsBump), 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, ke));
         LX_HIP(h, hipEventRecord(ln.ev_k, ke));
         // what has a size the host knows goes back at once; records and codes follow when the counts have arrived
         LX_HIP(h, hipStreamWaitEvent(h->stream2, ln.ev_k, 0));
@@ -340,7 +340,7 @@ private:
         uint64_t const ngroups = grp.size() / 2 - 1;
         // (measured on the ragged list of bench.py: a slot of a run of 8 costs ~1.1 x one of a run of 16 while the query fits a
         // panel; wider queries run (8,19) panels with compact codes at 16 and (16,13) panels with int16 pairs at 8 -- the
-        // padded columns and 0.0108 against 0.0156 ms per column, ckpt_cfg_for in lx_api.cpp, decide)
+        // padded columns and 0.0108 against 0.0156 ms per column, ckpt_cfg_for in lx_step_plan.cpp, decide)
         double const   cost16 = max_q > 208 ? (double)slots16 * (double)((max_q + 151) / 152 * 152) * 1.08 : (double)slots16 * 8.0;
         double const   cost8  = max_q > 208 ? (double)slots8 * (double)((max_q + 207) / 208 * 208) * 1.56 : (double)slots8 * 9.0;
         uint64_t const kRun   = cost8 < cost16 ? 8 : 16;
@@ -994,8 +994,8 @@ private:
         int                 rc2;
         LX_HIP(h, lx::launch_slot_scatter(d_orig, slots, static_cast<int32_t const *>(ln.d_score.ptr), static_cast<int32_t *>(h->d_score_all.ptr),
                                           static_cast<uint32_t *>(ln.d_src.ptr), d_cnt, pr.cap_sel, h->stream));
-        LX_HIP(h, hipMemcpyAsync(d_cnt + 3, h->d_ws_top, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
-        LX_HIP(h, hipMemcpyAsync(d_cnt + 4, h->d_ws_top + 6, sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+        LX_HIP(h, hipMemcpyAsync(d_cnt + 3, ws_word(h, kWsBump), 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+        LX_HIP(h, hipMemcpyAsync(d_cnt + 4, ws_word(h, kWsStatBeyond), sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
         if (by_range && (rc2 = ri->chunk_records->enqueue(pr.range, ln.d_hsp.ptr, ln.d_src.ptr, d_cnt, pr.cap_sel)))
             return rc2;
         LX_HIP(h, hipEventRecord(ln.ev_k, h->stream));

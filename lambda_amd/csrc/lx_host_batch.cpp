@@ -1,7 +1,7 @@
 // lx_host_batch.cpp -- the host-buffer entry points of the two passes by themselves and of the pre-extension filter (compiled with
 // hipcc): lx_score_batch (pass 1 of _performAlignment, /root/reference/src/search_algo.hpp:1246), lx_align_batch (pass 2, :1296),
 // band mode's plain path for score / align / extend, lx_prefilter_batch (seedLooksPromising, :426-481).  The list is binned by
-// kernel geometry on the host threads; the device entry points these drive live in lx_api.cpp.  The fused step on host buffers --
+// kernel geometry on the host threads; the launchers these drive live in lx_step.cpp.  The fused step on host buffers --
 // lx_extend_batch and its pipeline of chunks -- is lx_host.cpp.
 #include "lx_internal.h"
 #include "lx_level2.h"
@@ -271,8 +271,8 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
     {
         rc = launch_score_list(h, slot, h->d_q.ptr, sref.dev,
                                static_cast<lx_extension const *>(h->d_ext.ptr) + seg.first, seg.count,
-                               static_cast<int32_t *>(h->d_out.ptr) + seg.first, seg.cfg, seg.multi, seg.shared,
-                               h->stream, h->band_dev, seg.pair_cfg);
+                               static_cast<int32_t *>(h->d_out.ptr) + seg.first, plan_score_cfg(seg.cfg, seg.multi, seg.shared, h->opt_band, seg.pair_cfg),
+                               h->stream, h->band_dev);
         if (rc)
             return rc;
     }
@@ -347,7 +347,10 @@ int lx_align_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
     padded += (run + 3) / 4 * 4;
     bool const share = (padded - n) * 4 <= padded && padded <= 0xfffffff0ull; // (any query width: checkpoints carry across panels)
     uint64_t const slots = share ? padded : n;
+    int const      share_slots = share ? 4 : 0;
 
+    if (!plan_trace(h->facts[slot], ListLimits{max_q, max_s, 0, h->band_dev, h->opt_bs_rule}, share_slots, trace_options(h)).carry) // (one panel holds every query)
+        carry_pairs = 0;
     if (carry_pairs * 8 + 4096 > h->ws_grown)
         h->ws_grown = carry_pairs * 8 + 4096;
     if ((rc = ensure(h, h->d_q, q_bytes + kSlack)) ||
@@ -436,7 +439,7 @@ int lx_align_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
     LX_HIP(h, hipEventRecord(h->ev0, h->stream));
     rc = align_dev_impl(h, slot, h->d_q.ptr, sref.dev, static_cast<lx::Extension const *>(h->d_ext.ptr), slots,
                         static_cast<lx::Hsp *>(h->d_hsp.ptr), static_cast<uint8_t *>(h->d_ops.ptr),
-                        static_cast<uint64_t const *>(h->d_opsoff.ptr), h->stream, ListLimits{max_q, max_s, 0, h->band_dev, h->opt_bs_rule}, share ? 4 : 0,
+                        static_cast<uint64_t const *>(h->d_opsoff.ptr), h->stream, ListLimits{max_q, max_s, 0, h->band_dev, h->opt_bs_rule}, share_slots,
                         share ? static_cast<uint32_t const *>(h->d_sel_src.ptr) : nullptr, nullptr,
                         known_score ? static_cast<int32_t const *>(h->d_sel_score.ptr) : nullptr);
     if (rc)
@@ -521,7 +524,7 @@ int lxi::host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, u
     ListLimits const lim{max_q, max_s, 0, h->band_host.empty() ? nullptr : static_cast<int32_t const *>(h->d_band.ptr), h->opt_bs_rule};
     if (what == 0)
     {
-        if ((rc = prepare_workspace(h, h->stream, score_ws_pairs(h, lim, n))))
+        if ((rc = prepare_workspace(h, h->stream, plan_score(h->facts[slot], lim, score_options(h)).carry_pairs(n))))
             return rc;
         h->phase_ev.clear();
         h->ev_pool_used = 0;
@@ -538,7 +541,7 @@ int lxi::host_banded(lx_handle * h, int slot, int what, uint8_t const * q_res, u
     LX_HIP(h, hipMemcpyAsync(h->d_opsoff.ptr, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     if (what == 1)
     {
-        if ((rc = prepare_workspace(h, h->stream, max_q > 160 ? n * ((max_s + 3) & ~3ull) : 0)))
+        if ((rc = prepare_workspace(h, h->stream, plan_trace(h->facts[slot], lim, 0, trace_options(h)).carry_pairs(n))))
             return rc;
         int32_t const * d_known = nullptr;
         if (known_score)

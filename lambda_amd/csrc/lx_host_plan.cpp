@@ -45,8 +45,7 @@ uint64_t lxi::slot_dwords(int cfg, uint64_t pan, uint64_t maxs, bool wide, bool 
 bool lxi::mq_sweep_applies(lx_handle const * h, int slot)
 {
     SchemeFacts const & f = h->facts[slot];
-    return h->opt_mq >= 1 && h->opt_pass2 == 2 && h->opt_f16 && f.trace_ok && f.b8_ok && -f.gap_open <= lx::kC16MaxGap &&
-           f.gap_open <= f.gap_extend;
+    return h->opt_mq >= 1 && h->opt_pass2 == 2 && h->opt_f16 && f.trace_ok && f.b8_ok && compact_gaps_ok(f);
 }
 
 // the solo packing needs 16 byte profiles in a wavefront's share of the LDS: the alphabets of at most six rows
@@ -206,7 +205,7 @@ void HostPlan::run_starts()
 }
 
 // Multi-query sweep (lx_sweep_mq.hip) for lists that are not uniform: sub-blocks of 4 windows of one query, ordered by (geometry
-// class, longest window) ACROSS queries, four sub-blocks per wavefront -- see plan_pool.  Needs what fused_impl's mq branch needs;
+// class, longest window) ACROSS queries, four sub-blocks per wavefront -- see plan_pool.  Needs what plan_step's multi-query candidate needs;
 // uniform lists (one query length, one window length, runs that fill whole wavefronts) stay on the one-query-per-wavefront kernels.
 // The SOLO packing of that sweep (LX_OPT_QUERY_RUN = 1): a byte profile per window, 16 windows of any queries per wavefront -- where
 // 16 profiles fit a wavefront's share of the LDS (nucleotides, bisulfite).  A read set's seed list has one or two windows per read:

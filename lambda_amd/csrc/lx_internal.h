@@ -1,6 +1,7 @@
-// lx_internal.h -- what lx_api.cpp (handle, options, device entry points, the fused step) and lx_host.cpp (the host-buffer
-// entry points and their pipelines) share: the handle, the launchers of the kernel files, small host helpers.  Not part of
-// the ABI; include/lambda_ext.h is.
+// lx_internal.h -- what lx_api.cpp (the C exports of the device entry points), lx_handle.cpp (handle, options, scoring), lx_step.cpp
+// (the launchers and the fused step) and lx_host.cpp (the host-buffer entry points and their pipelines) share: the handle, the
+// launchers of the kernel files, small host helpers.  The plans they follow are in lx_step_plan.h.  Not part of the ABI;
+// include/lambda_ext.h is.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,58 +30,32 @@
 #include "lx_host_plan.h"
 #include "lx_host_pool.h"
 #include "lx_resources.h"
+#include "lx_step_plan.h"
 
 
 namespace lx
 {
 hipError_t launch_score(int cfg, ScoreParams const & p, bool multi, hipStream_t stream);
-int        score_cfg_panel(int cfg);
-int        score_cfg_groups(int cfg);
-int        score_cfg_count();
 hipError_t launch_score_pair(int cfg, ScoreParams const & p, hipStream_t stream);
-int        score_pair_cfg_for(uint32_t max_qlen);
 uint64_t   select_blocks(uint64_t nruns);
-int        score_pair_cfg_cols(int cfg);
-int        score_pair_cfg_for_runs_of_8(uint32_t max_qlen);
-int        score_pair_cfg_group(int cfg);
-size_t     score_pair_profile_bytes(int cfg, int nrows);
 hipError_t launch_trace_forward(TraceParams const & p, hipStream_t stream);
 hipError_t launch_backtrace(TraceParams const & p, hipStream_t stream);
 hipError_t launch_max_lens(Extension const * ext, uint64_t n, MaxLens * out, hipStream_t stream);
-int        trace_cfg_panel(int cfg);
-int        trace_cfg_group(int cfg);
-int        trace_cfg_words(int cfg);
 hipError_t launch_select(SelectParams const & p, hipStream_t stream);
 hipError_t launch_slot_gather(Extension const * ext_all, int32_t const * min_all, int32_t min_score_all, uint32_t const * orig, uint64_t slots,
                               Extension * out_ext, int32_t * out_min, hipStream_t stream);
 hipError_t launch_slot_scatter(uint32_t const * orig, uint64_t slots, int32_t const * score, int32_t * score_all, uint32_t * src,
                                uint64_t const * count_ptr, uint64_t cap, hipStream_t stream);
-uint64_t   ckpt_slot_dwords(int cfg, uint32_t steps_cap);
-uint64_t   ckpt16_slot_dwords(int cfg, uint32_t steps_cap);
 hipError_t launch_ckpt_forward(TraceParams const & p, hipStream_t stream);
 hipError_t launch_ckpt_backtrace(TraceParams const & p, hipStream_t stream);
 hipError_t launch_sweep_pair16(int trace_cfg, ScoreParams const & p, hipStream_t stream);
 hipError_t launch_score_pair16(ScoreParams const & p, hipStream_t stream);
 hipError_t launch_sweep_pair16_compact(int trace_cfg, ScoreParams const & p, hipStream_t stream);
 hipError_t launch_sweep_mq(int trace_cfg, ScoreParams const & p, hipStream_t stream);
-size_t     sweep_mq_lds_bytes(int trace_cfg, int nrows, int share);
 hipError_t launch_prefilter(PrefilterParams const & p, hipStream_t stream);
 hipError_t launch_rle_pack(PackParams const & p, hipStream_t stream);
 } // namespace lx
 
-namespace lxi
-{
-
-// what lx_set_scoring derives from a scheme besides the tables (one per scoring slot; plan_step decides by them): pass 2 applies
-// (every matrix - gap_extend in [-31, 31]), byte profiles apply (0 <= matrix - gap_open <= 255), the largest entry
-struct SchemeFacts
-{
-    int  alph = 0, gap_open = 0, gap_extend = 0, smax_entry = 0;
-    bool trace_ok = false, b8_ok = false;
-    int  nrows() const { return (alph + 1 + 3) / 4 * 4; } // rows of a query profile: the letters and the pad letter, in whole groups of 4
-};
-
-} // namespace lxi
 using lxi::DevBuf;
 using lxi::Pinned;
 
@@ -160,7 +135,7 @@ struct lx_handle
     DevBuf d_q, d_s, d_ext, d_out, d_ops, d_opsoff, d_keep, d_trace, d_ends, d_hsp, d_seeds, d_sel_ext, d_sel_src, d_sel_runs, d_sel_score, d_trace_score, d_db;
     // multi-panel carry workspace
     DevBuf     d_ws;
-    lxi::DevBlock<uint32_t> d_ws_top; // [0] = bump pointer, [1] = error flag, [2..3] = MaxLens, [4] = overflow checkpoint slots handed out, [5] = backtrace work queue
+    lxi::DevBlock<uint32_t> d_ws_top; // its control words (lxi::WsWord)
     // options
     uint64_t opt_max_qlen  = 0;
     uint64_t opt_query_run = 0;
@@ -377,67 +352,47 @@ void        m9_comment_parts(char const * program, lx_output_options const * opt
 // blocks, the same member bytes, the same download pipeline; `sink` takes each chunk's members in order.  The phase events of the
 // call so far stay.
 int bgzf_compress_dev(lx_handle * h, uint8_t const * d_in, uint64_t n, std::function<int(uint8_t const *, uint64_t)> const & sink);
-size_t pair_lds_limit();
-int    pick_cfg(uint32_t qlen, bool shared);
-int    ckpt_cfg_for(uint64_t max_q, bool packed16 = false);
 int    check_async_error(lx_handle * h);
 int    error_for_flag(lx_handle * h, uint32_t flag);
 
-// ---- the plan of a fused step (plan_step in lx_api.cpp is the one place that makes it)
-struct StepOptions
+// The control words of lx_handle::d_ws_top, named in one place.  kWsBump and kWsError are adjacent: one copy or memset takes both.
+enum WsWord
 {
-    uint64_t max_qlen = 0, max_slen = 0, query_run = 0, pass2 = 2, mq = 1, f16 = 1, band = 0, trace_bytes = 0, n = 0, adapt = 0;
-    int      mq_cfg = 0;
-    bool     mq_wide     = false; // the multi-query sweep writes int16-pair slots (lx_sweep_mq.hip: WIDE)
-    double   surv_frac   = -1.0;
+    kWsBump       = 0, // carry workspace: pairs handed out (every launch that carries starts from 0)
+    kWsError      = 1, // the device's error word (error_for_flag)
+    kWsMaxLens    = 2, // lx::MaxLens of launch_max_lens (two words)
+    kWsOvfCount   = 4, // single sweep: overflow checkpoint slots handed out
+    kWsWorkQueue  = 5, // checkpoint backtrace: the queue its persistent lanes take list positions from
+    kWsStatBeyond = 6, // multi-query sweep: windows beyond the compact codes
+    kWsWords      = 8
 };
-enum SweepFamily
+inline uint32_t * ws_word(lx_handle * h, WsWord w)
 {
-    kNoSweep        = 0, // pass 1, then pass 2 on the survivors (modes 0 / 1)
-    kHalfSweep      = 1, // lx_score_f16.hip score_pair_kernel<G,C,true>: packed half, compact codes, one panel
-    kI16CompactWide = 2, // lx_score_i16.hip sweep_pair16_kernel<8,19,true,true,true>: packed int16, compact codes, several panels
-    kI16Pairs       = 3, // lx_score_i16.hip sweep_pair16_kernel<G,C,MULTI>: packed int16, int16-pair slots
-    kInt32Sweep     = 4, // lx_ckpt.hip ckpt_forward_kernel<G,C,false,MULTI> alone
-    kMqSweep        = 5  // lx_sweep_mq.hip sweep_mq_kernel<C,MULTI>: byte profiles, up to four queries per wavefront
-};
-struct StepPlan
+    return h->d_ws_top + w;
+}
+inline int32_t * ws_error(lx_handle * h)
 {
-    bool        shared = false, sweep = false, adapted = false, compact = false, may_decline = true;
-    bool        packed = false; // a packed sweep's launch structure: a spare slot behind the batch's, an overflow area for what it declines
-    bool        wide   = false; // the multi-query sweep with int16-pair slots
-    SweepFamily family = kNoSweep;
-    int         cfg = 0, share = 0;
-    uint32_t    steps = 0, panels = 1;
-    uint64_t    stride = 0, stride32 = 0, ovf_cap = 0;
-};
-StepPlan plan_step(SchemeFacts const & sc, StepOptions const & o);
-void     describe_plan(StepPlan const & pl, char * buf, size_t len);
-int    mq_cfg_for(uint64_t max_q);
-// band_diag: band mode's centres, indexed like the list (NULL: the default diagonal)
-int    launch_score_list(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out, int cfg,
-                         bool multi, bool shared, hipStream_t stream, int32_t const * band_diag, int pair_cfg = -1, int pair_share = 0);
-int    prepare_workspace(lx_handle * h, hipStream_t stream, uint64_t pairs_hint = 0);
+    return reinterpret_cast<int32_t *>(ws_word(h, kWsError));
+}
 
-// What the caller of a device-list step states about the list: its widest query and longest window (0: unknown), the run of
-// consecutive extensions that share a query (LX_OPT_QUERY_RUN), band mode's centres indexed like the list, the match rule of the
-// backtrace (LX_OPT_BS_MATCH_RULE).  The device entry points take them from the handle's options; the pipelines from their chunks.
-struct ListLimits
-{
-    uint64_t        max_qlen = 0, max_slen = 0, query_run = 0;
-    int32_t const * band_diag = nullptr;
-    uint64_t        bs_rule   = 0;
-};
-// pass 1 over a device list: the carry pairs its launch may need (prepare_workspace's hint), then the launch itself (phase 0 of
-// the phase list; ev0 / ev1 are the caller's)
-uint64_t score_ws_pairs(lx_handle const * h, ListLimits const & lim, uint64_t n);
-int      score_dev_impl(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out,
-                        hipStream_t stream, ListLimits const & lim);
+// ---- lx_step.cpp: the launchers of pass 1, pass 2 and the fused step; each follows a plan of lx_step_plan.h
+// pairs_hint: carry pairs (8 bytes each) the call can need at most (a plan's carry_pairs(n)); the workspace grows to that (the
+// device cannot grow it, it can only report)
+int prepare_workspace(lx_handle * h, hipStream_t stream, uint64_t pairs_hint = 0);
+// the device entry points' limits and the plans' options: the handle's options
+ListLimits   option_limits(lx_handle const * h);
+ScoreOptions score_options(lx_handle const * h);
+TraceOptions trace_options(lx_handle const * h);
+// pass 1 over a device list as `pl` says; band_diag: band mode's centres, indexed like the list (NULL: the default diagonal)
+int launch_score_list(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out,
+                      ScorePlan const & pl, hipStream_t stream, int32_t const * band_diag);
+// ... planned from the list's limits (phase 0 of the phase list; ev0 / ev1 and the carry workspace are the caller's)
+int score_dev_impl(lx_handle * h, int slot, void const * d_q, void const * d_s, void const * d_ext, uint64_t n, void * d_out,
+                   hipStream_t stream, ListLimits const & lim);
 
 // padding of q/s staging buffers so that clamped / prefetching loads never leave the allocation
 constexpr size_t kSlack = 256;
 constexpr uint64_t kExtendChunk = 640ull << 10; // extensions per chunk of lx_extend_batch's pipeline unless LX_OPT_EXTEND_CHUNK says otherwise
-constexpr int kPair16    = 100; // launch_score_list's pair_cfg: the packed 16-bit integer kernel, any query width
-constexpr int kPair16Bin = 8;   // its bin among the packed geometries of lx_score_batch
 
 // Subject side of a host-buffer call: either the caller's buffer, uploaded into d_s, or -- s_res == NULL, s_bytes == 0
 // after lx_set_subjects -- the resident copy.

@@ -102,7 +102,7 @@ int reserve_pipeline(lx_handle * h, Forecast const & f, HostMarks & hm)
     }
     hm.mark("lanes");
     // the checkpoint slots of one chunk (what LX_OPT_TRACE_BYTES admits of them), its end cells, the survivor selection's lists
-    // (fused_impl in lx_api.cpp: room for every slot plus the padding of query runs), the carry workspace
+    // (select_stage in lx_step.cpp: room for every slot plus the padding of query runs), the carry workspace
     uint64_t const trace = std::min<uint64_t>(slots * slot_b, h->opt_trace_bytes);
     if ((rc = ensure(h, h->d_trace, trace)) || (rc = ensure(h, h->d_ends, slots * sizeof(lx::EndCell))) || (rc = ensure(h, h->d_sel_ext, 2 * slots * sizeof(lx_extension))) ||
         (rc = ensure(h, h->d_sel_src, 2 * slots * sizeof(uint32_t))) || (rc = ensure(h, h->d_sel_score, 2 * slots * sizeof(int32_t))) ||

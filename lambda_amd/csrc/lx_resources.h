@@ -81,7 +81,7 @@ static_assert(!std::is_copy_constructible<Stream>::value && !std::is_copy_assign
 static_assert(!std::is_copy_constructible<DevBlock<int>>::value && !std::is_copy_constructible<PinnedBlock<int>>::value, "a block has one owner");
 static_assert(std::is_nothrow_move_constructible<Event>::value && std::is_nothrow_move_constructible<DevBuf>::value, "owners move (std::vector<Event>)");
 
-// Room for `bytes` in b (lx_api.cpp).  A block that is too small is given back and a larger one taken: what it held is gone.
+// Room for `bytes` in b (lx_handle.cpp).  A block that is too small is given back and a larger one taken: what it held is gone.
 // ensure waits for the device first (kernels on a caller's stream may still read the old block) and leaves room to grow into.
 int ensure(lx_handle * h, DevBuf & b, size_t bytes);
 // A pinned block takes exactly `bytes` (kExact: the lanes of the BGZF and gunzip chunks, whose sizes have a fixed ceiling) or a quarter

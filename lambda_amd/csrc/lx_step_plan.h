@@ -1,0 +1,152 @@
+// lx_step_plan.h -- every decision about HOW a step runs: kernel family, geometry, panel count, slot layout, queries per wavefront,
+// carry workspace.  Pure functions of a scheme's facts, the list's limits and the options: no handle, no HIP call.  The launchers
+// (lx_step.cpp) follow these plans; lx_plan_step() shows plan_step to tests/test_plan.py.  The geometry tables the plans read stay
+// with their kernels (the .hip files); only their declarations are here.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/lambda_ext.h"
+
+namespace lx
+{
+int      score_cfg_panel(int cfg);
+int      score_cfg_groups(int cfg);
+int      score_cfg_count();
+int      score_pair_cfg_for(uint32_t max_qlen);
+int      score_pair_cfg_cols(int cfg);
+int      score_pair_cfg_for_runs_of_8(uint32_t max_qlen);
+int      score_pair_cfg_group(int cfg);
+size_t   score_pair_profile_bytes(int cfg, int nrows);
+int      trace_cfg_panel(int cfg);
+int      trace_cfg_group(int cfg);
+int      trace_cfg_words(int cfg);
+uint64_t ckpt_slot_dwords(int cfg, uint32_t steps_cap);
+uint64_t ckpt16_slot_dwords(int cfg, uint32_t steps_cap);
+size_t   sweep_mq_lds_bytes(int trace_cfg, int nrows, int share);
+} // namespace lx
+
+namespace lxi
+{
+
+// what lx_set_scoring derives from a scheme besides the tables (one per scoring slot; the plans decide by them): pass 2 applies
+// (every matrix - gap_extend in [-31, 31]), byte profiles apply (0 <= matrix - gap_open <= 255), the largest entry
+struct SchemeFacts
+{
+    int  alph = 0, gap_open = 0, gap_extend = 0, smax_entry = 0;
+    bool trace_ok = false, b8_ok = false;
+    int  nrows() const { return (alph + 1 + 3) / 4 * 4; } // rows of a query profile: the letters and the pad letter, in whole groups of 4
+};
+SchemeFacts scheme_facts(lx_scoring const & sc);
+
+// What the caller of a device-list step states about the list: its widest query and longest window (0: unknown), the run of
+// consecutive extensions that share a query (LX_OPT_QUERY_RUN), band mode's centres indexed like the list, the match rule of the
+// backtrace (LX_OPT_BS_MATCH_RULE).  The device entry points take them from the handle's options; the pipelines from their chunks.
+struct ListLimits
+{
+    uint64_t        max_qlen = 0, max_slen = 0, query_run = 0;
+    int32_t const * band_diag = nullptr;
+    uint64_t        bs_rule   = 0;
+};
+
+// ---- the rules the plans share, each written once
+// compact checkpoint codes (Ckpt16Layout) hold a gap's first character up to 31
+bool     compact_gaps_ok(SchemeFacts const & sc);
+// checkpoint slots hold int16 pairs and address 65 535 rows
+bool     fits_int16(SchemeFacts const & sc, uint64_t max_qlen, uint64_t max_slen);
+// the largest value the widest admitted query can reach in a sweep of `steps` steps of G-lane groups (the kernels test per wavefront,
+// on the actual query: this is the a-priori bound); beyond kCompactMaxScore the compact codes cannot hold it
+int64_t  score_bound(SchemeFacts const & sc, uint64_t max_qlen, uint32_t steps, int G);
+constexpr int64_t kCompactMaxScore = 2046;
+// steps of a window of max_slen rows in G-lane groups, in whole layout blocks of 16
+uint32_t steps_for(uint64_t max_slen, int G);
+// panels of `panel` columns that hold the query (at least one)
+uint32_t panels_for(uint64_t max_qlen, int panel);
+// the packed-half (pair) geometry with the same (G, C) as a checkpoint (trace) geometry: (8,19) / (8,13) / (8,25) / (16,13)
+int      pair_cfg_of(int trace_cfg);
+// carry pairs (8 bytes each) of n extensions wider than a panel: one per subject row
+uint64_t carry_pairs(uint64_t n, uint64_t max_slen);
+
+// ---- the geometry pickers
+size_t pair_lds_limit();
+int    pick_cfg(uint32_t qlen, bool shared);
+int    ckpt_cfg_for(uint64_t max_q, bool packed16 = false);
+int    mq_cfg_for(uint64_t max_q);
+
+// ---- pass 1 over a device list
+constexpr int kPair16    = 100; // ScorePlan::pair_cfg: the packed 16-bit integer kernel, any query width
+constexpr int kPair16Bin = 8;   // its bin among the packed geometries of lx_score_batch
+struct ScoreOptions
+{
+    bool     f16  = true;
+    uint64_t band = 0;
+};
+struct ScorePlan
+{
+    int      cfg = 0;                      // int32 geometry (score cfg); any geometry is correct for any query length (multi-panel path)
+    bool     multi = false, shared = false;
+    int      pair_cfg = -1, pair_share = 0; // packed kernel in front of the int32 one (-1: none; kPair16), lane groups per LDS profile
+    bool     narrow = false;               // band mode: (8,19) with one LDS profile per wavefront instead of the generic geometry
+    uint64_t band = 0;
+    bool     carry = false;                // a launch of the plan may use the carry workspace
+    uint64_t max_slen = 0;
+    int      launch_cfg() const { return band ? (narrow ? 6 : 0) : cfg; }
+    uint64_t carry_pairs(uint64_t n) const { return carry ? lxi::carry_pairs(n, max_slen) : 0; } // prepare_workspace's hint
+};
+ScorePlan plan_score(SchemeFacts const & sc, ListLimits const & lim, ScoreOptions const & o);
+// the int32 geometry of a list without query runs (lx_score_batch's bins, pass 2's own pass 1)
+ScorePlan plan_score_cfg(int cfg, bool multi, bool shared, uint64_t band, int pair_cfg = -1, int pair_share = 0);
+void      describe_score(ScorePlan const & pl, char * buf, size_t len); // what lx_last_kernel_name reports
+
+// ---- pass 2 over a device list.  share_slots = every aligned block of that many slots holds one query (0: no such guarantee); the
+// 8-lane geometry puts 8 extensions in a wavefront and needs blocks of >= 4 (two LDS profiles per wavefront).
+struct TraceOptions
+{
+    uint64_t band = 0, pass2 = 2, trace_bytes = 0;
+};
+struct TracePlan
+{
+    bool      ckpt = false;               // checkpoints (lx_ckpt.hip) instead of direction bits (lx_trace.hip)
+    int       cfg = 0, shared_profile = 0;
+    uint32_t  panels_cap = 1, steps_cap = 0;
+    uint64_t  stride = 0, per_ext = 0;    // uint32 / bytes of an extension's slot
+    uint64_t  budget_ext = 1;             // slots the trace budget holds (the launcher sizes its chunks from this and the buffer it has)
+    bool      carry = false;
+    uint64_t  max_slen = 0;
+    ScorePlan score;                      // pass 1 when no scores are handed in
+    uint64_t  carry_pairs(uint64_t n) const { return carry ? lxi::carry_pairs(n, max_slen) : 0; }
+};
+TracePlan plan_trace(SchemeFacts const & sc, ListLimits const & lim, int share_slots, TraceOptions const & o);
+void      describe_trace(TracePlan const & pl, char * buf, size_t len); // what lx_last_trace_kernel_name reports
+
+// ---- the fused step
+struct StepOptions
+{
+    uint64_t max_qlen = 0, max_slen = 0, query_run = 0, pass2 = 2, mq = 1, f16 = 1, band = 0, trace_bytes = 0, n = 0, adapt = 0;
+    int      mq_cfg = 0;
+    bool     mq_wide     = false; // the multi-query sweep writes int16-pair slots (lx_sweep_mq.hip: WIDE)
+    double   surv_frac   = -1.0;
+};
+enum SweepFamily
+{
+    kNoSweep        = 0, // pass 1, then pass 2 on the survivors (modes 0 / 1)
+    kHalfSweep      = 1, // lx_score_f16.hip score_pair_kernel<G,C,true>: packed half, compact codes, one panel
+    kI16CompactWide = 2, // lx_score_i16.hip sweep_pair16_kernel<8,19,true,true,true>: packed int16, compact codes, several panels
+    kI16Pairs       = 3, // lx_score_i16.hip sweep_pair16_kernel<G,C,MULTI>: packed int16, int16-pair slots
+    kInt32Sweep     = 4, // lx_ckpt.hip ckpt_forward_kernel<G,C,false,MULTI> alone
+    kMqSweep        = 5  // lx_sweep_mq.hip sweep_mq_kernel<C,MULTI>: byte profiles, up to four queries per wavefront
+};
+struct StepPlan
+{
+    bool        shared = false, sweep = false, adapted = false, compact = false, may_decline = true;
+    bool        packed = false; // a packed sweep's launch structure: a spare slot behind the batch's, an overflow area for what it declines
+    bool        wide   = false; // the multi-query sweep with int16-pair slots
+    SweepFamily family = kNoSweep;
+    int         cfg = 0, share = 0;
+    uint32_t    steps = 0, panels = 1;
+    uint64_t    stride = 0, stride32 = 0, ovf_cap = 0;
+};
+StepPlan plan_step(SchemeFacts const & sc, StepOptions const & o);
+void     describe_plan(StepPlan const & pl, char * buf, size_t len);
+
+} // namespace lxi

@@ -4,12 +4,12 @@ tests/test_limit_cases.py proves their true scores on the CPU):
   2046 / 2047   what the packed-half sweep and the compact 16-bit checkpoint codes hold: the a-priori bound per wavefront
                 (lx_score_f16.hip, lx_sweep_mq.hip) and the best score after the sweep (lx_score_i16.hip COMPACT && MULTI, lx_sweep_mq.hip)
   29695         0x7BFF - 2048, the biased 16-bit integer sweeps (kI16Limit, kMqLimit)
-  32000, 65535  the host's admission of checkpoint mode (lx_api.cpp)
+  32000, 65535  the host's admission of checkpoint mode (fits_int16, lx_step_plan.cpp)
   31            the gap field of the compact codes (kC16MaxGap)
 
 Every case: scores bit for bit against the oracle over the whole batch; for every survivor the record with its five counts and the op
 bytes (the run-length codes expanded, where the entry point has them); and the kernel that ran, so that no case passes through a
-fall-back.  (The single-panel COMPACT form of sweep_pair16_kernel is not here: nothing launches it -- fused_impl takes the compact
+fall-back.  (The single-panel COMPACT form of sweep_pair16_kernel is not here: nothing launches it -- plan_step takes the compact
 integer sweep only for queries wider than a panel.)"""
 import os
 import subprocess

@@ -1,4 +1,4 @@
-"""The ONE selection function of the fused step (plan_step, lambda_amd/csrc/lx_api.cpp) walked on the CPU through lx_plan_step:
+"""The ONE selection function of the fused step (plan_step, lambda_amd/csrc/lx_step_plan.cpp) walked on the CPU through lx_plan_step:
 query widths 1 ... 1 300 x query runs {0, 2, 4, 7, 8, 16, 24, 32} x the four scoring schemes of the reference's programs.  Every
 choice must be the documented one for its (width, run, alphabet) and must satisfy its own preconditions: the panels hold the
 query, the wavefront's LDS fits, compact codes only with gap costs they can hold, an int32 fix-up launch exactly where the
@@ -89,6 +89,53 @@ def test_plan_follows_budget_survivors_and_switches():
     p = capi.plan_step(wide_gap, 150, 176, 32, 1000)
     assert p.family in (capi.PLAN_I16_PAIRS, capi.PLAN_INT32) and p.compact_codes == 0
     assert capi.plan_step(wide_gap, 150, 176, 4, 1000).family == capi.PLAN_NO_SWEEP
+
+
+# one scheme per alphabet size: proteins (27 letters) and nucleotides (5).  The nucleotide one has an odd match score: with +2 / -2 the
+# a-priori bound is always even and never IS 2047.
+EDGE_SCHEMES = {
+    "protein": dict(method=62, gap_open=-11, gap_extend=-1),
+    "nucleotide": dict(method=0, match=3, mismatch=-3, gap_open=-5, gap_extend=-2),
+}
+
+
+@pytest.mark.parametrize("alphabet", list(EDGE_SCHEMES))
+@pytest.mark.parametrize("run", [32, 4])  # the packed-half sweep; the multi-query sweep
+def test_may_decline_flips_between_bounds_2046_and_2047(alphabet, run):
+    """score_bound (lx_step_plan.cpp), the a-priori bound of the widest admitted query: a one-panel packed sweep needs no int32 fix-up
+    launch up to 2046 -- what the compact codes hold -- and needs one from 2047 on.  Widths x window lengths are walked until both
+    values have turned up, so the flip is shown between neighbours and not merely somewhere."""
+    sc = capi.builtin_scoring(**EDGE_SCHEMES[alphabet])
+    want_family = capi.PLAN_HALF if run == 32 else capi.PLAN_MQ
+    seen = {}
+    for q in range(20, 153):
+        for k in range(8, 128):
+            p = capi.plan_step(sc, q, 16 * k - 7, run, 1000)  # (16 k steps of 8-lane groups)
+            if p.score_bound not in (2045, 2046, 2047, 2048) or p.panels != 1:
+                continue
+            assert p.family == want_family and p.compact_codes == 1, (q, k, p.name)
+            assert bool(p.may_decline) == (p.score_bound > 2046), (q, k, p.score_bound, p.may_decline)
+            assert (b"int32 fix-up" in p.name) == (p.score_bound > 2046), (q, k, p.name)
+            seen[p.score_bound] = seen.get(p.score_bound, 0) + 1
+    assert seen.get(2046, 0) > 0 and seen.get(2047, 0) > 0, seen
+
+
+@pytest.mark.parametrize("alphabet", list(EDGE_SCHEMES))
+def test_compact_codes_flip_between_gap_open_31_and_32(alphabet):
+    """compact_gaps_ok (lx_step_plan.cpp): the 5-bit gap field of the compact checkpoint codes holds a first gap character of up to 31.
+    At -31 the packed-half and the multi-query sweep run with compact codes; at -32 the one-query sweep writes int16 pairs and the
+    multi-query sweep, which has no other slots for one panel, does not apply."""
+    kw = dict(EDGE_SCHEMES[alphabet])
+    fits = capi.builtin_scoring(**dict(kw, gap_open=-31 - kw["gap_extend"]))
+    beyond = capi.builtin_scoring(**dict(kw, gap_open=-32 - kw["gap_extend"]))
+    assert (fits.gap_open, beyond.gap_open) == (-31, -32)  # (the scheme's gap_open is the cost of a gap's first character)
+    for q, ls in ((100, 122), (150, 176), (200, 230), (400, 442)):
+        p = capi.plan_step(fits, q, ls, 32, 1000)
+        assert p.family in (capi.PLAN_HALF, capi.PLAN_I16_COMPACT_WIDE) and p.compact_codes == 1, (q, p.name)
+        p = capi.plan_step(beyond, q, ls, 32, 1000)
+        assert p.family in (capi.PLAN_I16_PAIRS, capi.PLAN_INT32) and p.compact_codes == 0, (q, p.name)
+        assert capi.plan_step(fits, q, ls, 4, 1000).family == capi.PLAN_MQ
+        assert capi.plan_step(beyond, q, ls, 4, 1000).family == capi.PLAN_NO_SWEEP
 
 
 def test_solo_packing_only_where_sixteen_profiles_fit():
