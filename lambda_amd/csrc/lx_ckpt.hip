@@ -616,6 +616,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
 {
     using Lay               = CkptLayout<G, C>;
     using L16               = Ckpt16Layout<G, C>;
+    using LP                = CkptPairLayout<G, C>;
     constexpr int kNibDw    = (C + 7) / 8; // dwords of direction nibbles per tile row
     constexpr int kFar      = -(1 << 28);  // "minus infinity" that survives a few additions (multiple of 4)
     static_assert(kCkptEvery == 16, "the diagonal shortcut reads at most 16 residues per sequence");
@@ -652,15 +653,28 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     uint64_t panel_dw = Lay::slot_dwords(p.steps_cap), panel16_dw = L16::slot_dwords(p.steps_cap), bnd_dw = Lay::bnd_dwords(p.steps_cap);
 
     // ---- state of the extension this lane is working on
-    bool             have = false, blocked = false, done = false, need_col = false, scan = false, c16 = false;
+    bool             have = false, blocked = false, done = false, need_col = false, scan = false;
     uint64_t         po = 0;          // where the extension's record and ops slot are
     uint64_t         pos = 0;         // its position in the list
     EndCell          ec{};
     uint32_t const * slot = nullptr;
-    // compact slots whose wavefront's W = 128 / G slots are interleaved (ScoreParams::wave_slots, kEndWaveSlots): uint4 units between two
-    // groups of eight steps / two row checkpoints of ONE window, dwords from `slot` to its first row checkpoint
-    uint32_t         oct_mul = G, ck_mul = G * (L16::kCkDw / 4);
-    uint64_t         ck16_off = 0;
+    // The slot's kind, in one register (the (8,25) instantiation has none to spare): compact codes; compact slots whose wavefront's
+    // W = 128 / G slots are interleaved (ScoreParams::wave_slots, kEndWaveSlots); pair slots (kEndPairSlots, CkptPairLayout: a dword
+    // holds the codes of the two windows of a pair, `slot` is where the pair's first boundary quad is); the window is the odd one of
+    // its pair -- bit 4, so that kind & 16 is the shift that brings its half of a dword down.
+    uint32_t         kind = 0;
+    constexpr uint32_t kKindC16 = 1u, kKindPair = 2u, kKindWave = 4u, kKindOdd = 16u;
+    constexpr uint32_t kW16 = 128 / G; // windows of a packed-half wavefront
+    // compact slots: uint4 units between two groups of eight steps / two row checkpoints of ONE window (or pair)
+    static_assert(LP::bnd_quad_index(0, 8, 0) == kW16 * G, "a pair's two quads of four steps take the room of two windows' groups of eight");
+    auto oct_mul = [&]() -> uint32_t { return (kind & kKindWave) ? kW16 * G : (uint32_t)G; };
+    auto ck_mul  = [&]() -> uint32_t
+    {
+        return (kind & kKindPair)   ? LP::rowck_quad_index(0, 1, 0, 0)
+               : (kind & kKindWave) ? kW16 * G * (L16::kCkDw / 4)
+                                    : (uint32_t)(G * (L16::kCkDw / 4));
+    };
+    uint64_t         ck16_off = 0;    // compact slots: dwords from `slot` to its first row checkpoint
     uint8_t const *  q = nullptr, * s = nullptr;
     uint8_t *        ops_al = nullptr;
     uint32_t         cap = 0, a0 = 0, apos = 0, acc = 0, n = 0;
@@ -695,40 +709,55 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     bool const       rle_mode = p.rle != nullptr;
     uint32_t         run_op = 3, run_len = 0, ncodes = 0;
 
-    // Checkpoint words are int16 pairs (value, gap state).  Slots written by the packed-half sweep hold the compact
-    // codes of Ckpt16Layout instead: the loaders below expand them to the same pairs.  An extension that sweep declined
-    // has an int16-pair slot of its own in the overflow area.
+    // Checkpoint words are int16 pairs (value, gap state).  Slots written by the packed sweeps hold the compact codes of
+    // Ckpt16Layout instead -- the packed-half sweep's two windows of a pair to a dword (CkptPairLayout: every loader below takes
+    // this window's half) --: the loaders expand them to the same pairs.  An extension that sweep declined has an int16-pair
+    // slot of its own in the overflow area.
+    auto is_c16  = [&]() { return (kind & kKindC16) != 0; };
+    auto is_pair = [&]() { return (kind & kKindPair) != 0; };
     auto dec = [](uint32_t bits16) -> int { return (int)(int16_t)bits16; };
     auto expand = [](uint32_t code16) -> uint32_t
     {
         uint32_t const H = code16 & 0x7ffu;
         return H | ((H - (code16 >> 11)) << 16);
     };
+    // (pair slots: the code in the half of dword d that begins at bit sh -- two bit-field extracts, as many instructions as `expand`)
+    auto expand_half = [](uint32_t d, uint32_t sh) -> uint32_t
+    {
+        uint32_t const H = __builtin_amdgcn_ubfe(d, sh, 11u);
+        return H | ((H - __builtin_amdgcn_ubfe(d, sh + 11u, 5u)) << 16);
+    };
     // A query wider than one panel has one part per panel in its slot (int16 pairs or compact codes): global strip st = panel * G +
     // lane; a strip's step for row r is r + lane.
     // (compact codes: one part per panel as well)
-    auto bnd_of = [&](uint32_t pn) { return reinterpret_cast<uint4 const *>(slot + (uint64_t)pn * (c16 ? panel16_dw : panel_dw)); };
+    auto bnd_of = [&](uint32_t pn) { return reinterpret_cast<uint4 const *>(slot + (uint64_t)pn * (is_c16() ? panel16_dw : panel_dw)); };
     auto rowck_of = [&](uint32_t pn)
     {
-        return reinterpret_cast<uint4 const *>(slot + (c16 ? (uint64_t)pn * panel16_dw + ck16_off
+        return reinterpret_cast<uint4 const *>(slot + (is_c16() ? (uint64_t)pn * panel16_dw + ck16_off
                                                            : (uint64_t)pn * panel_dw + bnd_dw));
     };
     // Ckpt16Layout's index functions with the slots' spacing
-    auto oct16_index = [&](uint32_t o, uint32_t g_) -> uint32_t { return o * oct_mul + g_; };
-    auto ck16_index  = [&](uint32_t m_, uint32_t g_, uint32_t x_) -> uint32_t { return m_ * ck_mul + g_ * (L16::kCkDw / 4) + x_; };
+    // (uint4 that holds step k_'s code: the group of eight steps of one window, or the quad of four steps of a pair)
+    auto bnd16_index = [&](uint32_t k_, uint32_t g_) -> uint32_t { return (k_ / 8) * oct_mul() + (is_pair() ? ((k_ >> 2) & 1u) * G : 0u) + g_; };
+    auto ck16_index  = [&](uint32_t m_, uint32_t g_, uint32_t x_) -> uint32_t
+    {
+        return m_ * ck_mul() + g_ * (is_pair() ? (uint32_t)LP::kCkQuads : (uint32_t)(L16::kCkDw / 4)) + x_;
+    };
     // Word (H, F) of column c of strip st's row checkpoint m; word (H, E) of strip st's boundary at step k.  The shortcut pass wants
     // their H without waiting for it where it asks: the address of the word (a 16-bit code or an int16 pair), the load of the
     // dword around it, and the H taken from that dword later on.
     auto rowck_word_addr = [&](uint32_t m, uint32_t st, uint32_t c) -> uint8_t const *
     {
-        if (c16)
-            return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint16_t const *>(rowck_of(st / G) + ck16_index(m, st % G, c / 8)) + c % 8);
+        if (is_c16()) // (a quad holds eight columns of one window, or four of a pair)
+            return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint16_t const *>(rowck_of(st / G) + ck16_index(m, st % G, is_pair() ? c / 4 : c / 8))
+                                                     + (is_pair() ? ((c & 3u) << 1) | (kind >> 4) : c & 7u));
         return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint32_t const *>(rowck_of(st / G) + rowck_quad_index<G, Lay::kCkDw>(m, st % G, c / 4)) + c % 4);
     };
     auto bnd_word_addr = [&](uint32_t st, uint32_t k) -> uint8_t const *
     {
-        if (c16)
-            return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint16_t const *>(bnd_of(st / G) + oct16_index(k / 8, st % G)) + (k & 7));
+        if (is_c16())
+            return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint16_t const *>(bnd_of(st / G) + bnd16_index(k, st % G))
+                                                     + (is_pair() ? ((k & 3u) << 1) | (kind >> 4) : k & 7u));
         return reinterpret_cast<uint8_t const *>(reinterpret_cast<uint32_t const *>(bnd_of(st / G) + bnd_quad_index<G>(k / 4, st % G)) + (k & 3));
     };
     auto dword_around = [](uint8_t const * a) -> uint32_t
@@ -737,7 +766,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     };
     auto h_of_dword = [&](uint32_t dw, uint32_t upper_half) -> int // upper_half: bit 1 of the word's address
     {
-        return c16 ? (int)((dw >> (upper_half ? 16 : 0)) & 0x7ffu) : (int)(int16_t)(dw & 0xffffu);
+        return is_c16() ? (int)((dw >> (upper_half ? 16 : 0)) & 0x7ffu) : (int)(int16_t)(dw & 0xffffu);
     };
     // ops are produced end -> begin into the slot [0, cap): apos = misalignment of the slot start + offset of the next byte
     auto put_byte = [&](uint32_t byte)
@@ -801,7 +830,8 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
             p.out_hsp[po] = out;
             return;
         }
-        c16                = (ec.flags & kEndCompact) != 0;
+        bool const c16     = (ec.flags & kEndCompact) != 0;
+        kind               = c16 ? kKindC16 : 0u;
         uint32_t const ovf = (uint32_t)ec.flags >> kEndOverflowShift;
         slot               = ovf ? p.ovf + (uint64_t)(ovf - 1) * p.ovf_stride : p.trace + se * p.slot_stride;
         uint32_t steps_e   = p.steps_cap;
@@ -809,24 +839,32 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         {
             // the sweep's slots by wavefront (WfSlots): slot se % 16 of wavefront se / 16, laid out for that wavefront's steps and panels
             WfSlots const  t      = p.wf_tab[se / 16];
-            uint64_t const stride = (uint64_t)t.panels_cap * (c16 ? L16::slot_dwords(t.steps_cap) : Lay::slot_dwords(t.steps_cap));
+            uint64_t const stride = (uint64_t)t.panels_cap * (is_c16() ? L16::slot_dwords(t.steps_cap) : Lay::slot_dwords(t.steps_cap));
             slot                  = ((p.split_n != 0 && se >= p.split_n) ? p.trace2 : p.trace) + t.off_dw + (se % 16) * stride;
             steps_e               = t.steps_cap;
         }
         panel_dw           = Lay::slot_dwords(steps_e);
         panel16_dw         = L16::slot_dwords(steps_e);
         bnd_dw             = Lay::bnd_dwords(steps_e);
-        oct_mul            = G;
-        ck_mul             = G * (L16::kCkDw / 4);
         ck16_off           = L16::bnd_dwords(steps_e);
         if (!ovf && (ec.flags & kEndWaveSlots))
         {
-            constexpr uint32_t kW = 128 / G; // windows of a packed-half wavefront
+            constexpr uint32_t kW = kW16;
             uint64_t const     w  = se % kW;
-            slot     = p.trace + (se - w) * p.slot_stride + w * (G * 4);
-            oct_mul  = kW * G;
-            ck_mul   = kW * G * (L16::kCkDw / 4);
-            ck16_off = (uint64_t)kW * L16::bnd_dwords(steps_e) - w * (G * 4) + w * (G * L16::kCkDw);
+            kind |= kKindWave;
+            if (ec.flags & kEndPairSlots)
+            {
+                uint32_t const pr    = (uint32_t)w / 2;
+                uint32_t const first = LP::bnd_quad_index(pr, 0, 0) * 4; // dwords from the wavefront's region to the pair's first quad
+                kind |= kKindPair | (((uint32_t)w & 1u) ? kKindOdd : 0u);
+                slot     = p.trace + (se - w) * p.slot_stride + first;
+                ck16_off = (uint64_t)kW * LP::bnd_dwords(steps_e) - first + LP::rowck_quad_index(pr, 0, 0, 0) * 4;
+            }
+            else
+            {
+                slot     = p.trace + (se - w) * p.slot_stride + w * (G * 4);
+                ck16_off = (uint64_t)kW * L16::bnd_dwords(steps_e) - w * (G * 4) + w * (G * L16::kCkDw);
+            }
         }
         q                  = p.q_res + x.q_off;
         s                  = p.s_res + x.s_off;
@@ -942,13 +980,13 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     // begin_extension.  The small ones share one flag word; pointers and 64-bit offsets keep their value.
     auto park = [&](uint32_t e)
     {
-        uint32_t const flags = (blocked ? 1u : 0u) | (done ? 2u : 0u) | (need_col ? 4u : 0u) | (scan ? 8u : 0u) | (c16 ? 16u : 0u) |
+        uint32_t const flags = (blocked ? 1u : 0u) | (done ? 2u : 0u) | (need_col ? 4u : 0u) | (scan ? 8u : 0u) |
                                ((uint32_t)mode << 5) | (run_op << 7) | (run_len << 9) | (a0 << 16) | ((uint32_t)nar_cw << 18) |
                                ((uint32_t)res_col << 24);
         uint64_t const sp = reinterpret_cast<uintptr_t>(slot), qp = reinterpret_cast<uintptr_t>(q), spp = reinterpret_cast<uintptr_t>(s),
                        op = reinterpret_cast<uintptr_t>(ops_al);
         pool[0][e] = make_uint4(flags, (uint32_t)pos, (uint32_t)po, (uint32_t)ec.score);
-        pool[1][e] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), oct_mul, ck_mul);
+        pool[1][e] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), kind, 0u);
         pool[2][e] = make_uint4((uint32_t)ck16_off, (uint32_t)panel_dw, (uint32_t)panel16_dw, (uint32_t)bnd_dw);
         pool[3][e] = make_uint4((uint32_t)qp, (uint32_t)(qp >> 32), (uint32_t)spp, (uint32_t)(spp >> 32));
         pool[4][e] = make_uint4((uint32_t)op, (uint32_t)(op >> 32), cap, apos);
@@ -965,7 +1003,6 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         done     = (flags & 2u) != 0;
         need_col = (flags & 4u) != 0;
         scan     = (flags & 8u) != 0;
-        c16      = (flags & 16u) != 0;
         mode     = (int)((flags >> 5) & 3u);
         run_op   = (flags >> 7) & 3u;
         run_len  = (flags >> 9) & 127u;
@@ -976,8 +1013,7 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         po       = r[0].z;
         ec.score = (int32_t)r[0].w;
         slot     = reinterpret_cast<uint32_t const *>(((uint64_t)r[1].y << 32) | r[1].x);
-        oct_mul  = r[1].z;
-        ck_mul   = r[1].w;
+        kind     = r[1].z;
         ck16_off   = r[2].x;
         panel_dw   = r[2].y;
         panel16_dw = r[2].z;
@@ -1451,7 +1487,21 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         else
         {
             uint32_t      w[Lay::kCkDw];
-            if (c16)
+            if (is_pair())
+            {
+                uint32_t const sh = kind & kKindOdd;
+#pragma unroll
+                for (int xq = 0; xq < LP::kCkQuads; ++xq)
+                {
+                    uint4 const    v    = rowck[ck16_index((uint32_t)(m - 1), (uint32_t)gl, (uint32_t)xq)];
+                    uint32_t const d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (4 * xq + b < Lay::kCkDw)
+                            w[4 * xq + b] = expand_half(d[b], sh);
+                }
+            }
+            else if (is_c16())
             {
 #pragma unroll
                 for (int xq = 0; xq < L16::kCkDw / 4; ++xq)
@@ -1512,11 +1562,18 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         {
             if (!has_left || qd + qshift < 0)
                 return make_uint4(0, 0, 0, 0);
-            if (c16)
+            if (is_pair())
+            {
+                // the pair's quad of four steps: this window's halves
+                uint32_t const sh = kind & kKindOdd;
+                uint4 const    v  = bndL[bnd16_index(4u * (uint32_t)(qd + qshift), (uint32_t)gL)];
+                return make_uint4(expand_half(v.x, sh), expand_half(v.y, sh), expand_half(v.z, sh), expand_half(v.w, sh));
+            }
+            if (is_c16())
             {
                 // half of the 16-byte group of eight steps
                 int const   qs = qd + qshift;
-                uint2 const v  = reinterpret_cast<uint2 const *>(bndL + oct16_index((uint32_t)qs / 2, (uint32_t)gL))[qs & 1];
+                uint2 const v  = reinterpret_cast<uint2 const *>(bndL + bnd16_index(8u * ((uint32_t)qs / 2), (uint32_t)gL))[qs & 1];
                 return make_uint4(expand(v.x & 0xffffu), expand(v.x >> 16), expand(v.y & 0xffffu), expand(v.y >> 16));
             }
             return bndL[bnd_quad_index<G>((uint32_t)(qd + qshift), (uint32_t)gL)];
@@ -1534,7 +1591,8 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
         {
             if (__ballot(r_base + 4 * t <= i) == 0)
                 break;
-            uint4 const qnext = load_bq(qd0 + t + 1); // needed by the next iteration
+            // needed by the next iteration (the last one has none: in pair slots that quad is a line of its own)
+            uint4 const qnext = t + 1 < kCkptEvery / 4 ? load_bq(qd0 + t + 1) : make_uint4(0, 0, 0, 0);
             // subject letters of the 4 rows r_base + 4t ... (rows < 0 are virtual and skipped), loaded one iteration ahead
             // (reads run into the slack behind the residues at most)
             int const      row0 = r_base + 4 * t;
@@ -1752,7 +1810,17 @@ uint64_t ckpt_slot_dwords(int cfg, uint32_t steps_cap)
                       : CkptLayout<8, 19>::slot_dwords(steps_cap);
 }
 
-// compact slots of the packed-half sweep
+// pair slots of the packed-half sweep: what one window accounts for (a wavefront's region holds 128 / G of them)
+uint64_t ckpt_pair_slot_dwords(int cfg, uint32_t steps_cap)
+{
+    return cfg == 2   ? CkptPairLayout<16, 13>::slot_dwords(steps_cap)
+           : cfg == 3 ? CkptPairLayout<8, 13>::slot_dwords(steps_cap)
+           : cfg == 4 ? CkptPairLayout<8, 25>::slot_dwords(steps_cap)
+           : cfg == 5 ? CkptPairLayout<8, 11>::slot_dwords(steps_cap)
+                      : CkptPairLayout<8, 19>::slot_dwords(steps_cap);
+}
+
+// compact slots of the multi-query and the packed-int16 sweep
 uint64_t ckpt16_slot_dwords(int cfg, uint32_t steps_cap)
 {
     return cfg == 2   ? Ckpt16Layout<16, 13>::slot_dwords(steps_cap)

@@ -25,7 +25,8 @@ struct ScoringDev
     // "diagonal"), pad ranks = -125.  Valid when every (matrix - ge) lies in [-31, 31] (trace_ok).
     int8_t  mat_trace[kAlph * kAlph];
     int32_t trace_ok;
-    // packed-half pass 1 (lx_score_f16.hip): (matrix - ge) as IEEE half bits, pad ranks = -100; per query rank the
+    // packed-half pass 1 (lx_score_f16.hip): (matrix - ge) * 2^-24 as IEEE half bits (the kernel's unit: subnormals whose
+    // magnitude bits are the integer), pad ranks = -100; per query rank the
     // largest positive score of its row (upper bound of what one query column can contribute); largest entry
     int32_t  smax;
     int32_t  b8_ok;       // mat_b8 is valid: every real entry satisfies 0 <= matrix - go <= 255
@@ -96,13 +97,14 @@ struct ScoreParams
     WfSlots const *    wf_tab;
     uint32_t           wf_lo;
     // single sweep (lx_ckpt.hip layout): when set, the packed-half kernel also writes strip boundaries, row checkpoints
-    // (as the compact 16-bit codes of Ckpt16Layout) and the end cell of every extension
-    uint32_t *         ckpt;        // [n + 1] slots of ckpt_stride uint32 (the last one is the spare slot idle halves write to)
+    // (as compact 16-bit codes, Ckpt16Layout) and the end cell of every extension
+    uint32_t *         ckpt;        // ceil(n / W) * W slots of ckpt_stride uint32, W = 2 * 64 / G windows per wavefront
     uint64_t           ckpt_stride;
-    // 1 (set for the packed-half sweep, which always lays its slots out like this): the W = 2 * 64 / G slots of a wavefront's windows are INTERLEAVED piece by piece -- group
-    // of eight steps o of window w at [o][w][lane], row checkpoint m at [m][w][lane][quad] behind all boundary groups -- so that
-    // what one store instruction writes (the same piece of 16 windows) is one contiguous 2 KB instead of 16 lines 7.7 KB apart;
-    // the buffer holds ceil(n / W) * W slots, no spare one.  The end cell says so (kEndWaveSlots), the backtrace reads accordingly.
+    // 1 (set for the packed-half sweep, which always lays its slots out like this): the W slots of a wavefront's windows are one
+    // region, INTERLEAVED piece by piece, so that what one store instruction writes (the same piece of all its windows) is one
+    // contiguous 2 KB instead of 16 lines 7.7 KB apart.  Inside the region the packed-half sweep keeps the codes of a PAIR of
+    // windows in one dword (CkptPairLayout below).  The end cell says so (kEndWaveSlots | kEndPairSlots), the backtrace reads
+    // accordingly.
     int32_t            wave_slots;
     uint32_t           steps_cap;
     struct EndCell *   ends;        // [n]
@@ -131,6 +133,8 @@ constexpr int     kEndOverflowShift = 8; // flags >> 8 = 1 + index of the extens
 constexpr int     kEndNarrowShift   = 2;
 // the compact slots of the extension's WAVEFRONT are interleaved (ScoreParams::wave_slots): bit 4
 constexpr int32_t kEndWaveSlots     = 16;
+// the wavefront's slots hold the codes of a PAIR of windows in one dword (CkptPairLayout below): bit 5, beside kEndWaveSlots
+constexpr int32_t kEndPairSlots     = 32;
 __host__ __device__ constexpr int narrow_strip_cols(int C, int code) { return code == 0 ? C : code == 1 ? (3 * C + 3) / 4 : code == 2 ? (C + 1) / 2 : (C + 3) / 4; }
 constexpr int kNarrowest = 3; // the code of the narrowest strips
 // the code for a panel that has `rem` columns of the query left (rem >= 1), G lanes per group
@@ -139,7 +143,8 @@ __host__ __device__ constexpr int narrow_code_for(int C, int G, int rem)
     return rem <= G * ((C + 3) / 4) ? 3 : rem <= G * ((C + 1) / 2) ? 2 : rem <= G * ((3 * C + 3) / 4) ? 1 : 0;
 }
 
-// Compact checkpoint slots of the packed-half single sweep (lx_score_f16.hip writes, lx_ckpt.hip's backtrace reads).
+// Compact checkpoint slots (the multi-query and the packed-int16 sweep write them, lx_ckpt.hip's backtrace reads; the packed-half
+// single sweep writes the same codes into CkptPairLayout, below).
 // A boundary pair (H of a strip's last column, E entering the next strip) and a row-checkpoint pair (H of a cell, the
 // folded F entering the cell below) always satisfy  0 <= H - other <= |cost of a gap's first character|  (E >= H + go and
 // E <= H + ge because E of the same cell is <= H; likewise F), and the packed-half kernel only runs when every value
@@ -161,6 +166,38 @@ struct Ckpt16Layout
     __host__ __device__ static constexpr uint32_t rowck_quad_index(uint32_t m, uint32_t g, uint32_t x)
     {
         return (m * G + g) * (kCkDw / 4) + x; // lane-major (quad-major was measured in round 2: no difference)
+    }
+};
+
+// Pair slots (kEndPairSlots): what the packed-half single sweep writes.  Its registers hold the codes of the two windows of a
+// lane group side by side -- window A = the even one of the pair in the low half of a dword, window B in the high half -- and
+// the slots keep them so: a code dword is stored as the register holds it, and a reader takes its window's half by the window's
+// parity.  The W = 128 / G windows of a wavefront are W / 2 pairs; `slot_dwords` below is what ONE window accounts for (a
+// wavefront's region holds W of them, as with kEndWaveSlots), boundary groups first:
+//   boundary codes:  [step / 8][pair][(step / 4) & 1][lane] 16-byte quads of 4 steps' dwords -- a quad store of the G lanes of a
+//                    group fills a whole 128-byte line;
+//   row checkpoints: [checkpoint][pair][lane][column / 4] 16-byte quads of 4 columns' dwords, every 16 steps, behind all boundary
+//                    groups of the wavefront.
+// The codes themselves are Ckpt16Layout's.
+template <int G, int C>
+struct CkptPairLayout
+{
+    static constexpr int kPairs = 64 / G;      // pairs of windows per wavefront
+    static constexpr int kCkQuads = (C + 3) / 4; // 16-byte quads per lane and pair per row checkpoint
+    __host__ __device__ static constexpr uint64_t bnd_dwords(uint32_t steps_cap) { return (uint64_t)steps_cap / 2 * G; } // per window
+    __host__ __device__ static constexpr uint64_t slot_dwords(uint32_t steps_cap)
+    {
+        return bnd_dwords(steps_cap) + (uint64_t)(steps_cap / 16) * G * (kCkQuads * 2);
+    }
+    // uint4 index, from the wavefront's region, of the quad of steps 4 (k / 4) .. of lane g / from its first row checkpoint, of
+    // quad x of lane g's checkpoint m
+    __host__ __device__ static constexpr uint32_t bnd_quad_index(uint32_t pair, uint32_t k, uint32_t g)
+    {
+        return (((k / 8) * kPairs + pair) * 2 + ((k / 4) & 1)) * G + g;
+    }
+    __host__ __device__ static constexpr uint32_t rowck_quad_index(uint32_t pair, uint32_t m, uint32_t g, uint32_t x)
+    {
+        return ((m * kPairs + pair) * G + g) * kCkQuads + x;
     }
 };
 

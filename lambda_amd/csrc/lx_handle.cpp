@@ -421,10 +421,8 @@ int lx_set_scoring(lx_handle * h, int slot, lx_scoring const * sc)
         {
             bool const pad = a >= sc->alphabet_size || b >= sc->alphabet_size;
             int const  v   = pad ? lx::kNegPad : sc->matrix[a * LX_ALPH + b] - sc->gap_extend;
-            _Float16 const hv = (_Float16)(float)v; // integers of magnitude <= 128: exact
-            uint16_t       bits;
-            std::memcpy(&bits, &hv, 2);
-            d.mat_h[a * lx::kAlph + b]   = bits;
+            // v * 2^-24 as a half: a subnormal whose magnitude bits are |v| itself (|v| <= 131)
+            d.mat_h[a * lx::kAlph + b]   = (uint16_t)(v < 0 ? 0x8000 | -v : v);
             d.mat_i16[a * lx::kAlph + b] = (int16_t)v;
             if (!pad)
             {

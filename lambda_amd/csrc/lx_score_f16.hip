@@ -3,8 +3,10 @@
 // Same strip-systolic mapping and row-skewed recurrence as lx_score.hip (see there for the reference lines), but
 // every VGPR holds the DP value of TWO extensions (A in the low half, B in the high half) that share the query, and
 // the arithmetic is v_pk_add_f16 / v_pk_maximum3_f16.  On gfx950 the packed ops issue at the same rate as the
-// int32 max/max3 (tools/ubench.hip), so a cell costs 7.5 issue slots instead of 11.  Scores are small integers;
-// half precision represents every integer of magnitude <= 2048 exactly and -inf stands in for "minus infinity", so
+// int32 max/max3 (tools/ubench.hip), so a cell costs 7.5 issue slots instead of 11.  Scores are small integers, and
+// the kernel computes on them in units of 2^-24 (hunits below: subnormals and the first binade, on which gfx950 issues
+// at the same rate -- profiles/r11_ubench_subnormal.txt): half precision represents every n * 2^-24 with |n| <= 2048
+// exactly and -inf stands in for "minus infinity", so
 // the results are bit-identical to the int32 kernel AS LONG AS no intermediate exceeds 2048.  That is decided per
 // wavefront from an upper bound:
 //         sum_j max(0, max_b s(q_j, b))  +  |ge| * (rows processed)  +  max entry  <=  2046
@@ -43,10 +45,6 @@ __device__ __forceinline__ h2 hmax(h2 a, h2 b)
 {
     return __builtin_elementwise_maximum(a, b);
 }
-__device__ __forceinline__ h2 hsplat(float x)
-{
-    return h2{(_Float16)x, (_Float16)x};
-}
 __device__ __forceinline__ h2 as_h2(uint32_t x)
 {
     return __builtin_bit_cast(h2, x);
@@ -56,16 +54,26 @@ __device__ __forceinline__ uint32_t as_u32(h2 x)
     return __builtin_bit_cast(uint32_t, x);
 }
 
+// The kernel's unit is 2^-24: the integer n stands as n * 2^-24, a half-precision subnormal (|n| < 1024) or a value of the
+// first binade, both spaced 2^-24 -- sums and maxima of such values are as exact as those of the integers themselves as long
+// as |n| <= 2047, and the bit pattern of a non-negative value IS n (FP16 denormals are on in the kernel descriptor, the
+// compiler's default).  Minus infinity stays 0xfc00.  (a gap cost beyond -2047 acts like -2047: no value reaches that far)
+__device__ __forceinline__ h2 hunits(int n)
+{
+    uint32_t const m = (uint32_t)min(n < 0 ? -n : n, 2047);
+    return as_h2((n < 0 ? 0x8000u | m : m) * 0x10001u);
+}
+__device__ __forceinline__ int units_of(uint32_t half_bits) // of a value >= 0
+{
+    return (int)(half_bits & 0x7fffu);
+}
 constexpr uint32_t kHalfNegInf2 = 0xfc00fc00u; // (-inf, -inf)
 
-// Ckpt16Layout codes without a conversion instruction: an integer n in 0 .. 2047 scaled by 2^-24 is a half-precision
-// subnormal (n < 1024) or lies in the first binade (spacing 2^-24 as well), so the bit pattern of n * 2^-24 is n itself
-// (FP16 denormals are on in the kernel descriptor, the compiler's default).  Scaling by a power of two and adding
-// multiples of 2^-24 below 2048 * 2^-24 is exact.
-constexpr uint32_t kHalfTwoPowMinus24x2 = 0x00010001u; // (2^-24, 2^-24)
-__device__ __forceinline__ uint32_t c16_pack(h2 value_scaled, h2 diff_scaled)
+// Ckpt16Layout codes without a conversion instruction: both fields are non-negative values in the kernel's unit, whose bit
+// patterns are the integers themselves.
+__device__ __forceinline__ uint32_t c16_pack(h2 value, h2 diff)
 {
-    return (as_u32(diff_scaled) << 11) | as_u32(value_scaled); // both halves at once: diff < 32 stays inside its half
+    return (as_u32(diff) << 11) | as_u32(value); // both halves at once: diff < 32 stays inside its half
 }
 
 template <int G, int C>
@@ -81,7 +89,7 @@ struct PairGeo
 };
 
 // CKPT = single sweep: the kernel additionally writes what pass 2's backtrace needs (layout and meaning as in
-// lx_ckpt.hip: strip boundaries per step, row checkpoints every 16 steps, here as the compact codes of Ckpt16Layout) and
+// lx_ckpt.hip: strip boundaries per step, row checkpoints every 16 steps, here as the compact codes of CkptPairLayout) and
 // keeps, per strip and extension, the best value, the block of sixteen steps whose rows reached it first and whether a later block tied.
 template <int G, int C, bool CKPT>
 __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) void score_pair_kernel(ScoreParams p) // (25-column strips: 168 VGPRs spill, and their LDS profile leaves 9 wavefronts per CU anyway)
@@ -218,7 +226,7 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
         return;
     }
 
-    // ---- profile: prof[t][g][h] = (s(q_col, t) - ge) as half, lane-contiguous
+    // ---- profile: prof[t][g][h] = (s(q_col, t) - ge) as half (in the kernel's unit, as ScoringDev::mat_h holds it), lane-contiguous
     // Built by every lane of the block that shares it.  A unit of work is one dword column d of one strip (two query columns)
     // for eight letters: one 16-byte load from the matrix row of either column, eight permutes, eight LDS writes.  The units are
     // dealt round robin; letters at or beyond nrows are not built (the small alphabets have one group of eight).
@@ -265,8 +273,8 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     uint32_t const row_base  = (uint32_t)(slot_dw + g * Geo::kLaneDw) * 4u;
     constexpr uint32_t kRowBytes = Geo::kRowDw * 4;
 
-    h2 const GE = hsplat((float)ge), G2 = hsplat((float)sc->g2), NGE = hsplat((float)-ge);
-    h2       Z  = hsplat((float)(ge * g)); // z_i of the first processed row i = -g
+    h2 const GE = hunits(ge), G2 = hunits(sc->g2), NGE = hunits(-ge);
+    h2       Z  = hunits(ge * g); // z_i of the first processed row i = -g
     h2       Hrow[C], F0[C];
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -278,23 +286,22 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     h2 sendH = Z + GE;
     h2 sendE = as_h2(kHalfNegInf2);
     h2 recvE = as_h2(kHalfNegInf2); // E from the left: the shift's own `old`, so a group's first lane stays at -inf for good
-    h2 best  = hsplat(0.f);
+    h2 best  = hunits(0);
     // CKPT: first row that reached this strip's best value, "a later row reached it again" (bit 0 = A, bit 1 = B)
     int      rowA = 0, rowB = 0;
     uint32_t tie  = 0;
-    h2 const C24 = as_h2(kHalfTwoPowMinus24x2), NC24 = -C24, GEc = GE * C24;
-    h2       nZc = -(Z * C24); // -Z 2^-24, kept in step with Z
     h2       cmax = as_h2(kHalfNegInf2); // best un-skewed row maximum of the current chunk
-    using Lay = Ckpt16Layout<G, C>;
-    // (slot p.n is a spare one that idle halves write to; wave_slots: the W slots of this wavefront interleaved piece by piece --
-    // lx_device.h --, every half owns its place there)
+    // Pair slots (CkptPairLayout, lx_device.h): the region of this wavefront's W windows holds the code dwords as the registers
+    // do, window A in the low half and B in the high one -- nothing is re-paired on the way out.  An idle half's codes ride along
+    // in its pair's dwords; nobody reads them.
+    using Lay = CkptPairLayout<G, C>;
     constexpr uint32_t kW       = 2 * Geo::kGroups;
-    constexpr bool     wslots   = CKPT; // (always, for this kernel's checkpoints: a run-time choice costs the steady loop its registers)
-    uint32_t * const   waveBase = CKPT ? p.ckpt + (uint64_t)blockIdx.x * kW * p.ckpt_stride : nullptr;
-    uint32_t * const   slotA    = !CKPT ? nullptr : wslots ? waveBase + (2 * grp) * (G * 4) : p.ckpt + (actA ? eA : p.n) * p.ckpt_stride;
-    uint32_t * const   slotB    = !CKPT ? nullptr : wslots ? waveBase + (2 * grp + 1) * (G * 4) : p.ckpt + (actB ? eB : p.n) * p.ckpt_stride;
-    uint32_t const     octMul   = wslots ? kW * G : G;                          // uint4 units between two groups of eight steps
-    uint32_t const     ckMul    = (wslots ? kW * G : G) * (Lay::kCkDw / 4);     // ... between two row checkpoints
+    uint4 * const      waveBase = CKPT ? reinterpret_cast<uint4 *>(p.ckpt + (uint64_t)blockIdx.x * kW * p.ckpt_stride) : nullptr;
+    uint4 * const      bndBase  = CKPT ? waveBase + Lay::bnd_quad_index((uint32_t)grp, 0, (uint32_t)g) : nullptr;
+    uint4 * const      ckBase   = CKPT ? waveBase + kW * (uint32_t)(Lay::bnd_dwords(p.steps_cap) / 4) + Lay::rowck_quad_index((uint32_t)grp, 0, (uint32_t)g, 0) : nullptr;
+    constexpr uint32_t kOctMul  = Lay::bnd_quad_index(0, 8, 0);      // uint4 units between two groups of eight steps
+    constexpr uint32_t kHalfOct = Lay::bnd_quad_index(0, 4, 0);      // ... between the two quads of a group
+    constexpr uint32_t kCkMul   = Lay::rowck_quad_index(0, 1, 0, 0); // ... between two row checkpoints
     // staging of the boundary codes: [step % 8][lane] -- lane-minor, free of bank conflicts
     uint32_t * const stage = lds + ((Geo::kGroups + share_g - 1) / share_g) * (nrows * Geo::kRowDw) + lane;
 
@@ -354,19 +361,19 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
         h2 const cand = rowmax - Z;
         if constexpr (CKPT)
         {
-            cmax = hmax(cmax, cand); // the rose / met-again logic runs once per block of sixteen steps (book)
+            // (the rose / met-again logic runs once per block of sixteen steps -- book; the main loop's two unrolled steps share one
+            // v_pk_maximum3_f16 for this: the compiler folds the two maxima)
+            cmax = hmax(cmax, cand);
             // un-skewed boundary pair (H of the strip's last column, E as the next strip's first column uses it) as
-            // Ckpt16Layout codes of both extensions, staged for one 16-byte store per extension every eight steps
-            h2 const hc           = h * C24;
-            stage[slot8 * 64]     = c16_pack(hc + nZc, __builtin_elementwise_fma(Ecur, NC24, hc));
-            nZc                   = nZc + GEc; // Z grows by -ge per step
+            // 16-bit codes of both extensions in one dword, staged for two 16-byte stores per pair every eight steps
+            stage[slot8 * 64] = c16_pack(h - Z, h - Ecur);
         }
         else
             best = hmax(best, cand);
         Z = ZN;
     };
-    // CKPT: the staged codes of the eight steps up to k0 + 3 leave, re-paired per extension.  Unconditional (an idle half
-    // owns the spare slot behind the batch): whole 128-byte lines per lane group, no branch around the stores.
+    // CKPT: the staged codes of the eight steps up to k0 + 3 leave as they stand, two quads of four steps: whole 128-byte lines
+    // per lane group, no branch around the stores.
     auto flush_codes = [&](int k0)
     {
         if constexpr (CKPT)
@@ -375,11 +382,9 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 cw[u] = stage[u * 64];
-            uint32_t const oi = ((uint32_t)k0 / 8) * octMul + (uint32_t)g; // (Lay::bnd_oct_index with the slots' spacing)
-            reinterpret_cast<uint4 *>(slotA)[oi] = make_uint4(__builtin_amdgcn_perm(cw[1], cw[0], 0x05040100u), __builtin_amdgcn_perm(cw[3], cw[2], 0x05040100u),
-                                                              __builtin_amdgcn_perm(cw[5], cw[4], 0x05040100u), __builtin_amdgcn_perm(cw[7], cw[6], 0x05040100u));
-            reinterpret_cast<uint4 *>(slotB)[oi] = make_uint4(__builtin_amdgcn_perm(cw[1], cw[0], 0x07060302u), __builtin_amdgcn_perm(cw[3], cw[2], 0x07060302u),
-                                                              __builtin_amdgcn_perm(cw[5], cw[4], 0x07060302u), __builtin_amdgcn_perm(cw[7], cw[6], 0x07060302u));
+            uint4 * const dst = bndBase + ((uint32_t)k0 / 8) * kOctMul;
+            dst[0]        = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+            dst[kHalfOct] = make_uint4(cw[4], cw[5], cw[6], cw[7]);
         }
     };
     // CKPT: the best-value bookkeeping, once per block of sixteen steps (the backtrace's tiles are these blocks: its first tile looks
@@ -423,31 +428,21 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
         if constexpr (CKPT)
         {
             // Hrow is in the frame of the row just processed (z_i = Z + ge after the update), F0 in the next row's:
-            // H - F un-skewed = (Hrow - z_i) - (F0 - Z) = Hrow - F0 - ge
-            h2 const nzic = nZc - GEc, nGEc = -GEc; // -(Z + ge) 2^-24, -ge 2^-24
-            uint32_t code[2 * Lay::kCkDw];
+            // H - F un-skewed = (Hrow - z_i) - (F0 - Z) = Hrow - F0 - ge.  (Hrow - F0 alone is no field for a code: the folded F has
+            // the floor 0 of the local alignment in it, so where H < -ge the difference is negative.)
+            h2 const      zi  = Z + GE;
+            uint4 * const dst = ckBase + ((uint32_t)(k0 + 3) / 16) * kCkMul;
 #pragma unroll
-            for (int c = 0; c < 2 * Lay::kCkDw; ++c)
-                code[c] = c < C ? c16_pack(__builtin_elementwise_fma(Hrow[c < C ? c : 0], C24, nzic),
-                                           __builtin_elementwise_fma(Hrow[c < C ? c : 0] - F0[c < C ? c : 0], C24, nGEc))
-                                : 0u;
-            uint32_t const base0 = (uint32_t)(Lay::bnd_dwords(p.steps_cap) / 4);
-            uint4 * const  dA = wslots ? reinterpret_cast<uint4 *>(waveBase) + kW * base0 + (2 * grp) * (G * (Lay::kCkDw / 4)) : reinterpret_cast<uint4 *>(slotA) + base0;
-            uint4 * const  dB = wslots ? reinterpret_cast<uint4 *>(waveBase) + kW * base0 + (2 * grp + 1) * (G * (Lay::kCkDw / 4)) : reinterpret_cast<uint4 *>(slotB) + base0;
-#pragma unroll
-            for (int x = 0; x < Lay::kCkDw / 4; ++x)
+            for (int x = 0; x < Lay::kCkQuads; ++x)
             {
-                uint32_t wa[4], wb[4];
+                uint32_t code[4]; // columns 4 x .. 4 x + 3 of both windows
 #pragma unroll
                 for (int b = 0; b < 4; ++b)
                 {
-                    int const c = 2 * (4 * x + b); // columns c, c + 1 of extension A (low halves) / B (high halves)
-                    wa[b]       = __builtin_amdgcn_perm(code[c + 1], code[c], 0x05040100u);
-                    wb[b]       = __builtin_amdgcn_perm(code[c + 1], code[c], 0x07060302u);
+                    int const c = 4 * x + b;
+                    code[b]     = c < C ? c16_pack(Hrow[c < C ? c : 0] - zi, (Hrow[c < C ? c : 0] - F0[c < C ? c : 0]) + NGE) : 0u;
                 }
-                uint32_t const qi = ((uint32_t)(k0 + 3) / 16) * ckMul + (uint32_t)g * (Lay::kCkDw / 4) + (uint32_t)x; // (Lay::rowck_quad_index, spaced)
-                dA[qi] = make_uint4(wa[0], wa[1], wa[2], wa[3]);
-                dB[qi] = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+                dst[x] = make_uint4(code[0], code[1], code[2], code[3]);
             }
         }
     };
@@ -551,9 +546,9 @@ LX_UNROLL(LX_F16_UNROLL)
         if (is_first)
         {
             if (actA)
-                p.out_score[eA] = (int)(float)best.x;
+                p.out_score[eA] = units_of(as_u32(best));
             if (actB)
-                p.out_score[eB] = (int)(float)best.y;
+                p.out_score[eB] = units_of(as_u32(best) >> 16);
         }
     }
     else
@@ -580,14 +575,14 @@ LX_UNROLL(LX_F16_UNROLL)
                     ec.score = gbest;
                     ec.q_end = -(gstrip + 1); // the backtrace finds the column inside this strip
                     ec.s_end = grow + 1;
-                    ec.flags = (gtie ? kEndAmbiguous : 0) | kEndCompact | kEndWaveSlots; // compact slot, interleaved per wavefront
+                    ec.flags = (gtie ? kEndAmbiguous : 0) | kEndCompact | kEndWaveSlots | kEndPairSlots; // compact codes, a pair per dword
                 }
                 p.ends[e]      = ec;
                 p.out_score[e] = gbest;
             }
         };
-        finish((int)(float)best.x, rowA, (int)(tie & 1u), actA, eA);
-        finish((int)(float)best.y, rowB, (int)((tie >> 1) & 1u), actB, eB);
+        finish(units_of(as_u32(best)), rowA, (int)(tie & 1u), actA, eA);
+        finish(units_of(as_u32(best) >> 16), rowB, (int)((tie >> 1) & 1u), actB, eB);
     }
 }
 

@@ -406,7 +406,8 @@ SweepCand one_query_candidate(SchemeFacts const & sc, StepOptions const & o, Swe
     }
     if (c.packed)
     {
-        c.stride = (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.cfg, c.steps);
+        // (the packed-half sweep keeps a pair of windows in one dword: CkptPairLayout, never larger than two Ckpt16Layout slots)
+        c.stride = c.wide_compact ? (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.cfg, c.steps) : lx::ckpt_pair_slot_dwords(c.cfg, c.steps);
         c.runs   = packed_fits(o, c.stride);
         // (the packed kernel cannot decline when even the worst query passes its test)
         c.may_decline = score_bound(sc, o.max_qlen, c.steps, G) > kCompactMaxScore || c.wide_compact;

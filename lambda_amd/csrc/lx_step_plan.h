@@ -23,6 +23,7 @@ int      trace_cfg_group(int cfg);
 int      trace_cfg_words(int cfg);
 uint64_t ckpt_slot_dwords(int cfg, uint32_t steps_cap);
 uint64_t ckpt16_slot_dwords(int cfg, uint32_t steps_cap);
+uint64_t ckpt_pair_slot_dwords(int cfg, uint32_t steps_cap);
 size_t   sweep_mq_lds_bytes(int trace_cfg, int nrows, int share);
 } // namespace lx
 

@@ -4,6 +4,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #define CHECK(x)                                                                             \
@@ -154,6 +155,33 @@ DEF_KERNEL(k_addf16hi, I_ADDF16HI) DEF_KERNEL(k_addf16sel, I_ADDF16SEL) DEF_KERN
 DEF_KERNEL(k_madu16hi, I_MADU16HI) DEF_KERNEL(k_mixhi, I_MIXHI) DEF_KERNEL(k_mixlo, I_MIXLO)
 DEF_KERNEL(k_cnds, I_CNDS) DEF_KERNEL(k_bfi, I_BFI) DEF_KERNEL(k_pkaddsel, I_PKADDSEL) DEF_KERNEL(k_pkfma, I_PKFMA)
 
+// round 11: do the packed half add and maximum issue as fast on SUBNORMAL operands (bit patterns 1 .. 0x3ff, what the packed-half
+// sweep computes on once its unit is 2^-24) as on normal ones?  The kernels above start from small integers' bit patterns and add
+// without bound, so most of their operands are infinities or NaNs; here the operands stay where they start: the chains add x and
+// -x in turn (or take the maximum with x and -x).  A0 / X0 are the bit patterns of one half at lane 0, both halves carry the same.
+#define DEF_KERNEL_F16(NAME, INS_A, INS_B, A0, X0)                                                     \
+    __global__ __launch_bounds__(256) void NAME(int * out, int iters, int, int)                        \
+    {                                                                                                  \
+        int const t  = threadIdx.x;                                                                    \
+        int const b  = ((A0) + (t & 0x1ff)) * 0x10001;                                                 \
+        int a0 = b, a1 = b + 0x10001, a2 = b + 0x20002, a3 = b + 0x30003, a4 = b + 0x40004,            \
+            a5 = b + 0x50005, a6 = b + 0x60006, a7 = b + 0x70007;                                      \
+        int const vx = ((X0) + (t & 0xff)) * 0x10001, vy = vx | (int)0x80008000u;                      \
+        for (int i = 0; i < iters; ++i)                                                                \
+        {                                                                                              \
+            asm volatile(REP8(INS_A) REP8(INS_B) REP8(INS_A) REP8(INS_B)                               \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) \
+                         : "v"(vx), "v"(vy));                                                          \
+        }                                                                                              \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;            \
+    }
+#define I_PKADDF_NEG(R) "v_pk_add_f16 " R ", " R ", %9\n"
+// subnormal: a in 1 .. 0x207, x in 1 .. 0x100 (a + x <= 0x307); normal: a in [4, 6), x in [1, 1.25)
+DEF_KERNEL_F16(k_pkaddf_sub, I_PKADDF, I_PKADDF_NEG, 1, 1)
+DEF_KERNEL_F16(k_pkaddf_nrm, I_PKADDF, I_PKADDF_NEG, 0x4400, 0x3c00)
+DEF_KERNEL_F16(k_pkmax3f_sub, I_PKMAX3F, I_PKMAX3F, 1, 1)
+DEF_KERNEL_F16(k_pkmax3f_nrm, I_PKMAX3F, I_PKMAX3F, 0x4400, 0x3c00)
+
 // LDS: ds_read_b32 with a lane-linear address pattern
 __global__ __launch_bounds__(256) void k_lds_b32(int * out, int iters, int x, int y)
 {
@@ -204,13 +232,32 @@ static void run(char const * name, kern_t k, int * d_out, int waves_per_simd, do
            waves_per_simd, best, rate * 1e-12, rate / (cus * 2.4e9), ops_per_instr, rate * ops_per_instr * 1e-12);
 }
 
-int main()
+// `ubench.bin subnormal`: only these lines, three times each (their run-to-run spread is what the comparison is read against)
+static void run_subnormal(int * d_out)
+{
+    printf("---- packed half add / maximum3 on normal and on subnormal operands\n");
+    for (int w : {3, 8})
+        for (int rep = 0; rep < 3; ++rep)
+        {
+            run("pk_add_f16 normal", k_pkaddf_nrm, d_out, w, 2);
+            run("pk_add_f16 subnormal", k_pkaddf_sub, d_out, w, 2);
+            run("pk_maximum3_f16 normal", k_pkmax3f_nrm, d_out, w, 4);
+            run("pk_maximum3_f16 subnormal", k_pkmax3f_sub, d_out, w, 4);
+        }
+}
+
+int main(int argc, char ** argv)
 {
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     printf("device: %s  arch=%s  CUs=%d  clock=%d kHz\n", prop.name, prop.gcnArchName, prop.multiProcessorCount, prop.clockRate);
     int * d_out;
     CHECK(hipMalloc(&d_out, 256 * 64 * 256 * sizeof(int)));
+    if (argc > 1 && std::string(argv[1]) == "subnormal")
+    {
+        run_subnormal(d_out);
+        return 0;
+    }
     struct
     {
         char const * n;
@@ -252,5 +299,6 @@ int main()
         run("sweep_mix(x7)", k_sweepmix, d_out, w, 7);
         run("sweep_mix2(x7)", k_sweepmix2, d_out, w, 7);
     }
+    run_subnormal(d_out);
     return 0;
 }
