@@ -639,6 +639,28 @@ void lx_tax_dev_destroy(lx_tax_dev * t);
 int  lx_compute_lca_dev(lx_handle * h, lx_tax_dev const * t, lx_blast_match const * m, uint64_t n, lx_lca_options const * opt,
                         uint64_t * out_qid, uint32_t * out_lca, uint64_t * out_n);
 
+/* ---- restricting a search to taxa of the index (BLAST's -taxids / -negative_taxids, DIAMOND's --taxonlist / --taxon-exclude) ----
+ * Which subjects a list of taxa keeps.  The chain of a taxon t < n_taxa is t, parents[t], parents[parents[t]], ...; it ends with the
+ * first element c that has parents[c] <= 1, and where parents[c] == 1 taxon 1 belongs to it too (listing 1 selects everything
+ * connected to the root); on a tree lx_check_tax_tree admits it has at most max height + 2 elements.  t is UNDER THE LIST iff its
+ * chain holds a listed taxon; subject s is HIT iff one of its taxa s_tax_ids[s_tax_off[s] .. s_tax_off[s + 1]) is under the list. */
+typedef struct lx_taxon_filter
+{
+    uint32_t const * taxa;    /* listed taxa, any order, duplicates allowed */
+    uint64_t         n;       /* >= 1 */
+    int32_t          exclude; /* 0: keep subjects under a listed taxon; 1: keep the others */
+    uint32_t         reserved;
+} lx_taxon_filter;
+/* Bit s of mask (word s / 64, bit s % 64) = hit for exclude == 0, !hit for exclude != 0: a subject without taxa is dropped by an
+ * include list and kept by an exclude list (DIAMOND's rule).  Bits at and beyond n_s are 0; *n_kept = the number of set bits.
+ * known (may be NULL): known[i] = 1 iff taxa[i] is in the tree -- below n_taxa and with a parent, or the parent of some taxon, or a
+ * taxon of some subject --, else 0.  A listed taxon that is not known matches nothing and is no error here (the trees of
+ * lx_taxonomy_build skip and disconnect unassigned taxa of in-degree 1).  LX_EINVAL with a text in lx_last_output_error(): NULL
+ * arguments, n == 0, a listed taxon 0, a tree lx_check_tax_tree refuses.  No handle and no device is touched.  This function is the
+ * specification of lx_subject_mask_create_dev. */
+int lx_tax_subject_mask(lx_tax_tree const * tree, lx_taxon_filter const * f, uint64_t * mask /* [(n_s + 63) / 64] */, uint64_t * n_kept,
+                        uint8_t * known /* [f->n] or NULL */);
+
 /* What the writers need to know about the sequences (the reference reads these from lH.qryIds / indexFile.ids). */
 typedef struct lx_seq_names
 {
@@ -1106,6 +1128,35 @@ void const *  lx_seed_result_matches_dev(lx_seed_result const * r);
 /* Results are freed in any order, before their handle is destroyed (a freed result's device block is kept by the handle for the next call). */
 void          lx_seed_result_free(lx_seed_result * r);
 
+/* A subject mask: one bit per true subject id, as lx_tax_subject_mask lays them out, on the host and -- made with a handle -- on that
+ * handle's device too.  Destroy it before its handle.
+ *   lx_subject_mask_create_dev  the rule of lx_tax_subject_mask by kernels over the tree resident in t (h must be t's handle): the
+ *                               listed taxa go up in one small copy and are marked in a byte per taxon, one lane per taxon climbs its
+ *                               chain (every loop ends after max height + 2 steps), one lane per subject ORs over its taxa and a
+ *                               wavefront's ballot is one mask word.  The words equal lx_tax_subject_mask's bit for bit.  `known` is
+ *                               not computed here.  LX_EINVAL with a text (lx_last_error(h)): NULL arguments, n == 0, a listed
+ *                               taxon 0, a tree of another handle.
+ *   lx_subject_mask_create      from given words ((n_s + 63) / 64 of them, bits at and beyond n_s 0, else LX_EINVAL): h == NULL keeps
+ *                               them on the host, else they are also uploaded to h's device.
+ *   lx_subject_mask_info / _copy  the number of subjects and of set bits; the words. */
+typedef struct lx_subject_mask lx_subject_mask;
+int  lx_subject_mask_create_dev(lx_handle * h, lx_tax_dev const * t, lx_taxon_filter const * f, lx_subject_mask ** out);
+int  lx_subject_mask_create(lx_handle * h, uint64_t const * words, uint64_t n_s, lx_subject_mask ** out);
+int  lx_subject_mask_info(lx_subject_mask const * m, uint64_t * n_s, uint64_t * n_kept);
+int  lx_subject_mask_copy(lx_subject_mask const * m, uint64_t * words); /* [(n_s + 63) / 64] */
+void lx_subject_mask_destroy(lx_subject_mask * m);
+/* Drops from r's list every match whose subject's bit is 0 (subject = subjId / sbj_num_frames, sbj_num_frames 1 .. 6): a stable
+ * compaction, the kept matches in their old order.  *n_before / *n_kept (either may be NULL): the list's length before and after.
+ *   a device result (seeded with a handle): m must be a mask of the same handle.  A flag per match from the mask words, one sum scan,
+ *       a scatter of the records into a second device block that replaces the result's own; nothing of the list comes to the host.
+ *       Afterwards lx_seed_result_stats(r).n_matches is the kept count (the other fields are unchanged), lx_seed_result_matches_dev(r)
+ *       the new list, and a host copy made earlier is dropped (lx_seed_result_matches makes it anew).  At most 2^31 - 16 matches.
+ *   a host-path result: the same compaction of the host list; any mask serves.
+ * A match whose subject lies beyond the mask makes the call LX_EINVAL and leaves the result exactly as it was.  LX_EINVAL with a text
+ * (lx_last_error(h) for a device result, lx_last_output_error() always): NULL arguments, sbj_num_frames outside 1 .. 6, a device
+ * result with a host-only mask or a mask of another handle.  lx_last_phase_ms(h, 14, ...) = device time of the kernels. */
+int  lx_seed_result_filter(lx_seed_result * r, lx_subject_mask const * m, int32_t sbj_num_frames, uint64_t * n_before, uint64_t * n_kept);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Blocks until everything queued on the handle's stream has finished. */
 int lx_synchronize(lx_handle * h);
@@ -1123,7 +1174,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * 8 = the word table's kernels (lx_index_build on a handle; in slices: launches = the number of slices), 9 = the seeding kernel (lx_seed_queries on a handle),
  * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
  * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,
- * numbers, measure, scans, emit), 13 = the LCA kernels (lx_compute_lca_dev: query heads, fold; launches = the number of ranges). */
+ * numbers, measure, scans, emit), 13 = the LCA kernels (lx_compute_lca_dev: query heads, fold; launches = the number of ranges),
+ * 14 = the taxon filter's kernels (lx_subject_mask_create_dev: mark, climb, subjects; lx_seed_result_filter: flags + count, scatter). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

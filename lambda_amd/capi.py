@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
     "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_close",
     "lx_lca_options_default", "lx_compute_lca_ex", "lx_check_tax_tree", "lx_tax_dev_create", "lx_tax_dev_destroy", "lx_compute_lca_dev",
+    "lx_tax_subject_mask", "lx_subject_mask_create_dev", "lx_subject_mask_create", "lx_subject_mask_info", "lx_subject_mask_copy", "lx_subject_mask_destroy", "lx_seed_result_filter",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -101,6 +102,10 @@ class GunzipStats(C.Structure):
 class TaxTree(C.Structure):
     _fields_ = [("parents", C.c_void_p), ("heights", C.c_void_p), ("n_taxa", C.c_uint64), ("s_tax_off", C.c_void_p),
                 ("s_tax_ids", C.c_void_p), ("n_s", C.c_uint64)]
+
+
+class TaxonFilter(C.Structure):
+    _fields_ = [("taxa", C.c_void_p), ("n", C.c_uint64), ("exclude", C.c_int32), ("reserved", C.c_uint32)]
 
 
 class LcaOptions(C.Structure):
@@ -294,6 +299,14 @@ def load():
     lib.lx_tax_dev_destroy.argtypes = [vp]
     lib.lx_tax_dev_destroy.restype = None
     lib.lx_compute_lca_dev.argtypes = [vp, vp, vp, u64, C.POINTER(LcaOptions), vp, vp, C.POINTER(u64)]
+    lib.lx_tax_subject_mask.argtypes = [C.POINTER(TaxTree), C.POINTER(TaxonFilter), vp, C.POINTER(u64), vp]
+    lib.lx_subject_mask_create_dev.argtypes = [vp, vp, C.POINTER(TaxonFilter), C.POINTER(vp)]
+    lib.lx_subject_mask_create.argtypes = [vp, vp, u64, C.POINTER(vp)]
+    lib.lx_subject_mask_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.lx_subject_mask_copy.argtypes = [vp, vp]
+    lib.lx_subject_mask_destroy.argtypes = [vp]
+    lib.lx_subject_mask_destroy.restype = None
+    lib.lx_seed_result_filter.argtypes = [vp, vp, C.c_int32, C.POINTER(u64), C.POINTER(u64)]
     lib.lx_render_records.argtypes = [i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions), C.c_int64, C.POINTER(vp)]
     lib.lx_bytes_data.argtypes = [vp]
     lib.lx_bytes_data.restype = vp
@@ -438,6 +451,89 @@ class TaxDev:
 
     def __del__(self):
         self.close()
+
+
+def taxon_filter(taxa, exclude: bool = False):
+    """An lx_taxon_filter over `taxa` (returned with the array that must outlive the calls that read it)."""
+    arr = np.ascontiguousarray(taxa, dtype=np.uint32)
+    return TaxonFilter(arr.ctypes.data if len(arr) else None, len(arr), int(bool(exclude)), 0), arr
+
+
+def subject_mask(parents, heights, s_tax_off, s_tax_ids, taxa, exclude: bool = False):
+    """lx_tax_subject_mask, the rule on the host: (words as uint64, one bit per subject; n_kept; known, one byte per listed taxon)."""
+    tree, keep = _tax_tree(parents, heights, s_tax_off, s_tax_ids)
+    f, arr = taxon_filter(taxa, exclude)
+    words = np.zeros((int(tree.n_s) + 63) // 64, dtype=np.uint64)
+    known = np.zeros(max(len(arr), 1), dtype=np.uint8)
+    kept = C.c_uint64(0)
+    rc = load().lx_tax_subject_mask(C.byref(tree), C.byref(f), _ptr(words) if len(words) else words.ctypes.data, C.byref(kept), _ptr(known))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, last_output_error())
+    return words, int(kept.value), known[: len(arr)].copy()
+
+
+def mask_bits(words: np.ndarray, n_s: int) -> np.ndarray:
+    """The first n_s bits of mask words as a bool array (bit s of word s // 64)."""
+    return np.unpackbits(np.ascontiguousarray(words, dtype="<u8").view(np.uint8), bitorder="little")[:n_s].astype(bool)
+
+
+class SubjectMask:
+    """lx_subject_mask: one bit per subject.  from_words(handle or None, words, n_s) takes given words (with a handle they are also
+    uploaded); from_taxa(handle, tax_dev, taxa, exclude) makes them by kernels over a resident tree.  Close it before its handle."""
+
+    def __init__(self, m, handle=None):
+        self.lib, self.m, self.handle = load(), m, handle
+
+    @classmethod
+    def from_words(cls, handle: "Handle | None", words, n_s: int) -> "SubjectMask":
+        lib, w, out = load(), np.ascontiguousarray(words, dtype=np.uint64), C.c_void_p()
+        h = handle.h if handle is not None else None
+        rc = lib.lx_subject_mask_create(h, w.ctypes.data if len(w) else None, n_s, C.byref(out))
+        if rc != LX_OK:
+            raise LambdaExtError(rc, last_output_error())
+        return cls(out, handle)
+
+    @classmethod
+    def from_taxa(cls, handle: "Handle", tax_dev: "TaxDev", taxa, exclude: bool = False) -> "SubjectMask":
+        lib, out = load(), C.c_void_p()
+        f, arr = taxon_filter(taxa, exclude)
+        handle._check(lib.lx_subject_mask_create_dev(handle.h, tax_dev.t if tax_dev is not None else None, C.byref(f), C.byref(out)))
+        return cls(out, handle)
+
+    def info(self):
+        """(n_s, n_kept)"""
+        n_s, kept = C.c_uint64(0), C.c_uint64(0)
+        self.lib.lx_subject_mask_info(self.m, C.byref(n_s), C.byref(kept))
+        return int(n_s.value), int(kept.value)
+
+    def words(self) -> np.ndarray:
+        w = np.zeros((self.info()[0] + 63) // 64, dtype=np.uint64)
+        if self.lib.lx_subject_mask_copy(self.m, w.ctypes.data if len(w) else None) != LX_OK:
+            raise LambdaExtError(LX_EINVAL, last_output_error())
+        return w
+
+    def close(self):
+        if getattr(self, "m", None):
+            self.lib.lx_subject_mask_destroy(self.m)
+            self.m = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    __del__ = close
+
+
+def seed_result_filter(result: "SeedResult", mask: SubjectMask, sbj_num_frames: int = 1):
+    """lx_seed_result_filter: drops the matches whose subject (subjId // sbj_num_frames) has a 0 bit, in place and in order:
+    (n_before, n_kept)."""
+    before, kept = C.c_uint64(0), C.c_uint64(0)
+    rc = load().lx_seed_result_filter(result.r, mask.m if mask is not None else None, sbj_num_frames, C.byref(before), C.byref(kept))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, last_output_error())
+    return int(before.value), int(kept.value)
 
 
 def postprocess_records(bms: np.ndarray, max_matches: int = 25):

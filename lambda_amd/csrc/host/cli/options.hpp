@@ -41,7 +41,10 @@ struct Options
     std::string lca         = "auto"; // --lca gpu | host | auto: where the LCA per query is folded (the header comment)
     double      lcaTopPercent = 100;  // --lca-top-percent P: only the records within P percent of a query's best bit score enter its LCA (100: all)
     bool        lcaTopGiven = false;
-    int         threads     = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
+    std::vector<uint32_t> taxonList;     // --taxon-list T1,T2,... / --taxon-exclude T1,T2,...: search only the subjects under these taxa, or all but them
+    bool        taxonExclude = false;    // (the list came from --taxon-exclude)
+    std::string taxonFilter = "auto";    // --taxon-filter gpu | host | auto: where the subject mask is made and the match list filtered (auto: where the list stands)
+    int         threads    = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     bool        lazyQuery   = false; // --lazy-query 1: the query file block by block (the header comment)
     uint64_t    queryBlock  = 0;     // --query-block N: at most N reads per block; given and > 0, it implies --lazy-query 1
     bool        queryBlockGiven = false;
@@ -80,7 +83,11 @@ Options parse(int argc, char ** argv)
     if (argc < 2)
         throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.{fa,fq,fasta,fastq,fna,faa}[.gz] (-i DB.lba | -d DB.fasta[.gz]) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
                                  "[--devices 0,1,...] [-t THREADS]\n                 [--lca-top-percent P] [--lca gpu|host|auto]   the LCA per query (lcataxid, lt, ls) over the records within P percent of the query's best\n"
-                                 "                 bit score (0 .. 100, default 100: all records, the reference's rule), folded on the GPU or on the host (auto: the GPU)\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
+                                 "                 bit score (0 .. 100, default 100: all records, the reference's rule), folded on the GPU or on the host (auto: the GPU)\n                 [--taxon-list T1,T2,... | --taxon-exclude T1,T2,...] [--taxon-filter gpu|host|auto]   search only the subjects under the listed taxa of the\n"
+                                 "                 index's tree (mkindex* -m -x), or all but them (a subject without taxa is dropped by a list and kept by an exclusion); the promising\n"
+                                 "                 seeds on other subjects are dropped before the extension, on the GPU or on the host (auto: where the seeding left them); e-values\n"
+                                 "                 and bit scores keep the whole database's length; with --search0 1 a read whose hits all lie outside goes on to the second pass; the seeding aims\n"
+                                 "                 at -n + the number of dropped subjects (at most 64 matches per read, never fewer than -n) instead of -n\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
                                  "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
@@ -122,6 +129,23 @@ Options parse(int argc, char ** argv)
                 return v;
         throw std::runtime_error(message);
     };
+    auto taxa = [](std::string const & name, std::string const & v) // T1,T2,...: taxon ids, 1 .. 2^32 - 1
+    {
+        std::vector<uint32_t> out;
+        for (size_t at = 0; at <= v.size();)
+        {
+            size_t const      e = std::min(v.find(',', at), v.size());
+            std::string const t = v.substr(at, e - at);
+            bool const        digits = !t.empty() && t.size() <= 10 && std::all_of(t.begin(), t.end(), [](char c) { return c >= '0' && c <= '9'; });
+            unsigned long long const id = digits ? std::stoull(t) : 0;
+            if (!digits || id == 0 || id > 0xffffffffull)
+                throw std::runtime_error(name + " takes a comma-separated list of taxon ids (numbers from 1 to 4294967295), got '" + t + "' in '" + v + "'");
+            out.push_back((uint32_t)id);
+            at = e + 1;
+        }
+        return out;
+    };
+    bool taxonFilterGiven = false;
     for (int i = 2; i < argc; ++i)
     {
         std::string a = argv[i];
@@ -258,6 +282,18 @@ Options parse(int argc, char ** argv)
             inRange(a, o.lcaTopPercent, 0, 100);
             o.lcaTopGiven = true;
         }
+        else if (!mk && (a == "--taxon-list" || a == "--taxon-exclude"))
+        {
+            if (!o.taxonList.empty())
+                throw std::runtime_error("--taxon-list and --taxon-exclude are given once, and only one of them: search under some taxa or everything except some");
+            o.taxonList    = taxa(a, val());
+            o.taxonExclude = a == "--taxon-exclude";
+        }
+        else if (!mk && a == "--taxon-filter")
+        {
+            o.taxonFilter   = oneOf(val(), {"gpu", "host", "auto"}, "--taxon-filter takes gpu, host or auto");
+            taxonFilterGiven = true;
+        }
         else if (a == "--render")
             o.render = oneOf(val(), {"gpu", "host", "auto"}, "--render takes gpu, host or auto");
         else if (a == "--seeding")
@@ -306,6 +342,8 @@ Options parse(int argc, char ** argv)
     }
     if (o.query.empty() || o.db.empty())
         throw std::runtime_error("-q and -d (a FASTA file) or -i (an index made by lambda3 mkindex*) are required");
+    if (taxonFilterGiven && o.taxonList.empty())
+        throw std::runtime_error("--taxon-filter says where --taxon-list / --taxon-exclude is applied: give one of them");
     // "Setting a profile other than none always overwrites manually given command line arguments" (:563-566, applied :634-681)
     if (o.profile == "fast")
     {

@@ -4,6 +4,27 @@
 //   lambda3 searchp -q queries.fasta -d db.fasta -o out.m8 [-e 1e-2] [-n 25] [--seed-length 10] [--seed-offset 5]
 //                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--table-slice WORDS] [--seeding gpu|host] [--records gpu|host|auto]
 //                   [--render gpu|host|auto] [--lca-top-percent P] [--lca gpu|host|auto]
+//                   [--taxon-list T1,T2,... | --taxon-exclude T1,T2,...] [--taxon-filter gpu|host|auto]
+//
+// --taxon-list / --taxon-exclude (BLAST's -taxids / -negative_taxids, DIAMOND's --taxonlist / --taxon-exclude): search only the
+// subjects under the listed taxa of the index's tree (mkindex* -m -x), or all but them.  lx_tax_subject_mask has the rule: a taxon is
+// under the list if its chain of parents holds a listed taxon, a subject is hit if one of its taxa is; a subject without taxa is
+// dropped by a list and kept by an exclusion.  The mask is made once per worker; in every pass the promising seeds (the match list
+// of lx_seed_queries) on unwanted subjects are dropped before lx_iterate_matches*, so they cost no extension and take none of a
+// query's -n places.  --taxon-filter: gpu = the mask by kernels over the tree resident on the worker's device
+// (lx_subject_mask_create_dev) and a device match list compacted where it stands (lx_seed_result_filter); host = the mask by
+// lx_tax_subject_mask, a device list brought down and the pass run from host memory; auto = where the pass's list stands.  A list
+// in host memory (--seeding host) is always filtered there.  What is stated: e-values and bit scores keep the WHOLE database's length,
+// as BLAST's -taxids does; with --search0 1 the "read had a result" decision is made on the filtered results, so a read whose hits
+// all lie outside the list goes on to the second pass; the stage counters keep their meaning ("promising" counts the seeds before
+// the filter) and one more stderr line names the kept subjects, the dropped seeds, the place and the time.  The seeding itself does
+// not know the list, and it thins a read's seeds towards -n matches (adaptive elongation, the over-abundance cut): so that the
+// dropped subjects cannot use that budget up, with a list it aims at -n + the number of dropped subjects, capped at the 64 matches
+// per read a device launch has room for (never below -n: from -n 64 on the seeding is exactly the unrestricted run's; below it a
+// list can find kept subjects that the unrestricted run's thinning loses).  Refused while the options
+// are parsed: both options, an empty list, anything but numbers 1 .. 2^32 - 1, --taxon-filter without a list.  Refused once the index
+// is read: an index (or a -d FASTA database) without subject taxa and tree, and a --taxon-list taxon that the index's tree does not
+// hold (the reference's tree skips unassigned taxa with one child); --taxon-exclude of such a taxon is a warning.
 //
 // --lca-top-percent P (0 .. 100, default 100): which records of a query enter its LCA (lcataxid, lt, ls).  100 is the reference's
 // rule, every record (src/search_algo.hpp:884-907); below it only the records whose bit score lies within P percent of the query's
@@ -504,6 +525,51 @@ SearchSetup prepareSearch(Options const & opt, Run const & run, Inputs const & i
     return s;
 }
 
+// ---- --taxon-list / --taxon-exclude: the list against the index's taxonomy, once the index is read.  The host rule
+// (lx_tax_subject_mask) says which listed taxa the tree knows and gives the mask's words: the mask of --taxon-filter host and of
+// every pass whose match list stands in host memory, and the kept count of the stderr line.
+struct TaxonSetup
+{
+    bool                  on = false;
+    lx_tax_tree           tree{};
+    lx_taxon_filter       filter{};
+    std::vector<uint64_t> words;
+    uint64_t              nSubjects = 0, nKept = 0;
+
+    TaxonSetup(Options const & opt, Run const & run, IndexTaxonomy const & tax)
+    {
+        if (opt.taxonList.empty())
+            return;
+        if (!run.fromIndex || !tax.has || !tax.hasTree)
+            throw std::runtime_error(std::string(opt.taxonExclude ? "--taxon-exclude" : "--taxon-list") +
+                                     ": the index has no taxonomy: build it with mkindex* -m and -x");
+        on             = true;
+        tree.parents   = tax.parents.data();
+        tree.heights   = tax.heights.data();
+        tree.n_taxa    = tax.parents.size();
+        tree.s_tax_off = tax.off.data();
+        tree.s_tax_ids = tax.ids.data();
+        tree.n_s       = tax.off.size() - 1;
+        filter         = lx_taxon_filter{opt.taxonList.data(), opt.taxonList.size(), opt.taxonExclude ? 1 : 0, 0};
+        nSubjects      = tree.n_s;
+        words.assign((nSubjects + 63) / 64, 0);
+        std::vector<uint8_t> known(opt.taxonList.size(), 0);
+        if (lx_tax_subject_mask(&tree, &filter, words.data(), &nKept, known.data()) != LX_OK)
+            throw std::runtime_error(std::string("the taxon list: ") + lx_last_output_error());
+        for (size_t i = 0; i < known.size(); ++i)
+        {
+            if (known[i])
+                continue;
+            std::string const what = "taxon " + std::to_string(opt.taxonList[i]) +
+                                     ": the index's tree does not hold it (it has no subjects there, or the tree skipped it as an unassigned taxon with one "
+                                     "child: name a taxon above or below it)";
+            if (!opt.taxonExclude)
+                throw std::runtime_error("--taxon-list " + what);
+            std::cerr << "WARNING: --taxon-exclude " << what << "\n";
+        }
+    }
+};
+
 // everything a search stage reads, none of which changes once the search begins
 struct SearchContext
 {
@@ -512,6 +578,7 @@ struct SearchContext
     SearchSetup const & setup;
     SeqSet const &      db;
     Table const &       table;
+    TaxonSetup const &  taxon;
 };
 
 // what a worker keeps for its range of reads (--lazy-query: for its blocks, whose records stay with them)
@@ -527,6 +594,9 @@ struct Part
     lx_record_stats             rst{}; // --records gpu: _writeRecord's statistics of this worker's passes
     bool                        gpuSeeding = false; // the seeding stage of this worker ran on its device
     size_t                      nDeclined = 0, nPassesOnHost = 0; // reads the GPU seeding stage left to the host; passes whose match buffer was full
+    uint64_t                    nTaxonDropped = 0; // --taxon-list / --taxon-exclude: promising seeds on subjects the mask drops
+    double                      msTaxon = 0;       // ... the mask and the filter: the kernels' time on the GPU, the wall clock on the host
+    bool                        taxonOnGpu = false; // ... a pass of this worker filtered its list on the device
     std::string                 error;
 };
 
@@ -573,7 +643,8 @@ public:
         pt_.gpuSeeding = gpuIndex_ != nullptr;
         // with the seeding on the device its matches stay there: the sequence sets become resident for the Level-2 kernels
         // (LAMBDA3_HOST_LIST=1: the matches come down and go through lx_iterate_matches, the A/B switch of the tests)
-        deviceList_ = gpuIndex_ && !std::getenv("LAMBDA3_HOST_LIST");
+        // (--taxon-filter host: the list is filtered in host memory, so the passes take it from there)
+        deviceList_ = gpuIndex_ && !std::getenv("LAMBDA3_HOST_LIST") && !(c.taxon.on && opt.taxonFilter == "host");
         if (deviceList_)
             eng_.check(lx_set_subject_seqs(eng_.raw(), db.off.data(), db.len.data(), db.off.size()));
         // search() (src/search_algo.hpp:611-762) over the sorted table of reduced words: what both passes share
@@ -581,6 +652,8 @@ public:
         spar_.pre_scoring_thresh = opt.preScoringThresh, spar_.max_matches = opt.maxMatches, spar_.q_num_frames = c.run.qFrames;
         spar_.unknown_rank = c.run.prot ? 25 : c.run.bs ? 4 : 3; // 'X' / 'N'
         spar_.matrix = c.setup.sc.matrix, spar_.matrix_rev = c.run.bs ? c.setup.scRev.matrix : nullptr, spar_.host_threads = c.setup.seedThreads;
+        if (c.taxon.on)
+            makeTaxonMasks();
     }
 
     void search(Job const & job)
@@ -633,6 +706,86 @@ private:
             eng_.check(lx_reserve(eng_.raw(), est, est / 7, est / 12, c_.run.wantOps ? est / 12 * (len + len / 16) : 0));
     }
 
+    // --taxon-list / --taxon-exclude, once per handle: the mask in host memory for the lists that stand there, and -- where the
+    // matches stay on the device and --taxon-filter does not say host -- the tree resident on this handle and the mask by kernels
+    void makeTaxonMasks()
+    {
+        TaxonSetup const & tx = c_.taxon;
+        // The seeding thins a read's seeds towards -n matches (adaptive elongation, the over-abundance cut: src/search_algo.hpp:679-729)
+        // and does not know the mask: matches on subjects the filter drops would use that budget up, and an elongated seed would lose
+        // the kept subject that differs a little for the dropped ones that do not.  Every dropped subject can take one of the places,
+        // so the seeding aims at -n plus the number of dropped subjects -- but at no more than the 64 matches per read a device launch
+        // has room for (lx_seed_queries), unless -n itself is larger: from -n 64 on the seeding is the unrestricted run's.
+        constexpr uint64_t kLaunchRoomPerRead = 64;
+        if (c_.opt.maxMatches > 0)
+            spar_.max_matches = std::min<uint64_t>(c_.opt.maxMatches + (tx.nSubjects - tx.nKept), std::max<uint64_t>(c_.opt.maxMatches, kLaunchRoomPerRead));
+        lx_subject_mask * m = nullptr;
+        if (lx_subject_mask_create(nullptr, tx.words.data(), tx.nSubjects, &m) != LX_OK)
+            throw std::runtime_error(std::string("the taxon filter: ") + lx_last_output_error());
+        hostMask_.reset(m);
+        if (!deviceList_)
+        {
+            if (c_.opt.taxonFilter == "gpu")
+                std::cerr << "WARNING: --taxon-filter gpu: this worker's match lists stand in host memory and are filtered there\n";
+            return;
+        }
+        lx_tax_dev * t = nullptr;
+        eng_.check(lx_tax_dev_create(eng_.raw(), &tx.tree, &t));
+        taxDev_.reset(t);
+        eng_.check(lx_subject_mask_create_dev(eng_.raw(), t, &tx.filter, &m));
+        devMask_.reset(m);
+        float ms = 0;
+        if (lx_last_phase_ms(eng_.raw(), 14, &ms, nullptr) == LX_OK)
+            pt_.msTaxon += ms;
+        uint64_t kept = 0;
+        if (lx_subject_mask_info(m, nullptr, &kept) != LX_OK || kept != tx.nKept)
+            throw std::runtime_error("the taxon filter: the mask made on the GPU keeps another number of subjects than the host rule");
+    }
+
+    // drops the matches on subjects the mask does not keep from the pass's list, where the list stands; the number that stay.  A
+    // device list is compacted on the device; a host-path result by the library on its host list; a device result whose matches
+    // this worker takes from host memory (--taxon-filter host, LAMBDA3_HOST_LIST) in its host copy, here.
+    uint64_t filterByTaxon(lx_seed_result * sr)
+    {
+        bool const resultOnDevice = lx_seed_result_matches_dev(sr) != nullptr;
+        uint64_t   before = 0, kept = 0;
+        if (resultOnDevice && deviceList_)
+        {
+            eng_.check(lx_seed_result_filter(sr, devMask_.get(), c_.run.sFrames, &before, &kept));
+            float ms = 0;
+            if (lx_last_phase_ms(eng_.raw(), 14, &ms, nullptr) == LX_OK)
+                pt_.msTaxon += ms;
+            pt_.taxonOnGpu = true;
+            pt_.nTaxonDropped += before - kept;
+            return kept;
+        }
+        auto const tFilter = Clock::now();
+        if (!resultOnDevice)
+        {
+            if (lx_seed_result_filter(sr, hostMask_.get(), c_.run.sFrames, &before, &kept) != LX_OK)
+                throw std::runtime_error(std::string("the taxon filter: ") + lx_last_output_error());
+        }
+        else
+        {
+            before                = lx_seed_result_stats(sr).n_matches;
+            lx_match * const list = before ? lx_seed_result_matches(sr) : nullptr;
+            if (before && !list)
+                throw std::runtime_error("the match list did not fit into host memory");
+            uint64_t const frames = (uint64_t)c_.run.sFrames;
+            for (uint64_t k = 0; k < before; ++k)
+            {
+                uint64_t const s = list[k].subjId / frames;
+                if (s >= c_.taxon.nSubjects)
+                    throw std::runtime_error("the taxon filter: a match names a subject the index's taxonomy does not have");
+                if ((c_.taxon.words[s >> 6] >> (s & 63)) & 1)
+                    list[kept++] = list[k];
+            }
+        }
+        pt_.msTaxon += msSince(tFilter);
+        pt_.nTaxonDropped += before - kept;
+        return kept;
+    }
+
     // one pass: seed the frame sequences `which` of the job, extend (GPU), collect the records
     void pass(Job const & job, lambda_amd::SeedParams const & so, std::vector<uint64_t> const & which)
     {
@@ -671,13 +824,14 @@ private:
         pt_.sst.hitsAfterSeeding += sst.hits_after_seeding, pt_.sst.hitsFailedPreExtendTest += sst.hits_failed_pre_extend;
         pt_.nDeclined += sst.reads_declined, pt_.nPassesOnHost += sst.launches_full;
         // the matches where the seeding left them: the device list for the Level-2 kernels, else the list in host memory
+        // (--taxon-list / --taxon-exclude: without the matches on subjects the mask drops; "promising" counts them all the same)
+        uint64_t const     nMatches = c_.taxon.on && sst.n_matches ? filterByTaxon(sr) : sst.n_matches;
         void const * const dList    = deviceList_ ? lx_seed_result_matches_dev(sr) : nullptr;
-        uint64_t const     nMatches = sst.n_matches;
         lx_match * const   hList    = dList || nMatches == 0 ? nullptr : lx_seed_result_matches(sr);
         if (!dList && nMatches && !hList)
             throw std::runtime_error("the match list did not fit into host memory");
         pt_.msSeed += msSince(tSeed);
-        pt_.nPromising += nMatches;
+        pt_.nPromising += sst.n_matches;
         if (std::getenv("LAMBDA3_TRACE"))
             std::fprintf(stderr, "[worker %zu] %zu promising seeds -> extension\n", w_, (size_t)nMatches);
         if (nMatches == 0)
@@ -736,6 +890,9 @@ private:
     lx_index const *      gpuIndex_   = nullptr; // the table on this worker's handle (NULL: the seeding is the host threads')
     bool                  deviceList_ = false;
     lx_seed_params        spar_{};
+    // --taxon-list / --taxon-exclude (behind eng_: destroyed before the handle)
+    std::unique_ptr<lx_tax_dev, FreeWith<lx_tax_dev_destroy>>           taxDev_;
+    std::unique_ptr<lx_subject_mask, FreeWith<lx_subject_mask_destroy>> devMask_, hostMask_;
 };
 
 // worker w's thread: its set-up, then the jobs nextJob hands it (false: no more), each reported to jobDone with the worker's handle
@@ -1205,6 +1362,9 @@ struct Totals : Part
         msExtend   = std::max(msExtend, pt.msExtend);
         msRecords  = std::max(msRecords, pt.msRecords);
         msLca      = std::max(msLca, pt.msLca);
+        nTaxonDropped += pt.nTaxonDropped;
+        msTaxon    = std::max(msTaxon, pt.msTaxon);
+        taxonOnGpu = taxonOnGpu || pt.taxonOnGpu;
         rst += pt.rst;
     }
 };
@@ -1333,7 +1493,7 @@ RenderTimes writeEager(Options const & opt, Run const & run, int device, OutputS
 
 // ---- the summary on stderr: the counts, where the wall clock went (the reference prints its own at verbosity 2, src/search.cpp),
 // and for --lazy-query the blocks
-void report(Options const & opt, Run const & run, Inputs const & in, Table const & table, SearchSetup const & setup, Totals const & t,
+void report(Options const & opt, Run const & run, Inputs const & in, Table const & table, SearchSetup const & setup, TaxonSetup const & taxon, Totals const & t,
             LazyTotals const & lazy, RenderTimes const & times, double msSearch, double msOutput)
 {
     int const fmt = run.outFmt;
@@ -1362,6 +1522,10 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
     if (run.wantLca && (opt.lca == "gpu" || opt.lcaTopGiven))
         std::fprintf(stderr, "lambda3 LCA: records within %g percent of a query's best bit score, folded on the %s: %.1f ms%s\n", opt.lcaTopPercent,
                      opt.lca != "host" ? "GPU" : "host", run.lazy ? t.msLca : times.msLca, run.lazy ? " on the slowest worker" : "");
+    if (taxon.on)
+        std::fprintf(stderr, "lambda3 taxon filter: %llu of %llu subjects kept; %llu of %zu promising seeds dropped; on the %s (%.1f ms)\n",
+                     (unsigned long long)taxon.nKept, (unsigned long long)taxon.nSubjects, (unsigned long long)t.nTaxonDropped, t.nPromising,
+                     t.taxonOnGpu ? "GPU" : "host", t.msTaxon);
     if (run.lazy)
         std::fprintf(stderr, "lambda3 query blocks: %llu block(s) of at most %llu read(s), %llu read(s) in the largest, at most %llu block(s) alive at once\n",
                      (unsigned long long)lazy.counts.blocks, (unsigned long long)run.blockReads, (unsigned long long)lazy.counts.largest,
@@ -1381,9 +1545,10 @@ int main(int argc, char ** argv)
         if (run.mk)
             return runMkindex(opt, run, in, table);
         std::vector<uint8_t> const qRed = reduce(in.qs, run.red);
+        TaxonSetup const           taxon(opt, run, table.indexTax);
         SearchSetup const          setup = prepareSearch(opt, run, in);
         OutputSetup const          output(opt, run, table.indexTax);
-        SearchContext const        search{opt, run, setup, in.db, table};
+        SearchContext const        search{opt, run, setup, in.db, table, taxon};
         std::vector<Part>          parts(setup.nWorkers);
 
         auto const tSearch = Clock::now();
@@ -1397,7 +1562,7 @@ int main(int argc, char ** argv)
         auto const   tOut   = Clock::now();
         Totals const totals = sumParts(opt, run, parts, lazy);
         RenderTimes const times = run.lazy ? lazy.times : writeEager(opt, run, setup.devices[0], output, in, totals);
-        report(opt, run, in, table, setup, totals, lazy, times, msSearch, msSince(tOut));
+        report(opt, run, in, table, setup, taxon, totals, lazy, times, msSearch, msSince(tOut));
         return 0;
     }
     catch (std::exception const & e)

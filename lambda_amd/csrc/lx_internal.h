@@ -251,6 +251,22 @@ struct lx_handle
     {
         DevBuf d_qres, d_qred, d_qoff, d_qlen, d_reads, d_declined, d_cnt, d_matrix, d_sres, d_spare;
     } seed;
+    // lx_subject_mask_create_dev / lx_seed_result_filter (lx_taxfilter_host.cpp): the listed taxa and the two byte flags per taxon,
+    // the scan's tile values, the counter and error words
+    struct TaxFilter
+    {
+        DevBuf d_list, d_flags, d_tot, d_words;
+    } taxfilter;
+};
+
+// what lx_seed_queries returns (lx_seed_host.cpp); lx_seed_result_filter (lx_taxfilter_host.cpp) compacts its list
+struct lx_seed_result
+{
+    lx_handle *           h = nullptr; // NULL: a host-path result
+    lxi::DevBuf           d_out;
+    std::vector<lx_match> host;
+    bool                  have_host = false;
+    lx_seed_stats         st{};
 };
 
 namespace lxi

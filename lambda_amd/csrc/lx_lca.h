@@ -9,6 +9,8 @@
 
 #include <cstdint>
 
+#include "lx_resources.h"
+
 namespace lx
 {
 namespace lca
@@ -51,3 +53,15 @@ hipError_t launch_range(RangeParams const & p, hipStream_t stream);
 
 } // namespace lca
 } // namespace lx
+
+// a tree resident on its handle's device (lx_lca_host.cpp makes it; lx_taxfilter_host.cpp reads it too)
+struct lx_tax_dev
+{
+    lx_handle *                  h = nullptr;
+    uint64_t                     n_taxa = 0, n_s = 0;
+    uint32_t                     max_height = 0;
+    lxi::DevBlock<lx::lca::Node> d_nodes;
+    lxi::DevBlock<uint64_t>      d_off;
+    lxi::DevBlock<uint32_t>      d_ids;
+    ~lx_tax_dev();
+};

@@ -19,22 +19,12 @@
 
 using namespace lxi;
 
-struct lx_tax_dev
+// its handle's device bound and the launch stream through before the blocks go
+lx_tax_dev::~lx_tax_dev()
 {
-    lx_handle *            h = nullptr;
-    uint64_t               n_taxa = 0, n_s = 0;
-    uint32_t               max_height = 0;
-    DevBlock<lx::lca::Node> d_nodes;
-    DevBlock<uint64_t>     d_off;
-    DevBlock<uint32_t>     d_ids;
-
-    // its handle's device bound and the launch stream through before the blocks go
-    ~lx_tax_dev()
-    {
-        if (h && bind(h) == LX_OK)
-            (void)hipStreamSynchronize(h->stream);
-    }
-};
+    if (h && bind(h) == LX_OK)
+        (void)hipStreamSynchronize(h->stream);
+}
 
 namespace
 {

@@ -143,15 +143,6 @@ struct lx_index
     lxi::DevBlock<uint8_t>             d_sred;
 };
 
-struct lx_seed_result
-{
-    lx_handle *           h = nullptr; // NULL: a host-path result
-    lxi::DevBuf           d_out;
-    std::vector<lx_match> host;
-    bool                  have_host = false;
-    lx_seed_stats         st{};
-};
-
 namespace
 {
 
