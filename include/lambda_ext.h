@@ -1157,6 +1157,57 @@ void lx_subject_mask_destroy(lx_subject_mask * m);
  * result with a host-only mask or a mask of another handle.  lx_last_phase_ms(h, 14, ...) = device time of the kernels. */
 int  lx_seed_result_filter(lx_seed_result * r, lx_subject_mask const * m, int32_t sbj_num_frames, uint64_t * n_before, uint64_t * n_kept);
 
+/* ---- low-complexity masking of the queries ------------------------------------------------------
+ * Soft masking as BLAST does it: a masked query letter starts and carries no seed; pre-scoring, extension, statistics and output
+ * read the unmasked letters.  The rule is SEG's first two stages on alignment ranks, in integers (host and device cannot differ by
+ * a rounding):
+ *   T[c] = round(c * log2 c * 65536) for c = 0 .. 64 (T[0] = T[1] = 0); thr(k) = ceil(window * (log2 window - k) * 65536).
+ *   Window p of a sequence of L >= window letters covers letters [p, p + window); its score S(p) is the sum over ranks r of
+ *   T[count of r in the window] -- every rank is a letter, 'X' and '*' too --, and its entropy is <= k bits exactly when S(p) >= thr(k).
+ *   A run is a maximal stretch of consecutive windows with S >= thr(k2); a run that holds a window with S >= thr(k1) masks every
+ *   letter from its first window's first letter to its last window's last letter.  A sequence shorter than the window is never
+ *   masked; windows never reach across a sequence's end.
+ * SEG's third stage, which trims each raw segment to its least probable part, is NOT applied, so a mask is SEG's segment or wider (an
+ * SP repeat between ordinary flanks takes a few flank letters on either side along).  This is not NCBI's
+ * segmasker and does not reproduce its output.
+ * Ranges: window 4 .. 64 (default 12), 0 < k1 <= k2 <= log2 window in bits (defaults 2.2 and 2.5, SEG's). */
+typedef struct lx_seg_params
+{
+    int32_t window;
+    double  k1, k2;
+} lx_seg_params;
+void lx_seg_params_default(lx_seg_params * p);
+/* the rule's tables, as the host function and the kernels use them; LX_EINVAL outside the ranges above */
+int  lx_seg_tables(lx_seg_params const * p, int64_t T[65], int64_t * thr1, int64_t * thr2);
+/* A query mask: per letter of a sequence set (indexed like q_res) whether it is masked.  Destroy it before its handle.
+ *   lx_query_mask_create_seg  the rule above.  h != NULL: q_res and the sequence table go up and kernels on h's device and stream make
+ *                             the mask, which stays resident there (lx_last_phase_ms(h, 15, ...) = their device time); h == NULL:
+ *                             the same rule on host_threads host threads (0 = the library's share).
+ *   lx_query_mask_create      from given 0 / 1 bytes, indexed like q_res (any rule of the caller's); h != NULL: also uploaded.
+ *   lx_query_mask_info        letters of the set, masked letters, sequences with a masked letter (any may be NULL).
+ *   lx_query_mask_copy        0 / 1 per letter into masked[0 .. end of the last sequence), 0 between sequences; a device mask comes
+ *                             down on first use.
+ * LX_EINVAL with a text (lx_last_output_error(), and lx_last_error(h) with a handle), before any device work: NULL arguments,
+ * parameters outside the ranges, a sequence outside the address range, and sequences with letters that are not in ascending order
+ * without overlap (a letter of two sequences has no mask byte of its own). */
+typedef struct lx_query_mask lx_query_mask;
+int  lx_query_mask_create_seg(lx_handle * h, uint8_t const * q_res, uint64_t const * q_off, uint64_t const * q_len, uint64_t n_qseq, lx_seg_params const * p,
+                              uint32_t host_threads, lx_query_mask ** out);
+int  lx_query_mask_create(lx_handle * h, uint8_t const * masked, uint64_t const * q_off, uint64_t const * q_len, uint64_t n_qseq, lx_query_mask ** out);
+int  lx_query_mask_info(lx_query_mask const * m, uint64_t * n_letters, uint64_t * n_masked, uint64_t * n_seqs_masked);
+int  lx_query_mask_copy(lx_query_mask const * m, uint8_t * masked);
+void lx_query_mask_destroy(lx_query_mask * m);
+/* lx_seed_queries with a mask (m == NULL: exactly lx_seed_queries).  A start p of a sequence is blocked when one of the seed's first
+ * seed_length letters, [p, p + seed_length), is masked.  The loop that moves a start off the unknown letter passes a blocked start
+ * over in the same way; it stops at L - seed_length, and a start that is still blocked there makes no seed, which ends the frame.
+ * Adaptive elongation may run on over masked letters; the bookkeeping of the reads' lengths is unchanged.  On a handle the seeding
+ * kernel reads the device mask where it stands; only the reads the device declines use the host copy.  LX_EINVAL in addition to
+ * lx_seed_queries': a mask whose sequence table differs from the call's (n_qseq, offsets or lengths), a device call with a
+ * host-only mask or a mask of another handle. */
+int  lx_seed_queries_masked(lx_handle * h, lx_index const * ix, uint8_t const * s_res, uint8_t const * q_res, uint8_t const * q_red, uint64_t const * q_off,
+                            uint64_t const * q_len, uint64_t n_qseq, uint64_t const * reads, uint64_t n_reads, lx_query_mask const * m, lx_seed_params const * p,
+                            lx_seed_result ** out);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Blocks until everything queued on the handle's stream has finished. */
 int lx_synchronize(lx_handle * h);
@@ -1175,7 +1226,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
  * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,
  * numbers, measure, scans, emit), 13 = the LCA kernels (lx_compute_lca_dev: query heads, fold; launches = the number of ranges),
- * 14 = the taxon filter's kernels (lx_subject_mask_create_dev: mark, climb, subjects; lx_seed_result_filter: flags + count, scatter). */
+ * 14 = the taxon filter's kernels (lx_subject_mask_create_dev: mark, climb, subjects; lx_seed_result_filter: flags + count, scatter),
+ * 15 = the query masking kernels (lx_query_mask_create_seg on a handle: stops, flags, carries, fill, distances, count). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

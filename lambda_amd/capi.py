@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = [
     "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_close",
     "lx_lca_options_default", "lx_compute_lca_ex", "lx_check_tax_tree", "lx_tax_dev_create", "lx_tax_dev_destroy", "lx_compute_lca_dev",
     "lx_tax_subject_mask", "lx_subject_mask_create_dev", "lx_subject_mask_create", "lx_subject_mask_info", "lx_subject_mask_copy", "lx_subject_mask_destroy", "lx_seed_result_filter",
+    "lx_seg_params_default", "lx_seg_tables", "lx_query_mask_create_seg", "lx_query_mask_create", "lx_query_mask_info", "lx_query_mask_copy", "lx_query_mask_destroy",
+    "lx_seed_queries_masked",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -140,6 +142,14 @@ class SeedParams(C.Structure):
                 ("adaptive", C.c_int32), ("pre_scoring", C.c_int32), ("pre_scoring_thresh", C.c_double), ("max_matches", C.c_uint64),
                 ("q_num_frames", C.c_int32), ("unknown_rank", C.c_int32), ("matrix", C.c_void_p), ("matrix_rev", C.c_void_p),
                 ("host_threads", C.c_uint32)]
+
+
+class SegParams(C.Structure):
+    """lx_seg_params: window 4 .. 64, 0 < k1 <= k2 <= log2(window) in bits; the defaults are SEG's."""
+    _fields_ = [("window", C.c_int32), ("k1", C.c_double), ("k2", C.c_double)]
+
+    def __init__(self, window: int = 12, k1: float = 2.2, k2: float = 2.5):
+        super().__init__(window, k1, k2)
 
 
 class SeedStats(C.Structure):
@@ -345,6 +355,17 @@ def load():
     lib.lx_index_destroy.argtypes = [vp]
     lib.lx_index_destroy.restype = None
     lib.lx_seed_queries.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, C.POINTER(SeedParams), C.POINTER(vp)]
+    if hasattr(lib, "lx_seed_queries_masked"):  # (not in an older library loaded through LX_LIB_PATH: the yardstick of tools/query_mask_bench.py)
+        lib.lx_seed_queries_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, vp, C.POINTER(SeedParams), C.POINTER(vp)]
+        lib.lx_seg_params_default.argtypes = [C.POINTER(SegParams)]
+        lib.lx_seg_params_default.restype = None
+        lib.lx_seg_tables.argtypes = [C.POINTER(SegParams), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.lx_query_mask_create_seg.argtypes = [vp, vp, vp, vp, u64, C.POINTER(SegParams), C.c_uint32, C.POINTER(vp)]
+        lib.lx_query_mask_create.argtypes = [vp, vp, vp, vp, u64, C.POINTER(vp)]
+        lib.lx_query_mask_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        lib.lx_query_mask_copy.argtypes = [vp, vp]
+        lib.lx_query_mask_destroy.argtypes = [vp]
+        lib.lx_query_mask_destroy.restype = None
     lib.lx_seed_result_stats.argtypes = [vp]
     lib.lx_seed_result_stats.restype = SeedStats
     lib.lx_seed_result_matches.argtypes = [vp]
@@ -943,17 +964,98 @@ class SeedResult:
     __del__ = close
 
 
-def seed_queries(handle: "Handle | None", index: Index, s_res, q_res, q_red, q_off, q_len, params: SeedParams, reads=None) -> SeedResult:
+def seg_tables(params: "SegParams | None" = None):
+    """lx_seg_tables: (T, thr1, thr2) of the masking rule -- T[c] = round(c * log2 c * 65536), c = 0 .. 64, as int64."""
+    lib, p = load(), params if params is not None else SegParams()
+    T, t1, t2 = np.zeros(65, np.int64), C.c_int64(0), C.c_int64(0)
+    rc = lib.lx_seg_tables(C.byref(p), _ptr(T), C.byref(t1), C.byref(t2))
+    if rc != LX_OK:
+        raise LambdaExtError(rc, last_output_error())
+    return T, int(t1.value), int(t2.value)
+
+
+class QueryMask:
+    """lx_query_mask: which letters of a query set are masked.  seg(handle or None, q_res, q_off, q_len, params) applies the SEG rule
+    (with a handle: by kernels, the mask stays on its device); from_bytes(handle or None, masked, q_off, q_len) takes given 0 / 1
+    bytes indexed like q_res.  Close it before its handle."""
+
+    def __init__(self, m, handle, extent):
+        self.lib, self.m, self.handle, self.extent = load(), m, handle, extent
+
+    @staticmethod
+    def _table(q_off, q_len):
+        off, ln = np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(q_len, dtype=np.uint64)
+        return off, ln, int((off + ln)[ln > 0].max()) if (ln > 0).any() else 0
+
+    @classmethod
+    def seg(cls, handle: "Handle | None", q_res, q_off, q_len, params: "SegParams | None" = None, host_threads: int = 0) -> "QueryMask":
+        lib, out, p = load(), C.c_void_p(), params if params is not None else SegParams()
+        res = np.ascontiguousarray(q_res, dtype=np.uint8)
+        off, ln, extent = cls._table(q_off, q_len)
+        h = handle.h if handle is not None else None
+        rc = lib.lx_query_mask_create_seg(h, _ptr(res) if res.size else None, _ptr(off) if off.size else None, _ptr(ln) if ln.size else None, len(off),
+                                          C.byref(p), host_threads, C.byref(out))
+        if rc != LX_OK:
+            raise LambdaExtError(rc, last_output_error())
+        return cls(out, handle, extent)
+
+    @classmethod
+    def from_bytes(cls, handle: "Handle | None", masked, q_off, q_len) -> "QueryMask":
+        lib, out = load(), C.c_void_p()
+        msk = np.ascontiguousarray(masked, dtype=np.uint8)
+        off, ln, extent = cls._table(q_off, q_len)
+        if msk.size < extent:
+            raise LambdaExtError(LX_EINVAL, "QueryMask.from_bytes: fewer mask bytes than letters")
+        h = handle.h if handle is not None else None
+        rc = lib.lx_query_mask_create(h, _ptr(msk) if msk.size else None, _ptr(off) if off.size else None, _ptr(ln) if ln.size else None, len(off),
+                                      C.byref(out))
+        if rc != LX_OK:
+            raise LambdaExtError(rc, last_output_error())
+        return cls(out, handle, extent)
+
+    def info(self):
+        """(letters, masked letters, sequences with a masked letter)"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self.lib.lx_query_mask_info(self.m, C.byref(a), C.byref(b), C.byref(c))
+        return int(a.value), int(b.value), int(c.value)
+
+    def copy(self) -> np.ndarray:
+        """0 / 1 per letter, indexed like q_res up to the last sequence's end"""
+        out = np.zeros(max(self.extent, 1), np.uint8)
+        if self.lib.lx_query_mask_copy(self.m, _ptr(out)) != LX_OK:
+            raise LambdaExtError(LX_EINVAL, last_output_error())
+        return out[:self.extent]
+
+    def close(self):
+        if getattr(self, "m", None):
+            self.lib.lx_query_mask_destroy(self.m)
+            self.m = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    __del__ = close
+
+
+def seed_queries(handle: "Handle | None", index: Index, s_res, q_res, q_red, q_off, q_len, params: SeedParams, reads=None,
+                 mask: "QueryMask | None" = None) -> SeedResult:
     """lx_seed_queries: search() for the reads whose first frame sequences are listed (None: all).  s_res None with a handle: the
-    subjects lx_set_subjects made resident."""
+    subjects lx_set_subjects made resident.  mask: lx_seed_queries_masked -- no seed starts on or covers a masked letter."""
     lib = load()
     keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8) for a in (s_res, q_res, q_red)]
     keep = [a if a is None or a.size else np.zeros(1, np.uint8) for a in keep]
     off, ln = np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(q_len, dtype=np.uint64)
     rd = None if reads is None else np.ascontiguousarray(reads, dtype=np.uint64)
     h, out = (handle.h if handle is not None else None), C.c_void_p()
-    rc = lib.lx_seed_queries(h, index.ix, *[None if a is None else _ptr(a) for a in keep], _ptr(off), _ptr(ln), len(off),
-                             None if rd is None else _ptr(rd), 0 if rd is None else len(rd), C.byref(params), C.byref(out))
+    args = (h, index.ix, *[None if a is None else _ptr(a) for a in keep], _ptr(off), _ptr(ln), len(off), None if rd is None else _ptr(rd),
+            0 if rd is None else len(rd))
+    if mask is None:
+        rc = lib.lx_seed_queries(*args, C.byref(params), C.byref(out))
+    else:
+        rc = lib.lx_seed_queries_masked(*args, mask.m, C.byref(params), C.byref(out))
     if rc != LX_OK:
         _raise(lib, h, rc)
     return SeedResult(out)

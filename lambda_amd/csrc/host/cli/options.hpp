@@ -44,6 +44,10 @@ struct Options
     std::vector<uint32_t> taxonList;     // --taxon-list T1,T2,... / --taxon-exclude T1,T2,...: search only the subjects under these taxa, or all but them
     bool        taxonExclude = false;    // (the list came from --taxon-exclude)
     std::string taxonFilter = "auto";    // --taxon-filter gpu | host | auto: where the subject mask is made and the match list filtered (auto: where the list stands)
+    std::string queryMasking = "none";   // --query-masking none | seg: mask low-complexity query regions before seeding (searchp; the header comment)
+    std::string masking     = "auto";    // --masking gpu | host | auto: where the query mask is made (auto: where the seeding runs)
+    int         segWindow   = 12;        // --seg-window W, --seg-k1 X, --seg-k2 Y: the rule's window and its two entropy bounds in bits (SEG's defaults)
+    double      segK1 = 2.2, segK2 = 2.5;
     int         threads    = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     bool        lazyQuery   = false; // --lazy-query 1: the query file block by block (the header comment)
     uint64_t    queryBlock  = 0;     // --query-block N: at most N reads per block; given and > 0, it implies --lazy-query 1
@@ -87,7 +91,11 @@ Options parse(int argc, char ** argv)
                                  "                 index's tree (mkindex* -m -x), or all but them (a subject without taxa is dropped by a list and kept by an exclusion); the promising\n"
                                  "                 seeds on other subjects are dropped before the extension, on the GPU or on the host (auto: where the seeding left them); e-values\n"
                                  "                 and bit scores keep the whole database's length; with --search0 1 a read whose hits all lie outside goes on to the second pass; the seeding aims\n"
-                                 "                 at -n + the number of dropped subjects (at most 64 matches per read, never fewer than -n) instead of -n\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
+                                 "                 at -n + the number of dropped subjects (at most 64 matches per read, never fewer than -n) instead of -n\n                 [--query-masking none|seg] [--masking gpu|host|auto] [--seg-window W] [--seg-k1 X] [--seg-k2 Y]   searchp: mask low-complexity query regions\n"
+                                 "                 before seeding (default none): a window of W letters (4 .. 64, default 12) of at most Y bits of entropy (default 2.5) belongs to a\n"
+                                 "                 low-complexity run, a run with a window of at most X bits (default 2.2) is masked -- SEG's first two stages, without its trimming, so\n"
+                                 "                 a mask is SEG's segment or wider; not segmasker.  A masked letter starts and carries no seed; extension, statistics and output read\n"
+                                 "                 the unmasked query.  The mask is made on the GPU or on the host threads (auto: where the seeding runs)\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
                                  "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
@@ -146,6 +154,7 @@ Options parse(int argc, char ** argv)
         return out;
     };
     bool taxonFilterGiven = false;
+    std::string maskingDetail; // the first of --masking / --seg-* that was given
     for (int i = 2; i < argc; ++i)
     {
         std::string a = argv[i];
@@ -294,6 +303,24 @@ Options parse(int argc, char ** argv)
             o.taxonFilter   = oneOf(val(), {"gpu", "host", "auto"}, "--taxon-filter takes gpu, host or auto");
             taxonFilterGiven = true;
         }
+        else if (!mk && a == "--query-masking")
+        {
+            o.queryMasking = oneOf(val(), {"none", "seg"}, "--query-masking takes none or seg");
+            if (o.queryMasking == "seg" && !prot)
+                throw std::runtime_error("--query-masking seg masks protein and translated queries (searchp); for " + o.cmd +
+                                         " the nucleotide rule, DUST, is not built: run without --query-masking");
+        }
+        else if (!mk && (a == "--masking" || a == "--seg-window" || a == "--seg-k1" || a == "--seg-k2"))
+        {
+            if (maskingDetail.empty())
+                maskingDetail = a;
+            if (a == "--masking")
+                o.masking = oneOf(val(), {"gpu", "host", "auto"}, "--masking takes gpu, host or auto");
+            else if (a == "--seg-window")
+                o.segWindow = std::stoi(val());
+            else
+                (a == "--seg-k1" ? o.segK1 : o.segK2) = std::stod(val());
+        }
         else if (a == "--render")
             o.render = oneOf(val(), {"gpu", "host", "auto"}, "--render takes gpu, host or auto");
         else if (a == "--seeding")
@@ -339,6 +366,15 @@ Options parse(int argc, char ** argv)
         if (std::ifstream(o.index).good()) // :252-256
             throw std::runtime_error("ERROR: An output file already exists at " + o.index + "\n       Remove it, or choose a different location.");
         return o;
+    }
+    if (!maskingDetail.empty() && o.queryMasking != "seg")
+        throw std::runtime_error(maskingDetail + " belongs to --query-masking seg: give that too");
+    if (o.queryMasking == "seg")
+    {
+        lx_seg_params const sp{o.segWindow, o.segK1, o.segK2};
+        int64_t             T[65], thr1 = 0, thr2 = 0;
+        if (lx_seg_tables(&sp, T, &thr1, &thr2) != LX_OK)
+            throw std::runtime_error(std::string("--seg-window takes 4 .. 64, --seg-k1 and --seg-k2 bits with 0 < k1 <= k2 <= log2(window) (") + lx_last_output_error() + ")");
     }
     if (o.query.empty() || o.db.empty())
         throw std::runtime_error("-q and -d (a FASTA file) or -i (an index made by lambda3 mkindex*) are required");

@@ -5,6 +5,7 @@
 //                   [--devices 0,1,...] [-t THREADS] [--table gpu|host|auto] [--table-slice WORDS] [--seeding gpu|host] [--records gpu|host|auto]
 //                   [--render gpu|host|auto] [--lca-top-percent P] [--lca gpu|host|auto]
 //                   [--taxon-list T1,T2,... | --taxon-exclude T1,T2,...] [--taxon-filter gpu|host|auto]
+//                   [--query-masking none|seg] [--masking gpu|host|auto] [--seg-window W] [--seg-k1 X] [--seg-k2 Y]   (searchp)
 //
 // --taxon-list / --taxon-exclude (BLAST's -taxids / -negative_taxids, DIAMOND's --taxonlist / --taxon-exclude): search only the
 // subjects under the listed taxa of the index's tree (mkindex* -m -x), or all but them.  lx_tax_subject_mask has the rule: a taxon is
@@ -25,6 +26,19 @@
 // are parsed: both options, an empty list, anything but numbers 1 .. 2^32 - 1, --taxon-filter without a list.  Refused once the index
 // is read: an index (or a -d FASTA database) without subject taxa and tree, and a --taxon-list taxon that the index's tree does not
 // hold (the reference's tree skips unassigned taxa with one child); --taxon-exclude of such a taxon is a warning.
+//
+// --query-masking seg (searchp; default none: nothing is masked and every byte of output is what it was): low-complexity query regions
+// are masked before seeding, as BLAST does with SEG on the translated frames of blastx / tblastn queries.  Soft masking: a masked letter
+// starts and carries no seed; pre-scoring, extension, statistics and output read the unmasked query.  The rule (lx_query_mask_create_seg)
+// is SEG's first two stages on alignment ranks in integers -- windows of --seg-window letters (4 .. 64, default 12) with at most --seg-k2
+// bits of entropy (default 2.5) form runs, a run that holds a window with at most --seg-k1 bits (default 2.2; 0 < k1 <= k2 <= log2 W)
+// masks every letter its windows cover --, WITHOUT SEG's third stage, the trimming of each raw segment: a mask is SEG's segment or a few
+// letters wider, and is not NCBI segmasker's.  The mask is made once per query set after frame expansion (--lazy-query: once per block)
+// and both passes (--search0 and the main search) seed with it.  --masking: gpu = by kernels on the worker's device, where the seeding
+// kernel reads it; host = on the -t threads (and uploaded where the seeding runs on the device); auto = where --seeding runs (profiles/query_mask_bench.txt:
+// 10^6 reads x 6 frames x 50 letters take 147 ms on 16 host threads and 76 ms on the device, upload included; the kernels 27 ms).  One line on stderr reports the parameters, the letters masked, the sequences touched, the
+// place and the time.  Refused while the options are parsed: --query-masking seg on searchn / searchbs (the nucleotide rule, DUST, is
+// not built), --masking or --seg-* without --query-masking seg, parameters outside the ranges.
 //
 // --lca-top-percent P (0 .. 100, default 100): which records of a query enter its LCA (lcataxid, lt, ls).  100 is the reference's
 // rule, every record (src/search_algo.hpp:884-907); below it only the records whose bit score lies within P percent of the query's
@@ -597,6 +611,10 @@ struct Part
     uint64_t                    nTaxonDropped = 0; // --taxon-list / --taxon-exclude: promising seeds on subjects the mask drops
     double                      msTaxon = 0;       // ... the mask and the filter: the kernels' time on the GPU, the wall clock on the host
     bool                        taxonOnGpu = false; // ... a pass of this worker filtered its list on the device
+    // --query-masking seg: the masks this worker made (one per job: its query set, or each of its blocks)
+    uint64_t                    nMaskLetters = 0, nMasked = 0, nMaskSeqs = 0;
+    double                      msMask = 0;        // ... the calls' wall clock (on the GPU: upload included)
+    bool                        maskOnGpu = false;
     std::string                 error;
 };
 
@@ -660,6 +678,8 @@ public:
     {
         uint64_t const qFrames = (uint64_t)c_.run.qFrames;
         beginJob(job);
+        if (c_.opt.queryMasking == "seg")
+            makeQueryMask(job);
         std::vector<uint64_t> all;
         for (uint64_t i = job.rLo * qFrames; i < job.rHi * qFrames; ++i)
             all.push_back(i);
@@ -705,6 +725,38 @@ private:
         if (est >= 100000)
             eng_.check(lx_reserve(eng_.raw(), est, est / 7, est / 12, c_.run.wantOps ? est / 12 * (len + len / 16) : 0));
     }
+
+    // --query-masking seg, once per job (the eager path: the worker's query set; --lazy-query: each block), after frame expansion; both
+    // passes seed with it.  The mask is made where --masking says (auto: where the seeding runs).  Seeding on the device needs the mask
+    // on this handle: one made on the host goes up as bytes; the host seeder reads a device mask's copy, which comes down on first use.
+    void makeQueryMask(Job const & job)
+    {
+        SeqSet const &      qs = *job.q;
+        lx_seg_params const sp{c_.opt.segWindow, c_.opt.segK1, c_.opt.segK2};
+        bool const          onGpu = c_.opt.masking == "gpu" || (c_.opt.masking == "auto" && gpuIndex_);
+        auto const          tMask = Clock::now();
+        seedMask_.reset();
+        madeMask_.reset();
+        lx_query_mask * m = nullptr;
+        if (lx_query_mask_create_seg(onGpu ? eng_.raw() : nullptr, qs.res.data(), qs.off.data(), qs.len.data(), qs.off.size(), &sp, c_.setup.seedThreads, &m) != LX_OK)
+            throw std::runtime_error(std::string("--query-masking seg: ") + lx_last_output_error());
+        madeMask_.reset(m);
+        if (!onGpu && gpuIndex_)
+        {
+            std::vector<uint8_t> bytes(qs.res.size() + 1, 0);
+            lx_query_mask *      up = nullptr;
+            if (lx_query_mask_copy(m, bytes.data()) != LX_OK ||
+                lx_query_mask_create(eng_.raw(), bytes.data(), qs.off.data(), qs.len.data(), qs.off.size(), &up) != LX_OK)
+                throw std::runtime_error(std::string("--query-masking seg: ") + lx_last_output_error());
+            seedMask_.reset(up);
+        }
+        uint64_t letters = 0, masked = 0, seqs = 0;
+        (void)lx_query_mask_info(m, &letters, &masked, &seqs);
+        pt_.nMaskLetters += letters, pt_.nMasked += masked, pt_.nMaskSeqs += seqs;
+        pt_.msMask += msSince(tMask);
+        pt_.maskOnGpu = pt_.maskOnGpu || onGpu;
+    }
+    lx_query_mask const * queryMask() const { return seedMask_ ? seedMask_.get() : madeMask_.get(); }
 
     // --taxon-list / --taxon-exclude, once per handle: the mask in host memory for the lists that stand there, and -- where the
     // matches stay on the device and --taxon-filter does not say host -- the tree resident on this handle and the mask by kernels
@@ -807,8 +859,9 @@ private:
         lx_seed_result * sr = nullptr;
         // the device takes the reads; those it declines (words far beyond the table's keys with many occurrences) and those of
         // a launch whose match buffer filled up are finished on the host threads inside the call
-        if (gpuIndex_ && lx_seed_queries(eng_.raw(), gpuIndex_, nullptr, qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(), reads.data(),
-                                         reads.size(), &spar_, &sr) != LX_OK)
+        // (--query-masking seg: with the job's mask; without one the call is lx_seed_queries)
+        if (gpuIndex_ && lx_seed_queries_masked(eng_.raw(), gpuIndex_, nullptr, qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(), reads.data(),
+                                                reads.size(), queryMask(), &spar_, &sr) != LX_OK)
         {
             // a HIP error in the seeding stage (its match buffer did not fit, ...): this pass and the following ones are
             // seeded on the host threads, from a clean slate
@@ -816,8 +869,8 @@ private:
             gpuIndex_      = nullptr;
             pt_.gpuSeeding = false;
         }
-        if (!sr && lx_seed_queries(nullptr, c_.table.ix.get(), db.res.data(), qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(), reads.data(),
-                                   reads.size(), &spar_, &sr) != LX_OK)
+        if (!sr && lx_seed_queries_masked(nullptr, c_.table.ix.get(), db.res.data(), qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(),
+                                          reads.data(), reads.size(), madeMask_.get(), &spar_, &sr) != LX_OK)
             throw std::runtime_error(std::string("lambda_ext: ") + lx_last_output_error());
         std::unique_ptr<lx_seed_result, FreeWith<lx_seed_result_free>> const keepSeeds(sr);
         lx_seed_stats const sst = lx_seed_result_stats(sr);
@@ -893,6 +946,8 @@ private:
     // --taxon-list / --taxon-exclude (behind eng_: destroyed before the handle)
     std::unique_ptr<lx_tax_dev, FreeWith<lx_tax_dev_destroy>>           taxDev_;
     std::unique_ptr<lx_subject_mask, FreeWith<lx_subject_mask_destroy>> devMask_, hostMask_;
+    // --query-masking seg: the job's mask as it was made, and -- made on the host while the seeding runs on the device -- its upload
+    std::unique_ptr<lx_query_mask, FreeWith<lx_query_mask_destroy>> madeMask_, seedMask_;
 };
 
 // worker w's thread: its set-up, then the jobs nextJob hands it (false: no more), each reported to jobDone with the worker's handle
@@ -1343,6 +1398,7 @@ LazyTotals runLazy(SearchContext const & c, QueryStream & stream, OutputSetup co
 struct Totals : Part
 {
     uint64_t nHsp = 0, nOut = 0; // records before and after _writeRecord's cut
+    uint64_t maskSum[3] = {0, 0, 0};
 
     void add(Part const & pt)
     {
@@ -1365,6 +1421,11 @@ struct Totals : Part
         nTaxonDropped += pt.nTaxonDropped;
         msTaxon    = std::max(msTaxon, pt.msTaxon);
         taxonOnGpu = taxonOnGpu || pt.taxonOnGpu;
+        // (the eager path: every worker masks the whole query set, so the counts are one worker's; --lazy-query: the blocks' sums)
+        maskSum[0] += pt.nMaskLetters, maskSum[1] += pt.nMasked, maskSum[2] += pt.nMaskSeqs;
+        nMaskLetters = std::max(nMaskLetters, pt.nMaskLetters), nMasked = std::max(nMasked, pt.nMasked), nMaskSeqs = std::max(nMaskSeqs, pt.nMaskSeqs);
+        msMask    = std::max(msMask, pt.msMask);
+        maskOnGpu = maskOnGpu || pt.maskOnGpu;
         rst += pt.rst;
     }
 };
@@ -1526,6 +1587,10 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
         std::fprintf(stderr, "lambda3 taxon filter: %llu of %llu subjects kept; %llu of %zu promising seeds dropped; on the %s (%.1f ms)\n",
                      (unsigned long long)taxon.nKept, (unsigned long long)taxon.nSubjects, (unsigned long long)t.nTaxonDropped, t.nPromising,
                      t.taxonOnGpu ? "GPU" : "host", t.msTaxon);
+    if (opt.queryMasking == "seg")
+        std::fprintf(stderr, "lambda3 query masking: seg %d/%g/%g, %llu of %llu letters masked, %llu sequence(s) touched, on the %s, %.1f ms\n", opt.segWindow, opt.segK1,
+                     opt.segK2, (unsigned long long)(run.lazy ? t.maskSum[1] : t.nMasked), (unsigned long long)(run.lazy ? t.maskSum[0] : t.nMaskLetters),
+                     (unsigned long long)(run.lazy ? t.maskSum[2] : t.nMaskSeqs), t.maskOnGpu ? "GPU" : "host", t.msMask);
     if (run.lazy)
         std::fprintf(stderr, "lambda3 query blocks: %llu block(s) of at most %llu read(s), %llu read(s) in the largest, at most %llu block(s) alive at once\n",
                      (unsigned long long)lazy.counts.blocks, (unsigned long long)run.blockReads, (unsigned long long)lazy.counts.largest,

@@ -606,6 +606,8 @@ struct SeedingInput
     bool             halfExact, adaptive;
     int              preScoring;
     double           preScoringThresh;
+    // a query mask's distance bytes, indexed like qRes (lx_qmask.h): a start whose seed covers a masked letter is blocked (NULL: none)
+    uint8_t const *  qMaskDist = nullptr;
 };
 
 // search(lH), :611-762, for the (frame-expanded) query sequences listed in `which` (all frames of a read, in order)
@@ -633,13 +635,18 @@ inline void seedQueries(ReducedIndex const & ix, SeedingInput const & in, SeedPa
         uint64_t const        L   = in.qLen[i];
         uint8_t const * const red = in.qRed + in.qOff[i];
         uint8_t const * const res = in.qRes + in.qOff[i];
+        uint8_t const * const dist = in.qMaskDist ? in.qMaskDist + in.qOff[i] : nullptr;
+        auto const blocked = [&](uint64_t p) { return dist && dist[p] < (uint8_t)so.seedLength; };
         {
             for (uint64_t seedBegin = 0;; seedBegin += (uint64_t)so.seedOffset)
             {
-                // skip the unknown letter, skip a letter whose successor is the same (:655-660)
-                while (seedBegin < L - (uint64_t)so.seedLength && (res[seedBegin] == in.unknownRank || res[seedBegin] == res[seedBegin + 1]))
+                // skip the unknown letter, skip a letter whose successor is the same (:655-660), skip a start whose seed covers a masked letter
+                while (seedBegin < L - (uint64_t)so.seedLength &&
+                       (res[seedBegin] == in.unknownRank || res[seedBegin] == res[seedBegin + 1] || blocked(seedBegin)))
                     ++seedBegin;
                 if (seedBegin > L - (uint64_t)so.seedLength) // :663
+                    break;
+                if (blocked(seedBegin)) // (the last start, still blocked: the frame ends)
                     break;
                 cursors.clear();
                 if (so.maxSeedDist != 0)

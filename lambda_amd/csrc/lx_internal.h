@@ -269,6 +269,22 @@ struct lx_seed_result
     lx_seed_stats         st{};
 };
 
+// what lx_query_mask_create* return (lx_qmask_host.cpp); lx_seed_queries_masked (lx_seed_host.cpp) reads it.  One distance byte per
+// letter (lx_qmask.h), indexed like the letters: on the host, on the handle's device, or both.
+struct lx_query_mask
+{
+    lx_handle *                  h = nullptr; // NULL: on the host only
+    std::vector<uint64_t>        off, len;    // the sequence table it was made for
+    uint64_t                     extent = 0, n_letters = 0, n_masked = 0, n_seqs_masked = 0;
+    mutable std::vector<uint8_t> dist;        // a device mask's comes down on first use
+    mutable bool                 have_host = false;
+    mutable std::mutex           down;        // (host_dist fills `dist` once)
+    lxi::DevBlock<uint8_t>       d_dist;
+
+    uint8_t const * host_dist() const; // NULL: the copy failed
+    ~lx_query_mask();
+};
+
 namespace lxi
 {
 

@@ -40,6 +40,7 @@ struct SeedDev
     unsigned long long *                    counters; // [0] matches written, [1] hitsAfterSeeding, [2] hitsFailedPreExtendTest, [3] buffer full
     uint64_t                                outCap;
     uint8_t *                               declined; // per read of this launch: 1 = seed it on the host
+    uint8_t const *                         qMask;    // a query mask's distance bytes, indexed like qRes (NULL: no mask)
 };
 
 constexpr int      kMaxSecond   = 24;       // letters behind the exact part of a seed the depth-first walk holds

@@ -130,6 +130,9 @@ __device__ __forceinline__ bool dev_promising(uint8_t const * q, uint64_t qLen, 
     return false;
 }
 
+// MASKED: p.qMask holds a query mask's distance bytes (lx_qmask.h) and a start whose seed covers a masked letter is blocked; the
+// instantiation without a mask compiles the two tests away (profiles/query_mask_bench.txt: seeding without a mask takes what it took).
+template <bool MASKED>
 __global__ __launch_bounds__(64) void seed_reads_kernel(SeedDev p)
 {
     uint64_t const r = (uint64_t)blockIdx.x * 64 + threadIdx.x;
@@ -211,11 +214,15 @@ __global__ __launch_bounds__(64) void seed_reads_kernel(SeedDev p)
         uint64_t const        L   = p.qLen[i];
         uint8_t const * const red = p.qRed + p.qOff[i];
         uint8_t const * const res = p.qRes + p.qOff[i];
+        uint8_t const * const dist = MASKED ? p.qMask + p.qOff[i] : nullptr;
         for (uint64_t seedBegin = 0; ok; seedBegin += (uint64_t)p.seedOffset)
         {
-            while (seedBegin < L - (uint64_t)p.seedLength && (res[seedBegin] == (uint8_t)p.unknownRank || res[seedBegin] == res[seedBegin + 1]))
+            while (seedBegin < L - (uint64_t)p.seedLength && (res[seedBegin] == (uint8_t)p.unknownRank || res[seedBegin] == res[seedBegin + 1] ||
+                                                              (MASKED && dist[seedBegin] < (uint8_t)p.seedLength)))
                 ++seedBegin;
             if (seedBegin > L - (uint64_t)p.seedLength)
+                break;
+            if (MASKED && dist[seedBegin] < (uint8_t)p.seedLength) // (the last start, still blocked: the frame ends)
                 break;
             uint8_t const * const seed = red + seedBegin;
             int const firstHalf  = p.maxSeedDist == 0 ? p.seedLength : p.halfExact ? p.seedLength / 2 : 0;
@@ -607,7 +614,10 @@ hipError_t seed_launch_reads(SeedDev const & p, hipStream_t stream)
 {
     if (p.nReads == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(seed_reads_kernel, dim3((unsigned)((p.nReads + 63) / 64)), dim3(64), 0, stream, p);
+    if (p.qMask)
+        hipLaunchKernelGGL(seed_reads_kernel<true>, dim3((unsigned)((p.nReads + 63) / 64)), dim3(64), 0, stream, p);
+    else
+        hipLaunchKernelGGL(seed_reads_kernel<false>, dim3((unsigned)((p.nReads + 63) / 64)), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
 

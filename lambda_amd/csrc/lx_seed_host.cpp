@@ -571,6 +571,7 @@ struct SeedCall // a checked call
     std::vector<uint64_t>    reads;
     uint64_t                 q_extent = 0;
     unsigned                 threads  = 1;
+    lx_query_mask const *    mask     = nullptr; // (on the device: the kernel reads its resident bytes; the host copy is for declined reads)
 };
 
 int check_call(lx_handle * h, lx_index const * ix, uint8_t const * s_res, uint8_t const * q_res, uint8_t const * q_red, uint64_t const * q_off,
@@ -705,6 +706,7 @@ int seed_on_device(lx_handle * h, lx_index const * ix, SeedCall & c, lx_seed_res
     d.preScoringThresh = c.in.preScoringThresh;
     d.seedLength = c.so.seedLength, d.seedOffset = c.so.seedOffset, d.maxSeedDist = c.so.maxSeedDist;
     d.counters = static_cast<unsigned long long *>(S.d_cnt.ptr), d.declined = static_cast<uint8_t *>(S.d_declined.ptr);
+    d.qMask = c.mask ? c.mask->d_dist.raw : nullptr;
 
     // (development aids of the front end's tests: several launches on a small input; a small buffer exercises "buffer full")
     uint64_t launchReads = lx::kLaunchReads, forcedCap = 0;
@@ -795,6 +797,8 @@ int seed_on_device(lx_handle * h, lx_index const * ix, SeedCall & c, lx_seed_res
                 LXS_HIP(h, hipMemcpy(s_down.data(), d_sres, s_down.size(), hipMemcpyDeviceToHost));
             c.in.sRes = s_down.data();
         }
+        if (c.mask && !(c.in.qMaskDist = c.mask->host_dist()))
+            return fail(h, LX_EHIP, "lx_seed_queries_masked: the mask did not come down from the device");
         std::sort(declined.begin(), declined.end());
         std::vector<lx_match> more;
         seed_on_host(ix, c, declined, more, res.st);
@@ -817,6 +821,13 @@ int seed_on_device(lx_handle * h, lx_index const * ix, SeedCall & c, lx_seed_res
 int lx_seed_queries(lx_handle * h, lx_index const * ix, uint8_t const * s_res, uint8_t const * q_res, uint8_t const * q_red, uint64_t const * q_off,
                     uint64_t const * q_len, uint64_t n_qseq, uint64_t const * reads, uint64_t n_reads, lx_seed_params const * p, lx_seed_result ** out)
 {
+    return lx_seed_queries_masked(h, ix, s_res, q_res, q_red, q_off, q_len, n_qseq, reads, n_reads, nullptr, p, out);
+}
+
+int lx_seed_queries_masked(lx_handle * h, lx_index const * ix, uint8_t const * s_res, uint8_t const * q_res, uint8_t const * q_red, uint64_t const * q_off,
+                           uint64_t const * q_len, uint64_t n_qseq, uint64_t const * reads, uint64_t n_reads, lx_query_mask const * m, lx_seed_params const * p,
+                           lx_seed_result ** out)
+{
     if (!out)
         return say(h, LX_EINVAL, "lx_seed_queries: NULL out");
     *out = nullptr;
@@ -828,6 +839,19 @@ int lx_seed_queries(lx_handle * h, lx_index const * ix, uint8_t const * s_res, u
         int      rc = check_call(h, ix, s_res, q_res, q_red, q_off, q_len, n_qseq, reads, n_reads, p, c);
         if (rc)
             return rc;
+        if (m)
+        {
+            if (m->off.size() != n_qseq || !std::equal(m->off.begin(), m->off.end(), q_off) || !std::equal(m->len.begin(), m->len.end(), q_len))
+                return say(h, LX_EINVAL, "lx_seed_queries_masked: the mask was made for another sequence table (%llu sequences; the call has %llu)",
+                           (unsigned long long)m->off.size(), (unsigned long long)n_qseq);
+            if (h && !m->h)
+                return say(h, LX_EINVAL, "lx_seed_queries_masked: seeding on the device needs a mask made with its handle (this one is on the host only)");
+            if (h && m->h != h)
+                return say(h, LX_EINVAL, "lx_seed_queries_masked: the mask was made on another handle");
+            c.mask = m;
+            if (!h && !(c.in.qMaskDist = m->host_dist()))
+                return say(h, LX_EHIP, "lx_seed_queries_masked: the mask did not come down from its device");
+        }
         std::unique_ptr<lx_seed_result> res(new lx_seed_result());
         if (h)
         {
