@@ -3,6 +3,8 @@ path (h == NULL) as sorted match lists with equal counters -- on inputs the kern
 read with many hits --, the device list handed to lx_iterate_matches_dev_top without a copy, and the lifetimes of indexes and
 results.  The host path itself is checked against brute force in tests/test_level3_abi.py."""
 import ctypes as C
+import re
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -134,6 +136,64 @@ def test_reads_the_device_declines_are_finished_inside_the_call(handle):
         handle.set_subjects(c["s_res"])
         r = capi.seed_queries(handle, dev_ix, None, c["q_res"], c["q_red"], q_off, q_len, _params(c, adaptive=True, max_seed_dist=0, max_matches=10))
         assert r.stats.reads_declined == st.reads_declined and np.array_equal(L3.sorted_matches(r.matches()), L3.sorted_matches(d.matches()))
+
+
+def _identical_subjects(copies):
+    """the construction of the test above with `copies` identical subjects: every key_len-word occurs `copies` times"""
+    rng = np.random.default_rng(7)
+    one = synth.STD20[rng.integers(0, 20, 60)].astype(np.uint8)
+    s_off, s_len = L3.offsets([60] * copies)
+    others = [synth.STD20[rng.integers(0, 20, 45)].astype(np.uint8) for _ in range(6)]
+    seqs = [one, others[0], one[5:50], *others[1:]]
+    q_off, q_len = L3.offsets([len(x) for x in seqs])
+    return dict(mode="protein", alph=10, frames=1, unknown=25, s_res=np.tile(one, copies), s_red=L3.LI10[np.tile(one, copies)], s_off=s_off,
+                s_len=s_len, q_res=np.concatenate(seqs), q_red=L3.LI10[np.concatenate(seqs)], q_off=q_off, q_len=q_len)
+
+
+@pytest.mark.parametrize("copies", [32, 33])
+def test_a_range_of_32_entries_is_the_last_the_device_keeps(handle, copies):
+    """dev_extend (lx_seed.hip) beyond the key length: a range of exactly 32 entries gets the full mask (the shift by 32 is avoided), a
+    range of 33 makes the read decline.  Either way the list and the counters are the host path's."""
+    c = _identical_subjects(copies)
+    assert L3.max_word_count(c) == copies
+    with capi.Index.build(handle, c["s_red"], c["s_off"], c["s_len"], 10) as dev_ix, capi.Index.build(None, c["s_red"], c["s_off"], c["s_len"], 10) as host_ix:
+        d, st = _both(handle, dev_ix, host_ix, c, _params(c, adaptive=True, max_seed_dist=0, max_matches=10))
+        m = d.matches()
+        # the reads equal to the subject hit every copy, with seeds elongated beyond the key length (where the mask takes over)
+        assert st.n_matches >= 2 * copies and int((m["qryEnd"] - m["qryStart"]).max()) > L3.key_len(10)
+        assert len(np.unique(m["subjId"][m["qryId"] == 0])) == copies
+        if copies == 32:
+            assert (st.reads_declined, st.launches_full) == (0, 0)
+        else:
+            assert st.reads_declined >= 1
+
+
+K_MAX_SECOND = int(re.search(r"kMaxSecond\s*=\s*(\d+)", (Path(__file__).resolve().parents[1] / "lambda_amd" / "csrc" / "lx_seed.h").read_text()).group(1))
+
+
+@pytest.mark.parametrize("seed_length", [K_MAX_SECOND, K_MAX_SECOND + 1])
+def test_the_depth_first_walk_holds_seeds_of_up_to_kMaxSecond_letters(handle, seed_length):
+    """Nucleotide reads of 40 letters, seeds with one error anywhere (no exact half): the walk's stack holds the whole seed.  A seed of
+    kMaxSecond letters is the device's, one letter more sends every read that is long enough for a seed to the host."""
+    n_reads = 20
+    c = dict(L3.make_case("nucleotide", n_reads, CASE_SEEDS["nucleotide"]))
+    assert c["frames"] == 2
+    seqs = [c["q_res"][int(o):int(o) + 40] for o in c["q_off"]]
+    seqs[6], seqs[7] = seqs[6][:20], seqs[7][:20]  # read 3: both frames shorter than a seed
+    assert all(len(x) == 40 for k, x in enumerate(seqs) if k not in (6, 7))
+    c["q_res"] = np.concatenate(seqs)
+    c["q_red"] = L3.DNA4[c["q_res"]]
+    c["q_off"], c["q_len"] = L3.offsets([len(x) for x in seqs])
+    assert L3.max_word_count(c) <= 32  # (no read declines for the other reason)
+    with capi.Index.build(handle, c["s_red"], c["s_off"], c["s_len"], c["alph"]) as dev_ix, capi.Index.build(None, c["s_red"], c["s_off"], c["s_len"], c["alph"]) as host_ix:
+        total = 0
+        for kw in (dict(pre_scoring=0, pre_scoring_thresh=0.0), dict(), dict(adaptive=False)):
+            p = _params(c, seed_length=seed_length, seed_offset=8, half_exact=False, max_seed_dist=1, **kw)
+            d, st = _both(handle, dev_ix, host_ix, c, p)
+            assert st.launches_full == 0
+            assert st.reads_declined == (0 if seed_length <= K_MAX_SECOND else n_reads - 1), kw
+            total += st.n_matches
+        assert total >= 10, total
 
 
 def test_a_read_with_more_matches_than_its_share_of_the_buffer(handle):
