@@ -1197,6 +1197,25 @@ int  lx_query_mask_create(lx_handle * h, uint8_t const * masked, uint64_t const 
 int  lx_query_mask_info(lx_query_mask const * m, uint64_t * n_letters, uint64_t * n_masked, uint64_t * n_seqs_masked);
 int  lx_query_mask_copy(lx_query_mask const * m, uint8_t * masked);
 void lx_query_mask_destroy(lx_query_mask * m);
+/* The nucleotide rule: symmetric DUST (Morgulis et al. 2006) on alignment ranks, in integers.  A, C, G, T = 0 .. 3; any other rank
+ * (N) is a break: never masked, and in no interval, so a sequence is a set of maximal stretches of ranks 0 .. 3, each on its own.
+ * (These are lambda3 searchbs' ranks; a caller with the ranks A, C, G, N, T, as searchn's, exchanges 3 and 4 in the letters it
+ * passes here -- the rule does not care which of 0 .. 3 is which letter.)
+ *   Letter i of a stretch starts triplet 16 a[i] + 4 a[i + 1] + a[i + 2].  An interval of l consecutive triplets covers l + 2 letters;
+ *   with r = the sum over the 64 triplet kinds of c (c - 1) / 2, c the count of the kind in the interval, its score is r / (l - 1) for
+ *   l >= 2 and 0 for l = 1 (scores are compared by cross-multiplication).  An interval is perfect when 10 r > level (l - 1) and no
+ *   sub-interval scores strictly higher.  A letter is masked exactly when it lies in a perfect interval of at most `window` letters.
+ * dustmasker's -linker is NOT built, and the masks were not compared with dustmasker's or sdust's: the claim is the rule as stated.
+ * Ranges: window 4 .. 64 (default 64), level 1 .. 1000 (default 20): dustmasker's and sdust's defaults.
+ * lx_query_mask_create_dust has lx_query_mask_create_seg's contract (h != NULL: by kernels, resident, phase 15; h == NULL: on
+ * host_threads host threads; the same LX_EINVAL refusals) and makes an ordinary lx_query_mask. */
+typedef struct lx_dust_params
+{
+    int32_t window, level;
+} lx_dust_params;
+void lx_dust_params_default(lx_dust_params * p);
+int  lx_query_mask_create_dust(lx_handle * h, uint8_t const * q_res, uint64_t const * q_off, uint64_t const * q_len, uint64_t n_qseq, lx_dust_params const * p,
+                               uint32_t host_threads, lx_query_mask ** out);
 /* lx_seed_queries with a mask (m == NULL: exactly lx_seed_queries).  A start p of a sequence is blocked when one of the seed's first
  * seed_length letters, [p, p + seed_length), is masked.  The loop that moves a start off the unknown letter passes a blocked start
  * over in the same way; it stops at L - seed_length, and a start that is still blocked there makes no seed, which ends the frame.
@@ -1227,7 +1246,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
  * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,
  * numbers, measure, scans, emit), 13 = the LCA kernels (lx_compute_lca_dev: query heads, fold; launches = the number of ranges),
  * 14 = the taxon filter's kernels (lx_subject_mask_create_dev: mark, climb, subjects; lx_seed_result_filter: flags + count, scatter),
- * 15 = the query masking kernels (lx_query_mask_create_seg on a handle: stops, flags, carries, fill, distances, count). */
+ * 15 = the query masking kernels (lx_query_mask_create_seg on a handle: stops, flags, carries, fill, distances, count;
+ * lx_query_mask_create_dust on a handle: stops, breaks, sweep, cover, distances, count). */
 int lx_last_phase_ms(lx_handle * h, int phase, float * ms, int * launches);
 
 #ifdef __cplusplus

@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = [
     "lx_lca_options_default", "lx_compute_lca_ex", "lx_check_tax_tree", "lx_tax_dev_create", "lx_tax_dev_destroy", "lx_compute_lca_dev",
     "lx_tax_subject_mask", "lx_subject_mask_create_dev", "lx_subject_mask_create", "lx_subject_mask_info", "lx_subject_mask_copy", "lx_subject_mask_destroy", "lx_seed_result_filter",
     "lx_seg_params_default", "lx_seg_tables", "lx_query_mask_create_seg", "lx_query_mask_create", "lx_query_mask_info", "lx_query_mask_copy", "lx_query_mask_destroy",
-    "lx_seed_queries_masked",
+    "lx_seed_queries_masked", "lx_dust_params_default", "lx_query_mask_create_dust",
 ]
 
 LX_OPT_MAX_SLEN = 4
@@ -150,6 +150,14 @@ class SegParams(C.Structure):
 
     def __init__(self, window: int = 12, k1: float = 2.2, k2: float = 2.5):
         super().__init__(window, k1, k2)
+
+
+class DustParams(C.Structure):
+    """lx_dust_params: window 4 .. 64 letters, level 1 .. 1000 (ten times the score bound); the defaults are dustmasker's and sdust's."""
+    _fields_ = [("window", C.c_int32), ("level", C.c_int32)]
+
+    def __init__(self, window: int = 64, level: int = 20):
+        super().__init__(window, level)
 
 
 class SeedStats(C.Structure):
@@ -366,6 +374,10 @@ def load():
         lib.lx_query_mask_copy.argtypes = [vp, vp]
         lib.lx_query_mask_destroy.argtypes = [vp]
         lib.lx_query_mask_destroy.restype = None
+    if hasattr(lib, "lx_query_mask_create_dust"):
+        lib.lx_dust_params_default.argtypes = [C.POINTER(DustParams)]
+        lib.lx_dust_params_default.restype = None
+        lib.lx_query_mask_create_dust.argtypes = [vp, vp, vp, vp, u64, C.POINTER(DustParams), C.c_uint32, C.POINTER(vp)]
     lib.lx_seed_result_stats.argtypes = [vp]
     lib.lx_seed_result_stats.restype = SeedStats
     lib.lx_seed_result_matches.argtypes = [vp]
@@ -976,7 +988,7 @@ def seg_tables(params: "SegParams | None" = None):
 
 class QueryMask:
     """lx_query_mask: which letters of a query set are masked.  seg(handle or None, q_res, q_off, q_len, params) applies the SEG rule
-    (with a handle: by kernels, the mask stays on its device); from_bytes(handle or None, masked, q_off, q_len) takes given 0 / 1
+    (with a handle: by kernels, the mask stays on its device), dust(...) the nucleotide rule in the same way; from_bytes(handle or None, masked, q_off, q_len) takes given 0 / 1
     bytes indexed like q_res.  Close it before its handle."""
 
     def __init__(self, m, handle, extent):
@@ -995,6 +1007,19 @@ class QueryMask:
         h = handle.h if handle is not None else None
         rc = lib.lx_query_mask_create_seg(h, _ptr(res) if res.size else None, _ptr(off) if off.size else None, _ptr(ln) if ln.size else None, len(off),
                                           C.byref(p), host_threads, C.byref(out))
+        if rc != LX_OK:
+            raise LambdaExtError(rc, last_output_error())
+        return cls(out, handle, extent)
+
+    @classmethod
+    def dust(cls, handle: "Handle | None", q_res, q_off, q_len, params: "DustParams | None" = None, host_threads: int = 0) -> "QueryMask":
+        """the nucleotide rule, symmetric DUST, on alignment ranks A, C, G, T = 0 .. 3 (any other rank is a break)"""
+        lib, out, p = load(), C.c_void_p(), params if params is not None else DustParams()
+        res = np.ascontiguousarray(q_res, dtype=np.uint8)
+        off, ln, extent = cls._table(q_off, q_len)
+        h = handle.h if handle is not None else None
+        rc = lib.lx_query_mask_create_dust(h, _ptr(res) if res.size else None, _ptr(off) if off.size else None, _ptr(ln) if ln.size else None, len(off),
+                                           C.byref(p), host_threads, C.byref(out))
         if rc != LX_OK:
             raise LambdaExtError(rc, last_output_error())
         return cls(out, handle, extent)

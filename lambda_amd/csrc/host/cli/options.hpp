@@ -44,10 +44,11 @@ struct Options
     std::vector<uint32_t> taxonList;     // --taxon-list T1,T2,... / --taxon-exclude T1,T2,...: search only the subjects under these taxa, or all but them
     bool        taxonExclude = false;    // (the list came from --taxon-exclude)
     std::string taxonFilter = "auto";    // --taxon-filter gpu | host | auto: where the subject mask is made and the match list filtered (auto: where the list stands)
-    std::string queryMasking = "none";   // --query-masking none | seg: mask low-complexity query regions before seeding (searchp; the header comment)
+    std::string queryMasking = "none";   // --query-masking none | seg (searchp) | dust (searchn, searchbs): mask low-complexity query regions before seeding (the header comment)
     std::string masking     = "auto";    // --masking gpu | host | auto: where the query mask is made (auto: where the seeding runs)
     int         segWindow   = 12;        // --seg-window W, --seg-k1 X, --seg-k2 Y: the rule's window and its two entropy bounds in bits (SEG's defaults)
     double      segK1 = 2.2, segK2 = 2.5;
+    int         dustWindow = 64, dustLevel = 20; // --dust-window W, --dust-level L: DUST's longest interval in letters and ten times its score bound (dustmasker's defaults)
     int         threads    = 0;    // -t host threads for the word table and the seeding (default: what the machine grants)
     bool        lazyQuery   = false; // --lazy-query 1: the query file block by block (the header comment)
     uint64_t    queryBlock  = 0;     // --query-block N: at most N reads per block; given and > 0, it implies --lazy-query 1
@@ -95,7 +96,12 @@ Options parse(int argc, char ** argv)
                                  "                 before seeding (default none): a window of W letters (4 .. 64, default 12) of at most Y bits of entropy (default 2.5) belongs to a\n"
                                  "                 low-complexity run, a run with a window of at most X bits (default 2.2) is masked -- SEG's first two stages, without its trimming, so\n"
                                  "                 a mask is SEG's segment or wider; not segmasker.  A masked letter starts and carries no seed; extension, statistics and output read\n"
-                                 "                 the unmasked query.  The mask is made on the GPU or on the host threads (auto: where the seeding runs)\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
+                                 "                 the unmasked query.  The mask is made on the GPU or on the host threads (auto: where the seeding runs)\n                 [--query-masking none|dust] [--masking gpu|host|auto] [--dust-window W] [--dust-level L]   searchn, searchbs: the same with the nucleotide\n"
+                                 "                 rule, symmetric DUST (Morgulis et al. 2006) in integers: within a stretch of A, C, G, T an interval of l overlapping triplets scores\n"
+                                 "                 r / (l - 1), r = the sum over triplet kinds of c (c - 1) / 2; a letter is masked when it lies in an interval of at most W letters\n"
+                                 "                 (4 .. 64, default 64) that scores above L / 10 (1 .. 1000, default 20) and holds no sub-interval that scores higher; N is never\n"
+                                 "                 masked and ends every interval.  dustmasker's -linker is not built, and the masks were not compared with dustmasker's or sdust's\n"
+                                 "                 (10^6 reads x 2 frames x 150 letters: 1944 ms on 16 host threads, 39 ms on the GPU with the upload)\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
                                  "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
@@ -155,6 +161,8 @@ Options parse(int argc, char ** argv)
     };
     bool taxonFilterGiven = false;
     std::string maskingDetail; // the first of --masking / --seg-* that was given
+    std::string segDetail, dustDetail; // the first of --seg-* / of --dust-*
+    bool        maskingGiven = false;
     for (int i = 2; i < argc; ++i)
     {
         std::string a = argv[i];
@@ -305,21 +313,34 @@ Options parse(int argc, char ** argv)
         }
         else if (!mk && a == "--query-masking")
         {
-            o.queryMasking = oneOf(val(), {"none", "seg"}, "--query-masking takes none or seg");
-            if (o.queryMasking == "seg" && !prot)
-                throw std::runtime_error("--query-masking seg masks protein and translated queries (searchp); for " + o.cmd +
-                                         " the nucleotide rule, DUST, is not built: run without --query-masking");
+            std::string const v = val();
+            if (v == "seg" && !prot)
+                throw std::runtime_error("--query-masking seg: SEG is the protein rule (searchp); for " + o.cmd +
+                                         " the nucleotide form of SEG, unlike DUST, is not built: use --query-masking dust");
+            o.queryMasking = prot ? oneOf(v, {"none", "seg"}, "--query-masking takes none or seg (dust is the rule of searchn and searchbs)")
+                                  : oneOf(v, {"none", "dust"}, "--query-masking takes none or dust");
         }
         else if (!mk && (a == "--masking" || a == "--seg-window" || a == "--seg-k1" || a == "--seg-k2"))
         {
             if (maskingDetail.empty())
                 maskingDetail = a;
+            if (a != "--masking" && segDetail.empty())
+                segDetail = a;
             if (a == "--masking")
-                o.masking = oneOf(val(), {"gpu", "host", "auto"}, "--masking takes gpu, host or auto");
+            {
+                o.masking    = oneOf(val(), {"gpu", "host", "auto"}, "--masking takes gpu, host or auto");
+                maskingGiven = true;
+            }
             else if (a == "--seg-window")
                 o.segWindow = std::stoi(val());
             else
                 (a == "--seg-k1" ? o.segK1 : o.segK2) = std::stod(val());
+        }
+        else if (!mk && (a == "--dust-window" || a == "--dust-level"))
+        {
+            if (dustDetail.empty())
+                dustDetail = a;
+            (a == "--dust-window" ? o.dustWindow : o.dustLevel) = std::stoi(val());
         }
         else if (a == "--render")
             o.render = oneOf(val(), {"gpu", "host", "auto"}, "--render takes gpu, host or auto");
@@ -367,8 +388,21 @@ Options parse(int argc, char ** argv)
             throw std::runtime_error("ERROR: An output file already exists at " + o.index + "\n       Remove it, or choose a different location.");
         return o;
     }
-    if (!maskingDetail.empty() && o.queryMasking != "seg")
+    if (!dustDetail.empty() && o.queryMasking != "dust")
+        throw std::runtime_error(dustDetail + " belongs to --query-masking dust" + (prot ? ", the rule of searchn and searchbs" : ": give that too"));
+    if (prot && !maskingDetail.empty() && o.queryMasking != "seg")
         throw std::runtime_error(maskingDetail + " belongs to --query-masking seg: give that too");
+    if (!prot && !segDetail.empty())
+        throw std::runtime_error(segDetail + " belongs to --query-masking seg, the protein rule (searchp)");
+    if (!prot && maskingGiven && o.queryMasking != "dust")
+        throw std::runtime_error("--masking belongs to --query-masking dust: give that too");
+    if (o.queryMasking == "dust")
+    {
+        if (o.dustWindow < 4 || o.dustWindow > 64)
+            throw std::runtime_error("--dust-window takes 4 .. 64 (letters: the longest interval the rule scores)");
+        if (o.dustLevel < 1 || o.dustLevel > 1000)
+            throw std::runtime_error("--dust-level takes 1 .. 1000 (ten times the score bound; 20 is dustmasker's)");
+    }
     if (o.queryMasking == "seg")
     {
         lx_seg_params const sp{o.segWindow, o.segK1, o.segK2};

@@ -6,6 +6,7 @@
 //                   [--render gpu|host|auto] [--lca-top-percent P] [--lca gpu|host|auto]
 //                   [--taxon-list T1,T2,... | --taxon-exclude T1,T2,...] [--taxon-filter gpu|host|auto]
 //                   [--query-masking none|seg] [--masking gpu|host|auto] [--seg-window W] [--seg-k1 X] [--seg-k2 Y]   (searchp)
+//                   [--query-masking none|dust] [--masking gpu|host|auto] [--dust-window W] [--dust-level L]          (searchn, searchbs)
 //
 // --taxon-list / --taxon-exclude (BLAST's -taxids / -negative_taxids, DIAMOND's --taxonlist / --taxon-exclude): search only the
 // subjects under the listed taxa of the index's tree (mkindex* -m -x), or all but them.  lx_tax_subject_mask has the rule: a taxon is
@@ -37,8 +38,20 @@
 // and both passes (--search0 and the main search) seed with it.  --masking: gpu = by kernels on the worker's device, where the seeding
 // kernel reads it; host = on the -t threads (and uploaded where the seeding runs on the device); auto = where --seeding runs (profiles/query_mask_bench.txt:
 // 10^6 reads x 6 frames x 50 letters take 147 ms on 16 host threads and 76 ms on the device, upload included; the kernels 27 ms).  One line on stderr reports the parameters, the letters masked, the sequences touched, the
-// place and the time.  Refused while the options are parsed: --query-masking seg on searchn / searchbs (the nucleotide rule, DUST, is
-// not built), --masking or --seg-* without --query-masking seg, parameters outside the ranges.
+// place and the time.  Refused while the options are parsed: --query-masking seg on searchn / searchbs (SEG is the protein rule; theirs
+// is dust, below), --masking or --seg-* without --query-masking seg, parameters outside the ranges.
+//
+// --query-masking dust (searchn, searchbs; default none): the same soft masking with the nucleotide rule (lx_query_mask_create_dust),
+// symmetric DUST (Morgulis et al. 2006) in integers: within a maximal stretch of A, C, G, T letter i starts the triplet of letters i,
+// i + 1, i + 2; an interval of l consecutive triplets covers l + 2 letters and scores r / (l - 1), r = the sum over the 64 triplet kinds
+// of c (c - 1) / 2 with c the kind's count in the interval; a letter is masked exactly when it lies in an interval of at most
+// --dust-window letters (4 .. 64, default 64) whose score is above --dust-level / 10 (1 .. 1000, default 20) and which holds no
+// sub-interval that scores strictly higher.  N is never masked and ends every interval.  The defaults are dustmasker's and sdust's; its
+// -linker (joining masked intervals one letter apart) is NOT built, and no mask was compared with dustmasker's or sdust's output: what is
+// claimed is the rule as stated.  The mask is made on the read's own letters after frame expansion (searchbs: the unreduced letters;
+// the bisulfite reduction differs per frame), once per query set or lazy block, for both passes.  --masking as above (profiles/dust_mask_bench.txt: 10^6 reads x 2 frames x 150 letters take 1944 ms on 16 host threads and 39 ms on the device, upload included; the kernels 26 ms).  The report line reads "dust W/L" for the
+// parameters.  Refused while the options are parsed: --query-masking dust on searchp, --dust-* without --query-masking dust, --masking
+// on searchn / searchbs without it, --seg-* on searchn / searchbs, --dust-window outside 4 .. 64, --dust-level outside 1 .. 1000.
 //
 // --lca-top-percent P (0 .. 100, default 100): which records of a query enter its LCA (lcataxid, lt, ls).  100 is the reference's
 // rule, every record (src/search_algo.hpp:884-907); below it only the records whose bit score lies within P percent of the query's
@@ -611,7 +624,7 @@ struct Part
     uint64_t                    nTaxonDropped = 0; // --taxon-list / --taxon-exclude: promising seeds on subjects the mask drops
     double                      msTaxon = 0;       // ... the mask and the filter: the kernels' time on the GPU, the wall clock on the host
     bool                        taxonOnGpu = false; // ... a pass of this worker filtered its list on the device
-    // --query-masking seg: the masks this worker made (one per job: its query set, or each of its blocks)
+    // --query-masking seg | dust: the masks this worker made (one per job: its query set, or each of its blocks)
     uint64_t                    nMaskLetters = 0, nMasked = 0, nMaskSeqs = 0;
     double                      msMask = 0;        // ... the calls' wall clock (on the GPU: upload included)
     bool                        maskOnGpu = false;
@@ -678,7 +691,7 @@ public:
     {
         uint64_t const qFrames = (uint64_t)c_.run.qFrames;
         beginJob(job);
-        if (c_.opt.queryMasking == "seg")
+        if (c_.opt.queryMasking != "none")
             makeQueryMask(job);
         std::vector<uint64_t> all;
         for (uint64_t i = job.rLo * qFrames; i < job.rHi * qFrames; ++i)
@@ -726,20 +739,34 @@ private:
             eng_.check(lx_reserve(eng_.raw(), est, est / 7, est / 12, c_.run.wantOps ? est / 12 * (len + len / 16) : 0));
     }
 
-    // --query-masking seg, once per job (the eager path: the worker's query set; --lazy-query: each block), after frame expansion; both
+    // --query-masking seg | dust, once per job (the eager path: the worker's query set; --lazy-query: each block), after frame expansion; both
     // passes seed with it.  The mask is made where --masking says (auto: where the seeding runs).  Seeding on the device needs the mask
     // on this handle: one made on the host goes up as bytes; the host seeder reads a device mask's copy, which comes down on first use.
     void makeQueryMask(Job const & job)
     {
-        SeqSet const &      qs = *job.q;
-        lx_seg_params const sp{c_.opt.segWindow, c_.opt.segK1, c_.opt.segK2};
-        bool const          onGpu = c_.opt.masking == "gpu" || (c_.opt.masking == "auto" && gpuIndex_);
+        SeqSet const &       qs   = *job.q;
+        bool const           dust = c_.opt.queryMasking == "dust"; // (on qs.res, the read's own letters: searchbs reduces them per frame)
+        std::string const    what = "--query-masking " + c_.opt.queryMasking + ": ";
+        lx_seg_params const  sp{c_.opt.segWindow, c_.opt.segK1, c_.opt.segK2};
+        lx_dust_params const dp{c_.opt.dustWindow, c_.opt.dustLevel};
+        bool const           onGpu = c_.opt.masking == "gpu" || (c_.opt.masking == "auto" && gpuIndex_);
         auto const          tMask = Clock::now();
         seedMask_.reset();
         madeMask_.reset();
         lx_query_mask * m = nullptr;
-        if (lx_query_mask_create_seg(onGpu ? eng_.raw() : nullptr, qs.res.data(), qs.off.data(), qs.len.data(), qs.off.size(), &sp, c_.setup.seedThreads, &m) != LX_OK)
-            throw std::runtime_error(std::string("--query-masking seg: ") + lx_last_output_error());
+        lx_handle * const at = onGpu ? eng_.raw() : nullptr;
+        // (the rule reads A, C, G, T = 0 .. 3 and takes every other rank as a break: searchbs' ranks; searchn's are A, C, G, N, T, so its
+        // letters go in with 3 and 4 exchanged)
+        std::vector<uint8_t> swapped;
+        if (dust && c_.opt.cmd == "searchn")
+        {
+            swapped.resize(qs.res.size());
+            for (size_t j = 0; j < swapped.size(); ++j)
+                swapped[j] = qs.res[j] == 3 ? 4 : qs.res[j] == 4 ? 3 : qs.res[j];
+        }
+        if ((dust ? lx_query_mask_create_dust(at, swapped.empty() ? qs.res.data() : swapped.data(), qs.off.data(), qs.len.data(), qs.off.size(), &dp, c_.setup.seedThreads, &m)
+                  : lx_query_mask_create_seg(at, qs.res.data(), qs.off.data(), qs.len.data(), qs.off.size(), &sp, c_.setup.seedThreads, &m)) != LX_OK)
+            throw std::runtime_error(what + lx_last_output_error());
         madeMask_.reset(m);
         if (!onGpu && gpuIndex_)
         {
@@ -747,7 +774,7 @@ private:
             lx_query_mask *      up = nullptr;
             if (lx_query_mask_copy(m, bytes.data()) != LX_OK ||
                 lx_query_mask_create(eng_.raw(), bytes.data(), qs.off.data(), qs.len.data(), qs.off.size(), &up) != LX_OK)
-                throw std::runtime_error(std::string("--query-masking seg: ") + lx_last_output_error());
+                throw std::runtime_error(what + lx_last_output_error());
             seedMask_.reset(up);
         }
         uint64_t letters = 0, masked = 0, seqs = 0;
@@ -859,7 +886,7 @@ private:
         lx_seed_result * sr = nullptr;
         // the device takes the reads; those it declines (words far beyond the table's keys with many occurrences) and those of
         // a launch whose match buffer filled up are finished on the host threads inside the call
-        // (--query-masking seg: with the job's mask; without one the call is lx_seed_queries)
+        // (--query-masking seg | dust: with the job's mask; without one the call is lx_seed_queries)
         if (gpuIndex_ && lx_seed_queries_masked(eng_.raw(), gpuIndex_, nullptr, qs.res.data(), qRed.data(), qs.off.data(), qs.len.data(), qs.off.size(), reads.data(),
                                                 reads.size(), queryMask(), &spar_, &sr) != LX_OK)
         {
@@ -946,7 +973,7 @@ private:
     // --taxon-list / --taxon-exclude (behind eng_: destroyed before the handle)
     std::unique_ptr<lx_tax_dev, FreeWith<lx_tax_dev_destroy>>           taxDev_;
     std::unique_ptr<lx_subject_mask, FreeWith<lx_subject_mask_destroy>> devMask_, hostMask_;
-    // --query-masking seg: the job's mask as it was made, and -- made on the host while the seeding runs on the device -- its upload
+    // --query-masking seg | dust: the job's mask as it was made, and -- made on the host while the seeding runs on the device -- its upload
     std::unique_ptr<lx_query_mask, FreeWith<lx_query_mask_destroy>> madeMask_, seedMask_;
 };
 
@@ -1587,6 +1614,10 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
         std::fprintf(stderr, "lambda3 taxon filter: %llu of %llu subjects kept; %llu of %zu promising seeds dropped; on the %s (%.1f ms)\n",
                      (unsigned long long)taxon.nKept, (unsigned long long)taxon.nSubjects, (unsigned long long)t.nTaxonDropped, t.nPromising,
                      t.taxonOnGpu ? "GPU" : "host", t.msTaxon);
+    if (opt.queryMasking == "dust")
+        std::fprintf(stderr, "lambda3 query masking: dust %d/%d, %llu of %llu letters masked, %llu sequence(s) touched, on the %s, %.1f ms\n", opt.dustWindow,
+                     opt.dustLevel, (unsigned long long)(run.lazy ? t.maskSum[1] : t.nMasked), (unsigned long long)(run.lazy ? t.maskSum[0] : t.nMaskLetters),
+                     (unsigned long long)(run.lazy ? t.maskSum[2] : t.nMaskSeqs), t.maskOnGpu ? "GPU" : "host", t.msMask);
     if (opt.queryMasking == "seg")
         std::fprintf(stderr, "lambda3 query masking: seg %d/%g/%g, %llu of %llu letters masked, %llu sequence(s) touched, on the %s, %.1f ms\n", opt.segWindow, opt.segK1,
                      opt.segK2, (unsigned long long)(run.lazy ? t.maskSum[1] : t.nMasked), (unsigned long long)(run.lazy ? t.maskSum[0] : t.nMaskLetters),

@@ -236,6 +236,10 @@ struct QmaskDev
     unsigned long long * count; // [0] masked letters, [1] sequences with a masked letter; zero
 };
 hipError_t qmask_launch(QmaskDev const & p, hipStream_t stream);
+// the first and the last two passes alone, for a rule that writes the covered letters itself (lx_dust.hip): the stop bits; the distance
+// bytes and the two counters from F[w + 1] = the covered letters of word w
+hipError_t qmask_launch_stops(QmaskDev const & p, hipStream_t stream);
+hipError_t qmask_launch_covered(QmaskDev const & p, hipStream_t stream);
 
 } // namespace qmask
 } // namespace lx

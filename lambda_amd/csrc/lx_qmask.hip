@@ -12,6 +12,7 @@
 //   fill     the tile ops again, now with the carry that arrives: every word's windows whose run holds a trigger (F).
 //   dist     one lane per letter: the letters F's windows cover (F and the word in front of it, shifted W - 1 times), then the first
 //            covered letter among this one and the 63 behind it that no stop bit separates from it.  Counts the masked letters.
+//            (A second instantiation reads covered letters that another rule left in F: lx_dust.hip.)
 //   touched  one lane per sequence hops along its distance bytes to the first 0: the sequences with a masked letter.
 // Integer work only; the tables come from the host (lx_seg_tables).
 #include "lx_qmask.h"
@@ -162,6 +163,8 @@ __global__ __launch_bounds__(kTileWords) void fill_kernel(QmaskDev p)
         p.F[w + 1] = seg_word_fill(A, B, up, down);
 }
 
+// COVERED: F holds the covered letters themselves (word w at F[w + 1]), not the windows that cover them
+template <bool COVERED>
 __global__ __launch_bounds__(kFlagBlock) void dist_kernel(QmaskDev p)
 {
     uint64_t const g = (uint64_t)blockIdx.x * kFlagBlock + threadIdx.x, w = g >> 6; // (w is the wavefront's)
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(kFlagBlock) void dist_kernel(QmaskDev p)
         return;
     int const      lane = threadIdx.x & 63;
     uint64_t const f0 = p.F[w], f1 = p.F[w + 1], f2 = p.F[w + 2]; // the words w - 1, w, w + 1
-    uint64_t const m1 = seg_cover(f0, f1, p.W), m2 = seg_cover(f1, f2, p.W);
+    uint64_t const m1 = COVERED ? f1 : seg_cover(f0, f1, p.W), m2 = COVERED ? f2 : seg_cover(f1, f2, p.W);
     if (lane == 0 && m1 != 0)
         atomicAdd(p.count, (unsigned long long)__popcll((unsigned long long)m1));
     if (g >= p.extent)
@@ -214,7 +217,23 @@ hipError_t qmask_launch(QmaskDev const & p, hipStream_t stream)
     hipLaunchKernelGGL(tile_ops_kernel, dim3((unsigned)p.nTiles), dim3(kTileWords), 0, stream, p);
     hipLaunchKernelGGL(carries_kernel, dim3(1), dim3(64), 0, stream, p);
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)p.nTiles), dim3(kTileWords), 0, stream, p);
-    hipLaunchKernelGGL(dist_kernel, dim3(letterBlocks), dim3(kFlagBlock), 0, stream, p);
+    hipLaunchKernelGGL(dist_kernel<false>, dim3(letterBlocks), dim3(kFlagBlock), 0, stream, p);
+    hipLaunchKernelGGL(touched_kernel, dim3(seqBlocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t qmask_launch_stops(QmaskDev const & p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(stops_kernel, dim3((unsigned)((p.nSeq + 255) / 256)), dim3(256), 0, stream, p);
+    if (p.nGaps)
+        hipLaunchKernelGGL(gaps_kernel, dim3((unsigned)p.nGaps), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t qmask_launch_covered(QmaskDev const & p, hipStream_t stream)
+{
+    unsigned const seqBlocks = (unsigned)((p.nSeq + 255) / 256), letterBlocks = (unsigned)((p.nWords * 64 + kFlagBlock - 1) / kFlagBlock);
+    hipLaunchKernelGGL(dist_kernel<true>, dim3(letterBlocks), dim3(kFlagBlock), 0, stream, p);
     hipLaunchKernelGGL(touched_kernel, dim3(seqBlocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
-// lx_qmask_host.cpp -- low-complexity masking of the queries (include/lambda_ext.h: lx_seg_*, lx_query_mask_*).  lx_qmask.h has the
-// rule; here are its tables, the host path (the rule per sequence on the host threads), the device path (the letters and the
-// sequence table go up, lx_qmask.hip's kernels leave the distance bytes resident on the handle's device) and the mask object that
-// lx_seed_queries_masked reads.
+// lx_qmask_host.cpp -- low-complexity masking of the queries (include/lambda_ext.h: lx_seg_*, lx_dust_*, lx_query_mask_*).  lx_qmask.h
+// has the protein rule, SEG, lx_dust.h the nucleotide rule, DUST; here are SEG's tables, the host path (a rule per sequence on the
+// host threads), the device path (the letters and the sequence table go up, lx_qmask.hip's or lx_dust.hip's kernels leave the distance
+// bytes resident on the handle's device) and the mask object that lx_seed_queries_masked reads.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -10,6 +10,7 @@
 #include <new>
 
 #include "lx_internal.h"
+#include "lx_dust.h"
 #include "lx_qmask.h"
 #include "host/lx_seeding.hpp"
 
@@ -133,7 +134,15 @@ void over_sequences(lx_query_mask const & m, unsigned threads, F && f)
     lambda_amd::parallelChunks(threads, parts, [&](size_t c) { f(cut[c], cut[c + 1]); });
 }
 
-int mask_on_host(lx_query_mask & m, uint8_t const * q_res, qm::SegTables const & t, unsigned threads)
+// one of the two rules: SEG's tables or DUST's parameters
+struct Rule
+{
+    qm::SegTables const *  seg;
+    qm::DustParams const * dust;
+    char const *           who;
+};
+
+int mask_on_host(lx_query_mask & m, uint8_t const * q_res, Rule const & rule, unsigned threads)
 {
     m.dist.assign(m.extent, (uint8_t)qm::kSegFree);
     std::vector<uint64_t> masked(1, 0), touched(1, 0);
@@ -142,6 +151,7 @@ int mask_on_host(lx_query_mask & m, uint8_t const * q_res, qm::SegTables const &
                    [&](uint64_t a, uint64_t b)
                    {
                        std::vector<uint64_t> A, B, F;
+                       qm::DustWork          work;
                        uint64_t              nm = 0, nt = 0;
                        for (uint64_t s = a; s < b; ++s)
                        {
@@ -149,9 +159,10 @@ int mask_on_host(lx_query_mask & m, uint8_t const * q_res, qm::SegTables const &
                            if (L == 0)
                                continue;
                            size_t const words = (size_t)((L + 63) / 64);
-                           if (A.size() < words)
+                           if (rule.seg && A.size() < words)
                                A.resize(words), B.resize(words), F.resize(words);
-                           uint64_t const got = qm::seg_mask_sequence(q_res + m.off[s], L, t, m.dist.data() + m.off[s], A.data(), B.data(), F.data());
+                           uint64_t const got = rule.seg ? qm::seg_mask_sequence(q_res + m.off[s], L, *rule.seg, m.dist.data() + m.off[s], A.data(), B.data(), F.data())
+                                                         : qm::dust_mask_sequence(q_res + m.off[s], L, *rule.dust, m.dist.data() + m.off[s], work);
                            nm += got;
                            nt += got ? 1 : 0;
                        }
@@ -172,25 +183,29 @@ int dev_zeroed(lx_handle * h, lxi::DevBlock<T> & b, size_t count, hipStream_t st
     return LX_OK;
 }
 
-int mask_on_device(lx_handle * h, lx_query_mask & m, uint8_t const * q_res, qm::SegTables const & t, std::vector<uint64_t> const & gaps)
+int mask_on_device(lx_handle * h, lx_query_mask & m, uint8_t const * q_res, Rule const & rule, std::vector<uint64_t> const & gaps)
 {
     int rc = bind(h);
     if (rc)
         return rc;
     hipStream_t const st   = h->stream;
     uint64_t const    nSeq = m.off.size(), nWords = (m.extent + 63) / 64, nTiles = (nWords + qm::kTileWords - 1) / qm::kTileWords;
-    if (nWords * 64 / qm::kFlagBlock + 1 > 0x7fffffffull || gaps.size() / 2 > 0x7fffffffull)
-        return say(h, LX_EINVAL, "lx_query_mask_create_seg: %llu letters are beyond one launch: mask with h == NULL", (unsigned long long)m.extent);
-    lxi::DevBlock<uint8_t>            d_res, d_ops;
-    lxi::DevBlock<uint64_t>           d_off, d_len, d_A, d_B, d_F, d_gaps;
+    // (DUST's sweep has the most workgroups: one per dust_run(window) >= 195 letters)
+    if (nWords * 64 / (rule.dust ? 128 : qm::kFlagBlock) + 1 > 0x7fffffffull || gaps.size() / 2 > 0x7fffffffull)
+        return say(h, LX_EINVAL, "%s: %llu letters are beyond one launch: mask with h == NULL", rule.who, (unsigned long long)m.extent);
+    lxi::DevBlock<uint8_t>            d_res, d_ops, d_reach;
+    lxi::DevBlock<uint64_t>           d_off, d_len, d_A, d_B, d_F, d_gaps, d_brk;
     lxi::DevBlock<unsigned long long> d_stop, d_count;
     lxi::DevBlock<uint32_t>           d_T;
     LX_HIP(h, hipMalloc(reinterpret_cast<void **>(m.d_dist.out()), m.extent + 64));
     m.h = h;
     if ((rc = dev_zeroed(h, d_res, m.extent + 64, st)) || (rc = dev_zeroed(h, d_off, nSeq, st)) || (rc = dev_zeroed(h, d_len, nSeq, st)) ||
-        (rc = dev_zeroed(h, d_A, nWords, st)) || (rc = dev_zeroed(h, d_B, nWords, st)) || (rc = dev_zeroed(h, d_F, nWords + 2, st)) ||
-        (rc = dev_zeroed(h, d_stop, nWords + 2, st)) || (rc = dev_zeroed(h, d_count, 2, st)) || (rc = dev_zeroed(h, d_T, 65, st)) ||
-        (rc = dev_zeroed(h, d_ops, 2 * nTiles, st)) || (rc = dev_zeroed(h, d_gaps, gaps.size(), st)))
+        (rc = dev_zeroed(h, d_F, nWords + 2, st)) || (rc = dev_zeroed(h, d_stop, nWords + 2, st)) || (rc = dev_zeroed(h, d_count, 2, st)) ||
+        (rc = dev_zeroed(h, d_gaps, gaps.size(), st)))
+        return rc;
+    if (rule.seg ? (rc = dev_zeroed(h, d_A, nWords, st)) || (rc = dev_zeroed(h, d_B, nWords, st)) || (rc = dev_zeroed(h, d_T, 65, st)) ||
+                       (rc = dev_zeroed(h, d_ops, 2 * nTiles, st))
+                 : (rc = dev_zeroed(h, d_brk, nWords + 2, st)) || (rc = dev_zeroed(h, d_reach, nWords * 64 + 64, st)))
         return rc;
     if (!gaps.empty())
         LX_HIP(h, hipMemcpyAsync(d_gaps, gaps.data(), gaps.size() * 8, hipMemcpyHostToDevice, st));
@@ -202,14 +217,21 @@ int mask_on_device(lx_handle * h, lx_query_mask & m, uint8_t const * q_res, qm::
         LX_HIP(h, hipMemcpyAsync(d_off, m.off.data(), nSeq * 8, hipMemcpyHostToDevice, st));
         LX_HIP(h, hipMemcpyAsync(d_len, m.len.data(), nSeq * 8, hipMemcpyHostToDevice, st));
     }
-    LX_HIP(h, hipMemcpyAsync(d_T, t.T, sizeof(t.T), hipMemcpyHostToDevice, st));
     qm::QmaskDev p{};
     p.qRes = d_res, p.qOff = d_off, p.qLen = d_len, p.nSeq = nSeq, p.extent = m.extent, p.nWords = nWords, p.nTiles = nTiles;
-    p.W = t.W, p.thr1 = t.thr1, p.thr2 = t.thr2, p.T = d_T, p.stop = d_stop, p.A = d_A, p.B = d_B, p.F = d_F;
-    p.gaps = d_gaps, p.nGaps = gaps.size() / 2;
-    p.opUp = d_ops, p.opDown = d_ops.raw + nTiles, p.dist = m.d_dist, p.count = d_count;
+    p.stop = d_stop, p.F = d_F, p.gaps = d_gaps, p.nGaps = gaps.size() / 2, p.dist = m.d_dist, p.count = d_count;
+    if (rule.seg)
+    {
+        qm::SegTables const & t = *rule.seg;
+        LX_HIP(h, hipMemcpyAsync(d_T, t.T, sizeof(t.T), hipMemcpyHostToDevice, st));
+        p.W = t.W, p.thr1 = t.thr1, p.thr2 = t.thr2, p.T = d_T, p.A = d_A, p.B = d_B;
+        p.opUp = d_ops, p.opDown = d_ops.raw + nTiles;
+    }
     lxi::PhaseTimer timer(h, st, 15);
-    LX_HIP(h, qm::qmask_launch(p, st));
+    if (rule.seg)
+        LX_HIP(h, qm::qmask_launch(p, st));
+    else
+        LX_HIP(h, qm::dust_launch(p, qm::DustDev{rule.dust->window, rule.dust->level, d_brk, d_reach}, st));
     timer.close();
     unsigned long long count[2] = {0, 0};
     LX_HIP(h, hipMemcpyAsync(count, d_count, sizeof(count), hipMemcpyDeviceToHost, st));
@@ -266,7 +288,8 @@ int lx_query_mask_create_seg(lx_handle * h, uint8_t const * q_res, uint64_t cons
             return say(h, LX_EINVAL, "lx_query_mask_create_seg: NULL letters");
         qm::SegTables t;
         make_tables(*p, t);
-        rc = h ? mask_on_device(h, *m, q_res, t, gaps) : mask_on_host(*m, q_res, t, threads_or_share(host_threads));
+        Rule const rule{&t, nullptr, "lx_query_mask_create_seg"};
+        rc = h ? mask_on_device(h, *m, q_res, rule, gaps) : mask_on_host(*m, q_res, rule, threads_or_share(host_threads));
         if (rc)
             return rc;
         *out = m.release();
@@ -274,6 +297,50 @@ int lx_query_mask_create_seg(lx_handle * h, uint8_t const * q_res, uint64_t cons
     catch (std::bad_alloc const &)
     {
         return say(h, LX_ENOMEM, "lx_query_mask_create_seg: out of host memory");
+    }
+    return LX_OK;
+}
+
+void lx_dust_params_default(lx_dust_params * p)
+{
+    if (p)
+        *p = lx_dust_params{64, 20};
+}
+
+int lx_query_mask_create_dust(lx_handle * h, uint8_t const * q_res, uint64_t const * q_off, uint64_t const * q_len, uint64_t n_qseq, lx_dust_params const * p,
+                              uint32_t host_threads, lx_query_mask ** out)
+{
+    if (h)
+    {
+        h->phase_ev.clear(); // (a refused call reports no launch)
+        h->ev_pool_used = 0;
+    }
+    if (!out || !p)
+        return say(h, LX_EINVAL, "lx_query_mask_create_dust: NULL argument");
+    *out = nullptr;
+    if (p->window < qm::kDustMinWindow || p->window > qm::kDustMaxWindow)
+        return say(h, LX_EINVAL, "lx_query_mask_create_dust: window outside 4 .. 64");
+    if (p->level < qm::kDustMinLevel || p->level > qm::kDustMaxLevel)
+        return say(h, LX_EINVAL, "lx_query_mask_create_dust: level outside 1 .. 1000");
+    try
+    {
+        std::unique_ptr<lx_query_mask> m(new lx_query_mask);
+        std::vector<uint64_t>          gaps;
+        int                            rc = take_table(h, "lx_query_mask_create_dust", q_off, q_len, n_qseq, *m, &gaps);
+        if (rc)
+            return rc;
+        if (m->extent && !q_res)
+            return say(h, LX_EINVAL, "lx_query_mask_create_dust: NULL letters");
+        qm::DustParams const dp{p->window, p->level};
+        Rule const           rule{nullptr, &dp, "lx_query_mask_create_dust"};
+        rc = h ? mask_on_device(h, *m, q_res, rule, gaps) : mask_on_host(*m, q_res, rule, threads_or_share(host_threads));
+        if (rc)
+            return rc;
+        *out = m.release();
+    }
+    catch (std::bad_alloc const &)
+    {
+        return say(h, LX_ENOMEM, "lx_query_mask_create_dust: out of host memory");
     }
     return LX_OK;
 }
