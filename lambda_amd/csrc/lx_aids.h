@@ -15,7 +15,7 @@ struct DevAids
     unsigned host_threads;      // LX_HOST_THREADS       parts of a host loop (what LX_OPT_HOST_THREADS sets for a caller)          0         tools/host_curve.py
     bool     mq_no_wide;        // LX_MQ_NO_WIDE         multi-query sweep: compact codes always (windows beyond them: int32 launch) off       tools/profile_round.sh
     uint64_t mq_merge_below;    // LX_MQ_MERGE_BELOW     lx_extend_batch: lists of at most this many windows launch the pool with    200 000   tests/test_gpu_two_calls.py
-                                //                       the rest (0 = default); above: the pool first, in the first of two calls
+                                //                       the rest (0 = default); above: the pool first, in the first of two calls (lx_xb_wf.cpp)
     bool     iterate_on_host;   // LX_ITERATE_ON_HOST    lx_iterate_matches: widen / sort / merge on the host threads whatever the   off       tools/profile_round.sh
                                 //                       list's size
     int      bt_tile_at;        // LX_BT_TILE_AT         backtrace: lanes waiting for a tile that start the tile phase (0 = default) 0         tools/dev/bt_sweep.sh

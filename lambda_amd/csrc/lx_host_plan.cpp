@@ -772,3 +772,81 @@ void HostPlan::longest_first(uint64_t wlo, uint64_t whi)
                         std::memcpy(wf_maxs.data() + wlo + lo, tmp_maxs.data() + lo, (hi - lo) * sizeof(uint32_t));
                     });
 }
+
+// ---- cutting the plan into chunks
+
+uint64_t HostPlan::run_chunk_end(uint64_t k0, uint64_t chunk_target) const
+{
+    uint64_t k1 = std::min<uint64_t>(live, k0 + chunk_target);
+    while (k1 < live && !newrun[k1])
+        ++k1;
+    uint32_t const c0 = query_class(ext[idx[k0]].q_len);
+    if (query_class(ext[idx[k1 - 1]].q_len) != c0)
+    {
+        uint64_t lo = k0, hi = k1 - 1; // first position of another class: the classes ascend
+        while (hi - lo > 1)
+        {
+            uint64_t const mid = lo + (hi - lo) / 2;
+            (query_class(ext[idx[mid]].q_len) == c0 ? lo : hi) = mid;
+        }
+        k1 = hi;
+        while (k1 > k0 + 1 && !newrun[k1])
+            --k1;
+    }
+    return k1;
+}
+
+// The chunk's checkpoint slots must fit the trace budget (fused_impl leaves the sweep otherwise): every slot is sized for the chunk's
+// widest query and longest window -- compact codes, int16 pairs where the chunk may run WIDE -- plus room for the int32 overflow slots
+// of what the sweep may decline; the chunk ends where one more wavefront would break the budget, or where the pool ends.
+uint64_t HostPlan::wf_chunk_end(uint64_t w0, uint64_t per_chunk, uint64_t trace_bytes, bool maybe_wide, bool cut_at_pool) const
+{
+    uint64_t       w1 = w0, run_bytes = 0, run_q = 1, run_s = 1;
+    uint64_t const pool_end = (use_solo || preplanned) ? 0 : pool_wf;
+    while (w1 < nwf && w1 - w0 < per_chunk)
+    {
+        if (cut_at_pool && w0 < pool_end && w1 == pool_end)
+            break;
+        uint64_t const b2 = run_bytes + kWave * slot_dwords(mq_cfg, wf_pan[w1], wf_maxs[w1], maybe_wide, true) * 4;
+        uint64_t const q2 = std::max<uint64_t>(run_q, wf_pan[w1]), s2 = std::max<uint64_t>(run_s, wf_maxs[w1]);
+        if (w1 > w0 && !chunk_fits(b2, trace_bytes, (w1 + 1 - w0) * kWave, q2 * 8 + s2))
+            break;
+        run_bytes = b2, run_q = q2, run_s = s2;
+        ++w1;
+    }
+    return w1;
+}
+
+uint64_t HostPlan::redo_piece_end(uint64_t a, uint64_t end, uint64_t trace_bytes) const
+{
+    uint64_t b = a, bytes = 0;
+    while (b < end)
+    {
+        uint64_t const wb = wf_dwords(b, true) * 4;
+        if (b > a && !chunk_fits(bytes + wb, trace_bytes, 0, 0))
+            break;
+        bytes += wb;
+        ++b;
+    }
+    return b;
+}
+
+bool HostPlan::ranges_admitted(uint64_t const * cut_wf, uint64_t n_ranges, uint64_t per_chunk, uint64_t trace_bytes, bool wide_ok) const
+{
+    bool ok = cut_wf[0] == 0 && cut_wf[n_ranges] == nwf;
+    for (uint64_t r = 0; r < n_ranges && ok; ++r)
+    {
+        uint64_t const a = cut_wf[r], b = cut_wf[r + 1];
+        uint64_t       pm = 1, sm = 1;
+        for (uint64_t w = a; w < b; ++w)
+        {
+            pm = std::max<uint64_t>(pm, wf_pan[w]);
+            sm = std::max<uint64_t>(sm, wf_maxs[w]);
+        }
+        uint64_t const slot_b = slot_dwords(mq_cfg, pm, sm, false, true) * 4;
+        // (a range whose sweep overflows runs again WHOLE with int16-pair slots, about twice the codes': admitted against those too)
+        uint64_t const slot_w = wide_ok ? slot_dwords(mq_cfg, pm, sm, true) * 4 : 0;
+        ok = a < b && b - a <= 4 * per_chunk && chunk_fits((b - a) * kWave * std::max(slot_b, slot_w), trace_bytes, (b - a) * kWave, pm * 8 + sm);
+    }
+    return ok;
+}

@@ -1,7 +1,7 @@
 // lx_host_plan.h -- the host plan of lx_extend_batch* and of the Level-2 driver's resident lists (lx_host_plan.cpp): which
 // extensions are live, their order by query slice, the geometry classes of the one-query-per-wavefront kernels, and the
 // multi-query sweep's plan -- the solo packing, or the pool + the streamed part of the free packing.  Pure CPU integer work:
-// no HIP call is made here; lx_host.cpp runs the plan as a pipeline of chunks.
+// no HIP call is made here; the chunk drivers (lx_xb_run.cpp, lx_xb_wf.cpp) cut the plan into chunks with the members below and run them.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -31,12 +31,24 @@ inline uint32_t mq_steps(uint64_t maxs) { return (uint32_t)((maxs + 8 - 1 + 15) 
 // eighth of an int32 slot per panel -- the room a chunk keeps for the overflow slots of what the compact sweep declines
 uint64_t slot_dwords(int cfg, uint64_t pan, uint64_t maxs, bool wide, bool with_ovf = false);
 
+// The budget of a multi-query chunk: its checkpoint slots' bytes within `trace_bytes` (LX_OPT_TRACE_BYTES), its survivors' ops slots
+// -- `slots` of `ops_slot_bytes`, columns + rows of the chunk's widest query and longest window -- within 8 GiB.  The sites differ,
+// on purpose, in what they put in: the cut of the chunks (wf_chunk_end) and the admission of ranges (ranges_admitted) size every
+// slot with room for overflow slots (with_ovf) against the whole budget; ONE chunk in two calls (lx_xb_wf.cpp: two_calls) puts the
+// pool's table WITHOUT overflow room against HALF the budget -- the overflow area and the second call's slots come out of the rest --
+// and 16 slots + 4 bytes of margin into the ops side, since its slot count is an estimate; a redo (redo_piece_end) has wide slots
+// and no overflow area, and its ops slots were admitted when the chunk was first cut (slots = 0).
+inline bool chunk_fits(uint64_t slot_bytes, uint64_t trace_bytes, uint64_t slots, uint64_t ops_slot_bytes)
+{
+    return slot_bytes <= trace_bytes && slots * ops_slot_bytes <= (8ull << 30);
+}
+
 // Does the multi-query sweep serve this slot's lists (opt_band is NOT looked at: free_plan_applies adds it)?
 bool mq_sweep_applies(lx_handle const * h, int slot);
 
 // The host plan of one call.  It lives on the handle (lx_handle::plan), so that its vectors keep their pages between calls; the
-// stages are called in this order by lx_host.cpp, which uploads the caller's list between choose() and sort() and, for the free
-// packing, makes plan_stream() beside the pool's kernels.
+// stages are called in this order by extend_pipeline (lx_host.cpp), which uploads the caller's list between choose() and sort(); for the
+// free packing the wavefront driver (lx_xb_wf.cpp) makes plan_stream() beside the pool's kernels.
 struct HostPlan
 {
     // ---- what the pipeline reads
@@ -71,6 +83,20 @@ struct HostPlan
         uint64_t windows = 0, runs = 0, pan = 1, maxs = 1, dwords = 0;
     };
     StreamBound stream_bound(bool wide) const;
+
+    // ---- cutting the plan into chunks (the drivers issue what is cut here)
+    // checkpoint dwords of wavefront w's sixteen slots
+    uint64_t wf_dwords(uint64_t w, bool wide) const { return kWave * slot_dwords(mq_cfg, wf_pan[w], wf_maxs[w], wide); }
+    // one-query-per-wavefront chunks: where the chunk of the ordered list that starts at k0 ends -- about chunk_target extensions, never
+    // inside a query's run, never across geometry classes (the list is class-major)
+    uint64_t run_chunk_end(uint64_t k0, uint64_t chunk_target) const;
+    // multi-query chunks: where the chunk that starts at wavefront w0 ends -- at most per_chunk wavefronts within the budget (compact
+    // codes, int16 pairs where the chunk may run wide), and (cut_at_pool) not across the end of the pool
+    uint64_t wf_chunk_end(uint64_t w0, uint64_t per_chunk, uint64_t trace_bytes, bool maybe_wide, bool cut_at_pool) const;
+    // a redo of wavefronts [a, end) with int16-pair slots, twice the codes': where the piece that starts at a ends
+    uint64_t redo_piece_end(uint64_t a, uint64_t end, uint64_t trace_bytes) const;
+    // records by range (ResidentInput::ChunkRecords): is every range [cut_wf[r], cut_wf[r + 1]) of the plan a chunk the budgets admit?
+    bool ranges_admitted(uint64_t const * cut_wf, uint64_t n_ranges, uint64_t per_chunk, uint64_t trace_bytes, bool wide_ok) const;
 
 private:
     lx_extension const * ext      = nullptr; // the call's list

@@ -18,7 +18,7 @@ struct Forecast
     bool     free_plan = false; // the free packing will plan the list (a protein scheme is set), not the solo packing
     uint64_t nwf_solo = 0;  // a wavefront per 16 windows
     uint64_t nwf = 0;       // the plan's wavefronts: the solo packing's count, the free packing's bound
-    // survivor entries: the capacity the pipeline gives the call's survivor list (ExtendPipeline::keep_on_device in lx_host.cpp: the
+    // survivor entries: the capacity the pipeline gives the call's survivor list (device_sink in lx_xb_sinks.cpp: the
     // windows + a margin for the padding of every chunk's list).  Rows are reserved by it as well, where the call takes windows + 16
     // (RecordsJob::prepare): the larger figure serves both
     uint64_t entries = 0;
@@ -62,7 +62,7 @@ int reserve_records(lx_handle * h, Forecast const & f)
     return LX_OK;
 }
 
-// ---- the extension pipeline's two lanes (extend_pipeline: enqueue_mq), for chunks of the default size; the survivors' column slots for
+// ---- the extension pipeline's two lanes (lx_xb_wf.cpp: WfDriver::enqueue), for chunks of the default size; the survivors' column slots for
 // windows of up to three times the ordinary length (what a merged window comes to, src/search_algo.hpp:1153-1157); then the checkpoint
 // slots of one chunk and the survivor selection's lists
 int reserve_pipeline(lx_handle * h, Forecast const & f, HostMarks & hm)

@@ -152,7 +152,7 @@ int ckpt_cfg_for(uint64_t max_q, bool packed16)
 
 // Multi-query sweep (lx_sweep_mq.hip): checkpoint geometry for queries of up to max_q columns -- trace cfg 3 = (8,13),
 // 5 = (8,11), 1 = (8,19), as many panels as the query needs: the one with the least padded work (columns swept x instructions
-// per column: 3.75 per cell of the recurrence + ~12 per step and lane spread over the strip's columns).  lx_host.cpp deals
+// per column: 3.75 per cell of the recurrence + ~12 per step and lane spread over the strip's columns).  lx_host_plan.cpp deals
 // ragged lists to classes with the same function, so a chunk's geometry is the one its class was formed for.
 int mq_cfg_for(uint64_t max_q)
 {
@@ -349,7 +349,7 @@ SweepCand mq_candidate(SchemeFacts const & sc, StepOptions const & o)
     int const G = 8;
     c.steps     = steps_for(o.max_slen, G);
     c.stride32  = (uint64_t)c.panels * lx::ckpt_slot_dwords(c.cfg, c.steps);
-    // (mq_wide: int16-pair slots from the sweep itself -- lists whose windows score beyond the compact codes, lx_host.cpp)
+    // (mq_wide: int16-pair slots from the sweep itself -- lists whose windows score beyond the compact codes, lx_xb_wf.cpp)
     c.mq_wide   = o.mq_wide && c.cfg == 1;
     c.stride    = c.mq_wide ? c.stride32 : (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.cfg, c.steps);
     // lane groups per query: a wavefront's 16 slots hold 16 / 8 / 4 windows of one query, whatever divides the run

@@ -9,7 +9,7 @@ multi-query sweep (LX_OPT_MQ_SWEEP), which would take runs of 8 and ragged runs,
 
 lx_extend_batch pads every run to whole groups of 8 or 16 slots with empty windows, so an idle B half is the empty window
 beside a run's last real one.  It also orders a list by the queries' geometry class (lx_host_plan.h: query_class; at most 104
-columns, at most 152, ...) and never puts two classes into one chunk (lx_host.cpp: run_one), so on that entry point a query
+columns, at most 152, ...) and never puts two classes into one chunk (lx_host_plan.cpp: HostPlan::run_chunk_end), so on that entry point a query
 of at most 104 columns runs on the (8,13) strips whatever else the list holds.  The strip-edge cases therefore run twice:
 through lx_extend_batch, on the strips the library picks, and through lx_extend_batch_dev under the promise
 LX_OPT_MAX_QLEN = 152, which puts all seven lengths on the (8,19) strips -- with strips that lie wholly beyond the query."""

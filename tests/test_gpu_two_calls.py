@@ -1,4 +1,4 @@
-"""A multi-query chunk in two calls (lx_host.cpp: enqueue_mq_first / enqueue_mq_second): the plan's pool is swept while the
+"""A multi-query chunk in two calls (lx_xb_wf.cpp: two_calls -- enqueue_first / enqueue_second): the plan's pool is swept while the
 streamed part of the plan is still being made, the second call sweeps the rest and runs one selection and one backtrace over all
 slots.  Lists beyond 200 000 windows take that path; here a small list is sent there by the library's environment switch
 LX_MQ_MERGE_BELOW (read once per process: every case runs in a process of its own) and must give, byte for byte, what the same
