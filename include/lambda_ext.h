@@ -574,6 +574,46 @@ int lx_postprocess_records_dev(lx_handle * h, lx_blast_match * m, uint64_t n, ui
  * moved together on the host.  lx_last_phase_ms(h, 7, ...) = device time of the step's kernels in the call. */
 int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params,
                                uint64_t max_matches, lx_record_stats * rstats, lx_iterate_result ** out);
+/* Culling a query's records between _writeRecord's unique and its cut (BLAST's -max_hsps and -culling_limit; the reference has no
+ * counterpart).  Per run of equal n_qid, over the rows that survive the unique step, in the output order (bit score descending, ties
+ * by place in the first order); row a is BETTER than row b when it comes earlier in that order.
+ *   max_hsps = K > 0:      a row is dropped when at least K better rows have the same n_sid (hits_max_hsps).
+ *   culling_limit = L > 0: over the rows that max_hsps left, a row is dropped when at least L better rows have a query interval that
+ *                          envelops its own (lo_b <= lo and hi <= hi_b; equal intervals envelop each other) (hits_culled).  A row's
+ *                          query interval is the closed interval [min, max] of the 1-based qstart / qend that the .m8 writer prints:
+ *                          nucleotide positions for a translated query (q_translated != 0), mirrored by the query's length on a
+ *                          minus frame.  q_lens[n_qid], n_q entries, is the untranslated query length.
+ * Then the cut to max_matches, hits_abundant, pairs and the output order as before.  All zero (lx_cull_options_default): nothing
+ * changes anywhere.  q_lens may be NULL only when culling_limit == 0.  LX_EINVAL with culling_limit > 0, before any device work
+ * and with a text (lx_last_output_error() for the host form, lx_last_error(h) for the device forms): a row whose n_qid >= n_q, a
+ * row whose interval does not fit its query's length (q_start >= q_end, or an end behind the query's last letter), a query longer
+ * than 2^32 - 1 (device forms). */
+typedef struct lx_cull_options
+{
+    uint64_t         max_hsps;
+    uint64_t         culling_limit;
+    uint64_t const * q_lens;
+    uint64_t         n_q;
+    int32_t          q_translated;
+} lx_cull_options;
+typedef struct lx_cull_stats
+{
+    uint64_t hits_max_hsps, hits_culled;
+} lx_cull_stats;
+void lx_cull_options_default(lx_cull_options * o); /* all zero: both rules off */
+/* lx_postprocess_records with the two rules; opt == NULL or all zero: exactly lx_postprocess_records.  stats and cull_stats may be
+ * NULL.  Returns the new count (>= 0), or -- a refusal above -- LX_EINVAL (< 0) with m, *stats and *cull_stats as they were. */
+int64_t lx_postprocess_records_ex(lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_cull_options const * opt, lx_record_stats * stats,
+                                  lx_cull_stats * cull_stats);
+/* lx_postprocess_records_dev with the two rules as two more counting kernels (lx_toprec.hip); neither is launched when its option
+ * is 0.  Same rows, order and counters as lx_postprocess_records_ex. */
+int lx_postprocess_records_dev_ex(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_cull_options const * opt,
+                                  lx_record_stats * stats, lx_cull_stats * cull_stats, uint64_t * out_n);
+/* lx_iterate_matches_dev_top with the two rules.  The lengths are the resident q_orig_len of lx_set_queries and q_translated is
+ * params->q_frame_mode == LX_FRAMES_TRANSLATED: opt->q_lens, n_q and q_translated are ignored. */
+int lx_iterate_matches_dev_top_ex(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params,
+                                  uint64_t max_matches, lx_cull_options const * opt, lx_record_stats * rstats, lx_cull_stats * cull_stats,
+                                  lx_iterate_result ** out);
 
 /* The taxonomy the reference keeps in its index (indexFile.taxonParentIDs / taxonHeights / sTaxIds): parents[t] and heights[t]
  * for taxon t < n_taxa (parent 0 = unassigned or the root), and per true subject id the taxa it is assigned to in CSR form:
@@ -1240,7 +1280,8 @@ char const * lx_last_trace_kernel_name(lx_handle const * h);
 /* Device time (HIP events on the launch stream) the most recent call spent in one phase, summed over its launches:
  * phase 0 = pass-1 score kernel, 1 = survivor selection, 2 = pass-2 forward kernel, 3 = pass-2 backtrace kernel,
  * 4 = BGZF encoder (lx_bgzf_compress), 5 = BGZF decoder (lx_gunzip), 6 = accession-to-taxon join (lx_taxmap_*),
- * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top),
+ * 7 = _writeRecord's sort / unique / sort / cut on the device (lx_postprocess_records_dev, lx_iterate_matches_dev_top and their _ex
+ *     forms, whose two culling kernels count here as well),
  * 8 = the word table's kernels (lx_index_build on a handle; in slices: launches = the number of slices), 9 = the seeding kernel (lx_seed_queries on a handle),
  * 10 = the plain-member kernels of lx_gunzip (find, decode, resolve), 11 = the BAM record kernels (lx_render_bam_dev,
  * lx_write_bam_dev: groups, measure, scans, emit), 12 = the text record kernels (lx_render_text_dev, lx_write_text_dev: groups,

@@ -29,7 +29,8 @@ EXPORTED_SYMBOLS = [
     "lx_iterate_matches", "lx_set_queries", "lx_set_subject_seqs", "lx_iterate_matches_dev", "lx_widen_and_preprocess_dev", "lx_reserve", "lx_sort_words_dev", "lx_trim_result_cache",
     "lx_iterate_result_count", "lx_iterate_result_matches", "lx_iterate_result_ops", "lx_iterate_result_stats",
     "lx_iterate_result_free", "lx_karlin_params", "lx_length_adjustment", "lx_evalue", "lx_bitscore",
-    "lx_widen_and_preprocess", "lx_postprocess_records", "lx_postprocess_records_dev", "lx_iterate_matches_dev_top", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
+    "lx_widen_and_preprocess", "lx_postprocess_records", "lx_postprocess_records_dev", "lx_iterate_matches_dev_top",
+    "lx_cull_options_default", "lx_postprocess_records_ex", "lx_postprocess_records_dev_ex", "lx_iterate_matches_dev_top_ex", "lx_compute_lca", "lx_write_records", "lx_convert_ranks",
     "lx_set_subjects", "lx_extend_batch", "lx_extend_batch_rle", "lx_extend_batch_list", "lx_write_records_ex", "lx_check_output_options", "lx_write_footer", "lx_output_options_default", "lx_last_output_error", "lx_expand_ops", "lx_last_extend_stats", "lx_set_frames", "lx_untrue_qry_id", "lx_untrue_subj_id", "lx_translate_six_frames",
     "lx_plan_step", "lx_render_records", "lx_bytes_data", "lx_bytes_size", "lx_bytes_free", "lx_bgzf_bound", "lx_bgzf_compress",
     "lx_write_records_bgzf", "lx_render_bam_dev", "lx_write_bam_dev", "lx_format_number", "lx_render_text_dev", "lx_write_text_dev", "lx_gunzip", "lx_last_gunzip_stats", "lx_gunzip_decline_text", "lx_find_accessions", "lx_taxmap_create", "lx_taxmap_feed", "lx_taxmap_finish",
@@ -93,6 +94,15 @@ BLAST_MATCH_DTYPE = np.dtype([
 
 class RecordStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("qrys_with_hit", "hits_duplicate2", "hits_abundant", "hits_final", "pairs")]
+
+
+class CullOptions(C.Structure):
+    """lx_cull_options: max_hsps and culling_limit between _writeRecord's unique and its cut (0 = off)."""
+    _fields_ = [("max_hsps", C.c_uint64), ("culling_limit", C.c_uint64), ("q_lens", C.c_void_p), ("n_q", C.c_uint64), ("q_translated", C.c_int32)]
+
+
+class CullStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("hits_max_hsps", "hits_culled")]
 
 
 class GunzipStats(C.Structure):
@@ -302,6 +312,14 @@ def load():
     lib.lx_postprocess_records.restype = u64
     lib.lx_postprocess_records_dev.argtypes = [vp, vp, u64, u64, C.POINTER(RecordStats), C.POINTER(u64)]
     lib.lx_iterate_matches_dev_top.argtypes = [vp, i32, vp, u64, C.POINTER(SearchParams), u64, C.POINTER(RecordStats), C.POINTER(vp)]
+    if hasattr(lib, "lx_postprocess_records_ex"):  # (not in an older library loaded through LX_LIB_PATH: the yardstick of tools/records_bench.py)
+        lib.lx_cull_options_default.argtypes = [C.POINTER(CullOptions)]
+        lib.lx_cull_options_default.restype = None
+        lib.lx_postprocess_records_ex.argtypes = [vp, u64, u64, C.POINTER(CullOptions), C.POINTER(RecordStats), C.POINTER(CullStats)]
+        lib.lx_postprocess_records_ex.restype = C.c_int64
+        lib.lx_postprocess_records_dev_ex.argtypes = [vp, vp, u64, u64, C.POINTER(CullOptions), C.POINTER(RecordStats), C.POINTER(CullStats), C.POINTER(u64)]
+        lib.lx_iterate_matches_dev_top_ex.argtypes = [vp, i32, vp, u64, C.POINTER(SearchParams), u64, C.POINTER(CullOptions), C.POINTER(RecordStats),
+                                                      C.POINTER(CullStats), C.POINTER(vp)]
     lib.lx_write_records.argtypes = [C.c_char_p, i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp]
     lib.lx_write_records_ex.argtypes = [C.c_char_p, i32, i32, C.c_char_p, vp, u64, vp, C.POINTER(SeqNames), vp, vp, C.POINTER(OutputOptions)]
     lib.lx_write_footer.argtypes = [C.c_char_p, i32, u64]
@@ -584,6 +602,37 @@ def postprocess_records_dev(handle, bms: np.ndarray, max_matches: int = 25):
     n = C.c_uint64(0)
     handle._check(handle.lib.lx_postprocess_records_dev(handle.h, _ptr(m) if len(m) else None, len(m), max_matches, C.byref(st), C.byref(n)))
     return m[: int(n.value)], st
+
+
+def cull_options(max_hsps: int = 0, culling_limit: int = 0, q_lens=None, q_translated: bool = False):
+    """An lx_cull_options and the uint64 array it points into (keep it alive as long as the options): (CullOptions, array)."""
+    lens = None if q_lens is None else np.ascontiguousarray(q_lens, dtype=np.uint64)
+    opt = CullOptions()
+    load().lx_cull_options_default(C.byref(opt))
+    opt.max_hsps, opt.culling_limit, opt.q_translated = max_hsps, culling_limit, 1 if q_translated else 0
+    opt.q_lens, opt.n_q = (lens.ctypes.data if lens is not None and len(lens) else None), (0 if lens is None else len(lens))
+    return opt, lens
+
+
+def postprocess_records_ex(bms: np.ndarray, max_matches: int = 25, max_hsps: int = 0, culling_limit: int = 0, q_lens=None, q_translated: bool = False):
+    """lx_postprocess_records_ex: postprocess_records with --max-hsps / --culling-limit between the unique and the cut;
+    (rows, stats, cull stats).  Raises LambdaExtError with lx_last_output_error()'s text on a refusal."""
+    m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE).copy()
+    opt, _keep = cull_options(max_hsps, culling_limit, q_lens, q_translated)
+    st, cs = RecordStats(), CullStats()
+    n = load().lx_postprocess_records_ex(_ptr(m) if len(m) else None, len(m), max_matches, C.byref(opt), C.byref(st), C.byref(cs))
+    if n < 0:
+        raise LambdaExtError(int(n), last_output_error())
+    return m[: int(n)], st, cs
+
+
+def postprocess_records_dev_ex(handle, bms: np.ndarray, max_matches: int = 25, max_hsps: int = 0, culling_limit: int = 0, q_lens=None, q_translated: bool = False):
+    """lx_postprocess_records_dev_ex: postprocess_records_ex with the step as kernels on `handle`'s device; (rows, stats, cull stats)."""
+    m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE).copy()
+    opt, _keep = cull_options(max_hsps, culling_limit, q_lens, q_translated)
+    st, cs, n = RecordStats(), CullStats(), C.c_uint64(0)
+    handle._check(handle.lib.lx_postprocess_records_dev_ex(handle.h, _ptr(m) if len(m) else None, len(m), max_matches, C.byref(opt), C.byref(st), C.byref(cs), C.byref(n)))
+    return m[: int(n.value)], st, cs
 
 
 class OutputOptions(C.Structure):
@@ -1456,6 +1505,16 @@ class Handle:
         rst = RecordStats()
         self._check(self.lib.lx_iterate_matches_dev_top(self.h, slot, d_matches.data_ptr() if n else None, n, C.byref(params), max_matches, C.byref(rst), C.byref(res)))
         return (*self._take_iterate_result(res), rst)
+
+    def iterate_matches_dev_top_ex(self, d_matches, n: int, params: "SearchParams", max_matches: int = 25, max_hsps: int = 0, culling_limit: int = 0, slot: int = 0):
+        """lx_iterate_matches_dev_top_ex: iterate_matches_dev_top with --max-hsps / --culling-limit (the lengths are the resident
+        q_orig_len of set_queries); (records, ops, stats, record stats, cull stats)."""
+        res = C.c_void_p()
+        rst, cst = RecordStats(), CullStats()
+        opt, _ = cull_options(max_hsps, culling_limit)
+        self._check(self.lib.lx_iterate_matches_dev_top_ex(self.h, slot, d_matches.data_ptr() if n else None, n, C.byref(params), max_matches, C.byref(opt),
+                                                           C.byref(rst), C.byref(cst), C.byref(res)))
+        return (*self._take_iterate_result(res), rst, cst)
 
     def plan_free_packing_dev(self, d_ext, n: int, n_qseq: int, strip_cols: int = 19, cuts=None):
         """lx_plan_free_packing_dev: (plan [nwf, 16], wf_pan [nwf], wf_maxs [nwf], report [16]) for n lx_extension records in a device tensor."""

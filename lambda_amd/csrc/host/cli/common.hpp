@@ -101,6 +101,12 @@ lx_record_stats & operator+=(lx_record_stats & a, lx_record_stats const & b)
     return a;
 }
 
+lx_cull_stats & operator+=(lx_cull_stats & a, lx_cull_stats const & b)
+{
+    a.hits_max_hsps += b.hits_max_hsps, a.hits_culled += b.hits_culled;
+    return a;
+}
+
 lx_iterate_stats & operator+=(lx_iterate_stats & a, lx_iterate_stats const & b)
 {
     a.hits_duplicate += b.hits_duplicate, a.failed_bitscore += b.failed_bitscore, a.failed_evalue += b.failed_evalue;

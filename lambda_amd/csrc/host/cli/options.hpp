@@ -38,6 +38,8 @@ struct Options
                                       // the device declines are finished on the host threads inside the call --, or on the -t threads)
     std::string render      = "auto"; // --render gpu | host | auto: where the records of the output are made (the header comment)
     std::string records     = "auto"; // --records gpu | host | auto: where _writeRecord's sort / unique / sort / cut runs (the header comment)
+    uint64_t    maxHsps     = 0;      // --max-hsps K: at most K records per (query, subject) pair, the best ones (0: off; the header comment)
+    uint64_t    cullingLimit = 0;     // --culling-limit L: drop a record whose query interval L better records of its query envelop (0: off)
     std::string lca         = "auto"; // --lca gpu | host | auto: where the LCA per query is folded (the header comment)
     double      lcaTopPercent = 100;  // --lca-top-percent P: only the records within P percent of a query's best bit score enter its LCA (100: all)
     bool        lcaTopGiven = false;
@@ -87,7 +89,9 @@ Options parse(int argc, char ** argv)
     Options o;
     if (argc < 2)
         throw std::runtime_error("usage: lambda3 searchp|searchn|searchbs -q QUERY.{fa,fq,fasta,fastq,fna,faa}[.gz] (-i DB.lba | -d DB.fasta[.gz]) -o OUT.{m8,m9,sam,bam,m8.gz,m9.gz,sam.gz} [-e EVALUE] [-n N] "
-                                 "[--devices 0,1,...] [-t THREADS]\n                 [--lca-top-percent P] [--lca gpu|host|auto]   the LCA per query (lcataxid, lt, ls) over the records within P percent of the query's best\n"
+                                 "[--devices 0,1,...] [-t THREADS]\n                 [--max-hsps K] [--culling-limit L]   between the duplicate removal and the cut to -n, per query, best records first: drop a record\n"
+                                 "                 when K better ones hit the same subject; then drop a record when L better ones envelop its query interval (qstart .. qend as the\n"
+                                 "                 .m8 prints them; equal intervals envelop each other).  0 = off (default); the seeding's budget stays -n\n                 [--lca-top-percent P] [--lca gpu|host|auto]   the LCA per query (lcataxid, lt, ls) over the records within P percent of the query's best\n"
                                  "                 bit score (0 .. 100, default 100: all records, the reference's rule), folded on the GPU or on the host (auto: the GPU)\n                 [--taxon-list T1,T2,... | --taxon-exclude T1,T2,...] [--taxon-filter gpu|host|auto]   search only the subjects under the listed taxa of the\n"
                                  "                 index's tree (mkindex* -m -x), or all but them (a subject without taxa is dropped by a list and kept by an exclusion); the promising\n"
                                  "                 seeds on other subjects are dropped before the extension, on the GPU or on the host (auto: where the seeding left them); e-values\n"
@@ -291,6 +295,14 @@ Options parse(int argc, char ** argv)
         }
         else if (a == "--records")
             o.records = oneOf(val(), {"gpu", "host", "auto"}, "--records takes gpu, host or auto");
+        else if (!mk && (a == "--max-hsps" || a == "--culling-limit"))
+        {
+            std::string const v  = val();
+            bool const        ok = !v.empty() && v.size() <= 18 && std::all_of(v.begin(), v.end(), [](char c) { return c >= '0' && c <= '9'; });
+            if (!ok)
+                throw std::runtime_error(a + " takes a number (0 = off, the default), got '" + v + "'");
+            (a == "--max-hsps" ? o.maxHsps : o.cullingLimit) = std::stoull(v);
+        }
         else if (a == "--lca")
             o.lca = oneOf(val(), {"gpu", "host", "auto"}, "--lca takes gpu, host or auto");
         else if (a == "--lca-top-percent")

@@ -79,6 +79,19 @@
 // pass searches the queries WITHOUT records).  auto: see DESIGN.md ("_writeRecord on the device") for the measurement behind it.
 // The LCA (--lca) and the writers (--render) are fed with the kept records; the output is byte-identical either way.
 //
+// --max-hsps K, --culling-limit L (numbers >= 0, default 0 = off; BLAST's -max_hsps and -culling_limit, the reference has neither):
+// which of a query's records take the -n places.  Between _writeRecord's unique and its cut, per query, over the records in output
+// order (bit score descending, ties by place in the first order; a record is BETTER than another when it comes earlier): with K > 0 a
+// record is dropped when at least K better records have the same subject; then, over what is left, with L > 0 a record is dropped
+// when at least L better records have a query interval that envelops its own -- the interval is qstart .. qend as the .m8 prints
+// them (nucleotide positions for BLASTX, mirrored on the minus strand), equal intervals envelop each other, a partial overlap never
+// culls.  Then the cut to -n as always.  The rules run wherever the step runs (--records gpu: two more counting kernels of
+// lx_toprec.hip behind lx_iterate_matches_dev_top_ex; the host step of the eager path, of a --lazy-query block, and of a pass whose
+// list stands in host memory: lx_postprocess_records_ex); every record of a query comes out of one call or one block, so the rules
+// see all of them.  The output is byte-identical wherever they ran.  -n 0 keeps its meaning.  The seeding's budget stays -n: a
+// query whose seeding stopped at -n matches per read has no more records to promote.  With either option a line of its own on
+// stderr names K, L, what each rule dropped and where the step ran.
+//
 // --lazy-query 1 [--query-block N]: the query file block by block, in bounded memory -- the reference's batch loop with its reader
 // thread behind a bounded queue (src/search.cpp:389-459, src/search_algo.hpp:374-413).  One reader takes the file as a stream
 // (lx_gunzip_stream: BGZF groups and plain members of 8 MiB and more on the first device, other members on its thread), parses it piece by piece
@@ -608,6 +621,28 @@ struct SearchContext
     TaxonSetup const &  taxon;
 };
 
+// --max-hsps / --culling-limit as the library takes them, over the queries that the records' n_qid name (their untranslated lengths)
+lx_cull_options cullOptions(Options const & opt, Run const & run, SeqSet const & qs)
+{
+    lx_cull_options co;
+    lx_cull_options_default(&co);
+    co.max_hsps = opt.maxHsps, co.culling_limit = opt.cullingLimit;
+    co.q_lens = qs.orig_len.data(), co.n_q = qs.orig_len.size(), co.q_translated = run.blastx ? 1 : 0;
+    return co;
+}
+
+// _writeRecord's step on the host, with the two rules where they were asked for: the new count
+uint64_t hostRecordsStep(Options const & opt, Run const & run, SeqSet const & qs, lx_blast_match * m, uint64_t n, lx_record_stats * rst, lx_cull_stats * cst)
+{
+    if (!opt.maxHsps && !opt.cullingLimit)
+        return lx_postprocess_records(m, n, opt.maxMatches, rst);
+    lx_cull_options const co   = cullOptions(opt, run, qs);
+    int64_t const         kept = lx_postprocess_records_ex(m, n, opt.maxMatches, &co, rst, cst);
+    if (kept < 0)
+        throw std::runtime_error(std::string("lambda_ext: ") + lx_last_output_error());
+    return (uint64_t)kept;
+}
+
 // what a worker keeps for its range of reads (--lazy-query: for its blocks, whose records stay with them)
 struct Part
 {
@@ -619,6 +654,7 @@ struct Part
     double                      msSeed = 0, msExtend = 0, msRecords = 0;
     double                      msLca = 0; // (--lazy-query: the LCA of this worker's blocks)
     lx_record_stats             rst{}; // --records gpu: _writeRecord's statistics of this worker's passes
+    lx_cull_stats               cst{}; // ... and what --max-hsps / --culling-limit dropped there
     bool                        gpuSeeding = false; // the seeding stage of this worker ran on its device
     size_t                      nDeclined = 0, nPassesOnHost = 0; // reads the GPU seeding stage left to the host; passes whose match buffer was full
     uint64_t                    nTaxonDropped = 0; // --taxon-list / --taxon-exclude: promising seeds on subjects the mask drops
@@ -919,10 +955,17 @@ private:
         lx_iterate_result * res  = nullptr;
         auto const          tExt = Clock::now();
         lx_record_stats     passRst{};
+        lx_cull_stats       passCst{};
         bool                cutDone = false;
         if (dList && recordsOnGpu) // ... with _writeRecord's cut before the records come down
         {
-            eng_.check(lx_iterate_matches_dev_top(eng_.raw(), 0, dList, nMatches, &c_.setup.sp, opt.maxMatches, &passRst, &res));
+            if (opt.maxHsps || opt.cullingLimit) // (the lengths: the resident q_orig_len of beginJob's lx_set_queries)
+            {
+                lx_cull_options const co = cullOptions(opt, c_.run, qs);
+                eng_.check(lx_iterate_matches_dev_top_ex(eng_.raw(), 0, dList, nMatches, &c_.setup.sp, opt.maxMatches, &co, &passRst, &passCst, &res));
+            }
+            else
+                eng_.check(lx_iterate_matches_dev_top(eng_.raw(), 0, dList, nMatches, &c_.setup.sp, opt.maxMatches, &passRst, &res));
             float msTop = 0;
             if (lx_last_phase_ms(eng_.raw(), 7, &msTop, nullptr) == LX_OK)
                 pt_.msRecords += msTop;
@@ -942,11 +985,12 @@ private:
         {
             auto const tRec = Clock::now();
             cutRows.assign(bm, bm + n);
-            n  = lx_postprocess_records(cutRows.data(), n, opt.maxMatches, &passRst);
+            n  = hostRecordsStep(opt, c_.run, qs, cutRows.data(), n, &passRst, &passCst);
             bm = cutRows.data();
             pt_.msRecords += msSince(tRec);
         }
         pt_.rst += passRst;
+        pt_.cst += passCst;
         uint64_t const ob     = outOps.size();
         uint64_t       opsEnd = 0; // (the records are ordered by query, their ops as the passes produced them: bisulfite runs two)
         for (uint64_t k = 0; k < n && wantOps; ++k)
@@ -1136,6 +1180,7 @@ struct Block
     std::vector<uint8_t>        ops;
     uint64_t                    found = 0, kept = 0; // records before and after _writeRecord's cut
     lx_record_stats             rst{};               // (--records host: this block's step)
+    lx_cull_stats               cst{};
     std::vector<uint64_t>       lcaQid;
     std::vector<uint32_t>       lcaTax;
     uint64_t                    nLca = 0;
@@ -1316,7 +1361,7 @@ void searchBlocks(size_t w, SearchContext const & c, OutputSetup const & out, Bl
             if (!c.run.recordsOnGpu) // _writeRecord's cut: every record of a read is in its block
             {
                 auto const tRec = Clock::now();
-                b->kept         = lx_postprocess_records(b->bms.data(), b->bms.size(), c.opt.maxMatches, &b->rst);
+                b->kept         = hostRecordsStep(c.opt, c.run, b->qs, b->bms.data(), b->bms.size(), &b->rst, &b->cst);
                 part.msRecords += msSince(tRec);
             }
             if (out.lca)
@@ -1340,6 +1385,7 @@ struct LazyTotals
     BlockPipeline::Counts counts;
     uint64_t              hsps = 0, written = 0;
     lx_record_stats       rst{};
+    lx_cull_stats         cst{};
     RenderTimes           times;
 };
 
@@ -1402,6 +1448,7 @@ LazyTotals runLazy(SearchContext const & c, QueryStream & stream, OutputSetup co
         totals.hsps += b->found;
         totals.written += b->kept;
         totals.rst += b->rst;
+        totals.cst += b->cst;
         b.reset();
         pipe.release();
     }
@@ -1454,24 +1501,30 @@ struct Totals : Part
         msMask    = std::max(msMask, pt.msMask);
         maskOnGpu = maskOnGpu || pt.maskOnGpu;
         rst += pt.rst;
+        cst += pt.cst;
     }
 };
 
 // the parts summed; the eager path's records through _writeRecord's step where no pass has done it (--records gpu: every pass's
 // records are cut already), the lazy path's counts from its blocks
-Totals sumParts(Options const & opt, Run const & run, std::vector<Part> const & parts, LazyTotals const & lazy)
+Totals sumParts(Options const & opt, Run const & run, SeqSet const & qs, std::vector<Part> const & parts, LazyTotals const & lazy)
 {
     Totals t;
     for (Part const & pt : parts)
         t.add(pt);
-    t.nHsp = run.recordsOnGpu ? t.rst.hits_final + t.rst.hits_duplicate2 + t.rst.hits_abundant : run.lazy ? lazy.hsps : t.bms.size();
+    t.nHsp = run.recordsOnGpu ? t.rst.hits_final + t.rst.hits_duplicate2 + t.rst.hits_abundant + t.cst.hits_max_hsps + t.cst.hits_culled
+             : run.lazy       ? lazy.hsps
+                              : t.bms.size();
     t.nOut = run.lazy ? lazy.written : t.bms.size();
     if (run.lazy) // (the blocks' host steps; --records gpu counted in the passes above)
+    {
         t.rst += lazy.rst;
+        t.cst += lazy.cst;
+    }
     else if (!run.recordsOnGpu)
     {
         auto const tRec = Clock::now();
-        t.nOut          = lx_postprocess_records(t.bms.data(), t.bms.size(), opt.maxMatches, &t.rst);
+        t.nOut          = hostRecordsStep(opt, run, qs, t.bms.data(), t.bms.size(), &t.rst, &t.cst);
         t.msRecords     = msSince(tRec);
     }
     return t;
@@ -1607,6 +1660,10 @@ void report(Options const & opt, Run const & run, Inputs const & in, Table const
                  in.msRead, gunzipNote.c_str(), tableNote.c_str(), table.msIndex, msSearch, t.gpuSeeding ? "GPU" : "host", t.msSeed, t.nDeclined,
                  t.nPassesOnHost, t.msExtend, t.msRecords, run.recordsOnGpu ? "kernels on the GPU, slowest worker" : "host", msOutput - times.msCompress,
                  outputNote.c_str(), msSince(run.tStart));
+    if (opt.maxHsps || opt.cullingLimit)
+        std::fprintf(stderr, "lambda3 culling: --max-hsps %llu dropped %llu record(s), --culling-limit %llu dropped %llu record(s), %s\n",
+                     (unsigned long long)opt.maxHsps, (unsigned long long)t.cst.hits_max_hsps, (unsigned long long)opt.cullingLimit,
+                     (unsigned long long)t.cst.hits_culled, run.recordsOnGpu ? "on the GPU (the host for a pass whose list stood in host memory)" : "on the host");
     if (run.wantLca && (opt.lca == "gpu" || opt.lcaTopGiven))
         std::fprintf(stderr, "lambda3 LCA: records within %g percent of a query's best bit score, folded on the %s: %.1f ms%s\n", opt.lcaTopPercent,
                      opt.lca != "host" ? "GPU" : "host", run.lazy ? t.msLca : times.msLca, run.lazy ? " on the slowest worker" : "");
@@ -1656,7 +1713,7 @@ int main(int argc, char ** argv)
         double const msSearch = msSince(tSearch);
 
         auto const   tOut   = Clock::now();
-        Totals const totals = sumParts(opt, run, parts, lazy);
+        Totals const totals = sumParts(opt, run, in.qs, parts, lazy);
         RenderTimes const times = run.lazy ? lazy.times : writeEager(opt, run, setup.devices[0], output, in, totals);
         report(opt, run, in, table, setup, taxon, totals, lazy, times, msSearch, msSince(tOut));
         return 0;

@@ -27,6 +27,7 @@
 #include "../../../include/lambda_ext.h"
 #include "scoring_tables.hpp"
 
+#include "../lx_cull.h"      // the rule of lx_cull_options, shared with the kernels
 #include "../lx_host_pool.h" // the library's host threads
 
 namespace
@@ -417,11 +418,49 @@ void set_output_error(std::string const & msg)
 }
 } // namespace lxi
 
-extern "C" {
+namespace lxi
+{
+int cull_check(lx_blast_match const * m, uint64_t n, lx_cull_options const * opt, uint64_t max_len, std::string & why)
+{
+    if (!opt || opt->culling_limit == 0)
+        return LX_OK;
+    if (!opt->q_lens && n)
+    {
+        why = "lx_cull_options: culling_limit > 0 needs q_lens";
+        return LX_EINVAL;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+    {
+        if (m[i].n_qid >= opt->n_q)
+        {
+            why = "lx_cull_options: row " + std::to_string(i) + " names query " + std::to_string(m[i].n_qid) + ", q_lens has " + std::to_string(opt->n_q) + " entries";
+            return LX_EINVAL;
+        }
+        uint64_t const len = opt->q_lens[m[i].n_qid];
+        if (len > max_len)
+        {
+            why = "lx_cull_options: query " + std::to_string(m[i].n_qid) + " is " + std::to_string(len) + " letters long, the device step takes " + std::to_string(max_len) + " at most";
+            return LX_EINVAL;
+        }
+        uint64_t lo, hi;
+        if (!lx::cull::interval(m[i].q_start, m[i].q_end, m[i].q_frame, len, opt->q_translated != 0, lo, hi))
+        {
+            why = "lx_cull_options: the query interval of row " + std::to_string(i) + " does not fit its query's length of " + std::to_string(len);
+            return LX_EINVAL;
+        }
+    }
+    return LX_OK;
+}
+} // namespace lxi
 
-uint64_t lx_postprocess_records(lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats)
+namespace
+{
+
+// _writeRecord's step for a whole list; cull: NULL, or the two rules between the unique and the cut (lx_cull.h)
+uint64_t postprocessRecords(lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_cull_options const * cull, lx_record_stats * stats, lx_cull_stats * cull_stats)
 {
     lx_record_stats st{};
+    lx_cull_stats   cs{};
     uint64_t        w = 0;
     for (uint64_t lo = 0; lo < n;)
     {
@@ -451,6 +490,39 @@ uint64_t lx_postprocess_records(lx_blast_match * m, uint64_t n, uint64_t max_mat
         // output order: best bit score (= smallest e-value) first; stable like the reference's list sort (:865)
         std::stable_sort(rec.begin(), rec.end(),
                          [](lx_blast_match const & a, lx_blast_match const & b) { return a.bit_score > b.bit_score; });
+        // rec now stands in order 2: row j is better than row i exactly when j < i (lx_cull.h).  Every row's fate is a count over
+        // the better rows, as in the kernels of lx_toprec.hip
+        if (cull && cull->max_hsps)
+        {
+            std::vector<lx_blast_match> left;
+            for (size_t i = 0; i < rec.size(); ++i)
+            {
+                uint64_t same = 0;
+                for (size_t j = 0; j < i && same < cull->max_hsps; ++j)
+                    same += rec[j].n_sid == rec[i].n_sid;
+                if (same < cull->max_hsps)
+                    left.push_back(rec[i]);
+            }
+            cs.hits_max_hsps += rec.size() - left.size();
+            rec.swap(left);
+        }
+        if (cull && cull->culling_limit)
+        {
+            std::vector<uint64_t> lo(rec.size()), hi(rec.size());
+            for (size_t i = 0; i < rec.size(); ++i)
+                (void)lx::cull::interval(rec[i].q_start, rec[i].q_end, rec[i].q_frame, cull->q_lens[rec[i].n_qid], cull->q_translated != 0, lo[i], hi[i]);
+            std::vector<lx_blast_match> left;
+            for (size_t i = 0; i < rec.size(); ++i)
+            {
+                uint64_t around = 0;
+                for (size_t j = 0; j < i && around < cull->culling_limit; ++j)
+                    around += lx::cull::envelops(lo[j], hi[j], lo[i], hi[i]);
+                if (around < cull->culling_limit)
+                    left.push_back(rec[i]);
+            }
+            cs.hits_culled += rec.size() - left.size();
+            rec.swap(left);
+        }
         // at most max_matches records per query, the rest is counted (:867-872)
         if (rec.size() > max_matches)
         {
@@ -468,7 +540,38 @@ uint64_t lx_postprocess_records(lx_blast_match * m, uint64_t n, uint64_t max_mat
     }
     if (stats)
         *stats = st;
+    if (cull_stats)
+        *cull_stats = cs;
     return w;
+}
+
+} // namespace
+
+extern "C" {
+
+uint64_t lx_postprocess_records(lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats)
+{
+    return postprocessRecords(m, n, max_matches, nullptr, stats, nullptr);
+}
+
+void lx_cull_options_default(lx_cull_options * o)
+{
+    if (o)
+        *o = lx_cull_options{};
+}
+
+int64_t lx_postprocess_records_ex(lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_cull_options const * opt, lx_record_stats * stats,
+                                  lx_cull_stats * cull_stats)
+{
+    g_output_error.clear();
+    if (!m && n)
+    {
+        g_output_error = "lx_postprocess_records_ex: NULL rows";
+        return LX_EINVAL;
+    }
+    if (lxi::cull_check(m, n, opt, ~0ull, g_output_error) != LX_OK)
+        return LX_EINVAL;
+    return (int64_t)postprocessRecords(m, n, max_matches, opt, stats, cull_stats);
 }
 
 // computeLCA (src/search_misc.hpp:86-112): level the two nodes, then climb together; 0 = the paths never met

@@ -195,6 +195,7 @@ struct lx_handle
         // _writeRecord's sort / unique / sort / cut on the device (lx_toprec.hip): the rows that stay and their code words, the step's
         // scratch, its counters (per range of a Level-2 call) and the rows of lx_postprocess_records_dev on their way up and down
         DevBuf                d_toprows, d_topcodes, d_topwork, d_topcnt, d_topin;
+        DevBuf                d_cullqlen; // lx_postprocess_records_dev_ex: lx_cull_options::q_lens as 32-bit words
         Pinned                p_topcnt;
     } l2;
     // lx_bgzf_compress (lx_bgzf_host.cpp): one chunk's device buffers, its input in two pinned lanes, its members on the way out
@@ -367,6 +368,9 @@ int    bind(lx_handle * h);
 // (host/lx_output.cpp) an lx_bytes that takes over s; the message lx_last_output_error() returns
 lx_bytes * bytes_adopt(std::string && s);
 void       set_output_error(std::string const & msg);
+// (host/lx_output.cpp) the refusals of lx_cull_options for n rows in host memory (include/lambda_ext.h); `why` gets the text.
+// max_len: the longest query the caller can take (the device forms keep the intervals in 32-bit words)
+int        cull_check(lx_blast_match const * m, uint64_t n, lx_cull_options const * opt, uint64_t max_len, std::string & why);
 // (host/lx_output.cpp) for the device BAM writer: renderRecords' refusals for LX_OUT_BAM (program, NULL arguments, tag keys, the rows'
 // ids; lx_last_output_error() has its text) and the resolved tags as bits in kSamTags' order; the bytes in front of the records
 // (magic, SAM header text, reference list)

@@ -884,13 +884,25 @@ int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint
     return iterate_matches_dev(h, slot, d_matches, n_matches, params, nullptr, out);
 }
 
-int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, uint64_t max_matches,
-                               lx_record_stats * rstats, lx_iterate_result ** out)
+static int iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, uint64_t max_matches,
+                                   lx_cull_options const * opt, lx_record_stats * rstats, lx_cull_stats * cull_stats, lx_iterate_result ** out)
 {
     if (!h || !out || !params)
         return LX_EINVAL;
     TopRequest top;
     top.max_matches = max_matches;
+    if (opt && (opt->max_hsps || opt->culling_limit))
+    {
+        // the lengths are the resident q_orig_len of lx_set_queries (32-bit words per frame sequence, the query's own in front of
+        // its frames); iterate_matches_dev refuses a handle without them before any kernel reads them
+        auto & l2 = h->l2;
+        top.cull.max_hsps      = opt->max_hsps;
+        top.cull.culling_limit = opt->culling_limit;
+        top.cull.d_q_lens      = static_cast<uint32_t const *>(l2.d_qevlen.ptr);
+        top.cull.q_lens_n      = l2.q_len.size();
+        top.cull.stride        = (uint32_t)std::max(1, l2.q_frames);
+        top.cull.translated    = params->q_frame_mode == LX_FRAMES_TRANSLATED;
+    }
     int rc = iterate_matches_dev(h, slot, d_matches, n_matches, params, &top, out);
     if (rc != LX_OK)
         return rc;
@@ -903,7 +915,7 @@ int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, 
         if (res->matches.size() >= 0x7ffffff0ull)
             rc = fail(h, LX_EINVAL, "lx_iterate_matches_dev_top: at most 2^31 - 16 records per call");
         else
-            rc = toprec_host_rows(h, res->matches.data(), res->matches.size(), max_matches, &top.stats, &kept);
+            rc = toprec_host_rows(h, res->matches.data(), res->matches.size(), max_matches, &top.stats, &kept, &top.cull);
         if (rc == LX_OK && kept && res->ops.size())
         {
             lambda_amd::RawVec<uint8_t> packed;
@@ -937,7 +949,21 @@ int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, 
     }
     if (rstats)
         *rstats = top.stats;
+    if (cull_stats)
+        *cull_stats = top.cull.stats;
     return LX_OK;
+}
+
+int lx_iterate_matches_dev_top(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, uint64_t max_matches,
+                               lx_record_stats * rstats, lx_iterate_result ** out)
+{
+    return iterate_matches_dev_top(h, slot, d_matches, n_matches, params, max_matches, nullptr, rstats, nullptr, out);
+}
+
+int lx_iterate_matches_dev_top_ex(lx_handle * h, int slot, void const * d_matches, uint64_t n_matches, lx_search_params const * params, uint64_t max_matches,
+                                  lx_cull_options const * opt, lx_record_stats * rstats, lx_cull_stats * cull_stats, lx_iterate_result ** out)
+{
+    return iterate_matches_dev_top(h, slot, d_matches, n_matches, params, max_matches, opt, rstats, cull_stats, out);
 }
 
 // The Level-2 radix sort (lx_level2.hip: l2_launch_sort) for a caller's own (key, value) words in device memory -- what the front end's

@@ -36,11 +36,30 @@ inline uint64_t bits_below(uint64_t count) // mask of the bits a value in [0, co
 
 // what lx_iterate_matches_dev_top asks of a call: the cut, and where the parts' lx_record_stats add up (done: the step ran on
 // the device for every record of the result; else the caller runs it on the finished result)
+// lx_cull_options as the kernels take them (lx_cull.h): the lengths in device memory as 32-bit words, query n_qid's at
+// d_q_lens[n_qid * stride]; where the parts' lx_cull_stats add up
+struct CullRequest
+{
+    uint64_t         max_hsps = 0, culling_limit = 0;
+    uint32_t const * d_q_lens = nullptr;
+    uint64_t         q_lens_n = 0;
+    uint32_t         stride   = 1;
+    int              translated = 0;
+    lx_cull_stats    stats{};
+
+    void set(lx::TopParams & tp) const
+    {
+        tp.max_hsps = max_hsps, tp.culling_limit = culling_limit;
+        tp.q_lens = d_q_lens, tp.q_lens_n = q_lens_n, tp.q_len_stride = stride, tp.q_translated = translated;
+    }
+};
+
 struct TopRequest
 {
     uint64_t        max_matches = 0;
     lx_record_stats stats{};
     bool            done = false;
+    CullRequest     cull{};
 };
 
 // src/search_misc.hpp:46-50
@@ -65,12 +84,14 @@ int ensure_plan(lx_handle * h, uint64_t cap_wf);
 // max_entries entries (a tile per 256), counters for nr ranges on the device and nr_pinned on their way down
 int ensure_records(lx_handle * h, uint64_t rows, uint64_t max_win, uint64_t max_entries, uint64_t nr, uint64_t nr_pinned);
 // _writeRecord's cut on the device (lx_toprec.hip): `rows` rows that stay, scratch for ranges of up to max_win rows, counters for nr ranges
-int ensure_top_records(lx_handle * h, uint64_t rows, uint64_t max_win, uint64_t nr);
+// (cull: NULL, or the options whose kernels the ranges' launches will add)
+int ensure_top_records(lx_handle * h, uint64_t rows, uint64_t max_win, uint64_t nr, CullRequest const * cull = nullptr);
 // The counters of the cut's kernels (tc: [lx::kTopCounters]) over nrec records whose columns are max_ops at most: checked, and added
-// to *stats
-int top_account(lx_handle * h, uint64_t const * tc, uint64_t nrec, uint64_t max_ops, lx_record_stats * stats);
+// to *stats (and to *cull_stats, unless NULL)
+int top_account(lx_handle * h, uint64_t const * tc, uint64_t nrec, uint64_t max_ops, lx_record_stats * stats, lx_cull_stats * cull_stats = nullptr);
 // _writeRecord's sort / unique / sort / cut for rows in host memory: up, the kernels of lx_toprec.hip, the rows that stay down
-int toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n);
+// (cull: NULL, or the two rules of lx_cull.h with the lengths already in device memory; its stats are set, not added to)
+int toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n, CullRequest * cull = nullptr);
 
 // The tail of iterateMatchesFullSimd (src/search_algo.hpp:1287-1325) for a part of the window list whose survivors the extension
 // pipeline left on the device: statistics, order, identity cut-off, records as kernels (lx_records.hip), then ONE copy of finished

@@ -19,23 +19,27 @@ int lxi::ensure_records(lx_handle * h, uint64_t rows, uint64_t max_win, uint64_t
     return LX_OK;
 }
 
-int lxi::ensure_top_records(lx_handle * h, uint64_t rows, uint64_t max_win, uint64_t nr)
+int lxi::ensure_top_records(lx_handle * h, uint64_t rows, uint64_t max_win, uint64_t nr, CullRequest const * cull)
 {
     auto & l2 = h->l2;
     int    rc;
-    if ((rc = ensure(h, l2.d_toprows, rows * sizeof(lx_blast_match) + 16)) || (rc = ensure(h, l2.d_topwork, lx::toprec_work_bytes(max_win))) ||
+    if ((rc = ensure(h, l2.d_toprows, rows * sizeof(lx_blast_match) + 16)) ||
+        (rc = ensure(h, l2.d_topwork, lx::toprec_work_bytes(max_win, cull && cull->max_hsps, cull && cull->culling_limit))) ||
         (rc = ensure(h, l2.d_topcnt, nr * lx::kTopCounters * sizeof(uint64_t))))
         return rc;
     return LX_OK;
 }
 
-int lxi::top_account(lx_handle * h, uint64_t const * tc, uint64_t nrec, uint64_t max_ops, lx_record_stats * stats)
+int lxi::top_account(lx_handle * h, uint64_t const * tc, uint64_t nrec, uint64_t max_ops, lx_record_stats * stats, lx_cull_stats * cull_stats)
 {
-    if (tc[lx::kTopFinal] + tc[lx::kTopDuplicate] + tc[lx::kTopAbundant] != nrec || tc[lx::kTopOps] > max_ops)
-        return fail(h, LX_ESTATE, "the cut's kernels account for %llu of %llu records", (unsigned long long)(tc[lx::kTopFinal] + tc[lx::kTopDuplicate] + tc[lx::kTopAbundant]),
-                    (unsigned long long)nrec);
+    // (the two counters of lx_cull.h's kernels are zero where they did not run)
+    uint64_t const sum = tc[lx::kTopFinal] + tc[lx::kTopDuplicate] + tc[lx::kTopAbundant] + tc[lx::kTopMaxHsps] + tc[lx::kTopCulled];
+    if (sum != nrec || tc[lx::kTopOps] > max_ops)
+        return fail(h, LX_ESTATE, "the cut's kernels account for %llu of %llu records", (unsigned long long)sum, (unsigned long long)nrec);
     stats->qrys_with_hit += tc[lx::kTopQueries], stats->hits_duplicate2 += tc[lx::kTopDuplicate], stats->hits_abundant += tc[lx::kTopAbundant];
     stats->hits_final += tc[lx::kTopFinal], stats->pairs += tc[lx::kTopPairs];
+    if (cull_stats)
+        cull_stats->hits_max_hsps += tc[lx::kTopMaxHsps], cull_stats->hits_culled += tc[lx::kTopCulled];
     return LX_OK;
 }
 
@@ -104,7 +108,7 @@ int RecordsJob::prepare(lambda_amd::CutOffs & cutOffFor, std::vector<Range> rs, 
         return rc;
     }
     LX_HIP(h, hipMemsetAsync(l2.d_reccnt.ptr, 0, nr * lx::kRecCounters * sizeof(uint64_t), st));
-    if (top && ((rc = ensure_top_records(h, n_part + 16, max_win, nr)) || (rc = ensure(h, l2.d_topcodes, 3 * (n_part + 16) * sizeof(uint64_t) + 16)) ||
+    if (top && ((rc = ensure_top_records(h, n_part + 16, max_win, nr, &top->cull)) || (rc = ensure(h, l2.d_topcodes, 3 * (n_part + 16) * sizeof(uint64_t) + 16)) ||
                 (rc = ensure_pinned(h, l2.p_topcnt, nr * lx::kTopCounters * sizeof(uint64_t), kRoom))))
     {
         (void)hipStreamSynchronize(st);
@@ -177,6 +181,7 @@ int RecordsJob::enqueue(uint64_t r, void const * d_hsp, void const * d_src, void
         tp.max_matches = top->max_matches;
         tp.rebase_ops  = want_ops ? 1 : 0;
         tp.counters    = static_cast<uint64_t *>(l2.d_topcnt.ptr) + r * lx::kTopCounters;
+        top->cull.set(tp);
         PhaseTimer pt(h, st, 7);
         LX_HIP(h, lx::toprec_launch(tp, l2.d_topwork.ptr, st));
         pt.close();
@@ -219,7 +224,7 @@ int RecordsJob::flush(uint64_t r, bool gpu_busy)
     if (top && nrec)
     {
         uint64_t const * const tc = static_cast<uint64_t const *>(l2.p_topcnt.ptr) + r * lx::kTopCounters;
-        if (int const rc = top_account(h, tc, nrec, want_ops ? nops : ~0ull, &top->stats))
+        if (int const rc = top_account(h, tc, nrec, want_ops ? nops : ~0ull, &top->stats, &top->cull.stats))
             return rc;
         nkeep = tc[lx::kTopFinal];
         nops  = want_ops ? tc[lx::kTopOps] : nops;
@@ -288,16 +293,17 @@ int RecordsJob::flush(uint64_t r, bool gpu_busy)
     return LX_OK;
 }
 
-int lxi::toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n)
+int lxi::toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_record_stats * stats, uint64_t * out_n, CullRequest * cull)
 {
     auto &            l2 = h->l2;
     hipStream_t const st = h->stream;
     int               rc;
     lx_record_stats   rs{};
+    lx_cull_stats     cs{};
     *out_n = 0;
     if (n)
     {
-        if ((rc = ensure(h, l2.d_topin, n * sizeof(lx_blast_match) + 16)) || (rc = ensure_top_records(h, n, n, 1)))
+        if ((rc = ensure(h, l2.d_topin, n * sizeof(lx_blast_match) + 16)) || (rc = ensure_top_records(h, n, n, 1, cull)))
             return rc;
         LX_HIP(h, hipMemcpyAsync(l2.d_topin.ptr, m, n * sizeof(lx_blast_match), hipMemcpyHostToDevice, st));
         lx::TopParams tp{};
@@ -306,13 +312,15 @@ int lxi::toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_
         tp.n_cap       = n;
         tp.max_matches = max_matches;
         tp.counters    = static_cast<uint64_t *>(l2.d_topcnt.ptr);
+        if (cull)
+            cull->set(tp);
         PhaseTimer pt(h, st, 7);
         LX_HIP(h, lx::toprec_launch(tp, l2.d_topwork.ptr, st));
         pt.close();
         uint64_t cnt[lx::kTopCounters];
         LX_HIP(h, hipMemcpyAsync(cnt, tp.counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
         LX_HIP(h, hipStreamSynchronize(st));
-        if ((rc = top_account(h, cnt, n, ~0ull, &rs)))
+        if ((rc = top_account(h, cnt, n, ~0ull, &rs, &cs)))
             return rc;
         if (cnt[lx::kTopFinal])
         {
@@ -323,6 +331,8 @@ int lxi::toprec_host_rows(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_
     }
     if (stats)
         *stats = rs;
+    if (cull)
+        cull->stats = cs;
     return LX_OK;
 }
 
@@ -338,4 +348,47 @@ extern "C" int lx_postprocess_records_dev(lx_handle * h, lx_blast_match * m, uin
         return rc;
     h->phase_ev.clear();
     return toprec_host_rows(h, m, n, max_matches, stats, out_n);
+}
+
+extern "C" int lx_postprocess_records_dev_ex(lx_handle * h, lx_blast_match * m, uint64_t n, uint64_t max_matches, lx_cull_options const * opt,
+                                             lx_record_stats * stats, lx_cull_stats * cull_stats, uint64_t * out_n)
+{
+    if (!h || !out_n || (!m && n))
+        return LX_EINVAL;
+    *out_n = 0;
+    if (n >= 0x7ffffff0ull)
+        return fail(h, LX_EINVAL, "lx_postprocess_records_dev_ex: at most 2^31 - 16 rows per call");
+    std::string why;
+    if (cull_check(m, n, opt, 0xffffffffull, why) != LX_OK)
+        return fail(h, LX_EINVAL, "%s", why.c_str());
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    h->phase_ev.clear();
+    CullRequest cull;
+    if (opt)
+        cull.max_hsps = opt->max_hsps, cull.culling_limit = opt->culling_limit, cull.translated = opt->q_translated != 0;
+    if (cull.culling_limit && n)
+    {
+        // the lengths of the queries the rows name, as the 32-bit words the kernel reads (cull_check refused longer ones); queries
+        // that no row names keep 0
+        uint64_t max_qid = 0;
+        for (uint64_t i = 0; i < n; ++i)
+            max_qid = std::max<uint64_t>(max_qid, m[i].n_qid);
+        std::vector<uint32_t> lens(max_qid + 1, 0u);
+        for (uint64_t i = 0; i < n; ++i)
+            lens[m[i].n_qid] = (uint32_t)opt->q_lens[m[i].n_qid];
+        if ((rc = upload(h, h->l2.d_cullqlen, lens)))
+        {
+            (void)hipStreamSynchronize(h->stream);
+            return rc;
+        }
+        LX_HIP(h, hipStreamSynchronize(h->stream)); // (`lens` is a local)
+        cull.d_q_lens = static_cast<uint32_t const *>(h->l2.d_cullqlen.ptr);
+        cull.q_lens_n = lens.size();
+    }
+    rc = toprec_host_rows(h, m, n, max_matches, stats, out_n, &cull);
+    if (rc == LX_OK && cull_stats)
+        *cull_stats = cull.stats;
+    return rc;
 }

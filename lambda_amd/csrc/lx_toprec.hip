@@ -30,6 +30,20 @@
 // Sizes (cdna_hip_programming.md section 10 / MI355X_MICROARCH.md): 160 KiB of LDS per CU; kernel 1 declares 512 * 52 B = 26 KiB,
 // so 6 workgroups = 24 of the CU's 32 wavefront slots by LDS; kernels 2 and 3 (6 KiB) are limited by the 32 wavefronts alone.
 //
+// Between the unique and the cut, where lx_cull_options asks for it (the rule: lx_cull.h), two more counts of the same shape over the
+// rows that are no duplicates; "better" = earlier in order 2, which is the bit score and the place in order 1 that kernel 1 left:
+//   kernel 4 (max_hsps = K > 0) stages subject, bit score and place (20 bytes a row) and counts the better rows of the row's subject:
+//            K or more, and the row is dropped (hits_max_hsps);
+//   kernel 5 (culling_limit = L > 0) stages the two ends of the query interval, bit score and place (20 bytes a row) and counts the
+//            better rows, among those that kernel 4 left, whose interval envelops the row's: L or more, and the row is dropped
+//            (hits_culled).  The intervals are computed once per row by an elementwise kernel into two uint32_t arrays of `work`
+//            (a query beyond 2^32 - 1 letters is refused on the host).
+// Each writes a copy of kernel 1's word with the flag also set for the rows it dropped; kernel 2 reads the last copy (TopParams::live),
+// so that order 2's place and "stays" are counted among the rows that survive both.  Neither is launched when its option is 0: the
+// default path queues the kernels, and takes the scratch, that it did before they existed.  Kernels 4 and 5 declare 512 * 20 B =
+// 10 KiB of LDS each: 16 workgroups by LDS, more than the CU's 32 wavefront slots hold -- limited by the 32 wavefronts alone (8
+// workgroups), as kernels 2 and 3.
+//
 // Segments come from one scan (lx_scan.h): heads by comparing neighbours, segment number = heads up to the row, start of segment k
 // scattered by its head.  The rows' final places come from a second scan, over the flags "stays".  With alignment columns
 // (rebase_ops) a third scan, 64-bit, over n_ops of the rows in OUTPUT order gives every row its new ops_off.  The Level-2 driver's
@@ -42,6 +56,7 @@
 
 #include <algorithm>
 
+#include "lx_cull.h"
 #include "lx_level2.h"
 #include "lx_toprec.h"
 
@@ -190,6 +205,97 @@ __global__ __launch_bounds__(kTopBlock) void top_rank1_kernel(TopParams p)
     count_flag(sp.valid && dup, p.counters + kTopDuplicate);
 }
 
+// ---- kernel 4 (max_hsps > 0): the better rows of the same subject among the rows that are no duplicates ---------------------------
+__global__ __launch_bounds__(kTopBlock) void top_hsps_kernel(TopParams p)
+{
+    __shared__ uint64_t k_sid[kTopTile];
+    __shared__ double   k_bs[kTopTile];
+    __shared__ uint32_t k_r1[kTopTile];
+    Span const sp = span_of(p);
+    if (sp.first >= sp.n)
+        return;
+    uint64_t const sid = sp.valid ? p.in[sp.i].n_sid : 0;
+    double const   bs  = sp.valid ? p.in[sp.i].bit_score : 0.0;
+    uint32_t const r1  = sp.valid ? p.r1[sp.i] : kFlag;
+    uint32_t       same = 0;
+    for (uint32_t t0 = sp.lo; t0 < sp.hi; t0 += kTopTile)
+    {
+        uint32_t const t1 = min(sp.hi, t0 + kTopTile);
+        for (uint32_t j = t0 + threadIdx.x; j < t1; j += kTopBlock)
+        {
+            k_sid[j - t0] = p.in[j].n_sid;
+            k_bs[j - t0]  = p.in[j].bit_score;
+            k_r1[j - t0]  = p.r1[j];
+        }
+        __syncthreads();
+        uint32_t const a = max(sp.s, t0), b = min(sp.e, t1);
+        for (uint32_t j = a; j < b; ++j)
+        {
+            uint32_t const rj = k_r1[j - t0];
+            same += !(rj & kFlag) && k_sid[j - t0] == sid && cull::better(k_bs[j - t0], rj, bs, r1 & ~kFlag) ? 1u : 0u;
+        }
+        __syncthreads();
+    }
+    bool const dropped = sp.valid && !(r1 & kFlag) && (uint64_t)same >= p.max_hsps;
+    if (sp.valid)
+        p.live_hsps[sp.i] = r1 | (dropped ? kFlag : 0u);
+    count_flag(dropped, p.counters + kTopMaxHsps);
+}
+
+// ---- culling_limit > 0: every row's query interval, once ------------------------------------------------------------------------------
+__global__ __launch_bounds__(kTopBlock) void top_interval_kernel(TopParams p)
+{
+    uint64_t const i = (uint64_t)blockIdx.x * kTopBlock + threadIdx.x;
+    if (i >= rows_of(p))
+        return;
+    BlastMatchDev const & r  = p.in[i];
+    uint64_t const        at = r.n_qid * (uint64_t)p.q_len_stride;
+    // (the callers refuse rows whose query is not in the list or whose interval does not fit: such a row would get [0, 0] here)
+    uint64_t const len = r.n_qid < p.q_lens_n && at < p.q_lens_n ? p.q_lens[at] : 0;
+    uint64_t       lo, hi;
+    (void)cull::interval(r.q_start, r.q_end, r.q_frame, len, p.q_translated != 0, lo, hi);
+    p.iv_lo[i] = (uint32_t)min(lo, (uint64_t)0xffffffffu);
+    p.iv_hi[i] = (uint32_t)min(hi, (uint64_t)0xffffffffu);
+}
+
+// ---- kernel 5 (culling_limit > 0): the better rows whose interval envelops the row's, among the rows that kernel 4 left -----------------
+__global__ __launch_bounds__(kTopBlock) void top_cull_kernel(TopParams p, uint32_t const * __restrict__ left)
+{
+    __shared__ double   k_bs[kTopTile];
+    __shared__ uint32_t k_lo[kTopTile], k_hi[kTopTile], k_r1[kTopTile];
+    Span const sp = span_of(p);
+    if (sp.first >= sp.n)
+        return;
+    double const   bs = sp.valid ? p.in[sp.i].bit_score : 0.0;
+    uint32_t const r1 = sp.valid ? left[sp.i] : kFlag;
+    uint32_t const lo = sp.valid ? p.iv_lo[sp.i] : 0u, hi = sp.valid ? p.iv_hi[sp.i] : 0u;
+    uint32_t       around = 0;
+    for (uint32_t t0 = sp.lo; t0 < sp.hi; t0 += kTopTile)
+    {
+        uint32_t const t1 = min(sp.hi, t0 + kTopTile);
+        for (uint32_t j = t0 + threadIdx.x; j < t1; j += kTopBlock)
+        {
+            k_bs[j - t0] = p.in[j].bit_score;
+            k_lo[j - t0] = p.iv_lo[j];
+            k_hi[j - t0] = p.iv_hi[j];
+            k_r1[j - t0] = left[j];
+        }
+        __syncthreads();
+        uint32_t const a = max(sp.s, t0), b = min(sp.e, t1);
+        for (uint32_t j = a; j < b; ++j)
+        {
+            uint32_t const rj = k_r1[j - t0];
+            // (rows that are themselves culled count: lx_cull.h says why that changes nothing)
+            around += !(rj & kFlag) && cull::envelops(k_lo[j - t0], k_hi[j - t0], lo, hi) && cull::better(k_bs[j - t0], rj, bs, r1 & ~kFlag) ? 1u : 0u;
+        }
+        __syncthreads();
+    }
+    bool const culled = sp.valid && !(r1 & kFlag) && (uint64_t)around >= p.culling_limit;
+    if (sp.valid)
+        p.live[sp.i] = r1 | (culled ? kFlag : 0u);
+    count_flag(culled, p.counters + kTopCulled);
+}
+
 // ---- kernel 2: place in order 2 among the rows that are no duplicates, and the cut ----------------------------------------------
 __global__ __launch_bounds__(kTopBlock) void top_rank2_kernel(TopParams p)
 {
@@ -198,8 +304,9 @@ __global__ __launch_bounds__(kTopBlock) void top_rank2_kernel(TopParams p)
     Span const sp = span_of(p);
     if (sp.first >= sp.n)
         return;
+    // (p.live is r1, or -- lx_cull.h -- r1 with the flag also set for the rows that kernels 4 and 5 dropped: no survivors either)
     double const   bs = sp.valid ? p.in[sp.i].bit_score : 0.0;
-    uint32_t const r1 = sp.valid ? p.r1[sp.i] : kFlag;
+    uint32_t const r1 = sp.valid ? p.live[sp.i] : kFlag;
     uint32_t       before = 0;
     for (uint32_t t0 = sp.lo; t0 < sp.hi; t0 += kTopTile)
     {
@@ -207,7 +314,7 @@ __global__ __launch_bounds__(kTopBlock) void top_rank2_kernel(TopParams p)
         for (uint32_t j = t0 + threadIdx.x; j < t1; j += kTopBlock)
         {
             k_bs[j - t0] = p.in[j].bit_score;
-            k_r1[j - t0] = p.r1[j];
+            k_r1[j - t0] = p.live[j];
         }
         __syncthreads();
         uint32_t const a = max(sp.s, t0), b = min(sp.e, t1);
@@ -414,10 +521,12 @@ size_t up16(size_t x)
 }
 } // namespace
 
-size_t toprec_work_bytes(uint64_t n_cap)
+size_t toprec_work_bytes(uint64_t n_cap, bool max_hsps, bool culling_limit)
 {
     uint64_t const tiles = l2_scan_tiles(n_cap), otiles = (n_cap + kOpsTile - 1) / kOpsTile;
-    return 4 * up16(n_cap * sizeof(uint32_t)) + up16((n_cap + 1) * sizeof(uint32_t)) + up16((tiles + 1) * sizeof(uint32_t)) + up16((otiles + 1) * sizeof(uint64_t)) + 64;
+    // (kernel 4: its flags; kernel 5: its flags and the two ends of the intervals)
+    size_t const more = (max_hsps ? 1 : 0) + (culling_limit ? 3 : 0);
+    return (4 + more) * up16(n_cap * sizeof(uint32_t)) + up16((n_cap + 1) * sizeof(uint32_t)) + up16((tiles + 1) * sizeof(uint32_t)) + up16((otiles + 1) * sizeof(uint64_t)) + 64;
 }
 
 hipError_t toprec_launch(TopParams p, void * work, hipStream_t stream)
@@ -442,12 +551,31 @@ hipError_t toprec_launch(TopParams p, void * work, hipStream_t stream)
     p.seg_start   = static_cast<uint32_t *>(take((p.n_cap + 1) * sizeof(uint32_t)));
     p.block_tot   = static_cast<uint32_t *>(take((tiles + 1) * sizeof(uint32_t)));
     p.tile_ops    = static_cast<uint64_t *>(take((otiles + 1) * sizeof(uint64_t)));
+    // (behind what the step always takes, so that the default path's scratch lies where it lay)
+    if (p.culling_limit && !p.q_lens)
+        return hipErrorInvalidValue;
+    p.live_hsps = p.live = p.r1;
+    if (p.max_hsps)
+        p.live_hsps = p.live = static_cast<uint32_t *>(take(p.n_cap * sizeof(uint32_t)));
+    if (p.culling_limit)
+    {
+        p.live  = static_cast<uint32_t *>(take(p.n_cap * sizeof(uint32_t)));
+        p.iv_lo = static_cast<uint32_t *>(take(p.n_cap * sizeof(uint32_t)));
+        p.iv_hi = static_cast<uint32_t *>(take(p.n_cap * sizeof(uint32_t)));
+    }
     dim3 const sgrid((unsigned)tiles), sblock(kL2ScanBlock), grid((unsigned)((p.n_cap + kTopBlock - 1) / kTopBlock)), block(kTopBlock);
     SegVal const sv{p};
     hipLaunchKernelGGL((l2_scan_reduce_kernel<kOpSum, false, SegVal>), sgrid, sblock, 0, stream, sv, p.n_cap, p.block_tot);
     hipLaunchKernelGGL((l2_scan_tops_kernel<kOpSum>), dim3(1), sblock, 0, stream, p.block_tot, tiles);
     hipLaunchKernelGGL((l2_scan_apply_kernel<kOpSum, false, SegVal, SegOut>), sgrid, sblock, 0, stream, sv, SegOut{p}, p.n_cap, p.block_tot);
     hipLaunchKernelGGL(top_rank1_kernel, grid, block, 0, stream, p);
+    if (p.max_hsps)
+        hipLaunchKernelGGL(top_hsps_kernel, grid, block, 0, stream, p);
+    if (p.culling_limit)
+    {
+        hipLaunchKernelGGL(top_interval_kernel, grid, block, 0, stream, p);
+        hipLaunchKernelGGL(top_cull_kernel, grid, block, 0, stream, p, static_cast<uint32_t const *>(p.live_hsps));
+    }
     hipLaunchKernelGGL(top_rank2_kernel, grid, block, 0, stream, p);
     KeepVal const kv{p};
     hipLaunchKernelGGL((l2_scan_reduce_kernel<kOpSum, false, KeepVal>), sgrid, sblock, 0, stream, kv, p.n_cap, p.block_tot);

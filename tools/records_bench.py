@@ -10,12 +10,18 @@ and the bytes of rows + alignment columns that came down.  The lists: the protei
 the read list of configs[2] (bench.py --iterate), and an ABUNDANT protein list (lambda_amd/synth.py: families of --abundant-family
 members, so that every query has a few hundred surviving windows) -- all cut to --max-matches records per query.
 
+With --max-hsps K and / or --culling-limit L (lx_cull_options; 0 = off, the default) the step has the two rules between its unique
+and its cut: (a) ends in lx_postprocess_records_ex, (b) is lx_iterate_matches_dev_top_ex, and a further line names what each rule
+dropped.  --lists picks the lists (1, 2, abundant).  With both options off the tool calls what it always called, so that an older
+library (LX_LIB_PATH) can be timed with it.
+
     python tools/records_bench.py > profiles/records_bench.txt
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
+import os
 import statistics
 import sys
 import time
@@ -46,12 +52,21 @@ def main():
     ap.add_argument("--max-matches", type=int, default=25)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--max-hsps", type=int, default=0)
+    ap.add_argument("--culling-limit", type=int, default=0)
+    ap.add_argument("--lists", default="1,2,abundant", help="comma-separated: 1 (configs[1]), 2 (configs[2]), abundant")
     a = ap.parse_args()
     import torch
 
     lib = capi.load()
-    print(f"# records_bench: max_matches {a.max_matches}, {a.warmup} warm-ups + {a.runs} runs of each path per list; times in ms")
+    cull = a.max_hsps > 0 or a.culling_limit > 0
+    wanted = {"1": "configs[1]", "2": "configs[2]", "abundant": "abundant"}
+    picked = [wanted[x] for x in a.lists.split(",") if x]
+    print(f"# records_bench: max_matches {a.max_matches}, {a.warmup} warm-ups + {a.runs} runs of each path per list; times in ms"
+          + (f"; max_hsps {a.max_hsps}, culling_limit {a.culling_limit}" if cull else "") + f"; library build {lib.lx_build_id().decode()}" + (" (LX_LIB_PATH)" if os.environ.get("LX_LIB_PATH") else ""))
     for name, w, make, frames in lists(a):
+        if not any(name.startswith(x) for x in picked):
+            continue
         q, qoff, qlen, qorig, s, soff, slen, m = make()
         d = w.directions[0]
         m_, ma, mi, go, ge = d.scoring
@@ -68,6 +83,8 @@ def main():
             h.set_queries(q, qoff, qlen, qorig, frames)
             d_m = torch.from_numpy(m.view(np.uint8).copy()).to("cuda:0")
             torch.cuda.synchronize()
+            # (the untranslated lengths: what lx_set_queries keeps resident for the Level-2 form)
+            copt, _lens = capi.cull_options(a.max_hsps, a.culling_limit, qorig) if cull else (None, None)
 
             def size_of(r):
                 n = int(lib.lx_iterate_result_count(r))
@@ -83,20 +100,30 @@ def main():
                 t1 = time.perf_counter()
                 n, cols = size_of(r)  # (not timed)
                 t2 = time.perf_counter()
-                kept = lib.lx_postprocess_records(lib.lx_iterate_result_matches(r), n, a.max_matches, C.byref(st))
+                cst = capi.CullStats()
+                if cull:
+                    kept = lib.lx_postprocess_records_ex(lib.lx_iterate_result_matches(r), n, a.max_matches, C.byref(copt), C.byref(st), C.byref(cst))
+                    assert kept >= 0, capi.last_output_error()
+                else:
+                    kept = lib.lx_postprocess_records(lib.lx_iterate_result_matches(r), n, a.max_matches, C.byref(st))
                 t3 = time.perf_counter()
                 lib.lx_iterate_result_free(r)
-                return (t1 - t0 + t3 - t2) * 1e3, (t3 - t2) * 1e3, n, cols, int(kept), st
+                return (t1 - t0 + t3 - t2) * 1e3, (t3 - t2) * 1e3, n, cols, int(kept), st, cst
 
             def path_b():
                 r, st = C.c_void_p(), capi.RecordStats()
                 t0 = time.perf_counter()
-                h._check(lib.lx_iterate_matches_dev_top(h.h, 0, d_m.data_ptr(), len(m), C.byref(params), a.max_matches, C.byref(st), C.byref(r)))
+                cst = capi.CullStats()
+                if cull:
+                    h._check(lib.lx_iterate_matches_dev_top_ex(h.h, 0, d_m.data_ptr(), len(m), C.byref(params), a.max_matches, C.byref(copt), C.byref(st),
+                                                               C.byref(cst), C.byref(r)))
+                else:
+                    h._check(lib.lx_iterate_matches_dev_top(h.h, 0, d_m.data_ptr(), len(m), C.byref(params), a.max_matches, C.byref(st), C.byref(r)))
                 t1 = time.perf_counter()
                 kernel_ms, launches = h.last_phase_ms(7)
                 n, cols = size_of(r)
                 lib.lx_iterate_result_free(r)
-                return (t1 - t0) * 1e3, kernel_ms, n, cols, launches, st
+                return (t1 - t0) * 1e3, kernel_ms, n, cols, launches, st, cst
 
             for _ in range(a.warmup):
                 path_a(), path_b()
@@ -107,7 +134,7 @@ def main():
             ta, tb = [x[0] for x in ra], [x[0] for x in rb]
             n_a, cols_a, kept_a, st_a = ra[0][2:6]
             n_b, cols_b, _, st_b = rb[0][2:6]
-            same = kept_a == n_b and all(getattr(st_a, f) == getattr(st_b, f) for f, _ in capi.RecordStats._fields_)
+            same = kept_a == n_b and all(getattr(st_a, f) == getattr(st_b, f) for f, _ in capi.RecordStats._fields_) and bytes(ra[0][6]) == bytes(rb[0][6])
             med_a, med_b, spread = statistics.median(ta), statistics.median(tb), max(ta) - min(ta)
             print(f"\n## {name}: {len(m)} matches -> {n_a} records ({n_a / max(st_a.qrys_with_hit, 1):.1f} per query with hits) -> {kept_a} kept "
                   f"(duplicates {st_a.hits_duplicate2}, abundant {st_a.hits_abundant}); (b) gives the same count and statistics: {same}")
@@ -115,6 +142,9 @@ def main():
             print("    of which lx_postprocess_records alone:            " + " ".join(f"{x[1]:.2f}" for x in ra) + f" | median {statistics.median(x[1] for x in ra):.2f}")
             print("(b) lx_iterate_matches_dev_top:                       " + " ".join(f"{t:.2f}" for t in tb) + f" | median {med_b:.2f}, max - min {max(tb) - min(tb):.2f}")
             print("    of which the step's kernels (device time):        " + " ".join(f"{x[1]:.2f}" for x in rb) + f" | median {statistics.median(x[1] for x in rb):.2f} ({rb[0][4]} range(s))")
+            if cull:
+                print(f"max_hsps {a.max_hsps} dropped {ra[0][6].hits_max_hsps}, culling_limit {a.culling_limit} dropped {ra[0][6].hits_culled} (host step); "
+                      f"(b): {rb[0][6].hits_max_hsps}, {rb[0][6].hits_culled}")
             print(f"bytes down: (a) {n_a * 128 + cols_a} ({n_a} rows + {cols_a} columns), (b) {n_b * 128 + cols_b} ({n_b} rows + {cols_b} columns)")
             verdict = "gpu" if med_a - med_b > spread else "host"
             print(f"(a) - (b) = {med_a - med_b:.2f} ms against (a)'s spread of {spread:.2f} ms -> --records auto = {verdict} for lists of this kind")
