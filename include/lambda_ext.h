@@ -761,6 +761,18 @@ typedef struct lx_output_options
     uint32_t const *     lca_tax;
     uint64_t             n_lca;
     char const * const * tax_names;   /* scientific name per taxon (tag ls), NULL = "*"                                       */
+    /* base qualities of the queries (FASTQ, Phred+33), parallel to the writers' q_res_ascii: query q's are
+     * q_qual[q_ascii_off[q] .. + q_lens[q]).  NULL (the default) = none: every writer then makes the bytes it made before the
+     * field existed.  SAM and BAM write QUAL exactly where they write SEQ, over the same letters and in the same direction (the
+     * minus strand reversed, not complemented; hard clips cut it as they cut SEQ; a translated query's window is the nucleotides
+     * [3a + |f| - 1, 3e + |f| - 1) of the strand that was read); a record whose SEQ is "*" has QUAL "*".  SAM carries the
+     * characters as they stand, BAM byte - 33 per base, reduced modulo 256.  NOT CHECKED: the bytes are not validated (the
+     * documented precondition is '!' .. '~'; whatever is given, the host and the device writers do the same with it), and the
+     * buffer's extent is the caller's word, as q_res_ascii's is.  Honoured by every one-shot entry that takes options
+     * (lx_write_records_ex, lx_render_records, lx_write_records_bgzf, lx_render_bam_dev, lx_write_bam_dev, lx_render_text_dev,
+     * lx_write_text_dev); ignored by the tabular formats; not read when q_res_ascii or q_ascii_off is NULL; not read by
+     * lx_out_open (a piece's qualities go through lx_out_append_ex). */
+    uint8_t const * q_qual;
 } lx_output_options;
 void lx_output_options_default(lx_output_options * o);
 /* lx_write_records with options (NULL = defaults).  LX_EINVAL also for an unknown column specifier or tag key (the reference
@@ -787,7 +799,7 @@ void            lx_bytes_free(lx_bytes * b);
  * exactly what lx_write_records_ex + lx_write_footer put in a file.  For LX_OUT_BAM the uncompressed BAM stream (SAM/BAM
  * specification 4.2): magic, the SAM header text with one @SQ line per subject (BAM always carries the references, as seqan's
  * writeHeader does), the reference list, then the SAM writer's records in binary (refID = n_sid, MAPQ 255, bin by reg2bin over the
- * CIGAR's reference span, no mate, QUAL 0xFF; tag types ae f, AS ap S, ar ai C, qf sf c, lt NM IH I, st ls qs OC Z,
+ * CIGAR's reference span, no mate, QUAL 0xFF per base or opt->q_qual's bytes - 33; tag types ae f, AS ap S, ar ai C, qf sf c, lt NM IH I, st ls qs OC Z,
  * src/search_output.hpp:601-717).  LX_EINVAL as lx_write_records_ex; *out is released with lx_bytes_free. */
 int lx_render_records(int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
                       lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
@@ -877,7 +889,7 @@ int lx_write_text_dev(lx_handle * h, char const * path, int format, int bgzf, ch
  *
  * lx_out_open writes the header: the SAM header, or the BAM magic with header text and reference list, from `subjects` (only s_ids,
  * s_lens and n_s are read; they, opt->tax and opt->tax_names must stay valid until lx_out_close; the texts of opt are copied; its
- * lca_* are not read).  bgzf = 1, and LX_OUT_BAM always: the stream is BGZF-compressed on h's device, cut into 65 280-byte blocks
+ * lca_* and q_qual are not read).  bgzf = 1, and LX_OUT_BAM always: the stream is BGZF-compressed on h's device, cut into 65 280-byte blocks
  * exactly as lx_bgzf_compress cuts the whole stream.  Refusals are those of the one-shot writers -- an unknown format, program,
  * column or tag -- and bgzf or LX_OUT_BAM without a handle; all before `path` is created or truncated.  A failure behind them
  * (the encoder, the disk) removes the file again.  h may be NULL for a plain
@@ -906,6 +918,12 @@ int lx_out_open(lx_handle * h, char const * path, int format, int bgzf, char con
 int lx_out_append(lx_out * o, int where, lx_blast_match const * m, uint64_t n, uint8_t const * ops, uint64_t ops_bytes,
                   lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, uint64_t const * lca_qid,
                   uint32_t const * lca_tax, uint64_t n_lca);
+/* lx_out_append plus the piece's base qualities: q_qual is parallel to the piece's q_res_ascii, as lx_output_options::q_qual is to
+ * a one-shot writer's (same rule, same things not checked); NULL = none, which is what lx_out_append passes.  Pieces with and
+ * without qualities may follow each other in one file, rendered on either side. */
+int lx_out_append_ex(lx_out * o, int where, lx_blast_match const * m, uint64_t n, uint8_t const * ops, uint64_t ops_bytes,
+                     lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, uint8_t const * q_qual,
+                     uint64_t const * lca_qid, uint32_t const * lca_tax, uint64_t n_lca);
 int lx_out_close(lx_out * o, int64_t footer_records);
 
 /* Decompresses a gzip stream of one or more members (RFC 1952): BGZF members on h's device, other members on the calling

@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "lx_taxmap_destroy", "lx_taxonomy_build", "lx_taxonomy_get", "lx_taxonomy_free",
     "lx_index_build", "lx_index_plan_slices", "lx_index_load", "lx_index_save", "lx_index_attach", "lx_index_get_info", "lx_index_copy_entries", "lx_index_destroy",
     "lx_seed_queries", "lx_seed_result_stats", "lx_seed_result_matches", "lx_seed_result_matches_dev", "lx_seed_result_free",
-    "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_close",
+    "lx_gunzip_stream_open", "lx_gunzip_stream_next", "lx_gunzip_stream_close", "lx_out_open", "lx_out_append", "lx_out_append_ex", "lx_out_close",
     "lx_lca_options_default", "lx_compute_lca_ex", "lx_check_tax_tree", "lx_tax_dev_create", "lx_tax_dev_destroy", "lx_compute_lca_dev",
     "lx_tax_subject_mask", "lx_subject_mask_create_dev", "lx_subject_mask_create", "lx_subject_mask_info", "lx_subject_mask_copy", "lx_subject_mask_destroy", "lx_seed_result_filter",
     "lx_seg_params_default", "lx_seg_tables", "lx_query_mask_create_seg", "lx_query_mask_create", "lx_query_mask_info", "lx_query_mask_copy", "lx_query_mask_destroy",
@@ -415,6 +415,9 @@ def load():
                                       C.c_int64]
     lib.lx_out_open.argtypes = [vp, C.c_char_p, i32, i32, C.c_char_p, C.POINTER(SeqNames), C.POINTER(OutputOptions), C.POINTER(vp)]
     lib.lx_out_append.argtypes = [vp, i32, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, vp, vp, u64]
+    if hasattr(lib, "lx_out_append_ex"):  # (not in an older library loaded through LX_LIB_PATH: the yardstick of tools/bam_render_bench.py --parent)
+        lib.lx_out_append_ex.restype = i32
+        lib.lx_out_append_ex.argtypes = [vp, i32, vp, u64, vp, u64, C.POINTER(SeqNames), vp, vp, vp, vp, vp, u64]
     lib.lx_out_close.argtypes = [vp, C.c_int64]
     _lib = lib
     return lib
@@ -640,7 +643,7 @@ class OutputOptions(C.Structure):
     _fields_ = [("columns", C.c_char_p), ("sam_tags", C.c_char_p), ("sam_seq", C.c_int32), ("sam_hard_clip", C.c_int32),
                 ("sam_with_ref_header", C.c_int32), ("version_to_output", C.c_int32), ("version", C.c_char_p), ("command_line", C.c_char_p),
                 ("db_name", C.c_char_p), ("genetic_code", C.c_int32), ("reserved", C.c_int32), ("tax", C.c_void_p), ("lca_qid", C.c_void_p),
-                ("lca_tax", C.c_void_p), ("n_lca", C.c_uint64), ("tax_names", C.c_void_p)]
+                ("lca_tax", C.c_void_p), ("n_lca", C.c_uint64), ("tax_names", C.c_void_p), ("q_qual", C.c_void_p)]
 
 
 LX_SAM_SEQ_NEVER, LX_SAM_SEQ_UNIQ, LX_SAM_SEQ_ALWAYS = 0, 1, 2
@@ -665,8 +668,25 @@ def write_footer(path, fmt: int, n_records: int):
         raise LambdaExtError(rc, "lx_write_footer")
 
 
-def _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options):
-    """The arguments the writers share (the arrays are returned too: they must outlive the call)."""
+def _with_qual(options, q_qual):
+    """`options` with q_qual pointing at the bytes (a copy; the defaults for None), and the array that must outlive the call.  q_qual
+    None: `options` itself."""
+    if q_qual is None:
+        return options, None
+    o = OutputOptions()
+    if options is None:
+        load().lx_output_options_default(C.byref(o))
+    else:
+        C.memmove(C.byref(o), C.byref(options), C.sizeof(o))
+    arr = np.frombuffer(q_qual, dtype=np.uint8)
+    o.q_qual = arr.ctypes.data if len(arr) else None
+    return o, (arr, options)
+
+
+def _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual=None):
+    """The arguments the writers share (the arrays are returned too: they must outlive the call).  q_qual: the queries' Phred+33
+    qualities, parallel to q_ascii (lx_output_options::q_qual)."""
+    options, keep_qual = _with_qual(options, q_qual)
     m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE)
     qa = (C.c_char_p * len(q_ids))(*[x.encode() for x in q_ids])
     sa = (C.c_char_p * len(s_ids))(*[x.encode() for x in s_ids])
@@ -678,14 +698,14 @@ def _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, o
     qoff = np.ascontiguousarray(q_ascii_off, dtype=np.uint64) if q_ascii_off is not None else None
     args = (_ptr(m), len(m), _ptr(o), C.byref(names), _ptr(qasc) if qasc is not None else None, _ptr(qoff) if qoff is not None else None,
             C.byref(options) if options is not None else None)
-    return args, (m, qa, sa, ql, sl, names, o, qasc, qoff)
+    return args, (m, qa, sa, ql, sl, names, o, qasc, qoff, options, keep_qual)
 
 
 def render_records(fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", write_header=True,
-                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1) -> bytes:
+                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1, q_qual: bytes | None = None) -> bytes:
     """lx_render_records: the bytes of a text format (what write_records + write_footer put in a file), or the uncompressed BAM
     stream (LX_OUT_BAM).  footer_records < 0: no footer."""
-    args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+    args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual)
     lib = load()
     out = C.c_void_p()
     rc = lib.lx_render_records(fmt, 1 if write_header else 0, program.encode(), *args, footer_records, C.byref(out))
@@ -721,12 +741,17 @@ class Out:
             raise LambdaExtError(rc, self.lib.lx_last_error(self.handle.h).decode() if self.handle is not None else last_output_error())
 
     def append(self, where: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, q_ascii: bytes | None = None, q_ascii_off=None,
-               lca_qid=None, lca_tax=None):
+               lca_qid=None, lca_tax=None, q_qual: bytes | None = None):
+        """lx_out_append, or lx_out_append_ex when the piece's qualities are given (q_qual, parallel to q_ascii)."""
         args, keep = _writer_args(bms, ops, q_ids, q_lens, [], [], q_ascii, q_ascii_off, None)
         lq = np.ascontiguousarray(lca_qid, dtype=np.uint64) if lca_qid is not None else None
         lt = np.ascontiguousarray(lca_tax, dtype=np.uint32) if lca_tax is not None else None
-        self._check(self.lib.lx_out_append(self.o, where, *args[:3], len(ops), *args[3:6], _ptr(lq) if lq is not None and len(lq) else None,
-                                           _ptr(lt) if lt is not None and len(lt) else None, len(lq) if lq is not None else 0))
+        lca = (_ptr(lq) if lq is not None and len(lq) else None, _ptr(lt) if lt is not None and len(lt) else None, len(lq) if lq is not None else 0)
+        if q_qual is None:
+            self._check(self.lib.lx_out_append(self.o, where, *args[:3], len(ops), *args[3:6], *lca))
+        else:
+            qq = np.frombuffer(q_qual, dtype=np.uint8)
+            self._check(self.lib.lx_out_append_ex(self.o, where, *args[:3], len(ops), *args[3:6], _ptr(qq) if len(qq) else None, *lca))
 
     def close(self, footer_records: int = -1):
         o, self.o = self.o, C.c_void_p()
@@ -1158,7 +1183,7 @@ def taxonomy_build(nodes: bytes, names: bytes, present):
 
 
 def write_records(path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",
-                  write_header=True, q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None):
+                  write_header=True, q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, q_qual: bytes | None = None):
     m = np.ascontiguousarray(bms, dtype=BLAST_MATCH_DTYPE)
     qa = (C.c_char_p * len(q_ids))(*[x.encode() for x in q_ids])
     sa = (C.c_char_p * len(s_ids))(*[x.encode() for x in s_ids])
@@ -1168,6 +1193,7 @@ def write_records(path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_
     o = np.frombuffer(ops + b"\0", dtype=np.uint8)
     qasc = np.frombuffer(q_ascii, dtype=np.uint8) if q_ascii else None
     qoff = np.ascontiguousarray(q_ascii_off, dtype=np.uint64) if q_ascii_off is not None else None
+    options, _keep_qual = _with_qual(options, q_qual)
     rc = load().lx_write_records_ex(str(path).encode(), fmt, 1 if write_header else 0, program.encode(), _ptr(m), len(m), _ptr(o),
                                     C.byref(names), _ptr(qasc) if qasc is not None else None, _ptr(qoff) if qoff is not None else None,
                                     C.byref(options) if options is not None else None)
@@ -1572,15 +1598,15 @@ class Handle:
         return out[: got.value].tobytes()
 
     def write_records_bgzf(self, path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",
-                           q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1):
+                           q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1, q_qual: bytes | None = None):
         """lx_write_records_bgzf: header, records and footer (footer_records >= 0) of `fmt`, BGZF-compressed into `path`."""
-        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual)
         self._check(self.lib.lx_write_records_bgzf(self.h, str(path).encode(), fmt, program.encode(), *args, footer_records))
 
     def render_bam(self, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", write_header=True,
-                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None) -> bytes:
+                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, q_qual: bytes | None = None) -> bytes:
         """lx_render_bam_dev: render_records(LX_OUT_BAM, ...) with the records made by kernels on this handle's device; the same bytes."""
-        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual)
         out = C.c_void_p()
         rc = self.lib.lx_render_bam_dev(self.h, 1 if write_header else 0, program.encode(), *args[:3], len(ops), *args[3:], C.byref(out))
         self._check(rc)
@@ -1590,16 +1616,16 @@ class Handle:
             self.lib.lx_bytes_free(out)
 
     def write_bam(self, path, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp",
-                  q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None):
+                  q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, q_qual: bytes | None = None):
         """lx_write_bam_dev: write_records_bgzf(path, LX_OUT_BAM, ...) with the records rendered and compressed on the device; the same file."""
-        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual)
         self._check(self.lib.lx_write_bam_dev(self.h, str(path).encode(), program.encode(), *args[:3], len(ops), *args[3:]))
 
     def render_text(self, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", write_header=True,
-                    q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1) -> bytes:
+                    q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1, q_qual: bytes | None = None) -> bytes:
         """lx_render_text_dev: render_records(fmt, ...) for LX_OUT_BLAST_TAB, LX_OUT_BLAST_TAB_COMMENTS and LX_OUT_SAM with the records made
         by kernels on this handle's device; the same bytes."""
-        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual)
         out = C.c_void_p()
         rc = self.lib.lx_render_text_dev(self.h, fmt, 1 if write_header else 0, program.encode(), *args[:3], len(ops), *args[3:], footer_records,
                                          C.byref(out))
@@ -1610,10 +1636,10 @@ class Handle:
             self.lib.lx_bytes_free(out)
 
     def write_text(self, path, fmt: int, bms: np.ndarray, ops: bytes, q_ids, q_lens, s_ids, s_lens, program="blastp", bgzf=False,
-                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1):
+                   q_ascii: bytes | None = None, q_ascii_off=None, options: OutputOptions | None = None, footer_records: int = -1, q_qual: bytes | None = None):
         """lx_write_text_dev: the file write_records + write_footer (bgzf False) or write_records_bgzf (bgzf True) write for a text format,
         with the records rendered (and compressed) on the device; the same file."""
-        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options)
+        args, keep = _writer_args(bms, ops, q_ids, q_lens, s_ids, s_lens, q_ascii, q_ascii_off, options, q_qual)
         self._check(self.lib.lx_write_text_dev(self.h, str(path).encode(), fmt, 1 if bgzf else 0, program.encode(), *args[:3], len(ops), *args[3:],
                                                footer_records))
 

@@ -30,6 +30,7 @@ struct Options
     // output (:224-379): columns of .m8 / .m9, tags / sequence / clipping of .sam
     std::string outputColumns = "std", samTags = "AS NM ae ai qf", samSeq = "uniq", samClip = "hard";
     bool        samWithRefHeader = false, versionToOutput = true;
+    bool        samQual = false;      // --sam-bam-qual yes: a FASTQ query's base qualities into SAM's column 11 / BAM's qual (the header comment)
     std::string commandLine;
     std::vector<int> devices;         // --devices (default: every visible device)
     std::string table       = "auto"; // --table gpu | host | auto: where the word table is made (auto: search* on the GPU, mkindex* on the host)
@@ -106,7 +107,10 @@ Options parse(int argc, char ** argv)
                                  "                 (4 .. 64, default 64) that scores above L / 10 (1 .. 1000, default 20) and holds no sub-interval that scores higher; N is never\n"
                                  "                 masked and ends every interval.  dustmasker's -linker is not built, and the masks were not compared with dustmasker's or sdust's\n"
                                  "                 (10^6 reads x 2 frames x 150 letters: 1944 ms on 16 host threads, 39 ms on the GPU with the upload)\n                 [--lazy-query 1] [--query-block N]   search the query file block by block in bounded memory: at most N reads per block\n"
-                                 "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
+                                 "                 (default 1048576, not measured yet; a block also closes at 2^30 letters; a query read from a pipe is held whole, compressed)\n                 [--sam-bam-qual no|yes]   .sam, .sam.gz, .bam: write a FASTQ query's base qualities as QUAL (default no: '*' / 0xFF, the bytes\n"
+                                 "                 every earlier version wrote): exactly where SEQ is written (--sam-bam-seq, --sam-bam-clip), over the same letters, reversed on the\n"
+                                 "                 minus strand; a translated query's over the nucleotides of its window.  A byte outside '!' .. '~' in a quality line is refused; a\n"
+                                 "                 FASTA query has none (one note on stderr, QUAL stays '*').  Under yes a block of reads holds its letters twice (letters, qualities)\n       lambda3 mkindexp|mkindexn|mkindexbs -d DB.{fa,fq,fasta,fastq,fna,faa}[.gz] [-i DB.lba] [-r li10|murphy10|none] [-g CODE] [-t THREADS]\n                 [-m MAP.{accession2taxid,dat}[.gz] [-x TAXDUMP_DIR]]");
     o.cmd = argv[1];
     bool const mk = o.cmd == "mkindexp" || o.cmd == "mkindexn" || o.cmd == "mkindexbs";
     if (o.cmd != "searchp" && o.cmd != "searchn" && o.cmd != "searchbs" && !mk)
@@ -254,6 +258,8 @@ Options parse(int argc, char ** argv)
             o.samSeq = oneOf(val(), {"always", "uniq", "never"}, "--sam-bam-seq takes always, uniq or never");
         else if (a == "--sam-bam-clip")
             o.samClip = oneOf(val(), {"hard", "soft"}, "--sam-bam-clip takes hard or soft");
+        else if (!mk && a == "--sam-bam-qual")
+            o.samQual = oneOf(val(), {"no", "yes"}, "--sam-bam-qual takes no or yes") == "yes";
         else if (a == "--sam-with-refheader")
             o.samWithRefHeader = onOff(val());
         else if (a == "--version-to-outputfile")
@@ -466,6 +472,12 @@ Options parse(int argc, char ** argv)
         oo.sam_tags = o.samTags.c_str();
         if (lx_check_output_options(fmt, &oo) != LX_OK)
             throw std::runtime_error(lx_last_output_error());
+        if (o.samQual && fmt != LX_OUT_SAM && fmt != LX_OUT_BAM)
+            throw std::runtime_error("--sam-bam-qual yes: base qualities are a field of SAM and BAM records (.sam, .sam.gz, .bam); " + o.output +
+                                     " is a tabular format, which has no column for them");
+        if (o.samQual && o.samSeq == "never")
+            throw std::runtime_error("--sam-bam-qual yes with --sam-bam-seq never: QUAL is written where SEQ is written, over the same letters, so "
+                                     "without SEQ every record's QUAL would be '*'");
     }
     return o;
 }

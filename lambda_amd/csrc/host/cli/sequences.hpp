@@ -13,6 +13,7 @@ struct SeqSet
     std::vector<uint8_t>     res;   // ranks, concatenated (frame-expanded for nucleotide queries)
     std::vector<uint64_t>    off, len;
     std::string              ascii; // original letters of the untranslated sequences, concatenated
+    std::string              qual;  // --sam-bam-qual yes, a FASTQ file: their base qualities, parallel to `ascii`; else empty
     std::vector<uint64_t>    ascii_off, orig_len;
 };
 
@@ -112,16 +113,19 @@ InputText readInput(std::string const & path, int device)
 // incremental parser that is fed the whole text here.
 using lx_query_blocks::forEachRecord;
 
-// one record into the set: its letters, ranks and frames (`cur` is used up)
+// one record into the set: its letters, ranks and frames (`cur` is used up), and its qualities where they are kept (`qual`)
 // translate = six protein frames per nucleotide sequence (BLASTX queries: qryNumFrames = 6, translate_join)
 // bsFrames: 0 = none; 1 = bisulfite subjects (every sequence twice: views::duplicate, src/shared_definitions.hpp:249-250);
 // 2 = bisulfite queries (strand, strand, reverse complement, reverse complement: add_reverse_complement | duplicate, :260-261)
-void addRecord(SeqSet & out, std::string const & id, std::string & cur, bool protein, bool addRevComp, bool translate, int geneticCode, int bsFrames)
+void addRecord(SeqSet & out, std::string const & id, std::string & cur, bool protein, bool addRevComp, bool translate, int geneticCode, int bsFrames,
+               std::string const * qual = nullptr)
 {
     out.ids.push_back(id);
     out.ascii_off.push_back(out.ascii.size());
     out.orig_len.push_back(cur.size());
     out.ascii += cur;
+    if (qual)
+        out.qual += *qual;
     if (translate)
     {
         std::vector<uint8_t> nt(cur.size());
@@ -192,14 +196,23 @@ void addRecord(SeqSet & out, std::string const & id, std::string & cur, bool pro
 }
 
 void readFasta(std::string const & text, std::string const & path, bool protein, bool addRevComp, SeqSet & out, bool translate = false,
-               int geneticCode = 1, int bsFrames = 0)
+               int geneticCode = 1, int bsFrames = 0, bool keepQual = false)
 {
-    forEachRecord(text, path,
-                  [&](std::string const & id, std::string & letters)
-                  {
-                      addRecord(out, id, letters, protein, addRevComp, translate, geneticCode, bsFrames);
-                      return true;
-                  });
+    lx_query_blocks::RecordParser parser(path);
+    parser.keepQualities(keepQual);
+    auto f = [&](std::string const & id, std::string & letters)
+    {
+        addRecord(out, id, letters, protein, addRevComp, translate, geneticCode, bsFrames, keepQual ? &parser.quality() : nullptr);
+        return true;
+    };
+    if (parser.feed(text.data(), text.size(), f))
+        parser.finish(f);
+}
+
+// --sam-bam-qual yes: the set's qualities for the writers (lx_output_options::q_qual), NULL where the file had none (FASTA)
+uint8_t const * qualOf(SeqSet const & set)
+{
+    return !set.ascii.empty() && set.qual.size() == set.ascii.size() ? reinterpret_cast<uint8_t const *>(set.qual.data()) : nullptr;
 }
 
 // the reference lets BioC++ detect the query alphabet (src/search_options.hpp); here: nucleotide if >= 90 % of the
@@ -237,8 +250,9 @@ struct QueryStream
     bool                          ended = false;
     lx_query_blocks::RecordParser parser;
 
-    QueryStream(std::string const & path_, int device) : path(path_), parser(path_)
+    QueryStream(std::string const & path_, int device, bool keepQual = false) : path(path_), parser(path_)
     {
+        parser.keepQualities(keepQual);
         if (device >= 0)
             h = makeHandle(device);
         if (lx_gunzip_stream_open(h.get(), path.c_str(), kPiece, &s) != LX_OK)
@@ -303,7 +317,8 @@ struct QueryStream
         return vote.dna();
     }
     // f(id, letters) per record from where the last call stopped, until f returns false (true: more may follow) or the file ends
-    // (false).  A piece is parsed whole, so records f has not asked for wait in `kept`.
+    // (false).  A piece is parsed whole, so records f has not asked for wait in `kept`.  While f runs, quality() is the record's
+    // quality string (empty unless the stream was opened to keep them and the file is FASTQ).
     template <class F>
     bool records(F && f)
     {
@@ -316,6 +331,7 @@ struct QueryStream
                     return true;
             }
             kept.clear();
+            keptQual.clear();
             keptAt = 0;
             if (malformed) // (the records in front of it have been handed out)
                 std::rethrow_exception(malformed);
@@ -323,6 +339,8 @@ struct QueryStream
             {
                 kept.emplace_back(id, std::string());
                 kept.back().second.swap(letters);
+                keptQual.emplace_back();
+                keptQual.back().swap(parser.quality());
                 return true;
             };
             if (!ahead.empty()) // (a slice of the piece at a time: `kept` stays small)
@@ -361,7 +379,9 @@ struct QueryStream
                 return false;
         }
     }
+    std::string const & quality() const { return keptQual[keptAt - 1]; }
     std::vector<std::pair<std::string, std::string>> kept;
+    std::vector<std::string>                         keptQual; // parallel to `kept`
     size_t                                           keptAt = 0;
     uint64_t                                         pieceAt = 0; // bytes of ahead[0] the parser has
     bool                                             finished = false;

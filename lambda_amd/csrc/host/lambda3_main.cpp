@@ -111,7 +111,19 @@
 // fna, faa, each optionally .gz: src/search_options.hpp:157-167, src/mkindex_options.hpp:96-105); the format comes from the bytes
 // (gzip magic, then ">" or "@"), not the name.  lx_gunzip decompresses: BGZF members on the first device of --devices for search*
 // (mkindex*: on the host unless --table gpu), other members on the reading thread.  FASTQ qualities are read and dropped
-// (src/search_algo.hpp:342); bzip2 is refused.
+// (src/search_algo.hpp:342) unless --sam-bam-qual yes asks for them; bzip2 is refused.
+//
+// --sam-bam-qual no|yes (search*, .sam / .sam.gz / .bam; default no: every byte of output is what it was, QUAL '*' / 0xFF; the
+// reference has no such option): a FASTQ query's base qualities are kept by the parser (a byte outside '!' .. '~' in a quality line
+// is refused with the file, the read and the byte) and written as QUAL exactly where SEQ is written -- the rule of --sam-bam-seq
+// decides whether, the window of --sam-bam-clip which letters, the minus strand reverses (and does not complement) them; a
+// translated query's are those of the nucleotides [3a + |f| - 1, 3e + |f| - 1) of the strand that was read; a record whose SEQ is
+// '*' has QUAL '*'.  SAM carries the Phred+33 characters, BAM the values.  Both paths pass them: the eager writers in
+// lx_output_options::q_qual, a --lazy-query block its own through lx_out_append_ex; --render gpu | host | auto give the same bytes
+// (the rule of auto does not change).  Under yes a sequence set, and so a lazy block, holds its letters twice: the letters and as
+// many quality bytes.  A FASTA query under yes is accepted: one line on stderr says that the file has no qualities, QUAL stays '*'.
+// Refused while the options are parsed: yes with an output that is not SAM or BAM, and yes with --sam-bam-seq never (QUAL goes
+// where SEQ goes).
 //
 // What it mirrors from the reference, and what it does not:
 //   * subcommand split and the search command line (src/lambda.cpp:30-118; src/search_options.hpp:143-816): -q, -o (format from
@@ -119,7 +131,7 @@
 //     --search0, --adaptive-seeding, --seed-half-exact), --pre-scoring[-threshold], the scoring options (-s 45|62|80 for
 //     proteins, --score-match/-mismatch for nucleotides, --score-gap, --score-gap-open), the profiles (-p fast | sensitive |
 //     pairs-default | pairs-sensitive: they overwrite the seeding options, :634-681), the output options (--output-columns,
-//     --sam-bam-tags/-seq/-clip, --sam-with-refheader, --version-to-outputfile), -g, --input-alphabet;
+//     --sam-bam-tags/-seq/-clip (and this front end's --sam-bam-qual), --sam-with-refheader, --version-to-outputfile), -g, --input-alphabet;
 //   * the thread split of realMain (src/search.cpp:379-385): one worker per entry of --devices (default: all visible devices), each
 //     with its own handle -- one LocalDataHolder per thread there, one lx_handle = device + stream here --, the queries dealt to
 //     them in contiguous ranges, the records concatenated in range order before _writeRecord; -t host threads (default: what
@@ -299,6 +311,9 @@ void sideBySide(bool withQuery, bool secondThread, Q && queryHalf, D && dbHalf)
         throw std::runtime_error(error);
 }
 
+// --sam-bam-qual yes and a query file without qualities: said once
+char const * const kNoQualNote = "--sam-bam-qual yes: the query file has no qualities (FASTA); QUAL is written as '*'\n";
+
 // the two phases of loading: the files' bytes, decompressed (a handle each), then -- once the bytes have settled the alphabets, the
 // second half of `run` -- their records into sequence sets.  --lazy-query leaves the query file a stream; -i has read the subjects.
 Inputs loadInputs(Options const & opt, Run & run)
@@ -312,7 +327,7 @@ Inputs loadInputs(Options const & opt, Run & run)
         refuseOtherDomain(run, in.ifo);
     }
     if (run.lazy)
-        in.qStream.reset(new QueryStream(opt.query, run.gunzipDevice));
+        in.qStream.reset(new QueryStream(opt.query, run.gunzipDevice, opt.samQual));
     bool const eagerQuery = !run.mk && !run.lazy, secondThread = opt.threads != 1;
     InputText  qIn, dIn;
     sideBySide(
@@ -342,7 +357,7 @@ Inputs loadInputs(Options const & opt, Run & run)
     run.program = run.blastx ? (run.sTrans ? "tblastx" : "blastx") : run.sTrans ? "tblastn" : prot ? "blastp" : "blastn";
 
     sideBySide(
-        eagerQuery, secondThread, [&]() { readFasta(qIn.text, opt.query, prot, !prot, in.qs, run.blastx, run.geneticCodeQry, bs ? 2 : 0); },
+        eagerQuery, secondThread, [&]() { readFasta(qIn.text, opt.query, prot, !prot, in.qs, run.blastx, run.geneticCodeQry, bs ? 2 : 0, opt.samQual); },
         [&]()
         {
             if (fromIndex)
@@ -355,6 +370,8 @@ Inputs loadInputs(Options const & opt, Run & run)
         });
     if ((eagerQuery && in.qs.ids.empty()) || in.db.ids.empty())
         throw std::runtime_error("empty query or database file");
+    if (eagerQuery && opt.samQual && !qualOf(in.qs))
+        std::cerr << kNoQualNote;
     if (fromIndex && in.db.off.size() != in.db.ids.size() * (size_t)run.sFrames)
         throw std::runtime_error("index file " + opt.db + ": the frames of its sequences do not fit its alphabets");
     if (run.mk && opt.truncateIds) // src/mkindex_algo.hpp:123
@@ -1308,9 +1325,10 @@ private:
 };
 
 // the reader's thread: a place, then a block of the stream's next records; its error lets the blocks made so far go through
-void readBlocks(Run const & run, QueryStream & stream, BlockPipeline & pipe)
+void readBlocks(Run const & run, bool keepQual, QueryStream & stream, BlockPipeline & pipe)
 {
     bool holding = false; // a place taken for a block that is not in the queue yet
+    bool noted   = false; // kNoQualNote has been printed
     try
     {
         lx_query_blocks::BlockCutter cut(run.blockReads);
@@ -1322,11 +1340,16 @@ void readBlocks(Run const & run, QueryStream & stream, BlockPipeline & pipe)
                 [&](std::string const & id, std::string & letters)
                 {
                     uint64_t const n = letters.size();
-                    addRecord(b->qs, id, letters, run.prot, !run.prot, run.blastx, run.geneticCodeQry, run.bs ? 2 : 0);
+                    addRecord(b->qs, id, letters, run.prot, !run.prot, run.blastx, run.geneticCodeQry, run.bs ? 2 : 0, keepQual ? &stream.quality() : nullptr);
                     return !cut.add(n);
                 });
             if (b->qs.ids.empty()) // (the file ended where the last block closed)
                 break;
+            if (keepQual && !noted && !b->qs.ascii.empty() && !qualOf(b->qs))
+            {
+                std::cerr << kNoQualNote;
+                noted = true;
+            }
             b->red = reduce(b->qs, run.red);
             pipe.publish(std::move(b));
             holding = false;
@@ -1405,7 +1428,7 @@ LazyTotals runLazy(SearchContext const & c, QueryStream & stream, OutputSetup co
         BlockPipeline & p;
         ~HaltOnExit() { p.halt(); }
     } const haltOnExit{pipe};
-    reader = std::thread(readBlocks, std::cref(run), std::ref(stream), std::ref(pipe));
+    reader = std::thread(readBlocks, std::cref(run), opt.samQual, std::ref(stream), std::ref(pipe));
     for (size_t w = 0; w < parts.size(); ++w)
         pool.emplace_back(searchBlocks, w, std::cref(c), std::cref(output), std::ref(pipe), std::ref(parts[w]));
 
@@ -1436,9 +1459,9 @@ LazyTotals runLazy(SearchContext const & c, QueryStream & stream, OutputSetup co
         }
         std::vector<char const *> const qidB = cstrs(b->qs.ids);
         lx_seq_names const              nm{qidB.data(), b->qs.orig_len.data(), nullptr, nullptr, qidB.size(), 0};
-        if (lx_out_append(out.get(), dev ? LX_RENDER_DEV : LX_RENDER_HOST, b->bms.data(), b->kept, b->ops.data(), b->ops.size(), &nm,
-                          reinterpret_cast<uint8_t const *>(b->qs.ascii.data()), b->qs.ascii_off.data(), b->lcaQid.data(), b->lcaTax.data(),
-                          b->nLca) != LX_OK)
+        if (lx_out_append_ex(out.get(), dev ? LX_RENDER_DEV : LX_RENDER_HOST, b->bms.data(), b->kept, b->ops.data(), b->ops.size(), &nm,
+                             reinterpret_cast<uint8_t const *>(b->qs.ascii.data()), b->qs.ascii_off.data(), opt.samQual ? qualOf(b->qs) : nullptr,
+                             b->lcaQid.data(), b->lcaTax.data(), b->nLca) != LX_OK)
             throw std::runtime_error((dev ? "records on the GPU: " : "") + outputError(zh, opt.output));
         float msK = 0;
         if (dev && b->kept && lx_last_phase_ms(zh, fmt == LX_OUT_BAM ? 11 : 12, &msK, nullptr) == LX_OK)
@@ -1595,6 +1618,7 @@ RenderTimes writeEager(Options const & opt, Run const & run, int device, OutputS
     std::vector<char const *> const qid = cstrs(in.qs.ids), sid = cstrs(in.db.ids);
     lx_seq_names const names{qid.data(), in.qs.orig_len.data(), sid.data(), in.db.orig_len.data(), qid.size(), sid.size()};
     lx_output_options     oo = output.options;
+    oo.q_qual                = opt.samQual ? qualOf(in.qs) : nullptr; // (--sam-bam-qual yes: every eager writer reads it from the options)
     std::vector<uint64_t> lcaQid;
     std::vector<uint32_t> lcaTax;
     RenderTimes           times;

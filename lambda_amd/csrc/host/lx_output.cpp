@@ -335,9 +335,10 @@ int reg2bin(int64_t beg, int64_t end)
     return 0;
 }
 
-// one BAM alignment record from the fields the SAM line carries (MAPQ 255, no mate, QUAL absent = 0xFF per base)
+// one BAM alignment record from the fields the SAM line carries (MAPQ 255, no mate; QUAL: the Phred+33 string's bytes - 33, taken
+// modulo 256, or none = 0xFF per base)
 void bamRecord(std::string & o, int32_t refId, int64_t pos0, std::string const & qname, int flag, std::string const & cigar,
-               std::string const & seq, std::string const & tags)
+               std::string const & seq, std::string const * qual, std::string const & tags)
 {
     std::vector<uint32_t> ops;
     int64_t               span = 0;
@@ -388,7 +389,11 @@ void bamRecord(std::string & o, int32_t refId, int64_t pos0, std::string const &
         };
         o.push_back((char)(code(i) << 4 | code(i + 1)));
     }
-    o.append(lseq, (char)0xff);
+    if (qual && qual->size() == lseq) // (nullptr: none; the caller cuts it as it cuts SEQ)
+        for (char c : *qual)
+            o.push_back((char)(uint8_t)((uint8_t)c - 33));
+    else
+        o.append(lseq, (char)0xff);
     o += tags;
     uint32_t const bs = (uint32_t)(o.size() - at - 4);
     for (int i = 0; i < 4; ++i)
@@ -1018,6 +1023,10 @@ static int renderRecords(Sink * f, int format, int write_header, char const * pr
                 if (opt.sam_seq == LX_SAM_SEQ_UNIQ)
                     writeSeq = (k == lo) || b.q_frame != m[k - 1].q_frame || b.q_start != m[k - 1].q_start || b.q_end != m[k - 1].q_end;
                 uint64_t const qLen = names->q_lens[b.n_qid];
+                // QUAL (opt.q_qual): cut and turned exactly as SEQ is -- the same window, reversed (not complemented) on the minus
+                // strand -- and absent wherever SEQ is
+                bool        haveQual = false;
+                std::string qual;
                 if (isN && writeSeq && q_res_ascii && q_ascii_off)
                 {
                     // the aligned sequence is the frame's (the reverse complement on the minus strand); hard clips keep only the
@@ -1025,8 +1034,18 @@ static int renderRecords(Sink * f, int format, int write_header, char const * pr
                     seq.assign(reinterpret_cast<char const *>(q_res_ascii) + q_ascii_off[b.n_qid], qLen);
                     if (b.q_frame < 0)
                         reverseComplementAscii(seq);
+                    bool const cut = b.q_end <= qLen && b.q_start <= b.q_end;
                     if (hard)
-                        seq = b.q_end <= qLen && b.q_start <= b.q_end ? seq.substr(b.q_start, b.q_end - b.q_start) : std::string("*");
+                        seq = cut ? seq.substr(b.q_start, b.q_end - b.q_start) : std::string("*");
+                    if (opt.q_qual && (!hard || cut))
+                    {
+                        haveQual = true;
+                        qual.assign(reinterpret_cast<char const *>(opt.q_qual) + q_ascii_off[b.n_qid], qLen);
+                        if (b.q_frame < 0)
+                            std::reverse(qual.begin(), qual.end());
+                        if (hard)
+                            qual = qual.substr(b.q_start, b.q_end - b.q_start);
+                    }
                 }
                 else if (qTrans && writeSeq && q_res_ascii && q_ascii_off && b.q_frame != 0)
                 {
@@ -1045,9 +1064,19 @@ static int renderRecords(Sink * f, int format, int write_header, char const * pr
                         seq.assign(src + (qLen - (3 * e + fc)), 3 * (e - a));
                         reverseComplementAscii(seq);
                     }
+                    if (opt.q_qual && !(e > L || a > e))
+                    {
+                        haveQual = true;
+                        char const * const qsrc = reinterpret_cast<char const *>(opt.q_qual) + q_ascii_off[b.n_qid];
+                        qual.assign(qsrc + (b.q_frame > 0 ? 3 * a + fc : qLen - (3 * e + fc)), 3 * (e - a));
+                        if (b.q_frame < 0)
+                            std::reverse(qual.begin(), qual.end());
+                    }
                 } // BLASTP / TBLASTN: the query is protein -- no SEQ (:599)
                 if (seq.empty())
                     seq = "*";
+                if (seq == "*") // (also the one-letter sequence that reads "*": bamRecord takes it for the absent one)
+                    haveQual = false;
                 // POS: a translated subject is reported in nucleotide space (:493-499; the minus-strand branch there
                 // subtracts from the QUERY length -- restated as it stands)
                 uint64_t pos = b.s_start;
@@ -1058,8 +1087,8 @@ static int renderRecords(Sink * f, int format, int write_header, char const * pr
                         pos = qLen - pos;
                 }
                 if (!bam)
-                    f->print("%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t*", qn.c_str(), flag, sn.c_str(), (unsigned long long)(pos + 1),
-                             cigar.c_str(), seq.c_str());
+                    f->print("%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t%s", qn.c_str(), flag, sn.c_str(), (unsigned long long)(pos + 1),
+                             cigar.c_str(), seq.c_str(), haveQual ? qual.c_str() : "*");
                 // tags in the order myWriteRecord appends them (:601-719), with the widths it casts to; in BAM with the types it
                 // passes (f, S, C, c, I, Z)
                 tagBytes.clear();
@@ -1138,7 +1167,7 @@ static int renderRecords(Sink * f, int format, int write_header, char const * pr
                 if (bam)
                 {
                     rec.clear();
-                    bamRecord(rec, (int32_t)b.n_sid, (int64_t)pos, qn, flag, cigar, seq, tagBytes);
+                    bamRecord(rec, (int32_t)b.n_sid, (int64_t)pos, qn, flag, cigar, seq, haveQual ? &qual : nullptr, tagBytes);
                     f->write(rec.data(), rec.size());
                 }
                 else

@@ -8,11 +8,17 @@
 //     adds its non-blank characters to the record; lines in front of the first ">" are ignored;
 //   * FASTQ: empty lines between records are skipped; the "@" line, sequence lines up to a line starting with "+", then quality
 //     lines until there are as many quality characters as letters -- so a quality line may begin with "@", "+" or ">" --; the
-//     qualities are dropped, as the reference drops them (src/search_algo.hpp:342).
-// What is carried from piece to piece: the unfinished line, the unfinished record, and FASTQ's count of quality characters.
+//     qualities are only counted and dropped, as the reference drops them (src/search_algo.hpp:342), unless the parser was told to
+//     keep them (keepQualities): then the record's quality string is the bytes of its quality lines as they stand (the "\r" before
+//     "\n" dropped as for every line), it is there (quality()) while f runs, and a byte outside '!' .. '~' is refused with the file's
+//     path, the record's id and the byte.  The count rule is the same either way, and so are the records and the other error texts.
+//     A FASTA text has no qualities: quality() is empty.
+// What is carried from piece to piece: the unfinished line, the unfinished record, FASTQ's count of quality characters and, when
+// they are kept, the characters.
 #pragma once
 #include <cctype>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -24,6 +30,12 @@ class RecordParser
 {
 public:
     explicit RecordParser(std::string path) : path_(std::move(path)) {}
+
+    // keep the FASTQ records' qualities (before the first feed)
+    void keepQualities(bool keep) { keepQual_ = keep; }
+    // while f runs: the record's quality string, as long as its letters -- empty when they are not kept, and for a FASTA record.  f may
+    // take it away, like the letters
+    std::string & quality() { return qual_; }
 
     // the next piece of the text.  f(id, letters) per finished record (it may take `letters` away); false once f returned false:
     // the parser has stopped and takes nothing more.  Throws std::runtime_error for a malformed FASTQ record.
@@ -113,6 +125,18 @@ private:
         throw std::runtime_error(path_ + ": FASTQ record '" + id_ + "' has " + std::to_string(quals_) + " quality characters for " +
                                  std::to_string(cur_.size()) + " letters");
     }
+    // a quality line joins the record's string (only when the qualities are kept)
+    void appendQuality(char const * a, size_t len)
+    {
+        for (size_t i = 0; i < len; ++i)
+            if (a[i] < '!' || a[i] > '~')
+            {
+                char hex[8];
+                std::snprintf(hex, sizeof(hex), "0x%02x", (unsigned)(unsigned char)a[i]);
+                throw std::runtime_error(path_ + ": FASTQ record '" + id_ + "' has the byte " + hex + " among its qualities (they are '!' .. '~')");
+            }
+        qual_.append(a, len);
+    }
     void append(char const * a, size_t len)
     {
         for (size_t i = 0; i < len; ++i)
@@ -166,10 +190,13 @@ private:
                 return true;
             }
             quals_ = 0;
+            qual_.clear();
             state_ = Quality;
             break;
         case Quality:
             quals_ += len;
+            if (keepQual_)
+                appendQuality(a, len);
             break;
         }
         if (quals_ < cur_.size())
@@ -180,8 +207,8 @@ private:
         return f(id_, cur_);
     }
 
-    std::string path_, carry_, line_, id_, cur_;
-    bool        detected_ = false, fastq_ = false, have_ = false, stopped_ = false;
+    std::string path_, carry_, line_, id_, cur_, qual_;
+    bool        detected_ = false, fastq_ = false, have_ = false, stopped_ = false, keepQual_ = false;
     char        blankLine_ = 0; // the first character of the first non-empty line seen before the format was known
     State       state_ = Header;
     size_t      quals_ = 0;

@@ -42,6 +42,9 @@ struct BamCtx
     uint8_t const *        q_ascii; // the queries' letters, q_ascii_bytes of them (reads beyond are answered with 'N', never made)
     uint64_t               q_ascii_bytes;
     uint64_t const *       q_ascii_off;
+    uint8_t const *        q_qual; // the queries' base qualities, parallel to q_ascii, q_qual_bytes of them (NULL: none; reads beyond are
+                                   // answered with '!', never made)
+    uint64_t               q_qual_bytes;
     uint64_t const *       q_lens;
     uint8_t const *        qn_blob; // first words of the query ids, qn_off[q] .. qn_off[q + 1]
     uint64_t const *       qn_off;

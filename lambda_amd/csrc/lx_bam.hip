@@ -20,7 +20,7 @@
 //
 // Bounds: a record's bytes lie in [off, off + size) of its range by construction (emit lays out with the function measure sized with,
 // and takes the two walked counts from measure); ops reads stay inside the host-checked [ops_off, ops_off + n_ops); reads of the
-// queries' letters beyond the uploaded extent are answered with 'N' and never made.
+// queries' letters beyond the uploaded extent are answered with 'N' and never made, those of their qualities with '!'.
 //
 // What the text writer (lx_text.hip) needs as well -- rec_of, the op walks, reverse complement, the frame's codon, the scan functors --
 // is in lx_recdev.h.
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
         walk_cigar(c, r, o, b.n_ops, put);
     }
     w.p += 4 * (uint64_t)a.n_cigar;
-    // SEQ: two letters a byte, the odd last nibble 0; QUAL: absent
+    // SEQ: two letters a byte, the odd last nibble 0; QUAL: the qualities - 33 over SEQ's letters, or absent (0xFF)
     uint64_t const seq_bytes = (r.l_seq + 1) / 2;
     for (uint64_t i = lane; i < seq_bytes; i += 64)
     {
@@ -252,8 +252,12 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
         w.p[i] = (uint8_t)v;
     }
     w.p += seq_bytes;
-    for (uint64_t i = lane; i < r.l_seq; i += 64)
-        w.p[i] = 0xff;
+    if (c.q_qual)
+        for (uint64_t i = lane; i < r.l_seq; i += 64)
+            w.p[i] = (uint8_t)(qual_letter(c, r, i) - 33);
+    else
+        for (uint64_t i = lane; i < r.l_seq; i += 64)
+            w.p[i] = 0xff;
     w.p += r.l_seq;
     // the optional fields, in myWriteRecord's order
     uint32_t const t = c.tags;

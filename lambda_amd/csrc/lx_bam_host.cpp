@@ -1,7 +1,7 @@
 // lx_bam_host.cpp -- the host side of the BAM record kernels (lx_bam.hip): lx_render_bam_dev, lx_write_bam_dev.
 //
 // A call checks its arguments first (renderRecords' refusals, through lxi::bam_check, and the extent of the ops), flattens what the
-// kernels read -- rows, ops, the queries' letters and lengths, the first words of their ids, the taxonomy lists, one LCA (and name) per
+// kernels read -- rows, ops, the queries' letters, qualities (opt->q_qual) and lengths, the first words of their ids, the taxonomy lists, one LCA (and name) per
 // query group from lcaOf's own forward cursor, the genetic code over the 125 DNA5 triplets -- and uploads it.  The groups and measure
 // kernels run over the whole list; the host reads the 64-bit size totals of the tiles and cuts the list into RANGES of whole tiles
 // whose bytes stay within LX_OPT_BAM_RANGE_BYTES (a tile that alone exceeds it is a range of its own).  Per range: scan + emit into the
@@ -208,6 +208,13 @@ int rec_inputs(lx_handle * h, char const * who, int phase, uint32_t tags, bool w
     if (ascii && ((rc = rec_upload(h, B.d_ascii, q_res_ascii, extent, c.q_ascii)) || (rc = rec_upload(h, B.d_ascii_off, q_ascii_off, n_q, c.q_ascii_off))))
         return rc;
     c.q_ascii_bytes = ascii ? extent : 0;
+    // the qualities go up only where a record can carry them: a SAM or BAM writer (the ones that read the ops), a DNA query, SEQ written
+    if (ascii && opt.q_qual && with_ops && (c.is_n || c.q_trans) && opt.sam_seq != LX_SAM_SEQ_NEVER)
+    {
+        if ((rc = rec_upload(h, B.d_qual, opt.q_qual, extent, c.q_qual)))
+            return rc;
+        c.q_qual_bytes = extent;
+    }
     if ((tags & lx::kBamTagSt) && opt.tax && opt.tax->s_tax_off && (opt.tax->s_tax_ids || opt.tax->s_tax_off[opt.tax->n_s] == 0))
     {
         c.tax_n_s = opt.tax->n_s;

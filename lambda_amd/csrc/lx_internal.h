@@ -221,7 +221,7 @@ struct lx_handle
     // record, a range's stream (the carried part of a BGZF block in front), the tile totals on their way up
     struct Bam
     {
-        DevBuf d_rows, d_ops, d_ascii, d_ascii_off, d_qlens, d_qn_blob, d_qn_off, d_tax_off, d_tax_ids, d_grp_tab, d_name_blob, d_codon;
+        DevBuf d_rows, d_ops, d_ascii, d_qual, d_ascii_off, d_qlens, d_qn_blob, d_qn_off, d_tax_off, d_tax_ids, d_grp_tab, d_name_blob, d_codon;
         DevBuf d_grp, d_grp_first, d_aux, d_size, d_off, d_scan, d_tiles, d_stream;
         Pinned p_tiles;
     } bam;

@@ -5,8 +5,8 @@
 // open renders the header (lx_render_records, no records) and, for a compressed file, sends its whole blocks through the encoder.
 // append renders the piece's records without header and footer: on the host by lx_render_records, on the device by the kernels of
 // lx_render_text_dev / lx_render_bam_dev.  A piece holds whole query groups, and everything the records of a group depend on (the
-// comment lines of .m9, FLAG, IH, --sam-bam-seq uniq, the group's LCA) is decided inside the group, so nothing crosses a piece but
-// the BGZF carry: a compressed stream is cut into 65 280-byte blocks counted from its first byte, as lx_bgzf_compress cuts the whole
+// comment lines of .m9, FLAG, IH, --sam-bam-seq uniq, the group's LCA; QUAL from the piece's own qualities, lx_out_append_ex) is
+// decided inside the group, so nothing crosses a piece but the BGZF carry: a compressed stream is cut into 65 280-byte blocks counted from its first byte, as lx_bgzf_compress cuts the whole
 // stream, and the bytes that do not fill a block wait in front of the next piece -- in host memory behind a host append, on the
 // device (d_carry) behind a device append (lxi::text_append_dev, lxi::bam_append_dev: the records are compressed where they stand
 // and only members come down); a change of side moves less than a block.  close puts the .m9 footer behind the carry, compresses
@@ -173,6 +173,7 @@ int lx_out_open(lx_handle * h, char const * path, int format, int bgzf, char con
         o->opt.lca_qid = nullptr;
         o->opt.lca_tax = nullptr;
         o->opt.n_lca   = 0;
+        o->opt.q_qual  = nullptr; // (a piece's own: lx_out_append_ex)
         // the header; with it the refusals of the one-shot writers that need no record, before the file is touched
         lx_bytes * header = nullptr;
         int rc = lx_render_records(format, 1, program, nullptr, 0, nullptr, &o->subjects, nullptr, nullptr, &o->opt, -1, &header);
@@ -202,6 +203,14 @@ int lx_out_open(lx_handle * h, char const * path, int format, int bgzf, char con
 int lx_out_append(lx_out * o, int where, lx_blast_match const * m, uint64_t n, uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names,
                   uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, uint64_t const * lca_qid, uint32_t const * lca_tax, uint64_t n_lca)
 {
+    return lx_out_append_ex(o, where, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, nullptr, lca_qid, lca_tax, n_lca);
+}
+
+// (the refusals keep lx_out_append's name: it is the call with a NULL q_qual)
+int lx_out_append_ex(lx_out * o, int where, lx_blast_match const * m, uint64_t n, uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names,
+                     uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, uint8_t const * q_qual, uint64_t const * lca_qid,
+                     uint32_t const * lca_tax, uint64_t n_lca)
+{
     if (!o)
     {
         set_output_error("lx_out_append: NULL argument");
@@ -225,6 +234,7 @@ int lx_out_append(lx_out * o, int where, lx_blast_match const * m, uint64_t n, u
     opt.lca_qid            = lca_qid;
     opt.lca_tax            = lca_tax;
     opt.n_lca              = n_lca;
+    opt.q_qual             = q_qual;
     char const * const program = o->program.c_str();
     bool io_failed = false; // (told apart from a refusal by what happened, not by the code it shares with one)
     auto sink      = [&](uint8_t const * members, uint64_t bytes) -> int

@@ -48,7 +48,7 @@ int rec_upload(lx_handle * h, DevBuf & b, T const * src, uint64_t count, T const
 // The refusals beyond the writer's own (the extent of the ops, the kernels' counters), job.c filled from the arguments, everything
 // the kernels of both writers read flattened and uploaded into h->bam, the per-record arrays sized, the groups made (device time to
 // `phase`).  `tags`: the kBamTag* bits whose inputs are wanted (St: the subjects' taxa, Lt / Ls: the groups' LCA and its name, Qs: the
-// genetic code).  with_ops false: the writer does not read the ops (the tabular formats, like the host writer's), so their extent is
+// genetic code).  opt_in->q_qual goes up only for a writer with ops (SAM, BAM), a DNA query and a sam_seq other than never.  with_ops false: the writer does not read the ops (the tabular formats, like the host writer's), so their extent is
 // not checked and they are not uploaded.  n == 0: only the refusals and the flags of job.c.
 int rec_inputs(lx_handle * h, char const * who, int phase, uint32_t tags, bool with_ops, char const * program, lx_blast_match const * m, uint64_t n,
                uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,

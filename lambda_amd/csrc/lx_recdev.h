@@ -1,6 +1,6 @@
 // lx_recdev.h -- the device functions both record writers need (lx_bam.hip: BAM, lx_text.hip: .m8 / .m9 / .sam): what one record is
 // made of besides its ops (rec_of: the clips of cigarOf, --sam-bam-seq, SEQ, tag qs, POS, the taxonomy of its group), the walk over
-// the runs of its ops, the elements of the DNA CIGAR and of tag OC in the host writer's order, reverse complement, the codon of a
+// the runs of its ops, QUAL's character beside SEQ's letter, the elements of the DNA CIGAR and of tag OC in the host writer's order, reverse complement, the codon of a
 // translated query's frame, decimal digits, the functors of the group and size scans.  Restated from host/lx_output.cpp, which is the
 // specification.  Included inside `namespace lx { namespace { ... } }` of a .hip file, after lx_bam.h and lx_scan.h.
 #pragma once
@@ -65,6 +65,11 @@ __device__ __forceinline__ bool is_op(uint8_t o)
 __device__ __forceinline__ uint8_t letter(BamCtx const & c, uint64_t at)
 {
     return at < c.q_ascii_bytes ? c.q_ascii[at] : (uint8_t)'N';
+}
+
+__device__ __forceinline__ uint8_t quality(BamCtx const & c, uint64_t at)
+{
+    return at < c.q_qual_bytes ? c.q_qual[at] : (uint8_t)'!';
 }
 
 // what one record is made of besides its ops: the same values for measure and emit
@@ -319,6 +324,13 @@ __device__ __forceinline__ void walk_oc(BamCtx const & c, Rec const & r, uint8_t
 __device__ __forceinline__ uint8_t seq_letter(BamCtx const & c, Rec const & r, uint64_t i)
 {
     return r.minus ? rc_letter(letter(c, r.seq_at - 1 - i)) : letter(c, r.seq_at + i);
+}
+
+// character i of QUAL (i < r.l_seq, c.q_qual given): the quality of the read position seq_letter(c, r, i) comes from -- reversed on the
+// minus strand, not complemented
+__device__ __forceinline__ uint8_t qual_letter(BamCtx const & c, Rec const & r, uint64_t i)
+{
+    return quality(c, r.minus ? r.seq_at - 1 - i : r.seq_at + i);
 }
 
 // letter i of tag qs (i < r.qs_len): the query's own, or lx_translate_six_frames' codon of the frame's letter r.qs_a + i

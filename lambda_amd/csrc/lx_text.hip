@@ -13,7 +13,7 @@
 //            totals per kBamTile records for the host's range cuts.
 //   emit     per range: an exclusive scan of the sizes (uint32), then one wavefront per record runs THE SAME layout function over
 //            a writer that stages the line in kTextStage bytes of LDS: lane 0 puts the digits and separators, the strings (ids,
-//            SEQ, qs, number texts) are put by all lanes, and whenever the stage is full, and at the end, the 64 lanes store it to
+//            SEQ, QUAL, qs, number texts) are put by all lanes, and whenever the stage is full, and at the end, the 64 lanes store it to
 //            global memory, 64 consecutive bytes an instruction.  Every value of the layout is the same in all lanes of the
 //            wavefront (it depends on the record alone), so the control flow is uniform.
 //
@@ -21,7 +21,7 @@
 //
 // Bounds: a record's bytes lie in [off, off + size) of its range by construction (one layout function for measure and emit, the
 // validity of the ops taken from measure), and the stage's stores are clamped to the record's size besides; ops reads stay inside
-// the host-checked [ops_off, ops_off + n_ops); reads of the queries' letters beyond the uploaded extent are answered with 'N' and
+// the host-checked [ops_off, ops_off + n_ops); reads of the queries' letters beyond the uploaded extent are answered with 'N' (of their qualities: '!') and
 // never made; a number text has at most 19 characters (lx_numfmt.h: an F value below 10^15 with its sign), its slot 20.
 #include <hip/hip_runtime.h>
 
@@ -343,7 +343,12 @@ __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const 
         w.str(r.l_seq, [&](uint64_t i) { return seq_letter(c, r, i); });
     else
         w.ch('*');
-    put_lit(w, "\t*", 2);
+    // QUAL: where SEQ is, over the same letters
+    w.ch('\t');
+    if (c.q_qual && r.l_seq)
+        w.str(r.l_seq, [&](uint64_t i) { return qual_letter(c, r, i); });
+    else
+        w.ch('*');
     uint32_t const t = c.tags;
     if (t & kBamTagAe)
     {

@@ -8,6 +8,10 @@ render kernels (lx_last_phase_ms phase 11) and of the encoder (phase 4), and the
 uploads (host path: the rendered stream; device path: rows, ops, query letters, lengths, offsets and id words), down = the members.
 
     python tools/bam_render_bench.py > profiles/bam_render_bench.txt
+
+--qual gives every query base qualities (lx_output_options::q_qual; both paths then write them, and they count among the bytes up).
+--programs / --tags pick among the lists.  --dev-only times the device path alone and needs nothing a library from before --qual
+lacks, so that two builds can be compared on the same lists (LX_LIB_PATH=... python tools/bam_render_bench.py --dev-only --label parent).
 """
 from __future__ import annotations
 
@@ -42,25 +46,41 @@ def records(program: str, total: int):
     return big[:total].copy(), ops * reps, names, qa * reps, off
 
 
+def qualities(n: int) -> bytes:
+    """n Phred+33 characters, neighbours different."""
+    i = np.arange(n, dtype=np.int64)
+    return (33 + (7 * i + i // 94) % 94).astype(np.uint8).tobytes()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="*", default=[100_000, 1_000_000])
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--qual", action="store_true", help="write base qualities (q_qual)")
+    ap.add_argument("--programs", nargs="*", default=["blastn", "blastx"])
+    ap.add_argument("--tags", nargs="*", default=["default", "all"])
+    ap.add_argument("--dev-only", action="store_true", help="time lx_write_bam_dev alone")
+    ap.add_argument("--label", default="", help="copied into every line")
     a = ap.parse_args()
     lib = capi.load()
     tmp = Path(tempfile.mkdtemp(prefix="bam_render_bench_"))
     with capi.Handle(0) as h:
-        for program in ("blastn", "blastx"):
+        for program in a.programs:
             for rows in a.rows:
                 m, ops, names, qa, qoff = records(program, rows)
-                for tags in ("default", "all"):
+                qq = qualities(len(qa)) if a.qual else None
+                for tags in a.tags:
                     if tags == "all":
                         opt, keep = _options(program, ALL_TAGS, capi.LX_SAM_SEQ_UNIQ, 1, True, m, 200)
                     else:
                         opt, keep = capi.output_options(), None
-                    args, held = capi._writer_args(m, ops, names["q_ids"], names["q_lens"], names["s_ids"], names["s_lens"], qa, qoff, opt)
+                    if qq is not None:
+                        args, held = capi._writer_args(m, ops, names["q_ids"], names["q_lens"], names["s_ids"], names["s_lens"], qa, qoff, opt, qq)
+                    else:
+                        args, held = capi._writer_args(m, ops, names["q_ids"], names["q_lens"], names["s_ids"], names["s_lens"], qa, qoff, opt)
                     prog = program.encode()
                     p_host, p_dev = tmp / "host.bam", tmp / "dev.bam"
+                    ms = lambda xs, k: [round(x[k] * 1e3, 1) for x in xs]  # noqa: E731
 
                     def host_path():
                         t0 = time.perf_counter()
@@ -87,13 +107,21 @@ def main():
                         assert rc == capi.LX_OK, lib.lx_last_error(h.h)
                         return dict(total=t1 - t0, render_kernels_ms=h.last_phase_ms(11)[0], bgzf_kernels_ms=h.last_phase_ms(4)[0])
 
+                    if a.dev_only:
+                        dev_path()  # (buffers, code objects, pages)
+                        ds = [dev_path() for _ in range(a.reps)]
+                        print(json.dumps({"label": a.label, "program": program, "rows": rows, "tags": tags, "qual": a.qual, "bam_bytes": p_dev.stat().st_size,
+                                          "dev_path_ms": ms(ds, "total"), "dev_path_median_ms": round(statistics.median(ms(ds, "total")), 1),
+                                          "dev_render_kernels_ms": [round(x["render_kernels_ms"], 2) for x in ds],
+                                          "dev_bgzf_kernels_ms": [round(x["bgzf_kernels_ms"], 2) for x in ds]}), flush=True)
+                        del held, keep
+                        continue
                     host_path(), dev_path()  # (buffers, code objects, pages)
                     same = p_host.read_bytes() == p_dev.read_bytes()
                     hs = [host_path() for _ in range(a.reps)]
                     ds = [dev_path() for _ in range(a.reps)]
-                    ms = lambda xs, k: [round(x[k] * 1e3, 1) for x in xs]  # noqa: E731
-                    up_dev = (m.nbytes + len(ops) + len(qa) + 24 * len(names["q_ids"]) + sum(len(x.split()[0]) for x in names["q_ids"]))
-                    line = {"program": program, "rows": rows, "tags": tags, "files_identical": same, "stream_bytes": hs[0]["stream"],
+                    up_dev = (m.nbytes + len(ops) + len(qa) * (2 if a.qual else 1) + 24 * len(names["q_ids"]) + sum(len(x.split()[0]) for x in names["q_ids"]))
+                    line = {"program": program, "rows": rows, "tags": tags, "qual": a.qual, "files_identical": same, "stream_bytes": hs[0]["stream"],
                             "bam_bytes": hs[0]["members"],
                             "host_path_ms": ms(hs, "total"), "host_path_median_ms": round(statistics.median(ms(hs, "total")), 1),
                             "host_render_ms": ms(hs, "render"), "host_compress_ms": ms(hs, "compress"), "host_write_ms": ms(hs, "write"),
