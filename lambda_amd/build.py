@@ -20,7 +20,7 @@ LIB = CSRC / "liblambda_ext.so"
 ORACLE_DIR = ROOT / "oracle"
 ORACLE_LIB = ORACLE_DIR / "_build" / "liblx_oracle.so"
 
-HIP_SOURCES = ["lx_score.hip", "lx_score_f16.hip", "lx_score_i16.hip", "lx_sweep_mq.hip", "lx_trace.hip", "lx_ckpt.hip", "lx_select.hip", "lx_pack.hip", "lx_prefilter.hip", "lx_level2.hip", "lx_plan_free.hip", "lx_records.hip", "lx_toprec.hip", "lx_bgzf.hip", "lx_bgzf_host.cpp", "lx_bam.hip", "lx_bam_host.cpp", "lx_text.hip", "lx_text_host.cpp", "lx_out_host.cpp", "lx_gunzip.hip", "lx_pgunzip.hip", "lx_gunzip_host.cpp", "lx_taxmap.hip", "lx_taxmap_host.cpp", "lx_lca.hip", "lx_lca_host.cpp", "lx_taxfilter.hip", "lx_taxfilter_host.cpp", "lx_seed.hip", "lx_seed_host.cpp", "lx_qmask.hip", "lx_dust.hip", "lx_qmask_host.cpp", "lx_level2_host.cpp", "lx_level2_records.cpp", "lx_level2_reserve.cpp", "lx_api.cpp", "lx_handle.cpp", "lx_step.cpp", "lx_step_plan.cpp", "lx_host.cpp", "lx_xb_core.cpp", "lx_xb_sinks.cpp", "lx_xb_run.cpp", "lx_xb_wf.cpp", "lx_host_plan.cpp", "lx_host_batch.cpp", "lx_host_pool.cpp", "host/lx_driver.cpp", "host/lx_output.cpp", "host/lx_translate.cpp", "host/lx_taxonomy.cpp"]
+HIP_SOURCES = ["lx_score.hip", "lx_score_f16.hip", "lx_score_i16.hip", "lx_sweep_mq.hip", "lx_trace.hip", "lx_ckpt.hip", "lx_select.hip", "lx_pack.hip", "lx_prefilter.hip", "lx_level2.hip", "lx_plan_free.hip", "lx_records.hip", "lx_toprec.hip", "lx_bgzf.hip", "lx_bgzf_host.cpp", "lx_bam.hip", "lx_rec_host.cpp", "lx_bam_host.cpp", "lx_text.hip", "lx_text_host.cpp", "lx_out_host.cpp", "lx_gunzip.hip", "lx_pgunzip.hip", "lx_gunzip_host.cpp", "lx_taxmap.hip", "lx_taxmap_host.cpp", "lx_lca.hip", "lx_lca_host.cpp", "lx_taxfilter.hip", "lx_taxfilter_host.cpp", "lx_seed.hip", "lx_seed_host.cpp", "lx_qmask.hip", "lx_dust.hip", "lx_qmask_host.cpp", "lx_level2_host.cpp", "lx_level2_records.cpp", "lx_level2_reserve.cpp", "lx_api.cpp", "lx_handle.cpp", "lx_step.cpp", "lx_step_plan.cpp", "lx_host.cpp", "lx_xb_core.cpp", "lx_xb_sinks.cpp", "lx_xb_run.cpp", "lx_xb_wf.cpp", "lx_host_plan.cpp", "lx_host_batch.cpp", "lx_host_pool.cpp", "host/lx_driver.cpp", "host/lx_output.cpp", "host/lx_postprocess.cpp", "host/lx_translate.cpp", "host/lx_taxonomy.cpp"]
 
 
 def _hipcc() -> str:

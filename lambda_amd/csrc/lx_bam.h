@@ -1,6 +1,6 @@
 // lx_bam.h -- what the BAM record kernels (lx_bam.hip) and their host side (lx_bam_host.cpp) share.  Not part of the ABI.
 //
-// The kernels restate the record loop of renderRecords and bamRecord (host/lx_output.cpp) for LX_OUT_BAM: the same bytes.  Three steps
+// The kernels restate samFields and bamRecord (host/lx_output.cpp) for LX_OUT_BAM: the same bytes.  Three steps
 // per call: groups (a head flag per row and a sum scan: the row's group, the groups' first rows), measure (one lane per record: CIGAR
 // elements, the text length of tag OC, the record's bytes; 64-bit totals per kBamTile records, which is all the host reads to cut the
 // ranges), and per range an exclusive scan of the sizes (lx_scan.h, uint32: a range's stream stays below 4 GiB) and emit (one wavefront
@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "../../include/lambda_ext.h"
+#include "lx_vocab.h" // BamCtx::tags: tagBit(kTag*)
 
 namespace lx
 {
@@ -18,13 +19,6 @@ namespace lx
 constexpr int      kBamEmitBlock = 256;  // threads of an emit workgroup: four wavefronts = four records
 constexpr uint32_t kBamEmitRecs  = kBamEmitBlock / 64;
 constexpr uint64_t kBamTile      = 2048; // records per size total and per scan tile (= lx_scan.h's kL2ScanTile)
-
-// bits of BamCtx::tags, in the order of SamBamExtraTags (src/search_output.hpp:29-76) = kSamTags of host/lx_output.cpp
-enum
-{
-    kBamTagAS = 1 << 0, kBamTagOC = 1 << 1, kBamTagNM = 1 << 2, kBamTagIH = 1 << 3, kBamTagAr = 1 << 4, kBamTagAe = 1 << 5, kBamTagAi = 1 << 6,
-    kBamTagAp = 1 << 7, kBamTagQf = 1 << 8, kBamTagQs = 1 << 9, kBamTagSf = 1 << 10, kBamTagSt = 1 << 11, kBamTagLs = 1 << 12, kBamTagLt = 1 << 13
-};
 
 // what measure leaves per record for emit
 struct BamAux
@@ -51,7 +45,7 @@ struct BamCtx
     uint64_t const *       s_tax_off; // tag st (NULL: "*")
     uint32_t const *       s_tax_ids;
     uint64_t               tax_n_s;
-    uint32_t const *       grp_lca; // per group: lcaOf's value, and the name of tag ls (length 0xffffffff: "*")
+    uint32_t const *       grp_lca; // per group: LcaCursor's value, and the name of tag ls (length 0xffffffff: "*")
     uint32_t const *       grp_name_off;
     uint32_t const *       grp_name_len;
     uint8_t const *        name_blob;

@@ -1,5 +1,5 @@
-// lx_bam.hip -- BAM alignment records made on the device (gfx950): the record loop of renderRecords and bamRecord
-// (host/lx_output.cpp; myWriteRecord, /root/reference/src/search_output.hpp:463-733) restated as kernels, byte for byte.  The host
+// lx_bam.hip -- BAM alignment records made on the device (gfx950): samFields and bamRecord
+// (host/lx_output.cpp; myWriteRecord, src/search_output.hpp:463-733) restated as kernels, byte for byte.  The host
 // code is the specification: its quirks are kept (the CIGAR's runs and clips as cigarOf makes them, the truncated n_cigar_op /
 // l_read_name / bin, POS of a translated subject's minus strand taken from the QUERY length, the wrapping casts of the tags).
 //
@@ -72,29 +72,29 @@ __device__ __forceinline__ uint64_t tag_bytes(BamCtx const & c, Rec const & r, u
 {
     uint32_t const t = c.tags;
     uint64_t       s = 0;
-    s += (t & kBamTagAe) ? 7 : 0;
-    s += (t & kBamTagAS) ? 5 : 0;
-    s += (t & kBamTagAr) ? 4 : 0;
-    s += (t & kBamTagAi) ? 4 : 0;
-    s += (t & kBamTagAp) ? 5 : 0;
-    s += (t & kBamTagQf) ? 4 : 0;
-    s += (t & kBamTagSf) ? 4 : 0;
-    if (t & kBamTagSt)
+    s += (t & tagBit(kTagEValue)) ? 7 : 0;
+    s += (t & tagBit(kTagBitScore)) ? 5 : 0;
+    s += (t & tagBit(kTagScore)) ? 4 : 0;
+    s += (t & tagBit(kTagPIdent)) ? 4 : 0;
+    s += (t & tagBit(kTagPPos)) ? 5 : 0;
+    s += (t & tagBit(kTagQFrame)) ? 4 : 0;
+    s += (t & tagBit(kTagSFrame)) ? 4 : 0;
+    if (t & tagBit(kTagSTaxIds))
     {
         uint64_t len = 0;
         for (uint64_t x = r.st_lo; x < r.st_hi; ++x)
             len += dec_digits(c.s_tax_ids[x]) + (x > r.st_lo ? 1 : 0);
         s += 3 + (len ? len : 1) + 1;
     }
-    if (t & kBamTagLs)
+    if (t & tagBit(kTagLcaId))
         s += 3 + (r.name_len == 0xffffffffu ? 1u : r.name_len) + 1;
-    s += (t & kBamTagLt) ? 7 : 0;
-    if (t & kBamTagQs)
+    s += (t & tagBit(kTagLcaTaxId)) ? 7 : 0;
+    if (t & tagBit(kTagProtSeq))
         s += 3 + (r.qs_len ? r.qs_len : 1) + 1;
-    if (t & kBamTagOC)
+    if (t & tagBit(kTagProtCigar))
         s += 3 + (uint64_t)oc_len + 1;
-    s += (t & kBamTagNM) ? 7 : 0;
-    s += (t & kBamTagIH) ? 7 : 0;
+    s += (t & tagBit(kTagEditDistance)) ? 7 : 0;
+    s += (t & tagBit(kTagMatchCount)) ? 7 : 0;
     return s;
 }
 __global__ __launch_bounds__(256) void bam_measure_kernel(BamCtx c, unsigned long long * tile_total)
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void bam_measure_kernel(BamCtx c, unsigned lon
         lx_blast_match const & b = *r.b;
         uint8_t const * const  o = c.ops + b.ops_off;
         uint32_t               runs = 0, oc = 0;
-        bool const             need_oc = (c.tags & kBamTagOC) && !c.is_n;
+        bool const             need_oc = (c.tags & tagBit(kTagProtCigar)) && !c.is_n;
         bool const             valid   = (r.cig || need_oc) ? walk_runs(o, b.n_ops,
                                                                     [&](uint8_t, uint32_t cnt)
                                                                     {
@@ -261,42 +261,42 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
     w.p += r.l_seq;
     // the optional fields, in myWriteRecord's order
     uint32_t const t = c.tags;
-    if (t & kBamTagAe)
+    if (t & tagBit(kTagEValue))
     {
         w.tag('a', 'e', 'f');
         w.le<uint32_t>(__float_as_uint((float)b.e_value), 4);
     }
-    if (t & kBamTagAS)
+    if (t & tagBit(kTagBitScore))
     {
         w.tag('A', 'S', 'S');
         w.le<uint16_t>((uint16_t)(int32_t)b.bit_score, 2);
     }
-    if (t & kBamTagAr)
+    if (t & tagBit(kTagScore))
     {
         w.tag('a', 'r', 'C');
         w.le<uint8_t>((uint8_t)b.score, 1);
     }
-    if (t & kBamTagAi)
+    if (t & tagBit(kTagPIdent))
     {
         w.tag('a', 'i', 'C');
         w.le<uint8_t>((uint8_t)(int32_t)b.identity, 1);
     }
-    if (t & kBamTagAp)
+    if (t & tagBit(kTagPPos))
     {
         w.tag('a', 'p', 'S');
         w.le<uint16_t>(ppos_u16(b.num_positives, b.alignment_length), 2);
     }
-    if (t & kBamTagQf)
+    if (t & tagBit(kTagQFrame))
     {
         w.tag('q', 'f', 'c');
         w.le<uint8_t>((uint8_t)(int8_t)b.q_frame, 1);
     }
-    if (t & kBamTagSf)
+    if (t & tagBit(kTagSFrame))
     {
         w.tag('s', 'f', 'c');
         w.le<uint8_t>((uint8_t)(int8_t)b.s_frame, 1);
     }
-    if (t & kBamTagSt)
+    if (t & tagBit(kTagSTaxIds))
     {
         w.tag('s', 't', 'Z');
         uint64_t len = 0;
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
             w.p[len] = 0;
         w.p += len + 1;
     }
-    if (t & kBamTagLs)
+    if (t & tagBit(kTagLcaId))
     {
         w.tag('l', 's', 'Z');
         uint32_t len = r.name_len;
@@ -339,12 +339,12 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
             w.p[len] = 0;
         w.p += len + 1;
     }
-    if (t & kBamTagLt)
+    if (t & tagBit(kTagLcaTaxId))
     {
         w.tag('l', 't', 'I');
         w.le<uint32_t>(r.lca, 4);
     }
-    if (t & kBamTagQs)
+    if (t & tagBit(kTagProtSeq))
     {
         w.tag('q', 's', 'Z');
         uint64_t len = r.qs_len;
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
             w.p[len] = 0;
         w.p += len + 1;
     }
-    if (t & kBamTagOC)
+    if (t & tagBit(kTagProtCigar))
     {
         w.tag('O', 'C', 'Z');
         if (lane == 0)
@@ -387,12 +387,12 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
         }
         w.p += (uint64_t)a.oc_len + 1;
     }
-    if (t & kBamTagNM)
+    if (t & tagBit(kTagEditDistance))
     {
         w.tag('N', 'M', 'I');
         w.le<uint32_t>((uint32_t)(b.alignment_length - b.num_matches), 4);
     }
-    if (t & kBamTagIH)
+    if (t & tagBit(kTagMatchCount))
     {
         w.tag('I', 'H', 'I');
         w.le<uint32_t>(r.ih, 4);

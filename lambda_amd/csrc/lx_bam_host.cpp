@@ -1,22 +1,13 @@
-// lx_bam_host.cpp -- the host side of the BAM record kernels (lx_bam.hip): lx_render_bam_dev, lx_write_bam_dev.
+// lx_bam_host.cpp -- the host side of the BAM record kernels (lx_bam.hip): lx_render_bam_dev, lx_write_bam_dev, lxi::bam_append_dev.
 //
-// A call checks its arguments first (renderRecords' refusals, through lxi::bam_check, and the extent of the ops), flattens what the
-// kernels read -- rows, ops, the queries' letters, qualities (opt->q_qual) and lengths, the first words of their ids, the taxonomy lists, one LCA (and name) per
-// query group from lcaOf's own forward cursor, the genetic code over the 125 DNA5 triplets -- and uploads it.  The groups and measure
-// kernels run over the whole list; the host reads the 64-bit size totals of the tiles and cuts the list into RANGES of whole tiles
-// whose bytes stay within LX_OPT_BAM_RANGE_BYTES (a tile that alone exceeds it is a range of its own).  Per range: scan + emit into the
-// handle's stream buffer.  lx_render_bam_dev copies each range down behind the host-made header.  lx_write_bam_dev keeps the stream on
-// the device: the header is uploaded in front of the first range, the whole 65 280-byte blocks of a range go through the BGZF encoder
-// where they stand (lxi::bgzf_compress_dev), and the rest -- less than a block -- is carried to the front of the next range's buffer,
-// so the members are cut exactly where lx_bgzf_compress cuts them on the whole stream: the file is the one lx_write_records_bgzf
-// writes.  Only members come down.
-//
-// The steps the text writer (lx_text_host.cpp) shares -- the checks beyond the writer's own, flattening and upload, the groups, the
-// range cuts -- are lxi::rec_inputs and lxi::rec_ranges (lx_rec_host.h), defined here.
+// A call checks its arguments first (the host writer's refusals: lxi::resolve_output and lxi::check_rows; then lxi::rec_inputs'), has
+// lxi::rec_inputs flatten and upload what the kernels read and run the groups kernels, runs its measure kernel, and has lxi::rec_ranges
+// cut the list into ranges (lx_rec_host.h has the scheme).  Per range: scan + emit into the handle's stream buffer.  lx_render_bam_dev
+// copies each range down behind the host-made header (lxi::rec_drain).  lx_write_bam_dev keeps the stream on the device: the header
+// is uploaded in front of the first range and everything goes through the BGZF encoder where it stands (lxi::rec_encode_ranges): the
+// file is the one lx_write_records_bgzf writes.  Only members come down.
 //
 // lx_last_phase_ms: phase 11 = the render kernels (groups, measure, scans, emit), phase 4 = the encoder's, as for lx_bgzf_compress.
-#include <unordered_map>
-
 #include "lx_bgzf.h"
 #include "lx_rec_host.h"
 
@@ -25,286 +16,22 @@ using namespace lxi;
 namespace
 {
 
-constexpr uint64_t kDefaultRange = 256ull << 20;
-constexpr uint64_t kMaxRows      = (1ull << 31) - 16;
-constexpr uint64_t kMaxQlen      = 1ull << 30; // a record's bytes are counted in 32 bits
-constexpr uint32_t kMaxOps       = 1u << 26;
-constexpr uint64_t kMaxName      = kRecMaxName;
-
-using Range = RecRange;
-using Job   = RecJob;
-
-} // namespace
-
-namespace lxi
-{
-
-int rec_refuse(lx_handle * h, char const * who, int rc)
-{
-    return fail(h, rc, "%s: %s", who, *lx_last_output_error() ? lx_last_output_error() : "bad arguments");
-}
-
-int rec_begin(lx_handle * h)
-{
-    int const rc = bind(h);
-    if (rc)
-        return rc;
-    h->phase_ev.clear();
-    h->ev_pool_used = 0;
-    return LX_OK;
-}
-
-int rec_inputs(lx_handle * h, char const * who, int phase, uint32_t tags, bool with_ops, char const * program, lx_blast_match const * m, uint64_t n,
-               uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
-               lx_output_options const * opt_in, RecJob & job)
-{
-    auto refuse = rec_refuse;
-    int  rc     = LX_OK;
-    if (!with_ops)
-    {
-        ops       = nullptr;
-        ops_bytes = 0;
-    }
-    if ((!ops && ops_bytes) || (names->n_q && (!names->q_ids || !names->q_lens)))
-        return refuse(h, who, LX_EINVAL);
-    if (n > kMaxRows)
-    {
-        set_output_error("more records than the device writer takes in one call (2^31 - 16)");
-        return refuse(h, who, LX_EINVAL);
-    }
-    for (uint64_t k = 0; with_ops && k < n; ++k)
-        if (!lx_slice_ok(m[k].ops_off, m[k].n_ops, ops_bytes) || m[k].n_ops > kMaxOps)
-        {
-            set_output_error("a record's ops lie outside the ops buffer");
-            return refuse(h, who, LX_EINVAL);
-        }
-    lx_output_options opt;
-    lx_output_options_default(&opt);
-    if (opt_in)
-        opt = *opt_in;
-    bool const     ascii = q_res_ascii && q_ascii_off;
-    uint64_t const n_q   = names->n_q;
-    uint64_t       extent = 0;
-    for (uint64_t i = 0; i < n_q; ++i)
-    {
-        if (names->q_lens[i] > kMaxQlen)
-        {
-            set_output_error("a query longer than the device writer takes (2^30)");
-            return refuse(h, who, LX_EINVAL);
-        }
-        if (ascii)
-            extent = std::max(extent, q_ascii_off[i] + names->q_lens[i]);
-    }
-    lx::BamCtx & c = job.c;
-    c.tags         = tags;
-    c.sam_seq      = opt.sam_seq;
-    c.hard         = opt.sam_hard_clip != 0;
-    c.is_n         = std::strcmp(program, "blastn") == 0;
-    c.q_trans      = std::strcmp(program, "blastx") == 0 || std::strcmp(program, "tblastx") == 0;
-    c.s_trans      = std::strcmp(program, "tblastn") == 0 || std::strcmp(program, "tblastx") == 0;
-    c.n            = n;
-    if (n == 0)
-        return LX_OK;
-
-    // ---- what the kernels read
-    // first words of the query ids (firstWord of host/lx_output.cpp: up to the first blank or tab)
-    std::vector<uint64_t> qn_off(n_q + 1, 0);
-    std::atomic<bool>     name_too_long{false};
-    parallel_ranges(n_q, host_threads(n_q),
-                    [&](unsigned, uint64_t lo, uint64_t hi)
-                    {
-                        for (uint64_t i = lo; i < hi; ++i)
-                        {
-                            qn_off[i + 1] = names->q_ids[i] ? std::strcspn(names->q_ids[i], " \t") : 0;
-                            if (qn_off[i + 1] > kMaxName)
-                                name_too_long = true;
-                        }
-                    });
-    if (name_too_long)
-    {
-        set_output_error("a query id longer than the device writer takes (2^20)");
-        return refuse(h, who, LX_EINVAL);
-    }
-    for (uint64_t i = 0; i < n_q; ++i)
-        qn_off[i + 1] += qn_off[i];
-    std::vector<uint8_t> qn_blob(qn_off[n_q]);
-    parallel_ranges(n_q, host_threads(n_q),
-                    [&](unsigned, uint64_t lo, uint64_t hi)
-                    {
-                        for (uint64_t i = lo; i < hi; ++i)
-                            if (qn_off[i + 1] > qn_off[i])
-                                std::memcpy(qn_blob.data() + qn_off[i], names->q_ids[i], qn_off[i + 1] - qn_off[i]);
-                    });
-    // one LCA per query group, from lcaOf's forward-only cursor over (lca_qid, lca_tax); the name of tag ls beside it
-    bool const            want_lca = tags & (lx::kBamTagLt | lx::kBamTagLs);
-    std::vector<uint32_t> grp_tab; // [groups] lca, [groups] name offset, [groups] name length
-    std::vector<uint8_t>  name_blob;
-    uint64_t              groups = 0;
-    if (want_lca)
-    {
-        std::vector<uint32_t> lca, noff, nlen;
-        std::unordered_map<uint32_t, std::pair<uint32_t, uint32_t>> seen;
-        uint64_t                                                     lcaAt = 0;
-        for (uint64_t lo = 0; lo < n;)
-        {
-            uint64_t hi = lo + 1;
-            while (hi < n && m[hi].n_qid == m[lo].n_qid)
-                ++hi;
-            while (lcaAt < opt.n_lca && opt.lca_qid && opt.lca_qid[lcaAt] != m[lo].n_qid)
-                ++lcaAt;
-            uint32_t const t = (lcaAt < opt.n_lca && opt.lca_qid && opt.lca_tax) ? opt.lca_tax[lcaAt] : 0u;
-            lca.push_back(t);
-            std::pair<uint32_t, uint32_t> name{0u, 0xffffffffu};
-            if ((tags & lx::kBamTagLs) && opt.tax_names && opt.tax && t < opt.tax->n_taxa && opt.tax_names[t])
-            {
-                auto const it = seen.find(t);
-                if (it != seen.end())
-                    name = it->second;
-                else
-                {
-                    size_t const len = std::strlen(opt.tax_names[t]);
-                    if (len > kMaxName || name_blob.size() + len > 0xf0000000ull)
-                    {
-                        set_output_error("taxon names longer than the device writer takes");
-                        return refuse(h, who, LX_EINVAL);
-                    }
-                    name = {(uint32_t)name_blob.size(), (uint32_t)len};
-                    name_blob.insert(name_blob.end(), opt.tax_names[t], opt.tax_names[t] + len);
-                    seen.emplace(t, name);
-                }
-            }
-            noff.push_back(name.first);
-            nlen.push_back(name.second);
-            lo = hi;
-        }
-        groups = lca.size();
-        grp_tab.reserve(3 * groups);
-        grp_tab.insert(grp_tab.end(), lca.begin(), lca.end());
-        grp_tab.insert(grp_tab.end(), noff.begin(), noff.end());
-        grp_tab.insert(grp_tab.end(), nlen.begin(), nlen.end());
-    }
-    // tag qs of a translated query: the call's genetic code over all 125 DNA5 triplets, each translated by lx_translate_six_frames
-    uint8_t codon[125];
-    bool    have_codon = false;
-    if (c.q_trans && (tags & lx::kBamTagQs))
-    {
-        have_codon = true;
-        for (uint8_t x = 0; x < 125 && have_codon; ++x)
-        {
-            uint8_t const nt[3] = {(uint8_t)(x / 25), (uint8_t)(x / 5 % 5), (uint8_t)(x % 5)};
-            uint8_t       aa[8];
-            uint64_t      fo[6], fl[6];
-            have_codon = lx_translate_six_frames(nt, 3, opt.genetic_code, aa, sizeof(aa), fo, fl) == LX_OK;
-            codon[x]   = (uint8_t)lambda_amd::kSeqanOrder[std::min<uint8_t>(aa[fo[0]], 26)];
-        }
-    }
-
-    // ---- upload
-    auto & B = h->bam;
-    if ((rc = rec_upload(h, B.d_rows, m, n, c.rows)) || (rc = rec_upload(h, B.d_ops, ops, ops_bytes, c.ops)) ||
-        (rc = rec_upload(h, B.d_qlens, names->q_lens, n_q, c.q_lens)) || (rc = rec_upload(h, B.d_qn_off, qn_off.data(), n_q + 1, c.qn_off)) ||
-        (rc = rec_upload(h, B.d_qn_blob, qn_blob.data(), qn_blob.size(), c.qn_blob)))
-        return rc;
-    if (ascii && ((rc = rec_upload(h, B.d_ascii, q_res_ascii, extent, c.q_ascii)) || (rc = rec_upload(h, B.d_ascii_off, q_ascii_off, n_q, c.q_ascii_off))))
-        return rc;
-    c.q_ascii_bytes = ascii ? extent : 0;
-    // the qualities go up only where a record can carry them: a SAM or BAM writer (the ones that read the ops), a DNA query, SEQ written
-    if (ascii && opt.q_qual && with_ops && (c.is_n || c.q_trans) && opt.sam_seq != LX_SAM_SEQ_NEVER)
-    {
-        if ((rc = rec_upload(h, B.d_qual, opt.q_qual, extent, c.q_qual)))
-            return rc;
-        c.q_qual_bytes = extent;
-    }
-    if ((tags & lx::kBamTagSt) && opt.tax && opt.tax->s_tax_off && (opt.tax->s_tax_ids || opt.tax->s_tax_off[opt.tax->n_s] == 0))
-    {
-        c.tax_n_s = opt.tax->n_s;
-        if ((rc = rec_upload(h, B.d_tax_off, opt.tax->s_tax_off, c.tax_n_s + 1, c.s_tax_off)) ||
-            (rc = rec_upload(h, B.d_tax_ids, opt.tax->s_tax_ids, opt.tax->s_tax_off[c.tax_n_s], c.s_tax_ids)))
-            return rc;
-    }
-    if (want_lca)
-    {
-        uint32_t const * tab = nullptr;
-        if ((rc = rec_upload(h, B.d_grp_tab, grp_tab.data(), grp_tab.size(), tab)))
-            return rc;
-        c.grp_lca = tab;
-        if (tags & lx::kBamTagLs)
-        {
-            c.grp_name_off = tab + groups;
-            c.grp_name_len = tab + 2 * groups;
-            if ((rc = rec_upload(h, B.d_name_blob, name_blob.data(), name_blob.size(), c.name_blob)))
-                return rc;
-        }
-    }
-    if (have_codon && (rc = rec_upload(h, B.d_codon, codon, (uint64_t)125, c.codon)))
-        return rc;
-    uint64_t const tiles = (n + lx::kBamTile - 1) / lx::kBamTile;
-    if ((rc = ensure(h, B.d_grp, n * 4)) || (rc = ensure(h, B.d_grp_first, (n + 1) * 4)) || (rc = ensure(h, B.d_aux, n * sizeof(lx::BamAux))) ||
-        (rc = ensure(h, B.d_size, n * 4)) || (rc = ensure(h, B.d_off, n * 4)) ||
-        (rc = ensure(h, B.d_scan, (tiles + 2) * 4)) || (rc = ensure(h, B.d_tiles, tiles * 8)) || (rc = ensure_pinned(h, B.p_tiles, tiles * 8, kRoom)))
-        return rc;
-    c.grp       = static_cast<uint32_t *>(B.d_grp.ptr);
-    c.grp_first = static_cast<uint32_t *>(B.d_grp_first.ptr);
-    c.aux       = static_cast<lx::BamAux *>(B.d_aux.ptr);
-    c.size      = static_cast<uint32_t *>(B.d_size.ptr);
-
-    // ---- groups
-    PhaseTimer t(h, h->stream, phase);
-    LX_HIP(h, lx::bam_launch_groups(c, static_cast<uint32_t *>(B.d_scan.ptr), h->stream));
-    t.close();
-    LX_HIP(h, hipStreamSynchronize(h->stream)); // (the uploads' host arrays go with this frame)
-    return LX_OK;
-}
-
-int rec_ranges(lx_handle * h, char const * who, RecJob & job)
-{
-    auto &            B     = h->bam;
-    uint64_t const    n     = job.c.n;
-    uint64_t const    tiles = (n + lx::kBamTile - 1) / lx::kBamTile;
-    hipStream_t const s     = h->stream;
-    // ---- the tiles' totals for the cuts
-    LX_HIP(h, hipMemcpyAsync(B.p_tiles.ptr, B.d_tiles.ptr, tiles * 8, hipMemcpyDeviceToHost, s));
-    LX_HIP(h, hipStreamSynchronize(s));
-    uint64_t const * const tot    = static_cast<uint64_t const *>(B.p_tiles.ptr);
-    uint64_t const         budget = h->opt_bam_range ? h->opt_bam_range : kDefaultRange;
-    for (uint64_t t = 0; t < tiles;)
-    {
-        Range r{t * lx::kBamTile, 0, 0};
-        do
-        {
-            if (tot[t] > 0xf0000000ull)
-                return fail(h, LX_EINVAL, "%s: %llu bytes of records in one tile of %llu: more than a range holds", who, (unsigned long long)tot[t],
-                            (unsigned long long)lx::kBamTile);
-            r.bytes += tot[t];
-            ++t;
-        } while (t < tiles && r.bytes + tot[t] <= budget);
-        r.count       = std::min(n, t * lx::kBamTile) - r.first;
-        job.max_range = std::max(job.max_range, r.bytes);
-        job.total += r.bytes;
-        job.ranges.push_back(r);
-    }
-    return LX_OK;
-}
-
-} // namespace lxi
-
-namespace
-{
-
 // checks, flattening, upload, groups + measure, the ranges
 int prepare(lx_handle * h, char const * who, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
             uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, lx_output_options const * opt_in,
-            Job & job)
+            RecJob & job)
 {
     // ---- refusals, before any device work
-    uint32_t tags = 0;
-    int      rc   = bam_check(program, m, n, names, opt_in, &tags);
+    OutputRequest rq;
+    int           rc = resolve_output(LX_OUT_BAM, program, m, n, names, opt_in, rq);
+    if (rc == LX_OK)
+        rc = check_rows(m, n, names, nullptr); // (no text, where the text writer has one: "bad arguments" -- kept as it is)
     if (rc != LX_OK)
         return rec_refuse(h, who, rc);
-    if ((rc = rec_inputs(h, who, 11, tags, true, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt_in, job)))
+    if ((rc = rec_inputs(h, who, 11, rq, rq.tag_mask, true, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, job)))
         return rc;
     if (write_header)
-        job.header = bam_header(names, opt_in, tags);
+        job.header = bam_header(names, rq);
     if (n == 0)
         return LX_OK;
     // ---- sizes, and the tiles' totals for the cuts
@@ -317,7 +44,7 @@ int prepare(lx_handle * h, char const * who, int write_header, char const * prog
 }
 
 // one range's records into `out` (device)
-int emit_range(lx_handle * h, Job const & job, Range const & r, uint8_t * out)
+int emit_range(lx_handle * h, RecJob const & job, RecRange const & r, uint8_t * out)
 {
     auto &     B = h->bam;
     PhaseTimer t(h, h->stream, 11);
@@ -331,38 +58,6 @@ int emit_range(lx_handle * h, Job const & job, Range const & r, uint8_t * out)
 namespace lxi
 {
 
-int rec_append_ranges(lx_handle * h, RecJob const & job, std::function<int(RecRange const &, uint8_t *)> const & emit, uint8_t * d_carry,
-                      uint64_t * carry, MemberSink const & sink)
-{
-    // the stream buffer: what is carried (less than a block) + a range
-    int rc = ensure(h, h->bam.d_stream, lx::kBgzfBlock + job.max_range + 16);
-    if (rc)
-        return rc;
-    uint8_t * const   d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
-    hipStream_t const s = h->stream;
-    uint64_t          c = *carry;
-    if (c >= lx::kBgzfBlock)
-        return fail(h, LX_EINVAL, "lx_out_append: a carry of a block or more");
-    if (c)
-        LX_HIP(h, hipMemcpyAsync(d, d_carry, c, hipMemcpyDeviceToDevice, s));
-    for (RecRange const & r : job.ranges)
-    {
-        if ((rc = emit(r, d + c)))
-            return rc;
-        uint64_t const have = c + r.bytes, whole = have / lx::kBgzfBlock * lx::kBgzfBlock;
-        if (whole && (rc = bgzf_compress_dev(h, d, whole, sink)))
-            return rc;
-        c = have - whole;
-        if (c && whole) // (whole is at least a block, the rest less: the two do not overlap)
-            LX_HIP(h, hipMemcpyAsync(d, d + whole, c, hipMemcpyDeviceToDevice, s));
-    }
-    if (c)
-        LX_HIP(h, hipMemcpyAsync(d_carry, d, c, hipMemcpyDeviceToDevice, s));
-    LX_HIP(h, hipStreamSynchronize(s));
-    *carry = c;
-    return LX_OK;
-}
-
 int bam_append_dev(lx_handle * h, char const * who, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
                    uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
                    lx_output_options const * opt, uint8_t * d_carry, uint64_t * carry, MemberSink const & sink)
@@ -373,10 +68,10 @@ int bam_append_dev(lx_handle * h, char const * who, char const * program, lx_bla
     HostPool::Call in_call;
     try
     {
-        Job job;
+        RecJob job;
         if ((rc = prepare(h, who, 0, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, job)))
             return rc;
-        return rec_append_ranges(h, job, [&](Range const & r, uint8_t * out) { return emit_range(h, job, r, out); }, d_carry, carry, sink);
+        return rec_append_ranges(h, job, [&](RecRange const & r, uint8_t * out) { return emit_range(h, job, r, out); }, d_carry, carry, sink);
     }
     catch (std::bad_alloc const &)
     {
@@ -403,24 +98,14 @@ int lx_render_bam_dev(lx_handle * h, int write_header, char const * program, lx_
     HostPool::Call in_call;
     try
     {
-        Job job;
+        RecJob job;
         if ((rc = prepare(h, "lx_render_bam_dev", write_header, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, job)))
             return rc;
         std::string bytes;
         bytes.reserve(job.header.size() + job.total);
         bytes = job.header;
-        if ((rc = ensure(h, h->bam.d_stream, std::max<uint64_t>(job.max_range, 16))))
+        if ((rc = rec_drain(h, job, [&](RecRange const & r, uint8_t * d) { return emit_range(h, job, r, d); }, bytes)))
             return rc;
-        uint8_t * const d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
-        for (Range const & r : job.ranges)
-        {
-            if ((rc = emit_range(h, job, r, d)))
-                return rc;
-            size_t const at = bytes.size();
-            bytes.resize(at + r.bytes);
-            LX_HIP(h, hipMemcpyAsync(&bytes[at], d, r.bytes, hipMemcpyDeviceToHost, h->stream));
-            LX_HIP(h, hipStreamSynchronize(h->stream));
-        }
         *out = bytes_adopt(std::move(bytes));
     }
     catch (std::bad_alloc const &)
@@ -445,51 +130,22 @@ int lx_write_bam_dev(lx_handle * h, char const * path, char const * program, lx_
     std::vector<uint8_t> packed; // the members: the file is written at once, like lx_write_records_bgzf's
     try
     {
-        Job job;
-        if ((rc = prepare(h, "lx_write_bam_dev", 1, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, job)))
+        RecJob job;
+        if ((rc = prepare(h, "lx_write_bam_dev", 1, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, job)) ||
+            (rc = rec_stream_front(h, job, job.header, 0)))
             return rc;
-        // the stream buffer: what is carried (the header in front of the first range, less than a block later) + a range
-        uint64_t const carry_max = std::max<uint64_t>(job.header.size(), lx::kBgzfBlock);
-        if ((rc = ensure(h, h->bam.d_stream, carry_max + job.max_range + 16)))
-            return rc;
-        uint8_t * const   d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
-        hipStream_t const s = h->stream;
         packed.reserve((size_t)((job.header.size() + job.total) / 3 + 4096));
-        auto sink = [&](uint8_t const * members, uint64_t bytes) -> int
-        {
-            packed.insert(packed.end(), members, members + bytes);
-            return LX_OK;
-        };
         uint64_t carry = job.header.size();
-        LX_HIP(h, hipMemcpyAsync(d, job.header.data(), carry, hipMemcpyHostToDevice, s));
-        if (job.ranges.empty() && (rc = bgzf_compress_dev(h, d, carry, sink)))
+        if ((rc = rec_encode_ranges(h, job, [&](RecRange const & r, uint8_t * d) { return emit_range(h, job, r, d); }, &carry, nullptr, true,
+                                    rec_collect(packed))))
             return rc;
-        for (size_t i = 0; i < job.ranges.size(); ++i)
-        {
-            Range const & r = job.ranges[i];
-            if ((rc = emit_range(h, job, r, d + carry)))
-                return rc;
-            uint64_t const have  = carry + r.bytes;
-            uint64_t const whole = i + 1 == job.ranges.size() ? have : have / lx::kBgzfBlock * lx::kBgzfBlock;
-            if ((rc = bgzf_compress_dev(h, d, whole, sink)))
-                return rc;
-            carry = have - whole;
-            if (carry && whole) // (whole is at least a block, the rest less: the two do not overlap)
-                LX_HIP(h, hipMemcpyAsync(d, d + whole, carry, hipMemcpyDeviceToDevice, s));
-        }
-        LX_HIP(h, hipStreamSynchronize(s));
         packed.insert(packed.end(), lx::kEofMember, lx::kEofMember + sizeof(lx::kEofMember));
     }
     catch (std::bad_alloc const &)
     {
         return fail(h, LX_ENOMEM, "lx_write_bam_dev: out of host memory");
     }
-    std::FILE * f = std::fopen(path, "wb");
-    if (!f)
-        return fail(h, LX_EINVAL, "cannot open %s", path);
-    bool ok = std::fwrite(packed.data(), 1, packed.size(), f) == packed.size();
-    ok      = (std::fclose(f) == 0) && ok;
-    return ok ? LX_OK : fail(h, LX_EINVAL, "error while writing %s (disk full?)", path);
+    return rec_write_file(h, path, packed.data(), packed.size());
 }
 
 } // extern "C"

@@ -1,5 +1,5 @@
 // lx_cull.h -- the rule of --max-hsps and --culling-limit (include/lambda_ext.h: lx_cull_options), in plain integers and doubles,
-// shared by the host function (lx_postprocess_records_ex, host/lx_output.cpp) and the kernels (lx_toprec.hip).  Not part of the ABI.
+// shared by the host function (lx_postprocess_records_ex, host/lx_postprocess.cpp) and the kernels (lx_toprec.hip).  Not part of the ABI.
 //
 // Per run of equal n_qid, over the rows that survive _writeRecord's unique step, in its order 2 (bit score descending, ties by place
 // in order 1).  Row a is BETTER than row b when it comes earlier in that order: a strict total order.

@@ -29,6 +29,7 @@
 #include "lx_device.h"
 #include "lx_host_plan.h"
 #include "lx_host_pool.h"
+#include "lx_output_host.h"
 #include "lx_resources.h"
 #include "lx_step_plan.h"
 
@@ -365,25 +366,7 @@ struct PhaseTimer
     } while (0)
 
 int    bind(lx_handle * h);
-// (host/lx_output.cpp) an lx_bytes that takes over s; the message lx_last_output_error() returns
-lx_bytes * bytes_adopt(std::string && s);
-void       set_output_error(std::string const & msg);
-// (host/lx_output.cpp) the refusals of lx_cull_options for n rows in host memory (include/lambda_ext.h); `why` gets the text.
-// max_len: the longest query the caller can take (the device forms keep the intervals in 32-bit words)
-int        cull_check(lx_blast_match const * m, uint64_t n, lx_cull_options const * opt, uint64_t max_len, std::string & why);
-// (host/lx_output.cpp) for the device BAM writer: renderRecords' refusals for LX_OUT_BAM (program, NULL arguments, tag keys, the rows'
-// ids; lx_last_output_error() has its text) and the resolved tags as bits in kSamTags' order; the bytes in front of the records
-// (magic, SAM header text, reference list)
-int         bam_check(char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names, lx_output_options const * opt,
-                      uint32_t * tag_mask);
-std::string bam_header(lx_seq_names const * names, lx_output_options const * opt, uint32_t tag_mask);
-// (host/lx_output.cpp) for the device text writer: renderRecords' refusals for LX_OUT_BLAST_TAB / _COMMENTS / LX_OUT_SAM, with the
-// columns it resolved (indices into kColumns = lx_text.h's kTextCol*) or the tags as bits; the SAM header text; the three constant
-// parts of a query group's .m9 comment lines (in front of the query's id, between the id and the hit count, behind the count)
-int         text_check(int format, char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names,
-                       lx_output_options const * opt, std::vector<int> & cols, uint32_t * tag_mask);
-std::string sam_header(lx_seq_names const * names, lx_output_options const * opt, uint32_t tag_mask);
-void        m9_comment_parts(char const * program, lx_output_options const * opt, std::vector<int> const & cols, std::string (&parts)[3]);
+// (bytes_adopt, set_output_error, cull_check, the writers' resolved request and header texts: lx_output_host.h)
 // (lx_bgzf_host.cpp) lx_bgzf_compress's members of n bytes that stand on the device already (16-byte aligned): the same chunks of 512
 // blocks, the same member bytes, the same download pipeline; `sink` takes each chunk's members in order.  The phase events of the
 // call so far stay.

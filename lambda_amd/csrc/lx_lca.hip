@@ -1,6 +1,6 @@
 // lx_lca.hip -- the LCA step of _writeRecord (src/search_algo.hpp:884-907, computeLCA: src/search_misc.hpp:86-112) on the device
 // (gfx950), for one range of whole queries whose columns lx_lca_host.cpp has uploaded: the rule of lx_compute_lca_ex
-// (host/lx_output.cpp), restated.
+// (host/lx_postprocess.cpp), restated.
 //
 // Per range, on one stream:
 //   1. heads: a row is a query's head if it is the first of the range or its n_qid differs from the row's before it; one sum scan of
@@ -55,7 +55,7 @@ struct HeadOut
     }
 };
 
-// computeLCA (src/search_misc.hpp:86-112) as lca_of of host/lx_output.cpp has it: level the two nodes, then climb together.  false:
+// computeLCA (src/search_misc.hpp:86-112) as lca_of of host/lx_postprocess.cpp has it: level the two nodes, then climb together.  false:
 // the paths never met (err gets kErrNoRoot) or a loop hit its bound (kErrBound).
 __device__ __forceinline__ bool lca_of(TreeView const & t, uint32_t n1, uint32_t n2, uint32_t & out, uint32_t & err)
 {

@@ -1,5 +1,5 @@
 // lx_lca_host.cpp -- lx_tax_dev_* and lx_compute_lca_dev: the LCA step of _writeRecord (src/search_algo.hpp:884-907, computeLCA:
-// src/search_misc.hpp:86-112) with its fold as kernels (lx_lca.hip).  lx_compute_lca_ex (host/lx_output.cpp) is the specification.
+// src/search_misc.hpp:86-112) with its fold as kernels (lx_lca.hip).  lx_compute_lca_ex (host/lx_postprocess.cpp) is the specification.
 //
 // The tree goes up once (lx_tax_dev_create, after lx_check_tax_tree) and stays: {parent, height} per taxon, the subjects' taxon lists.
 // A call checks every row on the host threads (n_sid, and the bit score where the top-percent rule is on) before anything touches

@@ -40,7 +40,7 @@ __device__ __forceinline__ uint8_t rc_letter(uint8_t c)
         default: return 'N';
     }
 }
-// frameProtein's nucleotide ranks and lx_translate_six_frames' complement
+// QueryProteins' nucleotide ranks and lx_translate_six_frames' complement
 __device__ __forceinline__ uint32_t nt5(uint8_t c)
 {
     switch (up(c))
@@ -160,7 +160,7 @@ __device__ __forceinline__ Rec rec_of(BamCtx const & c, uint64_t k)
     r.qs_a     = 0;
     r.qs_mode  = 0;
     r.qs_shift = 0;
-    if ((c.tags & kBamTagQs) && !c.is_n && write_seq && ascii)
+    if ((c.tags & tagBit(kTagProtSeq)) && !c.is_n && write_seq && ascii)
     {
         uint64_t fl = 0;
         if (!c.q_trans)

@@ -1,13 +1,14 @@
 // lx_text.h -- what the text record kernels (lx_text.hip) and their host side (lx_text_host.cpp) share.  Not part of the ABI.
 //
-// The kernels restate formatRecord and the group loop of renderRecords (host/lx_output.cpp) for LX_OUT_BLAST_TAB and
-// LX_OUT_BLAST_TAB_COMMENTS, and its SAM branch for LX_OUT_SAM: the same bytes.  The steps are the BAM writer's (lx_bam.h), whose
+// The kernels restate formatRecord and the group loop of renderTable (host/lx_output.cpp) for LX_OUT_BLAST_TAB and
+// LX_OUT_BLAST_TAB_COMMENTS, and samFields / samLine for LX_OUT_SAM: the same bytes.  The steps are the BAM writer's (lx_bam.h), whose
 // context, groups and size scan they use, with one in front: numbers (one lane per record: the decimal texts of its e-value, bit
 // score, pident, ppos and ae by lx_numfmt.h, kept per record), measure (one lane per record: the bytes of its line, with the comment
 // lines of .m9 in front of a group's first record; 64-bit totals per kBamTile records), and per range a scan of the sizes and emit
 // (one wavefront per record, the line staged in LDS and stored 64 bytes an instruction).
 #pragma once
 #include "lx_bam.h"
+#include "lx_vocab.h" // TextCtx::cols: kCol*
 
 namespace lx
 {
@@ -15,15 +16,6 @@ namespace lx
 constexpr int      kTextEmitBlock = 256; // threads of an emit workgroup: four wavefronts = four records
 constexpr uint32_t kTextEmitRecs  = kTextEmitBlock / 64;
 constexpr uint32_t kTextStage     = 256; // bytes of LDS a wavefront stages its line in
-
-// the tabular columns, in the order of kColumns (host/lx_output.cpp): TextCtx::cols holds these
-enum
-{
-    kTextColQSeqId, kTextColSSeqId, kTextColPIdent, kTextColLength, kTextColMismatch, kTextColGapOpen, kTextColQStart, kTextColQEnd,
-    kTextColSStart, kTextColSEnd, kTextColEValue, kTextColBitScore, kTextColQLen, kTextColSLen, kTextColScore, kTextColNIdent,
-    kTextColPositive, kTextColGaps, kTextColPPos, kTextColFrames, kTextColQFrame, kTextColSFrame, kTextColSTaxIds, kTextColLcaTaxId,
-    kTextNumColumns
-};
 
 // a record's number texts: "%.1e" of e_value, "%.1f" of bit_score, "%.2f" of identity, "%.2f" of ppos, "%g" of (float)e_value
 enum

@@ -1,6 +1,6 @@
-// lx_text.hip -- .m8, .m9 and .sam records made on the device (gfx950): formatRecord and the group loop of renderRecords
-// (host/lx_output.cpp:925-1060; seqan's writeRecord for BlastTabular behind myWriteRecord, src/search_output.hpp:463-733) and
-// its SAM branch (:769-921) restated as kernels, byte for byte.  The host code is the specification: its quirks are kept (unsigned
+// lx_text.hip -- .m8, .m9 and .sam records made on the device (gfx950): formatRecord and the group loop of renderTable
+// (host/lx_output.cpp; seqan's writeRecord for BlastTabular behind myWriteRecord, src/search_output.hpp:463-733) and
+// samFields / samLine restated as kernels, byte for byte.  The host code is the specification: its quirks are kept (unsigned
 // wrap-around of coordinates that make no sense, the casts of the SAM tags, POS of a translated subject's minus strand taken from the
 // QUERY length, an empty CIGAR for a valid alignment without elements but "*" for tag OC).
 //
@@ -216,34 +216,34 @@ __device__ __forceinline__ void tab_record(W & w, TextCtx const & c, Rec const &
             w.ch('\t');
         switch (c.cols[i])
         {
-            case kTextColQSeqId: put_qname(w, c.b, r); break;
-            case kTextColSSeqId: put_sname(w, c, k); break;
-            case kTextColQLen: w.dec(r.qlen); break;
-            case kTextColSLen: w.dec(slen); break;
-            case kTextColQStart: w.dec(qs); break;
-            case kTextColQEnd: w.dec(qe); break;
-            case kTextColSStart: w.dec(ss); break;
-            case kTextColSEnd: w.dec(se); break;
-            case kTextColEValue: put_num(w, c, k, kTextNumEValue); break;
-            case kTextColBitScore: put_num(w, c, k, kTextNumBitScore); break;
-            case kTextColScore: put_sdec(w, b.score); break;
-            case kTextColLength: put_sdec(w, b.alignment_length); break;
-            case kTextColPIdent: put_num(w, c, k, kTextNumPIdent); break;
-            case kTextColNIdent: put_sdec(w, b.num_matches); break;
-            case kTextColMismatch: put_sdec(w, b.num_mismatches); break;
-            case kTextColPositive: put_sdec(w, b.num_positives); break;
-            case kTextColGapOpen: put_sdec(w, b.num_gap_opens); break;
-            case kTextColGaps: put_sdec(w, (int32_t)((uint32_t)b.num_gap_opens + (uint32_t)b.num_gap_extensions)); break;
-            case kTextColPPos: put_num(w, c, k, kTextNumPPos); break;
-            case kTextColFrames:
+            case kColQSeqId: put_qname(w, c.b, r); break;
+            case kColSSeqId: put_sname(w, c, k); break;
+            case kColQLen: w.dec(r.qlen); break;
+            case kColSLen: w.dec(slen); break;
+            case kColQStart: w.dec(qs); break;
+            case kColQEnd: w.dec(qe); break;
+            case kColSStart: w.dec(ss); break;
+            case kColSEnd: w.dec(se); break;
+            case kColEValue: put_num(w, c, k, kTextNumEValue); break;
+            case kColBitScore: put_num(w, c, k, kTextNumBitScore); break;
+            case kColScore: put_sdec(w, b.score); break;
+            case kColLength: put_sdec(w, b.alignment_length); break;
+            case kColPIdent: put_num(w, c, k, kTextNumPIdent); break;
+            case kColNIdent: put_sdec(w, b.num_matches); break;
+            case kColMismatch: put_sdec(w, b.num_mismatches); break;
+            case kColPositive: put_sdec(w, b.num_positives); break;
+            case kColGapOpen: put_sdec(w, b.num_gap_opens); break;
+            case kColGaps: put_sdec(w, (int32_t)((uint32_t)b.num_gap_opens + (uint32_t)b.num_gap_extensions)); break;
+            case kColPPos: put_num(w, c, k, kTextNumPPos); break;
+            case kColFrames:
                 put_sdec(w, b.q_frame);
                 w.ch('/');
                 put_sdec(w, b.s_frame);
                 break;
-            case kTextColQFrame: put_sdec(w, b.q_frame); break;
-            case kTextColSFrame: put_sdec(w, b.s_frame); break;
-            case kTextColSTaxIds: put_taxa(w, c.b, r); break;
-            case kTextColLcaTaxId: w.dec(r.lca); break;
+            case kColQFrame: put_sdec(w, b.q_frame); break;
+            case kColSFrame: put_sdec(w, b.s_frame); break;
+            case kColSTaxIds: put_taxa(w, c.b, r); break;
+            case kColLcaTaxId: w.dec(r.lca); break;
             default: break;
         }
     }
@@ -318,7 +318,7 @@ __device__ __forceinline__ void put_tag(W & w, char const * key, char type)
     w.ch(':');
 }
 
-// the line of host/lx_output.cpp:834-835 and the tags of :867-910; a.n_cigar / a.oc_len: whether the CIGAR / tag OC is made of the ops
+// the line of samLine and the tags of samTags (host/lx_output.cpp); a.n_cigar / a.oc_len: whether the CIGAR / tag OC is made of the ops
 // ("*" otherwise: another program, or a byte that is no op)
 template <class W>
 __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const & r, uint64_t k, BamAux a)
@@ -350,47 +350,47 @@ __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const 
     else
         w.ch('*');
     uint32_t const t = c.tags;
-    if (t & kBamTagAe)
+    if (t & tagBit(kTagEValue))
     {
         put_tag(w, "ae", 'f');
         put_num(w, tc, k, kTextNumAe);
     }
-    if (t & kBamTagAS)
+    if (t & tagBit(kTagBitScore))
     {
         put_tag(w, "AS", 'i');
         w.dec((uint16_t)(int32_t)b.bit_score);
     }
-    if (t & kBamTagAr)
+    if (t & tagBit(kTagScore))
     {
         put_tag(w, "ar", 'i');
         w.dec((uint8_t)b.score);
     }
-    if (t & kBamTagAi)
+    if (t & tagBit(kTagPIdent))
     {
         put_tag(w, "ai", 'i');
         w.dec((uint8_t)(int32_t)b.identity);
     }
-    if (t & kBamTagAp)
+    if (t & tagBit(kTagPPos))
     {
         put_tag(w, "ap", 'i');
         w.dec(ppos_u16(b.num_positives, b.alignment_length));
     }
-    if (t & kBamTagQf)
+    if (t & tagBit(kTagQFrame))
     {
         put_tag(w, "qf", 'i');
         put_sdec(w, (int8_t)b.q_frame);
     }
-    if (t & kBamTagSf)
+    if (t & tagBit(kTagSFrame))
     {
         put_tag(w, "sf", 'i');
         put_sdec(w, (int8_t)b.s_frame);
     }
-    if (t & kBamTagSt)
+    if (t & tagBit(kTagSTaxIds))
     {
         put_tag(w, "st", 'Z');
         put_taxa(w, c, r);
     }
-    if (t & kBamTagLs)
+    if (t & tagBit(kTagLcaId))
     {
         put_tag(w, "ls", 'Z');
         if (r.name_len == 0xffffffffu)
@@ -398,12 +398,12 @@ __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const 
         else
             w.str(r.name_len, [&](uint64_t i) { return c.name_blob[r.name_off + i]; });
     }
-    if (t & kBamTagLt)
+    if (t & tagBit(kTagLcaTaxId))
     {
         put_tag(w, "lt", 'i');
         w.dec(r.lca);
     }
-    if (t & kBamTagQs)
+    if (t & tagBit(kTagProtSeq))
     {
         put_tag(w, "qs", 'Z');
         if (r.qs_len)
@@ -411,7 +411,7 @@ __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const 
         else
             w.ch('*');
     }
-    if (t & kBamTagOC)
+    if (t & tagBit(kTagProtCigar))
     {
         put_tag(w, "OC", 'Z');
         // protCigarOf; a text without elements is "*"
@@ -426,12 +426,12 @@ __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const 
         else
             w.ch('*');
     }
-    if (t & kBamTagNM)
+    if (t & tagBit(kTagEditDistance))
     {
         put_tag(w, "NM", 'i');
         w.dec((uint32_t)(b.alignment_length - b.num_matches));
     }
-    if (t & kBamTagIH)
+    if (t & tagBit(kTagMatchCount))
     {
         put_tag(w, "IH", 'i');
         w.dec(r.ih);
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(256) void text_measure_kernel(TextCtx c, unsigned l
         BamAux    a{0, 0};
         if (c.format == LX_OUT_SAM)
         {
-            bool const need_oc = (c.b.tags & kBamTagOC) && !c.b.is_n;
+            bool const need_oc = (c.b.tags & tagBit(kTagProtCigar)) && !c.b.is_n;
             bool const valid   = (r.cig || need_oc) ? ops_valid(c.b.ops + r.b->ops_off, r.b->n_ops) : true;
             a                  = BamAux{r.cig && valid ? 1u : 0u, need_oc && valid ? 1u : 0u};
         }

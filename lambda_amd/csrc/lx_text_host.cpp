@@ -1,15 +1,15 @@
 // lx_text_host.cpp -- the host side of the text record kernels (lx_text.hip): lx_render_text_dev, lx_write_text_dev.
 //
-// A call checks its arguments first (renderRecords' refusals through lxi::text_check, LX_OUT_BAM, numbers outside the formatter's
-// domain, then what the BAM writer checks: lxi::rec_inputs -- the extent of the ops for SAM only: the tabular formats do not read them,
+// A call checks its arguments first (LX_OUT_BAM, the host writer's refusals: lxi::resolve_output and lxi::check_rows, numbers outside
+// the formatter's domain, then what the BAM writer checks: lxi::rec_inputs -- the extent of the ops for SAM only: the tabular formats do not read them,
 // as in the host writer, and a front end that wrote .m8 never kept them), and uploads what the kernels read: the BAM writer's inputs (rows, ops,
 // query letters, lengths and first words, taxonomy, the groups' LCA), and beside them the columns, the first words and lengths of the
 // subjects THE ROWS NAME (re-indexed: a large database's name list stays on the host), for .m9 the whole query ids and the constant
 // parts of the comment lines.  Numbers and measure run over the whole list, the host cuts ranges within LX_OPT_BAM_RANGE_BYTES from
-// the tiles' totals, and per range scan + emit fill the handle's stream buffer (lx_bam_host.cpp has the scheme).  The SAM header and
-// the .m9 footer are made on the host.  lx_render_text_dev copies each range down; lx_write_text_dev writes the ranges to the file
-// as they come (bgzf = 0), or keeps the stream on the device and compresses it where it stands, less than a block carried into the
-// next range, the footer uploaded behind the last (bgzf = 1): the members lx_write_records_bgzf makes.
+// the tiles' totals, and per range scan + emit fill the handle's stream buffer (lx_rec_host.h has the scheme).  The SAM header and
+// the .m9 footer are made on the host.  lx_render_text_dev copies each range down (lxi::rec_drain); lx_write_text_dev does the same
+// and writes the file (bgzf = 0), or keeps the stream on the device and compresses it where it stands, the footer uploaded behind the
+// last range (bgzf = 1, lxi::rec_encode_ranges): the members lx_write_records_bgzf makes.
 //
 // lx_last_phase_ms: phase 12 = the text record kernels (groups, numbers, measure, scans, emit), phase 4 = the encoder's.
 #include <unordered_map>
@@ -34,8 +34,8 @@ struct TextJob
 // what the arguments resolve to
 struct Checked
 {
-    std::vector<int> cols;
-    uint32_t         tags = 0, need = 0; // kBamTag* whose inputs are wanted, kTextNum* texts
+    OutputRequest rq;
+    uint32_t      tags = 0, need = 0; // tagBit(kTag*) whose inputs are wanted, kTextNum* texts
 };
 
 // (the handle may still be NULL here: the arguments are judged first, so that a caller learns what is wrong with them without a device)
@@ -44,11 +44,10 @@ int refuse(lx_handle * h, char const * who, int rc)
     return h ? rec_refuse(h, who, rc) : rc;
 }
 
-// the refusals that need no device: the format, renderRecords' own, the formatter's domain
+// the refusals that need no device: the format, the host writer's own, the formatter's domain
 int check_args(lx_handle * h, char const * who, int format, char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names,
                lx_output_options const * opt_in, Checked & ck)
 {
-    std::vector<int> & cols = ck.cols;
     if (format == LX_OUT_BAM)
     {
         set_output_error("LX_OUT_BAM is binary: lx_render_bam_dev / lx_write_bam_dev make it");
@@ -59,8 +58,9 @@ int check_args(lx_handle * h, char const * who, int format, char const * program
         set_output_error("unknown output format");
         return refuse(h, who, LX_EINVAL);
     }
-    uint32_t tags = 0;
-    int      rc   = text_check(format, program, m, n, names, opt_in, cols, &tags);
+    int rc = resolve_output(format, program, m, n, names, opt_in, ck.rq);
+    if (rc == LX_OK) // (the BAM writer has no text here)
+        rc = check_rows(m, n, names, "a record names a query or a subject the name lists do not have");
     if (rc != LX_OK)
         return refuse(h, who, rc);
     if (names->n_s && (!names->s_ids || !names->s_lens))
@@ -77,40 +77,37 @@ int check_args(lx_handle * h, char const * who, int format, char const * program
             return refuse(h, who, LX_EINVAL);
         }
     }
-    bool const sam = format == LX_OUT_SAM;
-    uint32_t   need = 0;
-    if (sam)
-        need = tags & lx::kBamTagAe ? 1u << lx::kTextNumAe : 0u;
+    uint32_t tags = ck.rq.tag_mask, need = 0;
+    if (ck.rq.sam)
+        need = ck.rq.tags[lx::kTagEValue] ? 1u << lx::kTextNumAe : 0u;
     else
-    {
-        tags = 0;
-        for (int c : cols)
+        for (int c : ck.rq.cols)
         {
-            tags |= c == lx::kTextColSTaxIds ? lx::kBamTagSt : c == lx::kTextColLcaTaxId ? lx::kBamTagLt : 0u;
-            need |= c == lx::kTextColEValue    ? 1u << lx::kTextNumEValue
-                    : c == lx::kTextColBitScore ? 1u << lx::kTextNumBitScore
-                    : c == lx::kTextColPIdent   ? 1u << lx::kTextNumPIdent
-                    : c == lx::kTextColPPos     ? 1u << lx::kTextNumPPos
-                                                : 0u;
+            tags |= c == lx::kColSTaxIds ? lx::tagBit(lx::kTagSTaxIds) : c == lx::kColLcaTaxId ? lx::tagBit(lx::kTagLcaTaxId) : 0u;
+            need |= c == lx::kColEValue    ? 1u << lx::kTextNumEValue
+                    : c == lx::kColBitScore ? 1u << lx::kTextNumBitScore
+                    : c == lx::kColPIdent   ? 1u << lx::kTextNumPIdent
+                    : c == lx::kColPPos     ? 1u << lx::kTextNumPPos
+                                            : 0u;
         }
-    }
     ck.tags = tags;
     ck.need = need;
     return LX_OK;
 }
 
-int prepare(lx_handle * h, char const * who, Checked const & ck, int format, int write_header, char const * program, lx_blast_match const * m,
-            uint64_t n, uint8_t const * ops, uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii,
-            uint64_t const * q_ascii_off, lx_output_options const * opt_in, int64_t footer_records, TextJob & job)
+int prepare(lx_handle * h, char const * who, Checked const & ck, int write_header, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
+            uint64_t ops_bytes, lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off, int64_t footer_records,
+            TextJob & job)
 {
-    std::vector<int> const & cols = ck.cols;
-    uint32_t const           tags = ck.tags, need = ck.need;
-    bool const               sam  = format == LX_OUT_SAM;
+    std::vector<int> const & cols   = ck.rq.cols;
+    uint32_t const           need   = ck.need;
+    int const                format = ck.rq.format;
+    bool const               sam    = ck.rq.sam;
     int                      rc;
-    if ((rc = rec_inputs(h, who, 12, tags, sam, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt_in, job.rec)))
+    if ((rc = rec_inputs(h, who, 12, ck.rq, ck.tags, sam, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, job.rec)))
         return rc;
     if (sam && write_header)
-        job.rec.header = sam_header(names, opt_in, tags);
+        job.rec.header = sam_header(names, ck.rq);
     if (format == LX_OUT_BLAST_TAB_COMMENTS && footer_records >= 0) // lx_write_footer
         job.footer = "# BLAST processed " + std::to_string((unsigned long long)footer_records) + " queries\n";
     if (n == 0)
@@ -190,12 +187,10 @@ int prepare(lx_handle * h, char const * who, Checked const & ck, int format, int
         for (uint64_t i = 0; i < n_q; ++i)
             if (qid_off[i + 1] > qid_off[i])
                 std::memcpy(qid_blob.data() + qid_off[i], names->q_ids[i] ? names->q_ids[i] : "(null)", qid_off[i + 1] - qid_off[i]);
-        std::string parts[3];
-        m9_comment_parts(program, opt_in, cols, parts);
         for (int i = 0; i < 3; ++i)
         {
             c.comment_off[i] = (uint32_t)comment.size();
-            comment += parts[i];
+            comment += ck.rq.m9[i];
         }
         c.comment_off[3] = (uint32_t)comment.size();
     }
@@ -238,6 +233,18 @@ int emit_range(lx_handle * h, TextJob const & job, RecRange const & r, uint8_t *
     return LX_OK;
 }
 
+// the whole text in host memory: the header, the ranges as they come down, the footer
+int drain(lx_handle * h, TextJob const & job, std::string & bytes)
+{
+    bytes.reserve(job.rec.header.size() + job.rec.total + job.footer.size());
+    bytes        = job.rec.header;
+    int const rc = rec_drain(h, job.rec, [&](RecRange const & r, uint8_t * d) { return emit_range(h, job, r, d); }, bytes);
+    if (rc)
+        return rc;
+    bytes += job.footer;
+    return LX_OK;
+}
+
 } // namespace
 
 namespace lxi
@@ -257,7 +264,7 @@ int text_append_dev(lx_handle * h, char const * who, int format, char const * pr
     try
     {
         TextJob job;
-        if ((rc = prepare(h, who, ck, format, 0, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, -1, job)))
+        if ((rc = prepare(h, who, ck, 0, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, -1, job)))
             return rc;
         return rec_append_ranges(h, job.rec, [&](RecRange const & r, uint8_t * out) { return emit_range(h, job, r, out); }, d_carry, carry, sink);
     }
@@ -294,25 +301,10 @@ int lx_render_text_dev(lx_handle * h, int format, int write_header, char const *
     try
     {
         TextJob job;
-        if ((rc = prepare(h, "lx_render_text_dev", ck, format, write_header, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt,
-                          footer_records, job)))
-            return rc;
         std::string bytes;
-        bytes.reserve(job.rec.header.size() + job.rec.total + job.footer.size());
-        bytes = job.rec.header;
-        if ((rc = ensure(h, h->bam.d_stream, std::max<uint64_t>(job.rec.max_range, 16))))
+        if ((rc = prepare(h, "lx_render_text_dev", ck, write_header, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, footer_records, job)) ||
+            (rc = drain(h, job, bytes)))
             return rc;
-        uint8_t * const d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
-        for (RecRange const & r : job.rec.ranges)
-        {
-            if ((rc = emit_range(h, job, r, d)))
-                return rc;
-            size_t const at = bytes.size();
-            bytes.resize(at + r.bytes);
-            LX_HIP(h, hipMemcpyAsync(&bytes[at], d, r.bytes, hipMemcpyDeviceToHost, h->stream));
-            LX_HIP(h, hipStreamSynchronize(h->stream));
-        }
-        bytes += job.footer;
         *out = bytes_adopt(std::move(bytes));
     }
     catch (std::bad_alloc const &)
@@ -340,76 +332,27 @@ int lx_write_text_dev(lx_handle * h, char const * path, int format, int bgzf, ch
     if ((rc = rec_begin(h)))
         return rc;
     HostPool::Call       in_call;
-    std::vector<uint8_t> packed; // bgzf: the members; plain: the text.  The file is written at once, when everything is made
+    std::string          text;   // plain: the file.  It is written at once, when everything is made
+    std::vector<uint8_t> packed; // bgzf: its members
     try
     {
         TextJob job;
-        if ((rc = prepare(h, "lx_write_text_dev", ck, format, 1, program, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, opt, footer_records,
-                          job)))
+        if ((rc = prepare(h, "lx_write_text_dev", ck, 1, m, n, ops, ops_bytes, names, q_res_ascii, q_ascii_off, footer_records, job)))
             return rc;
-        RecJob const &    rec = job.rec;
-        hipStream_t const s   = h->stream;
         if (!bgzf)
         {
-            packed.reserve((size_t)(rec.header.size() + rec.total + job.footer.size()));
-            packed.assign(rec.header.begin(), rec.header.end());
-            if ((rc = ensure(h, h->bam.d_stream, std::max<uint64_t>(rec.max_range, 16))))
+            if ((rc = drain(h, job, text)))
                 return rc;
-            uint8_t * const d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
-            for (RecRange const & r : rec.ranges)
-            {
-                if ((rc = emit_range(h, job, r, d)))
-                    return rc;
-                size_t const at = packed.size();
-                packed.resize(at + r.bytes);
-                LX_HIP(h, hipMemcpyAsync(&packed[at], d, r.bytes, hipMemcpyDeviceToHost, s));
-                LX_HIP(h, hipStreamSynchronize(s));
-            }
-            packed.insert(packed.end(), job.footer.begin(), job.footer.end());
         }
         else
         {
-            // the stream buffer: what is carried (the header in front of the first range, less than a block later) + a range + the footer
-            uint64_t const carry_max = std::max<uint64_t>(rec.header.size(), lx::kBgzfBlock);
-            if ((rc = ensure(h, h->bam.d_stream, carry_max + rec.max_range + job.footer.size() + 16)))
+            if ((rc = rec_stream_front(h, job.rec, job.rec.header, job.footer.size())))
                 return rc;
-            uint8_t * const d = static_cast<uint8_t *>(h->bam.d_stream.ptr);
-            packed.reserve((size_t)((rec.header.size() + rec.total) / 3 + 4096));
-            auto sink = [&](uint8_t const * members, uint64_t bytes) -> int
-            {
-                packed.insert(packed.end(), members, members + bytes);
-                return LX_OK;
-            };
-            uint64_t carry = rec.header.size();
-            if (carry)
-                LX_HIP(h, hipMemcpyAsync(d, rec.header.data(), carry, hipMemcpyHostToDevice, s));
-            if (rec.ranges.empty())
-            {
-                if (!job.footer.empty())
-                    LX_HIP(h, hipMemcpyAsync(d + carry, job.footer.data(), job.footer.size(), hipMemcpyHostToDevice, s));
-                if (carry + job.footer.size() && (rc = bgzf_compress_dev(h, d, carry + job.footer.size(), sink)))
-                    return rc;
-            }
-            for (size_t i = 0; i < rec.ranges.size(); ++i)
-            {
-                RecRange const & r    = rec.ranges[i];
-                bool const       last = i + 1 == rec.ranges.size();
-                if ((rc = emit_range(h, job, r, d + carry)))
-                    return rc;
-                uint64_t have = carry + r.bytes;
-                if (last && !job.footer.empty())
-                {
-                    LX_HIP(h, hipMemcpyAsync(d + have, job.footer.data(), job.footer.size(), hipMemcpyHostToDevice, s));
-                    have += job.footer.size();
-                }
-                uint64_t const whole = last ? have : have / lx::kBgzfBlock * lx::kBgzfBlock;
-                if ((rc = bgzf_compress_dev(h, d, whole, sink)))
-                    return rc;
-                carry = have - whole;
-                if (carry && whole) // (whole is at least a block, the rest less: the two do not overlap)
-                    LX_HIP(h, hipMemcpyAsync(d, d + whole, carry, hipMemcpyDeviceToDevice, s));
-            }
-            LX_HIP(h, hipStreamSynchronize(s));
+            packed.reserve((size_t)((job.rec.header.size() + job.rec.total) / 3 + 4096));
+            uint64_t carry = job.rec.header.size();
+            if ((rc = rec_encode_ranges(h, job.rec, [&](RecRange const & r, uint8_t * d) { return emit_range(h, job, r, d); }, &carry, &job.footer,
+                                        true, rec_collect(packed))))
+                return rc;
             packed.insert(packed.end(), lx::kEofMember, lx::kEofMember + sizeof(lx::kEofMember));
         }
     }
@@ -417,12 +360,7 @@ int lx_write_text_dev(lx_handle * h, char const * path, int format, int bgzf, ch
     {
         return fail(h, LX_ENOMEM, "lx_write_text_dev: out of host memory");
     }
-    std::FILE * f = std::fopen(path, "wb");
-    if (!f)
-        return fail(h, LX_EINVAL, "cannot open %s", path);
-    bool ok = std::fwrite(packed.data(), 1, packed.size(), f) == packed.size();
-    ok      = (std::fclose(f) == 0) && ok;
-    return ok ? LX_OK : fail(h, LX_EINVAL, "error while writing %s (disk full?)", path);
+    return bgzf ? rec_write_file(h, path, packed.data(), packed.size()) : rec_write_file(h, path, text.data(), text.size());
 }
 
 } // extern "C"

@@ -1,5 +1,5 @@
 // lx_toprec.hip -- _writeRecord's sort / unique / sort / cut (/root/reference/src/search_algo.hpp:820-882; the host form is
-// lx_postprocess_records, host/lx_output.cpp) for lx_blast_match rows that stand in device memory grouped by n_qid (gfx950).
+// lx_postprocess_records, host/lx_postprocess.cpp) for lx_blast_match rows that stand in device memory grouped by n_qid (gfx950).
 //
 // Per run of equal n_qid (a "segment"; a run, not a query: rows that are not grouped give one segment per run, as on the host):
 //   order 1   ascending by (n_sid, q_start, q_end, s_start, s_end, q_frame, s_frame) -- the five coordinates as unsigned 64-bit
