@@ -65,7 +65,7 @@ int lx_plan_step(lx_scoring const * sc, uint64_t max_qlen, uint64_t max_slen, ui
         default: out->lds_bytes = (uint64_t)out->queries_per_wavefront * lx::score_pair_profile_bytes(lxi::pair_cfg_of(pl.cfg), nrows) + 64 * 8 * 4; break;
     }
     // the a-priori bound may_decline is derived from
-    out->score_bound = (uint64_t)lxi::score_bound(f, max_qlen, pl.steps, G);
+    out->score_bound = (uint64_t)(lxi::score_bound(f, max_qlen, pl.steps, G) + (pl.family == lxi::kHalfSweep ? lxi::half_frame_bias(f, G) : 0));
     return LX_OK;
 }
 

@@ -9,10 +9,30 @@
 // exactly and -inf stands in for "minus infinity", so
 // the results are bit-identical to the int32 kernel AS LONG AS no intermediate exceeds 2048.  That is decided per
 // wavefront from an upper bound:
-//         sum_j max(0, max_b s(q_j, b))  +  |ge| * (rows processed)  +  max entry  <=  2046
-// (a local alignment cannot score more than the sum of the best positive score of each query column).  A wavefront
+//         sum_j max(0, max_b s(q_j, b))  +  |ge| * (rows processed)  +  max entry  +  B  <=  2046
+// (a local alignment cannot score more than the sum of the best positive score of each query column; B: below).  A wavefront
 // that fails the test writes the sentinel -1 for its extensions and the host follows up with the int32 kernel in
 // "fix-up" mode, which recomputes exactly those.  Nothing is approximated.
+//
+// The biased frame.  Two of the three adds per pair of cells add a wave-constant gap cost: A = h + g2 and E = max(E, A) + ge.
+// The bit pattern of a non-negative value n * 2^-24 is n, so such an add is ONE 32-bit integer subtract of |c| * 0x10001 for
+// both halves -- v_sub_u32 with two VGPR operands, which gfx950 issues at about 1.75 times the rate of the packed ops
+// (profiles/r03_ubench_valu_issue_rates.txt; in the sweep's dependent mix: profiles/r12_ubench_swar.txt) -- as long as no half
+// borrows, i.e. the minuend is a non-negative pattern >= the subtrahend in BOTH halves.  For that the skewed frame is raised by
+//         B = |g2| + |ge| * G :      Z starts at ge * g + B  >=  |g2| + |ge|  (smallest in lane group G - 1 at step 0)
+// and grows by |ge| per step.  Then, in every lane, half and step:
+//   * F0 >= Z: it starts at Z and is max3(F0, A, ZN) afterwards, ZN being the next step's Z;
+//   * h = max3(tt, E, F0) >= F0 >= Z > 0, whatever tt and E are: columns beyond the query and rows before or behind the window
+//     (profile rows of the pad letter, tt far below) and the first lane group's E = -inf only lose that maximum;
+//   * A = h - |g2| >= Z - |g2| >= |ge|: no borrow, A is finite and >= 0;
+//   * max(E, A) >= A is finite (-inf, 0xfc00, never reaches a subtract), and E' = max(E, A) - |ge| >= 0: no borrow.
+// An idle half (an extension beyond the list) is always the HIGH half or the whole pair: its letters are pad letters or valid
+// subject bytes and the same argument holds; and a borrow out of the high half would leave the register, never enter the low one.
+// Everything that leaves the kernel is a difference of two values of one frame -- the codes h - Z, h - E, Hrow - z_i,
+// Hrow - F0 - ge, and rowmax - Z for the best score -- so B cancels: nothing but Z's start value, the two subtracts and the
+// exactness test knows about it.  The third add, tt = dg + sub, adds a profile entry that may be negative: it stays packed.
+// B is tested as the plain integer it is (never through hunits' clamp); lx_set_scoring admits |g2| <= 119 and |ge| <= 27, so
+// B <= 551, and the planner adds the same B to its a-priori bound (lx_step_plan.cpp, half_frame_bias).
 //
 // LDS: one query profile per wavefront in half precision, lane-contiguous rows (24 halves = 48 B per lane per subject
 // letter, read with two ds_read_b128 + one ds_read_b64); the two subject letters of a lane give two reads whose
@@ -179,7 +199,8 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     // wavefront, the residues need not be looked at: two dependent loads per column in front of everything else)
     int const col0  = g * C;
     int       bound = lq * sc->smax;
-    if (__ballot(bound + (-ge) * (steps + G + 2) + sc->smax + 2 > 2046) != 0)
+    int const bias  = (-sc->g2) + (-ge) * G; // B of the biased frame (header comment): plain integers, never hunits' clamp
+    if (__ballot(bound + (-ge) * (steps + G + 2) + sc->smax + 2 + bias > 2046) != 0)
     {
         bound = 0;
 #pragma unroll
@@ -194,7 +215,7 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
             bound += __shfl_xor(bound, off * kGs);
     }
     // (every group summed its own query; one block over the limit sends the whole wavefront to the fix-up launch)
-    bool too_big = __ballot((lq > Geo::kPanel) || (bound + (-ge) * (steps + G + 2) + sc->smax + 2 > 2046)) != 0;
+    bool too_big = __ballot((lq > Geo::kPanel) || (bound + (-ge) * (steps + G + 2) + sc->smax + 2 + bias > 2046)) != 0;
     if constexpr (CKPT)
     {
         // LX_OPT_MAX_QLEN / LX_OPT_MAX_SLEN promise broken: reported here (the int32 launch, which would report it too, is
@@ -273,8 +294,17 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
     uint32_t const row_base  = (uint32_t)(slot_dw + g * Geo::kLaneDw) * 4u;
     constexpr uint32_t kRowBytes = Geo::kRowDw * 4;
 
-    h2 const GE = hunits(ge), G2 = hunits(sc->g2), NGE = hunits(-ge);
-    h2       Z  = hunits(ge * g); // z_i of the first processed row i = -g
+    h2 const GE = hunits(ge), NGE = hunits(-ge);
+    // the two wave-constant gap adds of the column step as 32-bit integer subtracts of both halves at once (header comment);
+    // the constants are pinned in VGPRs: v_sub_u32 is full-rate only with two VGPR operands (tools/ubench.hip)
+    // (the 24-column score-only form keeps the packed adds: it stands at 167 VGPRs, and two more cost it the third wavefront per
+    // SIMD -- 192-column queries, pass 1 alone: 15.14 -> 15.31 ms with the subtracts)
+    constexpr bool kIntSub = CKPT || C != 24;
+    h2 const       G2 = hunits(sc->g2);
+    uint32_t       G2u = (uint32_t)(-sc->g2) * 0x10001u, GEu = (uint32_t)(-ge) * 0x10001u;
+    if constexpr (kIntSub)
+        asm volatile("" : "+v"(G2u), "+v"(GEu));
+    h2       Z  = hunits(ge * g + bias); // z_i of the first processed row i = -g, plus the frame's bias
     h2       Hrow[C], F0[C];
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -347,9 +377,9 @@ __global__ __launch_bounds__(64, (CKPT ? (C > 19 ? 2 : LX_F16_CKPT_WAVES) : 1)) 
             h2 const       tt  = dg + sub;
             dg                 = Hrow[c];
             h                  = hmax3(tt, Ecur, F0[c]);
-            h2 const A         = h + G2;
+            h2 const A         = kIntSub ? as_h2(as_u32(h) - G2u) : h + G2; // h + g2: h >= Z >= |g2| in both halves
             F0[c]              = hmax3(F0[c], A, ZN); // (floating-point max is not re-associated: no fences needed)
-            Ecur               = hmax(Ecur, A) + GE;
+            Ecur               = kIntSub ? as_h2(as_u32(hmax(Ecur, A)) - GEu) : hmax(Ecur, A) + GE; // max(E, A) + ge: A is finite and >= |ge|
             Hrow[c]            = h;
             if (c & 1)
                 rowmax = hmax3(rowmax, Hrow[c - 1], h);

@@ -50,6 +50,12 @@ int64_t score_bound(SchemeFacts const & sc, uint64_t max_qlen, uint32_t steps, i
     return (int64_t)max_qlen * std::max(sc.smax_entry, 0) + (int64_t)(-sc.gap_extend) * ((int64_t)steps + G + 2) + (sc.smax_entry - sc.gap_extend) + 2;
 }
 
+int64_t half_frame_bias(SchemeFacts const & sc, int G)
+{
+    // (|g2| + |ge| * G with g2 = gap_open - gap_extend, as lx_score_f16.hip adds it to its exactness test)
+    return (int64_t)(sc.gap_extend - sc.gap_open) + (int64_t)(-sc.gap_extend) * G;
+}
+
 uint32_t steps_for(uint64_t max_slen, int G)
 {
     return (uint32_t)((max_slen + G - 1 + 15) & ~15ull);
@@ -410,7 +416,8 @@ SweepCand one_query_candidate(SchemeFacts const & sc, StepOptions const & o, Swe
         c.stride = c.wide_compact ? (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.cfg, c.steps) : lx::ckpt_pair_slot_dwords(c.cfg, c.steps);
         c.runs   = packed_fits(o, c.stride);
         // (the packed kernel cannot decline when even the worst query passes its test)
-        c.may_decline = score_bound(sc, o.max_qlen, c.steps, G) > kCompactMaxScore || c.wide_compact;
+        // (the packed-half kernel computes in a frame raised by half_frame_bias and tests with it in; the int16 one has no bias)
+        c.may_decline = c.wide_compact || score_bound(sc, o.max_qlen, c.steps, G) + half_frame_bias(sc, G) > kCompactMaxScore;
         if (c.runs && c.may_decline)
             c.ovf_cap = overflow_slots(o, c);
     }

@@ -59,6 +59,9 @@ bool     fits_int16(SchemeFacts const & sc, uint64_t max_qlen, uint64_t max_slen
 // on the actual query: this is the a-priori bound); beyond kCompactMaxScore the compact codes cannot hold it
 int64_t  score_bound(SchemeFacts const & sc, uint64_t max_qlen, uint32_t steps, int G);
 constexpr int64_t kCompactMaxScore = 2046;
+// what the packed-half sweep (kHalfSweep) adds to that bound: the constant its frame is raised by so that no value of the sweep is
+// negative (lx_score_f16.hip, "the biased frame"); the other families have none
+int64_t  half_frame_bias(SchemeFacts const & sc, int G);
 // steps of a window of max_slen rows in G-lane groups, in whole layout blocks of 16
 uint32_t steps_for(uint64_t max_slen, int G);
 // panels of `panel` columns that hold the query (at least one)

@@ -182,6 +182,43 @@ DEF_KERNEL_F16(k_pkaddf_nrm, I_PKADDF, I_PKADDF_NEG, 0x4400, 0x3c00)
 DEF_KERNEL_F16(k_pkmax3f_sub, I_PKMAX3F, I_PKMAX3F, 1, 1)
 DEF_KERNEL_F16(k_pkmax3f_nrm, I_PKMAX3F, I_PKMAX3F, 0x4400, 0x3c00)
 
+// round 12: the sweep's mix with two of its three packed adds done as v_sub_u32 on VGPR operands (full-rate class), which is exact
+// on the 2^-24 unit's non-negative patterns.  Does the full-rate class pay when each subtract feeds a dependent half-rate
+// instruction on the same register, as it does in the column step (max3 -> sub -> max3, max -> sub -> ...)?
+// "sweep_mix" above adds without bound and so runs on infinities; these two templates are compared with each other on the SAME
+// in-range operands and compute the same values: both halves stay in 0x200 .. 0x30e (the chain adds x = 2k, then takes k off
+// twice, k in 1 .. 0x80; every maximum is with +-x <= the chain's value; the permute's selector is the identity on the chain).
+// k_sweepmix_rng is sweep_mix's order and classes with v_pk_add_f16 (the kernel's own add), k_sweepmix3 the variant.
+#define DEF_KERNEL_SWAR(NAME, INS)                                                                     \
+    __global__ __launch_bounds__(256) void NAME(int * out, int iters, int, int)                        \
+    {                                                                                                  \
+        int const t  = threadIdx.x;                                                                    \
+        int const b  = (0x200 + (t & 0x7)) * 0x10001;                                                  \
+        int a0 = b, a1 = b + 0x10001, a2 = b + 0x20002, a3 = b + 0x30003, a4 = b + 0x40004,            \
+            a5 = b + 0x50005, a6 = b + 0x60006, a7 = b + 0x70007;                                      \
+        int const k   = (1 + (t & 0x7f)) * 0x10001;                                                    \
+        int const vx  = 2 * k, vy = vx | (int)0x80008000u; /* +x, -x */                                \
+        int const vkn = k | (int)0x80008000u;              /* -k as packed halves */                   \
+        int const sel = 0x07060504 + (t >> 8);             /* identity on src0; t < 256 */             \
+        for (int i = 0; i < iters; ++i)                                                                \
+        {                                                                                              \
+            asm volatile(REP8(INS) REP8(INS) REP8(INS) REP8(INS)                                       \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) \
+                         : "v"(vx), "v"(vy), "v"(k), "v"(vkn), "v"(sel));                              \
+        }                                                                                              \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;            \
+    }
+#define I_SWEEPMIX_RNG(R)                                                                                                   \
+    "v_pk_add_f16 " R ", " R ", %8\n v_pk_maximum3_f16 " R ", " R ", %8, %9\n v_pk_add_f16 " R ", " R ", %11\n"              \
+    "v_pk_maximum3_f16 " R ", " R ", %9, %8\n v_pk_maximum3_f16 " R ", " R ", %8, %8\n v_pk_add_f16 " R ", " R ", %11\n"      \
+    "v_perm_b32 " R ", " R ", %8, %12\n"
+#define I_SWEEPMIX3(R)                                                                                                      \
+    "v_pk_add_f16 " R ", " R ", %8\n v_pk_maximum3_f16 " R ", " R ", %8, %9\n v_sub_u32 " R ", " R ", %10\n"                 \
+    "v_pk_maximum3_f16 " R ", " R ", %9, %8\n v_pk_maximum3_f16 " R ", " R ", %8, %8\n v_sub_u32 " R ", " R ", %10\n"         \
+    "v_perm_b32 " R ", " R ", %8, %12\n"
+DEF_KERNEL_SWAR(k_sweepmix_rng, I_SWEEPMIX_RNG)
+DEF_KERNEL_SWAR(k_sweepmix3, I_SWEEPMIX3)
+
 // LDS: ds_read_b32 with a lane-linear address pattern
 __global__ __launch_bounds__(256) void k_lds_b32(int * out, int iters, int x, int y)
 {
@@ -246,6 +283,31 @@ static void run_subnormal(int * d_out)
         }
 }
 
+// `ubench.bin swar`: the round-12 gate.  sweep_mix (unbounded operands, for reference), its in-range form and sweep_mix3, three
+// times each at 2, 3, 4 and 8 wavefronts per SIMD; first a check that the two in-range templates compute the same values.
+static void run_swar(int * d_out)
+{
+    size_t const         n = 256 * 256;
+    std::vector<int>     a(n), b(n);
+    hipLaunchKernelGGL(k_sweepmix_rng, dim3(256), dim3(256), 0, 0, d_out, 100, 0, 0);
+    CHECK(hipMemcpy(a.data(), d_out, n * sizeof(int), hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL(k_sweepmix3, dim3(256), dim3(256), 0, 0, d_out, 100, 0, 0);
+    CHECK(hipMemcpy(b.data(), d_out, n * sizeof(int), hipMemcpyDeviceToHost));
+    size_t diff = 0;
+    for (size_t i = 0; i < n; ++i)
+        diff += a[i] != b[i];
+    // lane 0 of block 0: eight chains back at their start values 0x200 .. 0x207 in both halves
+    printf("---- sweep_mix_rng vs sweep_mix3: %zu of %zu outputs differ; out[0] = 0x%08x (expected 0x%08x)\n", diff, n,
+           (unsigned)a[0], (unsigned)((8 * 0x200 + 28) * 0x10001));
+    for (int w : {2, 3, 4, 8})
+        for (int rep = 0; rep < 3; ++rep)
+        {
+            run("sweep_mix(x7)", k_sweepmix, d_out, w, 7);
+            run("sweep_mix_rng(x7)", k_sweepmix_rng, d_out, w, 7);
+            run("sweep_mix3(x7)", k_sweepmix3, d_out, w, 7);
+        }
+}
+
 int main(int argc, char ** argv)
 {
     hipDeviceProp_t prop;
@@ -256,6 +318,11 @@ int main(int argc, char ** argv)
     if (argc > 1 && std::string(argv[1]) == "subnormal")
     {
         run_subnormal(d_out);
+        return 0;
+    }
+    if (argc > 1 && std::string(argv[1]) == "swar")
+    {
+        run_swar(d_out);
         return 0;
     }
     struct
