@@ -800,7 +800,9 @@ void            lx_bytes_free(lx_bytes * b);
  * specification 4.2): magic, the SAM header text with one @SQ line per subject (BAM always carries the references, as seqan's
  * writeHeader does), the reference list, then the SAM writer's records in binary (refID = n_sid, MAPQ 255, bin by reg2bin over the
  * CIGAR's reference span, no mate, QUAL 0xFF per base or opt->q_qual's bytes - 33; tag types ae f, AS ap S, ar ai C, qf sf c, lt NM IH I, st ls qs OC Z,
- * src/search_output.hpp:601-717).  LX_EINVAL as lx_write_records_ex; *out is released with lx_bytes_free. */
+ * src/search_output.hpp:601-717).  LX_EINVAL as lx_write_records_ex, and, for LX_OUT_BAM here and in every other call that makes BAM,
+ * for a subject of more than 2^31 - 1 letters (l_ref and pos have 32 signed bits; lx_last_output_error() names the subject; the text
+ * formats are not limited).  *out is released with lx_bytes_free. */
 int lx_render_records(int format, int write_header, char const * program, lx_blast_match const * m, uint64_t n, uint8_t const * ops,
                       lx_seq_names const * names, uint8_t const * q_res_ascii, uint64_t const * q_ascii_off,
                       lx_output_options const * opt, int64_t footer_records, lx_bytes ** out);

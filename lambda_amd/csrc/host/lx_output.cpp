@@ -114,7 +114,7 @@ std::string cigarOf(lx_blast_match const & m, uint8_t const * ops, uint64_t qLen
     std::string c;
     for (auto const & e : el)
         c += std::to_string(e.second) + e.first;
-    return c;
+    return c.empty() ? "*" : c; // (no element at all: the field is "*" in SAM, as BAM's empty list reads; [UPSTREAM-RECALL] seqan's SAM writer)
 }
 
 // The protein-space cigar of tag OC: blastMatchOneCigar for a protein query (transFac 1, no frame clips: BLASTP / TBLASTN,
@@ -346,15 +346,21 @@ struct SamFields
     bool                  haveQual = false; // (false: QUAL is absent; qual is cut as SEQ is)
     int                   flag     = 0;
     int32_t               refId    = 0;
-    uint64_t              pos      = 0; // 0-based
+    int64_t               pos      = 0;     // 0-based; of an untranslated subject: the 64 unsigned bits of s_start
+    bool                  posSigned = false; // a translated subject's: it is negative for most minus-frame hits
     std::vector<TagValue> tags;         // in the order myWriteRecord appends them (:601-719)
 };
 
 // the SAM line of a record; the integer tags print as i whatever width BAM gives them
 void samLine(Sink & f, SamFields const & r)
 {
-    f.print("%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t%s", r.qname.c_str(), r.flag, r.sname.c_str(), (unsigned long long)(r.pos + 1), r.cigar.c_str(),
-            r.seq.c_str(), r.haveQual ? r.qual.c_str() : "*");
+    unsigned long long const pos1 = (unsigned long long)r.pos + 1;
+    f.print("%s\t%d\t%s\t", r.qname.c_str(), r.flag, r.sname.c_str());
+    if (r.posSigned)
+        f.print("%lld", (long long)pos1);
+    else
+        f.print("%llu", pos1);
+    f.print("\t255\t%s\t*\t0\t0\t%s\t%s", r.cigar.c_str(), r.seq.c_str(), r.haveQual ? r.qual.c_str() : "*");
     for (TagValue const & t : r.tags)
         if (t.type == 'f')
             f.print("\t%s:f:%g", t.key, (double)t.f);
@@ -395,7 +401,7 @@ void bamRecord(std::string & o, SamFields const & r)
 {
     std::string const & cigar = r.cigar, & seq = r.seq, & qname = r.qname;
     std::string const * const qual = r.haveQual ? &r.qual : nullptr;
-    int64_t const       pos0 = (int64_t)r.pos;
+    int64_t const       pos0 = r.pos; // (BAM keeps its low 32 bits)
     int const           flag = r.flag;
     std::vector<uint32_t> ops;
     int64_t               span = 0;
@@ -589,6 +595,16 @@ int resolve_output(int format, char const * program, lx_blast_match const * m, u
         return LX_EINVAL;
     if (format == LX_OUT_BLAST_TAB_COMMENTS)
         m9Texts(program, rq);
+    // BAM holds a reference's length and a record's position in 32 signed bits (specification 4.2): a longer subject would wrap both
+    // silently.  Every BAM entry point resolves its request here, before a file or a device is touched; the text formats print 64 bits
+    if (format == LX_OUT_BAM && names->s_lens)
+        for (uint64_t i = 0; i < names->n_s; ++i)
+            if (names->s_lens[i] > 0x7fffffffull)
+            {
+                g_output_error = "subject \"" + firstWord(names->s_ids ? names->s_ids[i] : nullptr) + "\" (number " + std::to_string(i) + ") has " +
+                                 std::to_string(names->s_lens[i]) + " letters: BAM holds at most 2147483647 (2^31 - 1) per reference";
+                return LX_EINVAL;
+            }
     return LX_OK;
 }
 
@@ -860,13 +876,14 @@ bool samFields(OutputRequest const & rq, Records const & in, uint64_t lo, uint64
     if (writeSeq && in.q_res_ascii && in.q_ascii_off)
         samSeqQual(rq, in, b, r);
     // POS: a translated subject is reported in nucleotide space (:493-499; the minus-strand branch there
-    // subtracts from the QUERY length -- restated as it stands)
-    r.pos = b.s_start;
+    // subtracts from the QUERY length -- restated as it stands).  That difference is a signed quantity: beginPos is, and a query is
+    // shorter than where most hits begin
+    r.pos       = (int64_t)b.s_start;
+    r.posSigned = rq.s_trans;
     if (rq.s_trans)
     {
-        r.pos = b.s_start * 3 + (uint64_t)std::abs((int)b.s_frame) - (b.s_frame != 0 ? 1 : 0);
-        if (b.s_frame < 0)
-            r.pos = qLen - r.pos;
+        uint64_t const p = b.s_start * 3 + (uint64_t)std::abs((int)b.s_frame) - (b.s_frame != 0 ? 1 : 0);
+        r.pos            = (int64_t)(b.s_frame < 0 ? qLen - p : p);
     }
     samTags(rq, in, b, hi - lo, lca, writeSeq, protCigar, proteins, r.tags);
     return true;

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kBamEmitBlock) void bam_emit_kernel(BamCtx c, uint6
             md += (uint64_t)__shfl_xor((unsigned long long)md, s);
         span = (int64_t)(md * r.trans);
     }
-    int64_t const pos0 = (int64_t)r.pos;
+    int64_t const pos0 = r.pos; // (its low 32 bits are stored)
     int const     flag = (r.first ? 0 : 256) | (r.minus ? 16 : 0);
     w.le<uint32_t>(size - 4, 4); // block_size
     w.le<int32_t>((int32_t)b.n_sid, 4);

@@ -49,7 +49,8 @@ struct LcaCursor
 };
 
 // The refusals that need no look at a row, in the host writer's order: NULL names / rows / program, an unknown program, an unknown
-// tag key or column specifier (lx_last_output_error() has that text).  A format that is neither SAM nor BAM counts as tabular.
+// tag key or column specifier, for LX_OUT_BAM a subject of more than 2^31 - 1 letters (lx_last_output_error() has that text).  A format
+// that is neither SAM nor BAM counts as tabular.
 int resolve_output(int format, char const * program, lx_blast_match const * m, uint64_t n, lx_seq_names const * names,
                    lx_output_options const * opt_in, OutputRequest & rq);
 // LX_EINVAL if a row names a query or a subject the name lists do not have; `text` (or none: NULL) becomes lx_last_output_error()

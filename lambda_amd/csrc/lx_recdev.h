@@ -87,7 +87,7 @@ struct Rec
     uint64_t               qs_shift;
     uint64_t               qn_at;
     uint32_t               qn_len;
-    uint64_t               pos;
+    int64_t                pos; // 0-based; signed where the subject is translated (c.s_trans), else the 64 unsigned bits of s_start
     uint32_t               lca, name_off, name_len; // name_len 0xffffffff: "*"
     uint64_t               st_lo, st_hi;            // the subject's taxa (st_lo == st_hi: "*")
 };
@@ -183,14 +183,13 @@ __device__ __forceinline__ Rec rec_of(BamCtx const & c, uint64_t k)
         else
             r.qs_len = fl;
     }
-    // POS (the minus-strand branch subtracts from the QUERY length, as the host writer does)
-    r.pos = b.s_start;
+    // POS (the minus-strand branch subtracts from the QUERY length, as the host writer does: a signed difference)
+    r.pos = (int64_t)b.s_start;
     if (c.s_trans)
     {
-        int const sf = (int)b.s_frame;
-        r.pos        = b.s_start * 3 + (uint64_t)(sf < 0 ? -sf : sf) - (sf != 0 ? 1 : 0);
-        if (sf < 0)
-            r.pos = r.qlen - r.pos;
+        int const      sf = (int)b.s_frame;
+        uint64_t const p  = b.s_start * 3 + (uint64_t)(sf < 0 ? -sf : sf) - (sf != 0 ? 1 : 0);
+        r.pos             = (int64_t)(sf < 0 ? r.qlen - p : p);
     }
     // taxonomy
     r.lca      = c.grp_lca ? c.grp_lca[r.g] : 0u;

@@ -2,7 +2,7 @@
 // (host/lx_output.cpp; seqan's writeRecord for BlastTabular behind myWriteRecord, src/search_output.hpp:463-733) and
 // samFields / samLine restated as kernels, byte for byte.  The host code is the specification: its quirks are kept (unsigned
 // wrap-around of coordinates that make no sense, the casts of the SAM tags, POS of a translated subject's minus strand taken from the
-// QUERY length, an empty CIGAR for a valid alignment without elements but "*" for tag OC).
+// QUERY length -- a signed number).
 //
 //   groups   lx_bam.hip's (bam_launch_groups): the row's group, the groups' first rows -- the comment lines and hit count of .m9,
 //            FLAG's secondary bit, tag IH, --sam-bam-seq uniq, the group's LCA.
@@ -47,6 +47,7 @@ static_assert(sizeof(TextNum::t[0]) >= 20, "a number text fits its slot");
 struct Count
 {
     uint64_t n = 0;
+    __device__ __forceinline__ uint64_t mark() const { return n; } // grows by the bytes put
     __device__ __forceinline__ void ch(uint8_t) { ++n; }
     __device__ __forceinline__ void dec(uint64_t v) { n += dec_digits(v); }
     template <class G>
@@ -64,6 +65,8 @@ struct Stage
     uint64_t  left; // bytes of the record not yet stored
     uint32_t  fill;
     int       lane;
+    // grows by the bytes put (a flush takes `fill` bytes off both)
+    __device__ __forceinline__ uint64_t mark() const { return fill - left; }
     __device__ __forceinline__ void flush()
     {
         __builtin_amdgcn_wave_barrier();
@@ -332,11 +335,18 @@ __device__ __forceinline__ void sam_record(W & w, TextCtx const & tc, Rec const 
     w.ch('\t');
     put_sname(w, tc, k);
     w.ch('\t');
-    w.dec(r.pos + 1);
+    uint64_t pos1 = (uint64_t)r.pos + 1;
+    if (c.s_trans && (int64_t)pos1 < 0) // samLine: signed where the subject is translated
+    {
+        w.ch('-');
+        pos1 = 0 - pos1;
+    }
+    w.dec(pos1);
     put_lit(w, "\t255\t", 5);
+    uint64_t const before = w.mark();
     if (a.n_cigar)
         put_cigar(w, c, r, o, b.n_ops);
-    else
+    if (w.mark() == before) // (another program, a byte that is no op, or cigarOf's list without an element)
         w.ch('*');
     put_lit(w, "\t*\t0\t0\t", 7);
     if (r.l_seq)
