@@ -516,7 +516,10 @@ int lx_iterate_matches_dev(lx_handle * h, int slot, void const * d_matches, uint
  * changes; the plan's wavefronts are laid out range by range.  out_plan: [bound * 16] slots -- position in the list, bit 31 = filler (a
  * copy that never survives), 0xffffffff beyond the plan's wavefronts --, out_pan / out_maxs: [bound] columns per lane of a wavefront's
  * widest query / its longest window, bound = lx_plan_free_packing_bound(n, n_qseq, nranges); out_report: [16] = {wavefronts, error
- * flag (0), runs, quads of the pool, first wavefront of range 0, 1, ..., nranges}.  tests/test_gpu_plan.py checks every slot. */
+ * flag (0), runs, quads of the pool, first wavefront of range 0, 1, ..., nranges}.  n_qseq: the number of query slices in the list, or
+ * more; a list with more runs than that allows (it is not grouped by query slice, or n_qseq is too small) and any other non-zero
+ * flag are LX_ESTATE with a text, the outputs then hold no plan.  tests/test_gpu_plan.py checks every slot against these promises,
+ * tests/test_gpu_plan_edges.py against a sequential model of the plan's rules. */
 uint64_t lx_plan_free_packing_bound(uint64_t n, uint64_t n_qseq, uint32_t nranges);
 int      lx_plan_free_packing_dev(lx_handle * h, void const * d_ext, uint64_t n, uint64_t n_qseq, int32_t strip_cols, uint32_t nranges, uint64_t const * cut,
                                   uint32_t * out_plan, uint32_t * out_pan, uint32_t * out_maxs, uint32_t * out_report);

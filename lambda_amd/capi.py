@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ.get("LX_LIB_PATH") or Path(__file__).resolve().parent
 LX_ALPH = 32
 LX_OK = 0
 LX_EINVAL = -1
+LX_ESTATE = -6
 LX_OPT_MAX_QLEN = 1
 LX_OPT_QUERY_RUN = 2
 LX_OPT_WORKSPACE_BYTES = 3

@@ -264,6 +264,17 @@ static int launch_free_plan(lx_handle * h, void const * d_ext, uint64_t n_qseq, 
     return LX_OK;
 }
 
+// A plan whose report carries a flag (report[1], FpLayout::overflow of lx_plan_free.hip) is no plan: what the flag says, as LX_ESTATE.
+static int free_plan_flag(lx_handle * h, uint64_t n, uint64_t n_qseq, uint64_t nwf, uint64_t cap_wf, uint32_t flag)
+{
+    if (flag == 3)
+        return fail(h, LX_ESTATE, "the free-packing plan of %llu windows: the list has more runs than the run bound %llu (fp_run_bound of %llu query sequences): "
+                                  "it is not grouped by query, or it holds more queries than stated",
+                    (unsigned long long)n, (unsigned long long)lx::fp_run_bound(n, n_qseq), (unsigned long long)n_qseq);
+    return fail(h, LX_ESTATE, "the free-packing plan of %llu windows reports %llu wavefronts (at most %llu), flag %u", (unsigned long long)n, (unsigned long long)nwf,
+                (unsigned long long)cap_wf, flag);
+}
+
 namespace
 {
 
@@ -540,8 +551,7 @@ private:
         uint32_t const * const rep = h_report();
         pt.nwf = rep[0];
         if (rep[1] || pt.nwf == 0 || pt.nwf > pt.cap_wf)
-            return fail(h, LX_ESTATE, "the free-packing plan of %llu windows reports %llu wavefronts (at most %llu), flag %u", (unsigned long long)pt.n,
-                        (unsigned long long)pt.nwf, (unsigned long long)pt.cap_wf, rep[1]);
+            return free_plan_flag(h, pt.n, l2.q_len.size(), pt.nwf, pt.cap_wf, rep[1]);
         for (size_t r = 0; r < pt.ranges(); ++r)
             pt.cut_wf.push_back(rep[4 + r + 1]);
         if (pt.cut_wf.back() != pt.nwf)
@@ -1050,6 +1060,8 @@ int lx_plan_free_packing_dev(lx_handle * h, void const * d_ext, uint64_t n, uint
     LX_HIP(h, hipMemcpyAsync(out_pan, fa.wf_pan, cap * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     LX_HIP(h, hipMemcpyAsync(out_maxs, fa.wf_maxs, cap * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     LX_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_report[1])
+        return free_plan_flag(h, n, n_qseq, out_report[0], cap, out_report[1]);
     return LX_OK;
 }
 

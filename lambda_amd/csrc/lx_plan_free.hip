@@ -6,22 +6,27 @@
 // a wavefront's eight lane groups hold windows of at most four queries.  The same plan lx_host.cpp's extend_pipeline makes on the
 // host threads for lists it is handed in host memory, made where the Level-2 driver's window list stands (lx_level2_host.cpp):
 //   * RUNS: the windows of one query slice (the list is sorted by query), cut every 512 list positions so that the per-run work
-//     below is bounded -- inside a run the windows are ranked by length, longest first, by counting;
+//     below is bounded -- inside a run the windows are ranked by length, longest first (ties: list order), by counting;
 //   * POOL: a run's windows clearly longer than its median (the merged windows, up to three times the ordinary length,
 //     :1153-1157) and those clearly shorter (windows clipped at their subject's end, :919-938 -- a tenth of a protein list), each
-//     kind filled up with the run's nearest ordinary windows to QUADS of four; the quads of the whole list are sorted by (columns
-//     per lane their query sweeps, length) and dealt four to a wavefront: a long window stretches three companions, not fifteen,
+//     kind filled up with the run's nearest ordinary windows to QUADS of four ("clearly": by more than slack = max(8, med / 8) rows
+//     beside med, the length at the run's sorted place c / 2; the short ones only where med > slack; the last quad of either kind
+//     may hold one to three windows); the quads of the whole list are sorted by (columns per lane their query sweeps, length of
+//     their FIRST window: fp_key16, stably, in run order) and dealt four to a wavefront: a long window stretches three companions, not fifteen,
 //     and a short one is swept beside windows of its own length instead of idling -- and forcing the sweep's checked steps on its
 //     wavefront -- for the rest of a long one's rows;
 //   * STREAM: everything else, run by run in order of (columns per lane, longest streamed window), PAIR by pair into wavefronts
-//     that close at eight pairs or before a fifth query.  The closing rule is sequential; it runs per SHARE of 64 runs (one
-//     wavefront of the plan kernel per share, a share starts a new wavefront), which leaves one wavefront per share partly empty;
+//     that close at eight pairs or before a fifth RUN (a query cut at 512 list positions counts once per run: never more than
+//     four queries, at times fewer than four would fit; a run that crosses into a wavefront is that wavefront's first).  The
+//     closing rule is sequential; it runs per SHARE of 64 runs (one wavefront of the plan kernel per share, a share starts a new
+//     wavefront), which leaves one wavefront per share partly empty;
 //   * RANGES: the list is cut into up to eight ranges of queries (the pipeline's chunks: a range's records are made while the
 //     next range is swept); range is the major key of both sorts, and the plan's wavefronts are laid out range by range, each as
 //     [its pool | its stream], so that a range is a contiguous piece of the plan.
 // Every window then knows its slot; what is left empty (the second half of a run's last pair, the end of a closed wavefront, of a
 // range's last pool wavefront) is filled with a copy of the slot before it, marked as filler (bit 31): it costs what the window
 // costs and never survives -- how the reference pads its SIMD batches (:1063-1067).
+// tests/plan_model.py restates these rules sequentially; tests/test_gpu_plan_edges.py holds every word of the plan against it.
 // Integer list work, HBM- and launch-bound; no DP here.
 #include <hip/hip_runtime.h>
 
@@ -40,11 +45,13 @@ namespace
 constexpr uint32_t kFpRunCut   = 512; // a run is cut at every multiple of this many list positions
 constexpr uint32_t kFpShare    = 64;  // sorted runs per share of the stream's closing rule
 constexpr uint32_t kFpEmpty    = 0xffffffffu;
+constexpr uint32_t kFpRunsOver = 3;   // FpLayout::overflow: the list has more runs than fp_run_bound (not grouped by query, or n_qseq understated)
 
 // device-side facts of a plan (FpArgs::layout)
 struct FpLayout
 {
-    uint32_t nruns, nquads, nwf, overflow;        // overflow: a slot beyond the plan's capacity (the bound of fp_wavefront_bound is wrong)
+    uint32_t nruns, nquads, nwf, overflow;        // overflow: 1 = a slot beyond the plan's capacity (the bound of fp_wavefront_bound is wrong),
+                                                  // 2 = a wavefront without a first slot, kFpRunsOver = more runs than the run-sized arrays hold
     uint32_t run_first[kFpMaxRanges + 1];         // first run of each range (run_first[nranges] = nruns): also the ranges' places in the sorted run order
     uint32_t quad_first[kFpMaxRanges + 1];        // first quad of each range: also its place in the sorted quad order
     uint32_t share_first[kFpMaxRanges + 1];       // first share of each range
@@ -122,22 +129,26 @@ struct RunHeadOut
 {
     uint32_t * rid;
     uint32_t * run_start;
+    uint32_t   rm;
     __device__ void operator()(uint64_t i, uint32_t incl, uint32_t ex) const
     {
         rid[i] = incl - 1u;
-        if (incl != ex)
+        if (incl != ex && incl - 1u < rm) // (a run beyond the bound has no entry: fp_runs_done_kernel raises the flag)
             run_start[incl - 1u] = (uint32_t)i;
     }
 };
 
-__global__ void fp_runs_done_kernel(FpWork w, uint64_t tiles, uint32_t n, FpRanges rg)
+// The list's run count against the bound every run-sized array was made for.  Beyond it the count is clamped and the flag raised:
+// no kernel below reads rid (which may hold runs >= rm) once it is, and every run is planned as an empty one -- no quad, no pair,
+// no wavefront --, so that the sorts, the scans and the layout still run over defined words.
+__global__ void fp_runs_done_kernel(FpWork w, uint64_t tiles, uint32_t n, uint32_t rm, FpRanges rg)
 {
-    uint32_t const nruns = w.block_tot[tiles];
-    w.layout->nruns      = nruns;
-    w.layout->overflow   = 0;
-    w.run_start[nruns]   = n;
+    uint32_t const counted = w.block_tot[tiles], nruns = min(counted, rm);
+    w.layout->nruns        = nruns;
+    w.layout->overflow     = counted > rm ? kFpRunsOver : 0u;
+    w.run_start[nruns]     = n;
     for (uint32_t r = 0; r < rg.n; ++r)
-        w.layout->run_first[r] = rg.cut[r] < n ? w.rid[rg.cut[r]] : nruns; // (a range begins where the query changes: with a run)
+        w.layout->run_first[r] = rg.cut[r] < n ? min(w.rid[rg.cut[r]], nruns) : nruns; // (a range begins where the query changes: with a run)
     w.layout->run_first[rg.n] = nruns;
 }
 
@@ -145,7 +156,7 @@ __global__ void fp_runs_done_kernel(FpWork w, uint64_t tiles, uint32_t n, FpRang
 __global__ __launch_bounds__(256) void fp_rank_kernel(Extension const * ext, uint32_t n, FpWork w)
 {
     uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
+    if (i >= n || w.layout->overflow)
         return;
     uint32_t const r = w.rid[i], a = w.run_start[r], b = w.run_start[r + 1];
     uint32_t const mine = ext[i].s_len;
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(256) void fp_run_kernel(Extension const * ext, uint
     uint32_t const r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rm)
         return;
-    uint32_t const nruns = w.layout->nruns;
+    uint32_t const nruns = w.layout->overflow ? 0u : w.layout->nruns; // (more runs than the bound: none was ranked, none is planned)
     if (r >= nruns)
     {
         // (beyond the list's runs: sorted behind every range's, takes no slot)
@@ -238,7 +249,7 @@ __global__ __launch_bounds__(256) void fp_quad_init_kernel(uint32_t qm, uint32_t
 __global__ __launch_bounds__(256) void fp_quad_keys_kernel(Extension const * ext, uint32_t n, int C, int no_narrow, FpRanges rg, FpWork w)
 {
     uint32_t const k = blockIdx.x * blockDim.x + threadIdx.x; // sorted position
-    if (k >= n)
+    if (k >= n || w.layout->overflow)
         return;
     uint32_t const r = w.rid[k], a = w.run_start[r], d = k - a, c = w.run_start[r + 1] - a;
     uint32_t const phi = w.run_npool[r] & 0xffffu, plo = w.run_npool[r] >> 16, d0 = c - plo; // [0, phi): the long quads, [d0, c): the short ones
@@ -388,6 +399,8 @@ __global__ __launch_bounds__(256) void fp_fill_kernel(Extension const * ext, int
                                                       FpWork w)
 {
     uint64_t const o    = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w.layout->overflow == kFpRunsOver) // (raised before any launch of this grid: uniform)
+        return;
     uint32_t const nwf  = min(w.layout->nwf, cap_wf);
     bool const     in   = o < 16ull * nwf;
     uint32_t       v    = in ? plan[o] : kFpEmpty;
@@ -426,7 +439,7 @@ __global__ __launch_bounds__(256) void fp_fill_kernel(Extension const * ext, int
     }
 }
 
-// what the host reads of the plan: [0] wavefronts, [1] flag, [2] runs, [3] quads, [4 + r] first wavefront of range r (r <= ranges)
+// what the host reads of the plan: [0] wavefronts, [1] flag (FpLayout::overflow; 3: more runs than fp_run_bound), [2] runs, [3] quads, [4 + r] first wavefront of range r (r <= ranges)
 __global__ void fp_report_kernel(FpLayout const * L, uint32_t nranges, uint32_t * report)
 {
     uint32_t const t = threadIdx.x;
@@ -549,8 +562,8 @@ hipError_t fp_launch_plan(FpArgs const & p, hipStream_t st)
         RunHeadVal const hv{p.ext};
         hipLaunchKernelGGL((l2_scan_reduce_kernel<kOpSum, false, RunHeadVal>), dim3((unsigned)tiles), sblock, 0, st, hv, n, w.block_tot);
         hipLaunchKernelGGL((l2_scan_tops_kernel<kOpSum>), dim3(1), sblock, 0, st, w.block_tot, tiles);
-        hipLaunchKernelGGL((l2_scan_apply_kernel<kOpSum, false, RunHeadVal, RunHeadOut>), dim3((unsigned)tiles), sblock, 0, st, hv, RunHeadOut{w.rid, w.run_start}, n, w.block_tot);
-        hipLaunchKernelGGL(fp_runs_done_kernel, dim3(1), dim3(1), 0, st, w, tiles, n32, rg);
+        hipLaunchKernelGGL((l2_scan_apply_kernel<kOpSum, false, RunHeadVal, RunHeadOut>), dim3((unsigned)tiles), sblock, 0, st, hv, RunHeadOut{w.rid, w.run_start, (uint32_t)z.rm}, n, w.block_tot);
+        hipLaunchKernelGGL(fp_runs_done_kernel, dim3(1), dim3(1), 0, st, w, tiles, n32, (uint32_t)z.rm, rg);
     }
     hipLaunchKernelGGL(fp_rank_kernel, grid(n), block, 0, st, p.ext, n32, w);
     hipLaunchKernelGGL(fp_run_kernel, grid(rm), block, 0, st, p.ext, rm, p.C, p.no_narrow, rg, w);

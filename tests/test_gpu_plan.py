@@ -2,6 +2,8 @@
 plans protein window lists with, where the reference sorts its list of alignments by the slices' lengths so that a SIMD batch's
 windows take about as many steps (/root/reference/src/search_algo.hpp:1229-1235).  Checked slot by slot, against the promises
 the sweep kernel relies on (LX_OPT_QUERY_RUN = 2) and against what makes a plan a good one."""
+import zlib
+
 import numpy as np
 import pytest
 
@@ -94,7 +96,7 @@ CASES = {
 @pytest.mark.parametrize("case", list(CASES))
 def test_every_slot_of_the_device_plan(handle, case):
     nq, windows, qlen, merged = CASES[case]
-    rng = np.random.default_rng(hash(case) % (1 << 31))
+    rng = np.random.default_rng(zlib.crc32(case.encode()))  # (fixed in the file: a failing list can be drawn again)
     ext = make_list(rng, nq, windows, qlen, merged)
     n = len(ext)
     plan, pan, maxs, rep = handle.plan_free_packing_dev(on_device(ext), n, nq)
