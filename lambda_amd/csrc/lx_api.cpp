@@ -46,7 +46,7 @@ int lx_plan_step(lx_scoring const * sc, uint64_t max_qlen, uint64_t max_slen, ui
     lxi::describe_plan(pl, out->name, sizeof(out->name));
     if (pl.family == lxi::kNoSweep)
         return LX_OK;
-    int const G = lx::trace_cfg_group(pl.cfg), C = lx::trace_cfg_panel(pl.cfg) / G, nrows = f.nrows();
+    int const G = pl.geo.g, C = pl.geo.c, nrows = f.nrows();
     out->group_lanes           = G;
     out->strip_cols            = C;
     out->panels                = (int32_t)pl.panels;
@@ -60,9 +60,9 @@ int lx_plan_step(lx_scoring const * sc, uint64_t max_qlen, uint64_t max_slen, ui
         out->queries_per_wavefront = 4; // (free packing: up to four, in any split of the eight lane groups)
     switch (pl.family)
     {
-        case lxi::kMqSweep: out->lds_bytes = lx::sweep_mq_lds_bytes(pl.cfg, pl.share < 0 ? sc->alphabet_size + 1 : nrows, pl.share); break;
+        case lxi::kMqSweep: out->lds_bytes = lx::sweep_mq_lds_bytes(pl.geo, pl.share < 0 ? sc->alphabet_size + 1 : nrows, pl.share); break;
         case lxi::kInt32Sweep: out->lds_bytes = (uint64_t)out->queries_per_wavefront * nrows * ((C + 3) / 4 * G) * 4 + 64 * 4 * 4; break;
-        default: out->lds_bytes = (uint64_t)out->queries_per_wavefront * lx::score_pair_profile_bytes(lxi::pair_cfg_of(pl.cfg), nrows) + 64 * 8 * 4; break;
+        default: out->lds_bytes = (uint64_t)out->queries_per_wavefront * lx::score_pair_profile_bytes(pl.geo, nrows) + 64 * 8 * 4; break;
     }
     // the a-priori bound may_decline is derived from
     out->score_bound = (uint64_t)(lxi::score_bound(f, max_qlen, pl.steps, G) + (pl.family == lxi::kHalfSweep ? lxi::half_frame_bias(f, G) : 0));

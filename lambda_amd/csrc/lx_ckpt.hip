@@ -1798,36 +1798,26 @@ __global__ __launch_bounds__(64, LX_BT_WAVES) void ckpt_backtrace_kernel(TracePa
     }
 }
 
-// ---- host-visible launchers: checkpoint geometries follow the trace geometries (cfg 1 = (8,19), cfg 2 = (16,13)), plus
-// cfg 3 = (8,13) for queries of up to 104 columns and cfg 4 = (8,25) for 153-200 columns --------
+// ---- host-visible launchers: the checkpoint geometries are the shared-profile ones of the direction bits, (8,19) and (16,13), plus
+// (8,13) for queries of up to 104 columns, (8,25) for 153-200 columns and (8,11) for the multi-query sweep --------
+using CkptGeos = GeoList<GeoT<8, 19>, GeoT<16, 13>, GeoT<8, 13>, GeoT<8, 25>, GeoT<8, 11>>;
 
-uint64_t ckpt_slot_dwords(int cfg, uint32_t steps_cap)
+// uint32 of one slot (0: no such layout): int16 pairs
+uint64_t ckpt_slot_dwords(Geo geo, uint32_t steps_cap)
 {
-    return cfg == 2   ? CkptLayout<16, 13>::slot_dwords(steps_cap)
-           : cfg == 3 ? CkptLayout<8, 13>::slot_dwords(steps_cap)
-           : cfg == 4 ? CkptLayout<8, 25>::slot_dwords(steps_cap)
-           : cfg == 5 ? CkptLayout<8, 11>::slot_dwords(steps_cap)
-                      : CkptLayout<8, 19>::slot_dwords(steps_cap);
+    return geo_dispatch(CkptGeos{}, geo, (uint64_t)0, [&](auto t) { return (uint64_t)CkptLayout<t.g, t.c>::slot_dwords(steps_cap); });
 }
 
 // pair slots of the packed-half sweep: what one window accounts for (a wavefront's region holds 128 / G of them)
-uint64_t ckpt_pair_slot_dwords(int cfg, uint32_t steps_cap)
+uint64_t ckpt_pair_slot_dwords(Geo geo, uint32_t steps_cap)
 {
-    return cfg == 2   ? CkptPairLayout<16, 13>::slot_dwords(steps_cap)
-           : cfg == 3 ? CkptPairLayout<8, 13>::slot_dwords(steps_cap)
-           : cfg == 4 ? CkptPairLayout<8, 25>::slot_dwords(steps_cap)
-           : cfg == 5 ? CkptPairLayout<8, 11>::slot_dwords(steps_cap)
-                      : CkptPairLayout<8, 19>::slot_dwords(steps_cap);
+    return geo_dispatch(CkptGeos{}, geo, (uint64_t)0, [&](auto t) { return (uint64_t)CkptPairLayout<t.g, t.c>::slot_dwords(steps_cap); });
 }
 
 // compact slots of the multi-query and the packed-int16 sweep
-uint64_t ckpt16_slot_dwords(int cfg, uint32_t steps_cap)
+uint64_t ckpt16_slot_dwords(Geo geo, uint32_t steps_cap)
 {
-    return cfg == 2   ? Ckpt16Layout<16, 13>::slot_dwords(steps_cap)
-           : cfg == 3 ? Ckpt16Layout<8, 13>::slot_dwords(steps_cap)
-           : cfg == 4 ? Ckpt16Layout<8, 25>::slot_dwords(steps_cap)
-           : cfg == 5 ? Ckpt16Layout<8, 11>::slot_dwords(steps_cap)
-                      : Ckpt16Layout<8, 19>::slot_dwords(steps_cap);
+    return geo_dispatch(CkptGeos{}, geo, (uint64_t)0, [&](auto t) { return (uint64_t)Ckpt16Layout<t.g, t.c>::slot_dwords(steps_cap); });
 }
 
 template <int G, int C>
@@ -1867,11 +1857,7 @@ hipError_t launch_ckpt_forward(TraceParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
-    return p.cfg == 2   ? launch_ckpt_forward_cfg<16, 13>(p, stream)
-           : p.cfg == 3 ? launch_ckpt_forward_cfg<8, 13>(p, stream)
-           : p.cfg == 4 ? launch_ckpt_forward_cfg<8, 25>(p, stream)
-           : p.cfg == 5 ? launch_ckpt_forward_cfg<8, 11>(p, stream)
-                        : launch_ckpt_forward_cfg<8, 19>(p, stream);
+    return geo_dispatch(CkptGeos{}, p.geo, hipErrorInvalidValue, [&](auto t) { return launch_ckpt_forward_cfg<t.g, t.c>(p, stream); });
 }
 
 static int backtrace_resident_waves()
@@ -1904,16 +1890,14 @@ hipError_t launch_ckpt_backtrace(TraceParams const & p_in, hipStream_t stream)
     hipError_t e = hipMemsetAsync(p.work_counter, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess)
         return e;
-    if (p.cfg == 2)
-        hipLaunchKernelGGL((ckpt_backtrace_kernel<16, 13>), dim3((unsigned)b2), dim3(64), 0, stream, p);
-    else if (p.cfg == 3)
-        hipLaunchKernelGGL((ckpt_backtrace_kernel<8, 13>), dim3((unsigned)b2), dim3(64), 0, stream, p);
-    else if (p.cfg == 4)
-        hipLaunchKernelGGL((ckpt_backtrace_kernel<8, 25>), dim3((unsigned)b2), dim3(64), 0, stream, p);
-    else if (p.cfg == 5)
-        hipLaunchKernelGGL((ckpt_backtrace_kernel<8, 11>), dim3((unsigned)b2), dim3(64), 0, stream, p);
-    else
-        hipLaunchKernelGGL((ckpt_backtrace_kernel<8, 19>), dim3((unsigned)b2), dim3(64), 0, stream, p);
+    e = geo_dispatch(CkptGeos{}, p.geo, hipErrorInvalidValue,
+                     [&](auto t)
+                     {
+                         hipLaunchKernelGGL((ckpt_backtrace_kernel<t.g, t.c>), dim3((unsigned)b2), dim3(64), 0, stream, p);
+                         return hipSuccess;
+                     });
+    if (e != hipSuccess)
+        return e;
 #ifdef LX_BT_COUNT
     {
         unsigned long long c[5] = {};
@@ -1927,8 +1911,8 @@ hipError_t launch_ckpt_backtrace(TraceParams const & p_in, hipStream_t stream)
             e = hipMemcpyToSymbol(HIP_SYMBOL(lx_bt_counts), z, sizeof(z));
         if (e != hipSuccess)
             return e;
-        fprintf(stderr, "LX_BT_COUNT cfg %d n %llu waves %llu: shortcut passes %llu, lanes/pass %.2f; tile phases %llu, lanes/phase %.2f\n",
-                p.cfg, (unsigned long long)p.n, c[4], c[0], c[0] ? (double)c[1] / (double)c[0] : 0.0, c[2],
+        fprintf(stderr, "LX_BT_COUNT geometry (%d,%d) n %llu waves %llu: shortcut passes %llu, lanes/pass %.2f; tile phases %llu, lanes/phase %.2f\n",
+                p.geo.g, p.geo.c, (unsigned long long)p.n, c[4], c[0], c[0] ? (double)c[1] / (double)c[0] : 0.0, c[2],
                 c[2] ? (double)c[3] / (double)c[2] : 0.0);
         unsigned long long cy[kBtSections + 5] = {};
         e = hipMemcpyFromSymbol(cy, HIP_SYMBOL(lx_bt_cycles), sizeof(cy));

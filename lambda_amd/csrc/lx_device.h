@@ -1,6 +1,9 @@
 // lx_device.h -- structures shared between the host side of the C ABI and the gfx950 kernels.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+#include "lx_geo.h"
 
 namespace lx
 {
@@ -229,7 +232,7 @@ struct TraceParams
     int32_t            nrows;
     int32_t            bs_match_rule; // computeAlignmentStats variant: 1 = match iff score(c0,c1)==score(c0,c0)
     int32_t            shared_profile;
-    int32_t            cfg;           // 0 = (16,10), 1 = (8,19)
+    Geo                geo;           // the launch's geometry: host side only, no kernel reads it (in the place of a former int32)
     // single-sweep mode (lx_ckpt.hip): the forward kernel runs over ALL extensions without a known score, writes the
     // best score here and an end cell whose column is still to be resolved; the backtrace then addresses checkpoint
     // slots and end cells by src[e] instead of by e
@@ -259,6 +262,15 @@ struct TraceParams
     uint64_t           split_n;
     uint32_t *         trace2;
 };
+static_assert(offsetof(TraceParams, geo) == offsetof(TraceParams, shared_profile) + 4 && offsetof(TraceParams, geo) + 4 == offsetof(TraceParams, score_out),
+              "Geo sits where the int32 sat: the kernels' parameter layout does not move");
+
+// Pass 1's two families: what launch_score (lx_score.hip: 160, 64, 320, 640, 104, 128, 152, 208, 256 columns) and the plain form of
+// launch_score_pair (lx_score_f16.hip: 152, 104, 128, 64, 192, 208, 160, 200) are instantiated for.  Here, not with the kernels,
+// because lx_host_batch.cpp bins a list by the position in these lists.  G = 8 geometries put 8 extensions in a wavefront and are
+// only used with one shared profile per wavefront (LX_OPT_QUERY_RUN / host-side binning).
+using ScoreGeos     = GeoList<GeoT<16, 10>, GeoT<8, 8>, GeoT<32, 10>, GeoT<64, 10>, GeoT<8, 13>, GeoT<8, 16>, GeoT<8, 19>, GeoT<16, 13>, GeoT<16, 16>>;
+using ScorePairGeos = GeoList<GeoT<8, 19>, GeoT<8, 13>, GeoT<8, 16>, GeoT<8, 8>, GeoT<8, 24>, GeoT<16, 13>, GeoT<16, 10>, GeoT<8, 25>>;
 
 // survivor selection between the passes (the filter loop of iterateMatchesFullSimd, src/search_algo.hpp:1251-1283,
 // with the e-value / bit-score tests turned into per-extension integer score cut-offs by the host)

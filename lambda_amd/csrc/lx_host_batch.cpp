@@ -121,10 +121,12 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
 
     // ---- bin query runs by kernel geometry.  A run whose padding to a whole number of wavefront slots wastes
     // <= 25 % goes to a "shared profile" launch (8-lane geometries allowed), the rest to per-extension profiles.
-    // bin index: kind 0 = per-extension profiles, 1 = one profile per wavefront (int32): cfg * 2 + kind;
-    // kind 2 = packed half (16 extensions of one query per wavefront): ncfg * 2 + pair geometry
-    int const    ncfg  = lx::score_cfg_count();
-    size_t const nbins = (size_t)ncfg * 2 + 9;
+    // bin index (private to this function): kind 0 = per-extension profiles, 1 = one profile per wavefront (int32): the geometry's
+    // position in ScoreGeos * 2 + kind; kind 2 = packed half (16 extensions of one query per wavefront): behind those, by the position
+    // in ScorePairGeos, and last the packed 16-bit integer kernel's
+    using lx::Geo;
+    int const    nscore = lx::ScoreGeos::size, npair = lx::ScorePairGeos::size, pair16_bin = nscore * 2 + npair;
+    size_t const nbins  = (size_t)pair16_bin + 1;
     struct Run
     {
         uint64_t first, count, pad; // positions in idx, padded slot count
@@ -143,43 +145,37 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
             ++k1;
         uint64_t const run  = k1 - k;
         uint32_t const qlen = ext[idx[k]].q_len;
-        int            kind = 0, cfg = 0;
+        int            kind = 0;
+        Geo            geo; // (kind 2: the packed-half geometry, {} = the packed 16-bit integer kernel)
         uint64_t       pad  = run;
-        int const      pcfg = h->opt_f16 ? lx::score_pair_cfg_for(qlen) : -1;
         uint64_t const pad16 = (run + 15) / 16 * 16;
-        if (pcfg >= 0 && (pad16 - run) * 4 <= pad16)
+        if (h->opt_f16 && (pad16 - run) * 4 <= pad16)
         {
             kind = 2;
-            cfg  = pcfg;
-            pad  = pad16;
-        }
-        else if (pcfg < 0 && h->opt_f16 && (pad16 - run) * 4 <= pad16)
-        {
-            kind = 2; // wider than every packed-half geometry: the packed 16-bit integer kernel, panel by panel
-            cfg  = kPair16Bin;
+            geo  = score_pair_cfg_for(qlen); // ({}: wider than every packed-half geometry -- the packed 16-bit integer kernel, panel by panel)
             pad  = pad16;
         }
         else
         {
-            cfg          = pick_cfg(qlen, true);
-            uint64_t grp = (uint64_t)lx::score_cfg_groups(cfg);
+            geo          = pick_cfg(qlen, true);
+            uint64_t grp = (uint64_t)geo.groups();
             pad          = (run + grp - 1) / grp * grp;
             kind         = (grp > 1 && (pad - run) * 4 <= pad) ? 1 : 0;
             if (kind == 0)
             {
-                cfg  = pick_cfg(qlen, false);
-                grp  = (uint64_t)lx::score_cfg_groups(cfg);
+                geo  = pick_cfg(qlen, false);
+                grp  = (uint64_t)geo.groups();
                 pad  = (run + grp - 1) / grp * grp;
                 kind = (grp > 1 && (pad - run) * 4 <= pad) ? 1 : 0;
                 if (kind == 0)
                     pad = run;
             }
         }
-        uint32_t const bin = kind == 2 ? (uint32_t)(ncfg * 2 + cfg) : (uint32_t)(cfg * 2 + kind);
+        uint32_t const bin = kind != 2 ? (uint32_t)(lx::ScoreGeos::index_of(geo) * 2 + kind) : (uint32_t)(geo.chosen() ? nscore * 2 + lx::ScorePairGeos::index_of(geo) : pair16_bin);
         runs.push_back(Run{k, run, pad, bin, 0});
         bin_slots[bin] += pad;
         bin_maxq[bin] = std::max(bin_maxq[bin], qlen);
-        if ((kind != 2 && (int)qlen > lx::score_cfg_panel(cfg)) || (kind == 2 && cfg == kPair16Bin))
+        if ((kind != 2 && (int)qlen > geo.panel()) || (kind == 2 && !geo.chosen()))
             for (size_t j = k; j < k1; ++j)
                 carry_pairs += ext[idx[j]].s_len;
         k = k1;
@@ -189,10 +185,11 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
 
     struct Seg
     {
-        int      cfg;
+        Geo      geo;
         uint64_t first, count;
         bool     multi, shared;
-        int      pair_cfg;
+        Geo      pair_geo;
+        bool     pair16;
     };
     std::vector<Seg>      segs;
     std::vector<uint64_t> bin_cursor(nbins, 0);
@@ -202,16 +199,17 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
         if (!bin_slots[b])
             continue;
         bin_cursor[b] = total_slots;
-        if (b < (size_t)ncfg * 2)
+        if (b < (size_t)nscore * 2)
         {
-            int const cfg = (int)(b / 2);
-            segs.push_back(Seg{cfg, total_slots, bin_slots[b], bin_maxq[b] > (uint32_t)lx::score_cfg_panel(cfg), (b & 1) == 1, -1});
+            Geo const geo = lx::ScoreGeos::at((int)(b / 2));
+            segs.push_back(Seg{geo, total_slots, bin_slots[b], bin_maxq[b] > (uint32_t)geo.panel(), (b & 1) == 1, Geo{}, false});
         }
         else // the int32 fix-up launch over the same list uses the shared-profile geometry of the longest query
         {
-            int const pair = (int)(b - (size_t)ncfg * 2), fcfg = pick_cfg(bin_maxq[b], true);
-            segs.push_back(Seg{fcfg, total_slots, bin_slots[b], pair == kPair16Bin && bin_maxq[b] > (uint32_t)lx::score_cfg_panel(fcfg), true,
-                               pair == kPair16Bin ? kPair16 : pair});
+            bool const pair16 = b == (size_t)pair16_bin;
+            Geo const  fgeo   = pick_cfg(bin_maxq[b], true);
+            segs.push_back(Seg{fgeo, total_slots, bin_slots[b], pair16 && bin_maxq[b] > (uint32_t)fgeo.panel(), true,
+                               pair16 ? Geo{} : lx::ScorePairGeos::at((int)(b - (size_t)nscore * 2)), pair16});
         }
         total_slots += bin_slots[b];
     }
@@ -271,7 +269,7 @@ int lx_score_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
     {
         rc = launch_score_list(h, slot, h->d_q.ptr, sref.dev,
                                static_cast<lx_extension const *>(h->d_ext.ptr) + seg.first, seg.count,
-                               static_cast<int32_t *>(h->d_out.ptr) + seg.first, plan_score_cfg(seg.cfg, seg.multi, seg.shared, h->opt_band, seg.pair_cfg),
+                               static_cast<int32_t *>(h->d_out.ptr) + seg.first, plan_score_cfg(seg.geo, seg.multi, seg.shared, h->opt_band, seg.pair_geo, seg.pair16),
                                h->stream, h->band_dev);
         if (rc)
             return rc;
@@ -335,7 +333,7 @@ int lx_align_batch(lx_handle * h, int slot, uint8_t const * q_res, uint64_t q_by
         max_q     = std::max<uint64_t>(max_q, x.q_len);
         max_s     = std::max<uint64_t>(max_s, x.s_len);
         ops_bytes = std::max<uint64_t>(ops_bytes, ops_off[i] + x.q_len + x.s_len);
-        if ((int)x.q_len > lx::trace_cfg_panel(1)) // (the narrowest panel pass 2 may pick)
+        if ((int)x.q_len > lx::kGeo8x19.panel()) // (the narrowest panel pass 2 may pick)
             carry_pairs += x.s_len;
         if (i > 0 && (x.q_off != ext[i - 1].q_off || x.q_len != ext[i - 1].q_len))
         {

@@ -1,6 +1,7 @@
 // lx_host_plan.cpp -- the host plan of lx_extend_batch* (lx_host_plan.h): validation, the order by query slice, the geometry
 // classes, and the multi-query sweep's plans.  lx_plan_free.hip plans lists that stand on the device; no HIP call here.
 #include "lx_internal.h"
+#include "lx_level2_plan.h" // choose_strips
 using namespace lxi;
 
 namespace
@@ -33,13 +34,13 @@ void radix_sort(std::vector<uint32_t> & order, std::vector<uint32_t> & tmp, std:
 
 } // namespace
 
-uint64_t lxi::slot_dwords(int cfg, uint64_t pan, uint64_t maxs, bool wide, bool with_ovf)
+uint64_t lxi::slot_dwords(lx::Geo geo, uint64_t pan, uint64_t maxs, bool wide, bool with_ovf)
 {
-    uint64_t const pc     = (uint64_t)lx::trace_cfg_panel(cfg) / 8;
+    uint64_t const pc     = (uint64_t)geo.c;
     uint64_t const panels = std::max<uint64_t>(1, (pan + pc - 1) / pc);
     uint32_t const steps  = mq_steps(maxs);
-    uint64_t const d32    = lx::ckpt_slot_dwords(cfg, steps);
-    return panels * ((wide ? d32 : lx::ckpt16_slot_dwords(cfg, steps)) + (with_ovf ? d32 / 8 : 0));
+    uint64_t const d32    = lx::ckpt_slot_dwords(geo, steps);
+    return panels * ((wide ? d32 : lx::ckpt16_slot_dwords(geo, steps)) + (with_ovf ? d32 / 8 : 0));
 }
 
 bool lxi::mq_sweep_applies(lx_handle const * h, int slot)
@@ -49,7 +50,7 @@ bool lxi::mq_sweep_applies(lx_handle const * h, int slot)
 }
 
 // the solo packing needs 16 byte profiles in a wavefront's share of the LDS: the alphabets of at most six rows
-static bool solo_fits(lx_handle const * h, int slot) { return lx::sweep_mq_lds_bytes(1, h->sc_host[slot].alphabet_size + 1, -1) <= 20 * 1024; }
+static bool solo_fits(lx_handle const * h, int slot) { return lx::sweep_mq_lds_bytes(lx::kGeo8x19, h->sc_host[slot].alphabet_size + 1, -1) <= 20 * 1024; }
 
 // does the multi-query sweep serve this slot's lists at all (free packing: what protein lists are planned for)?
 bool lxi::free_plan_applies(lx_handle const * h, int slot) { return mq_sweep_applies(h, slot) && !h->opt_band; }
@@ -67,7 +68,7 @@ int HostPlan::order(lx_handle * h, lx_extension const * ext_, uint64_t n, uint64
     nthreads   = host_threads(n);
     preplanned = preplanned_;
     use_mq = use_solo = false;
-    mq_cfg            = 1;
+    mq_geo            = lx::kGeo8x19;
     mq_cells = nwf = pool_wf = 0;
     starts.clear();
     if (preplanned)
@@ -310,8 +311,8 @@ void HostPlan::sort(HostMarks & hm)
 // step): whole panels, the last one with the narrowest strips that cover what is left (lx_device.h: narrow_code_for)
 uint32_t HostPlan::mq_panels(uint32_t lq) const
 {
-    int const      C     = lx::trace_cfg_panel(mq_cfg) / 8;
-    uint64_t const panel = (uint64_t)lx::trace_cfg_panel(mq_cfg);
+    int const      C     = mq_geo.c;
+    uint64_t const panel = (uint64_t)mq_geo.panel();
     uint64_t const P     = std::max<uint64_t>(1, ((uint64_t)lq + panel - 1) / panel);
     int const      rem   = (int)((uint64_t)std::max<uint32_t>(lq, 1) - (P - 1) * panel);
     int const      code  = lx::narrow_code_for(C, 8, rem);
@@ -342,7 +343,7 @@ void HostPlan::plan_pool(ResidentInput const * ri, HostMarks & hm)
 {
     if (use_mq && preplanned)
     {
-        mq_cfg   = ri->mq_cfg;
+        mq_geo   = ri->mq_geo;
         mq_cells = ri->cells;
         nwf = pool_wf = ri->nwf;
         wf_pan.assign(ri->wf_pan, ri->wf_pan + nwf);
@@ -369,7 +370,7 @@ void HostPlan::plan_pool(ResidentInput const * ri, HostMarks & hm)
 void HostPlan::choose_cfg()
 {
     uint64_t const      nruns   = starts.size() - 1;
-    int const           cand[3] = {1, 3, 5};
+    int const           cand[3] = {19, 13, 11}; // columns per lane, in choose_strips' order
     std::vector<double> tc(3 * (size_t)nthreads, 0.0);
     parallel_ranges(nruns, nthreads,
                     [&](unsigned t, uint64_t rlo, uint64_t rhi)
@@ -380,8 +381,8 @@ void HostPlan::choose_cfg()
                             uint64_t const lq = ext[idx[starts[r]]].q_len, nw = use_solo ? starts[r + 1] - starts[r] : (starts[r + 1] - starts[r] + 1) / 2 * 2;
                             for (int k = 0; k < 3; ++k)
                             {
-                                uint64_t const panel = (uint64_t)lx::trace_cfg_panel(cand[k]), P = std::max<uint64_t>(1, (lq + panel - 1) / panel);
-                                int const      Cc = (int)panel / 8, rem = (int)(std::max<uint64_t>(lq, 1) - (P - 1) * panel);
+                                uint64_t const panel = 8 * (uint64_t)cand[k], P = std::max<uint64_t>(1, (lq + panel - 1) / panel);
+                                int const      Cc = cand[k], rem = (int)(std::max<uint64_t>(lq, 1) - (P - 1) * panel);
                                 int const      code = lx::narrow_code_for(Cc, 8, rem);
                                 // (a step costs 3.75 instructions per column and 12 besides, whatever the strip width)
                                 c[k] += (double)nw * ((double)(P - 1) * (3.75 * Cc + 12.0) + 3.75 * lx::narrow_strip_cols(Cc, code) + 12.0);
@@ -390,21 +391,13 @@ void HostPlan::choose_cfg()
                         for (int k = 0; k < 3; ++k)
                             tc[3 * t + k] = c[k];
                     });
-    double best = 1e300;
+    double cost[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k)
-    {
-        double c = 0;
         for (unsigned t = 0; t < nthreads; ++t)
-            c += tc[3 * t + k];
-        // (narrower strips: more panels -- carries, profile builds -- and more tiles per walk in the backtrace; measured on the
-        // ragged list of bench.py: 22.2 / 21.5 ms with 13 / 11 columns against 19.7 ms with 19, at 8 / 10 % fewer cells)
-        c *= cand[k] == 1 ? 1.0 : 1.15;
-        if (c < best)
-        {
-            best   = c;
-            mq_cfg = cand[k];
-        }
-    }
+            cost[k] += tc[3 * t + k];
+    // (narrower strips must save 15 %: more panels -- carries, profile builds -- and more tiles per walk in the backtrace; measured on
+    // the ragged list of bench.py: 22.2 / 21.5 ms with 13 / 11 columns against 19.7 ms with 19, at 8 / 10 % fewer cells)
+    mq_geo = choose_strips(cost);
 }
 
 // The solo plan is a sort: all windows by (columns per lane, length), longest first, 16 to a wavefront.  Keys: most columns per
@@ -704,7 +697,7 @@ HostPlan::StreamBound HostPlan::stream_bound(bool wide) const
             ++b.runs;
             b.pan  = std::max(b.pan, pan);
             b.maxs = std::max(b.maxs, maxs);
-            b.dwords += (cnt + 1) / 2 * 2 * slot_dwords(mq_cfg, pan, maxs, wide);
+            b.dwords += (cnt + 1) / 2 * 2 * slot_dwords(mq_geo, pan, maxs, wide);
         }
     return b;
 }
@@ -807,7 +800,7 @@ uint64_t HostPlan::wf_chunk_end(uint64_t w0, uint64_t per_chunk, uint64_t trace_
     {
         if (cut_at_pool && w0 < pool_end && w1 == pool_end)
             break;
-        uint64_t const b2 = run_bytes + kWave * slot_dwords(mq_cfg, wf_pan[w1], wf_maxs[w1], maybe_wide, true) * 4;
+        uint64_t const b2 = run_bytes + kWave * slot_dwords(mq_geo, wf_pan[w1], wf_maxs[w1], maybe_wide, true) * 4;
         uint64_t const q2 = std::max<uint64_t>(run_q, wf_pan[w1]), s2 = std::max<uint64_t>(run_s, wf_maxs[w1]);
         if (w1 > w0 && !chunk_fits(b2, trace_bytes, (w1 + 1 - w0) * kWave, q2 * 8 + s2))
             break;
@@ -843,9 +836,9 @@ bool HostPlan::ranges_admitted(uint64_t const * cut_wf, uint64_t n_ranges, uint6
             pm = std::max<uint64_t>(pm, wf_pan[w]);
             sm = std::max<uint64_t>(sm, wf_maxs[w]);
         }
-        uint64_t const slot_b = slot_dwords(mq_cfg, pm, sm, false, true) * 4;
+        uint64_t const slot_b = slot_dwords(mq_geo, pm, sm, false, true) * 4;
         // (a range whose sweep overflows runs again WHOLE with int16-pair slots, about twice the codes': admitted against those too)
-        uint64_t const slot_w = wide_ok ? slot_dwords(mq_cfg, pm, sm, true) * 4 : 0;
+        uint64_t const slot_w = wide_ok ? slot_dwords(mq_geo, pm, sm, true) * 4 : 0;
         ok = a < b && b - a <= 4 * per_chunk && chunk_fits((b - a) * kWave * std::max(slot_b, slot_w), trace_bytes, (b - a) * kWave, pm * 8 + sm);
     }
     return ok;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/lambda_ext.h"
+#include "lx_geo.h"
 
 namespace lxi
 {
@@ -26,10 +27,10 @@ inline uint32_t query_class(uint32_t lq)
 // steps of a multi-query slot whose longest window has `maxs` rows
 inline uint32_t mq_steps(uint64_t maxs) { return (uint32_t)((maxs + 8 - 1 + 15) & ~15ull); }
 
-// Checkpoint dwords of one multi-query slot in strip geometry `cfg` (trace cfg), sized for a wavefront whose widest query sweeps
+// Checkpoint dwords of one multi-query slot in strip geometry `geo`, sized for a wavefront whose widest query sweeps
 // `pan` columns per lane and whose longest window is `maxs`: int16 pairs (wide) or compact codes, per panel, + (with_ovf) an
 // eighth of an int32 slot per panel -- the room a chunk keeps for the overflow slots of what the compact sweep declines
-uint64_t slot_dwords(int cfg, uint64_t pan, uint64_t maxs, bool wide, bool with_ovf = false);
+uint64_t slot_dwords(lx::Geo geo, uint64_t pan, uint64_t maxs, bool wide, bool with_ovf = false);
 
 // The budget of a multi-query chunk: its checkpoint slots' bytes within `trace_bytes` (LX_OPT_TRACE_BYTES), its survivors' ops slots
 // -- `slots` of `ops_slot_bytes`, columns + rows of the chunk's widest query and longest window -- within 8 GiB.  The sites differ,
@@ -57,7 +58,7 @@ struct HostPlan
     std::vector<uint8_t>  newrun;       // [live + 1]: 1 where a run of one query slice begins (the sentinel is 1)
     std::vector<uint64_t> starts;       // the positions where runs begin + the sentinel `live` (made when a stage needs them)
     bool                  use_mq = false, use_solo = false;
-    int                   mq_cfg   = 1; // the multi-query sweep's strip geometry (trace cfg)
+    lx::Geo               mq_geo = lx::kGeo8x19; // the multi-query sweep's strip geometry
     uint64_t              mq_cells = 0; // sum q_len * s_len of the list (lx_last_extend_stats)
     uint64_t              nwf = 0, pool_wf = 0;       // wavefronts planned so far; the pool's (they come first)
     std::vector<uint32_t> plan_slot, wf_pan, wf_maxs; // caller index per slot (bit 31: filler); per wavefront: columns per lane, longest window
@@ -70,7 +71,7 @@ struct HostPlan
     int choose(lx_handle * h, int slot, ResidentInput const * ri, bool as_list);
     // the one-query-per-wavefront order (classes, then windows by length inside a run) where the plan needs it
     void sort(HostMarks & hm);
-    // mq_cfg and the solo plan, or the pool of the free packing (a device plan is taken over)
+    // mq_geo and the solo plan, or the pool of the free packing (a device plan is taken over)
     void plan_pool(ResidentInput const * ri, HostMarks & hm);
     // the streamed part of the free packing, behind the pool
     void plan_stream();
@@ -86,7 +87,7 @@ struct HostPlan
 
     // ---- cutting the plan into chunks (the drivers issue what is cut here)
     // checkpoint dwords of wavefront w's sixteen slots
-    uint64_t wf_dwords(uint64_t w, bool wide) const { return kWave * slot_dwords(mq_cfg, wf_pan[w], wf_maxs[w], wide); }
+    uint64_t wf_dwords(uint64_t w, bool wide) const { return kWave * slot_dwords(mq_geo, wf_pan[w], wf_maxs[w], wide); }
     // one-query-per-wavefront chunks: where the chunk of the ordered list that starts at k0 ends -- about chunk_target extensions, never
     // inside a query's run, never across geometry classes (the list is class-major)
     uint64_t run_chunk_end(uint64_t k0, uint64_t chunk_target) const;

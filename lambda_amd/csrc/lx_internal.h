@@ -36,8 +36,8 @@
 
 namespace lx
 {
-hipError_t launch_score(int cfg, ScoreParams const & p, bool multi, hipStream_t stream);
-hipError_t launch_score_pair(int cfg, ScoreParams const & p, hipStream_t stream);
+hipError_t launch_score(Geo geo, ScoreParams const & p, bool multi, hipStream_t stream);
+hipError_t launch_score_pair(Geo geo, ScoreParams const & p, hipStream_t stream);
 uint64_t   select_blocks(uint64_t nruns);
 hipError_t launch_trace_forward(TraceParams const & p, hipStream_t stream);
 hipError_t launch_backtrace(TraceParams const & p, hipStream_t stream);
@@ -49,10 +49,10 @@ hipError_t launch_slot_scatter(uint32_t const * orig, uint64_t slots, int32_t co
                                uint64_t const * count_ptr, uint64_t cap, hipStream_t stream);
 hipError_t launch_ckpt_forward(TraceParams const & p, hipStream_t stream);
 hipError_t launch_ckpt_backtrace(TraceParams const & p, hipStream_t stream);
-hipError_t launch_sweep_pair16(int trace_cfg, ScoreParams const & p, hipStream_t stream);
+hipError_t launch_sweep_pair16(Geo geo, ScoreParams const & p, hipStream_t stream);
 hipError_t launch_score_pair16(ScoreParams const & p, hipStream_t stream);
-hipError_t launch_sweep_pair16_compact(int trace_cfg, ScoreParams const & p, hipStream_t stream);
-hipError_t launch_sweep_mq(int trace_cfg, ScoreParams const & p, hipStream_t stream);
+hipError_t launch_sweep_pair16_compact(Geo geo, ScoreParams const & p, hipStream_t stream);
+hipError_t launch_sweep_mq(Geo geo, ScoreParams const & p, hipStream_t stream);
 hipError_t launch_prefilter(PrefilterParams const & p, hipStream_t stream);
 hipError_t launch_rle_pack(PackParams const & p, hipStream_t stream);
 } // namespace lx
@@ -470,7 +470,7 @@ struct StepCall
     FusedExtra   fx;
     ListLimits   lim;
     MqTab        tab;                 // (dev == NULL: slots by region)
-    int          mq_cfg      = 0;     // the strip geometry (trace cfg) the call chose for its chunks (0 = plan_step picks per chunk)
+    lx::Geo      mq_geo;              // the strip geometry the call chose for its chunks ({}: plan_step picks per chunk)
     bool         mq_wide     = false; // the multi-query sweep writes int16-pair slots (many windows of the last chunks scored beyond the compact codes)
     bool         keep_events = false; // the phase events of earlier steps stay (lx_extend_batch: lx_last_phase_ms sums its chunks')
 };
@@ -485,12 +485,12 @@ struct ResidentInput
     void const * d_min_all = nullptr;
     // a plan made on the device (the solo packing): the slot list (16 per wavefront: position in the list, bit 31 = filler), and
     // on the host per wavefront the columns per lane its widest query sweeps and its longest window, the strip geometry
-    // (trace cfg), the list's cells
+    // (which the caller sets), the list's cells
     uint32_t const * d_plan  = nullptr;
     uint64_t         nwf     = 0;
     uint32_t const * wf_pan  = nullptr;
     uint32_t const * wf_maxs = nullptr;
-    int              mq_cfg  = 0;
+    lx::Geo          mq_geo;
     bool             free_packing = false; // the device plan is the free packing (pairs of one query, at most four queries per wavefront), not the solo one
     uint64_t         cells   = 0;
     // the survivors stay on the device (lx_handle::Level2::d_surv_*; taken where the plan above is served: ResidentSurvivors says so),

@@ -286,7 +286,7 @@ struct Part
     uint64_t              lo = 0, n = 0;
     int                   slot = 0;
     bool                  solo = false;          // the solo packing, else the free packing
-    int                   cfg  = 1;              // the strip geometry (trace cfg)
+    lx::Geo               geo  = lx::kGeo8x19;   // the strip geometry
     std::vector<uint64_t> bounds;                // the ranges in the part: {0, cut, ..., n}
     std::vector<uint64_t> cut_wf;                // the ranges' first wavefronts, and where the last one ends
     uint64_t              nwf = 0, cap_wf = 0;   // (cap_wf: what the per-wavefront arrays are spaced by on the device)
@@ -438,15 +438,15 @@ private:
     // ---- the range plan (lx_level2_plan.h): the strip geometry, how many ranges, and the cuts from the windows around their targets
     int plan_ranges(Part & pt)
     {
-        pt.cfg = l2_choose_cfg(cost + 4 * pt.pi);
+        pt.geo = choose_strips(cost + 4 * pt.pi);
         uint64_t const forced = lx::dev_aids().l2_ranges;
         uint64_t       need = 0, have = 1;
         if (records_on_device && !forced)
         {
-            uint64_t const panel  = (uint64_t)lx::trace_cfg_panel(pt.cfg);
+            uint64_t const panel  = (uint64_t)pt.geo.panel();
             uint64_t const panels = std::max<uint64_t>(1, ((uint64_t)l2.max_qlen + panel - 1) / panel);
             uint64_t const steps  = ((uint64_t)cost[8 + pt.pi] + 8 - 1 + 15) & ~15ull; // (the part's longest window)
-            uint64_t const slot_b = panels * (lx::ckpt16_slot_dwords(pt.cfg, (uint32_t)std::min<uint64_t>(steps, 65520)) + lx::ckpt_slot_dwords(pt.cfg, (uint32_t)std::min<uint64_t>(steps, 65520)) / 8) * 4;
+            uint64_t const slot_b = panels * (lx::ckpt16_slot_dwords(pt.geo, (uint32_t)std::min<uint64_t>(steps, 65520)) + lx::ckpt_slot_dwords(pt.geo, (uint32_t)std::min<uint64_t>(steps, 65520)) / 8) * 4;
             need = l2_slot_need_bytes(pt.n, slot_b);
             have = std::min<uint64_t>(h->opt_trace_bytes, std::max<uint64_t>(h->d_trace.cap, kL2FreshSlotBytes));
         }
@@ -528,7 +528,7 @@ private:
             uint64_t * key = static_cast<uint64_t *>(l2.d_pair[0].ptr), * key_tmp = static_cast<uint64_t *>(l2.d_pair[1].ptr);
             uint64_t * idx = static_cast<uint64_t *>(l2.d_s0[0].ptr), * idx_tmp = static_cast<uint64_t *>(l2.d_s0[1].ptr);
             uint64_t const w0 = pt.cut_wf[r];
-            LX_HIP(h, lx::l2_launch_plan(static_cast<lx::Extension const *>(pt.ri.d_ext_all) + pt.bounds[r], pt.bounds[r + 1] - pt.bounds[r], lx::trace_cfg_panel(pt.cfg) / 8,
+            LX_HIP(h, lx::l2_launch_plan(static_cast<lx::Extension const *>(pt.ri.d_ext_all) + pt.bounds[r], pt.bounds[r + 1] - pt.bounds[r], pt.geo.c,
                                          0, &key, &key_tmp, &idx, &idx_tmp, static_cast<uint32_t *>(l2.d_hist.ptr),
                                          static_cast<uint32_t *>(l2.d_plan.ptr) + w0 * 16, d_pan() + w0, d_maxs(pt) + w0, st, (uint32_t)pt.bounds[r],
                                          lx::l2_plan_key_bits(l2.max_qlen, cost[8 + pt.pi])));
@@ -540,7 +540,7 @@ private:
     int plan_free(Part & pt)
     {
         lx::FpArgs fa;
-        if (int const rc = launch_free_plan(h, pt.ri.d_ext_all, l2.q_len.size(), lx::trace_cfg_panel(pt.cfg) / 8, pt.bounds, fa))
+        if (int const rc = launch_free_plan(h, pt.ri.d_ext_all, l2.q_len.size(), pt.geo.c, pt.bounds, fa))
             return rc;
         LX_HIP(h, hipMemcpyAsync(h_report(), fa.report, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         return LX_OK;
@@ -581,7 +581,7 @@ private:
         pt.ri.nwf          = pt.nwf;
         pt.ri.wf_pan       = h_pan;
         pt.ri.wf_maxs      = h_maxs;
-        pt.ri.mq_cfg       = pt.cfg;
+        pt.ri.mq_geo       = pt.geo;
         pt.ri.free_packing = !pt.solo;
         pt.ri.cells        = cost[4 * pt.pi + 3];
         return LX_OK;

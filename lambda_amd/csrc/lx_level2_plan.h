@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "lx_geo.h"
+
 namespace lx
 {
 
@@ -124,24 +126,32 @@ inline std::vector<uint64_t> l2_cuts(lx::L2Window const * win, std::vector<L2Pro
 
 // ---- the strip geometry ---------------------------------------------------------------------------------------------------------
 // ONE strip geometry per call, the one that sweeps the list cheapest (lx_host.cpp has the measurement behind "one" and behind
-// the 15 % that narrower strips must save): cost[k] = the list's cost at 19 / 13 / 11 columns per lane (trace cfg 1 / 3 / 5)
+// the 15 % that narrower strips must save): cost[k] = the list's cost at 19 / 13 / 11 columns per lane, compared as doubles.  The
+// host plan of lx_extend_batch (HostPlan::choose_cfg, sums of doubles) and the Level-2 driver (sums of uint64) decide by this function.
 constexpr double kL2NarrowStripsMustSave = 1.15;
 
-inline int l2_choose_cfg(uint64_t const cost[3])
+template <class Cost>
+lx::Geo choose_strips(Cost const * cost)
 {
-    int const cand[3] = {1, 3, 5};
-    int       cfg     = 1;
-    double    best    = 1e300;
+    lx::Geo const cand[3] = {{8, 19}, {8, 13}, {8, 11}};
+    lx::Geo       geo     = cand[0];
+    double        best    = 1e300;
     for (int k = 0; k < 3; ++k)
     {
-        double const c = (double)cost[k] * (cand[k] == 1 ? 1.0 : kL2NarrowStripsMustSave);
+        double const c = (double)cost[k] * (k == 0 ? 1.0 : kL2NarrowStripsMustSave);
         if (c < best)
         {
             best = c;
-            cfg  = cand[k];
+            geo  = cand[k];
         }
     }
-    return cfg;
+    return geo;
+}
+
+// ... as the columns per lane of the strips chosen (what tests/native/level2_plan_check.cpp answers a cfg request with)
+inline int l2_choose_cfg(uint64_t const cost[3])
+{
+    return choose_strips(cost).c;
 }
 
 } // namespace lxi

@@ -71,13 +71,13 @@ int reserve_pipeline(lx_handle * h, Forecast const & f, HostMarks & hm)
     int            rc;
     uint64_t const chunk  = h->opt_extend_chunk ? std::max<uint64_t>(h->opt_extend_chunk, 1024) : lxi::kExtendChunk;
     uint64_t const nwf_x  = f.free_plan ? f.nwf_solo + f.nwf_solo / 8 + 64 : f.nwf_solo; // (what a free-packing plan comes to, not its bound)
-    uint64_t const panel  = (uint64_t)lx::trace_cfg_panel(1);
+    uint64_t const panel  = (uint64_t)lx::kGeo8x19.panel();
     uint64_t const max_q  = std::max<uint64_t>(1, ((uint64_t)l2.max_qlen + panel - 1) / panel) * panel;
     // (the longest ORDINARY window, query + band on either side, :919-938: a list whose merged windows are longer grows its first chunk's
     // slots in the call)
     uint64_t const max_s  = (uint64_t)l2.max_qlen + 2 * (uint64_t)bandSize(l2.max_qlen) + 16, stride = (max_q + 3 * max_s + 3) & ~3ull;
     uint64_t const steps  = (max_s + 8 - 1 + 15) & ~15ull;
-    uint64_t const slot_b = max_q / panel * (lx::ckpt16_slot_dwords(1, (uint32_t)steps) + lx::ckpt_slot_dwords(1, (uint32_t)steps) / 8) * 4;
+    uint64_t const slot_b = max_q / panel * (lx::ckpt16_slot_dwords(lx::kGeo8x19, (uint32_t)steps) + lx::ckpt_slot_dwords(lx::kGeo8x19, (uint32_t)steps) / 8) * 4;
     // (a device plan's chunks are the RANGES of the list, admitted up to four default chunks: the lanes and the checkpoint slots are
     // sized for the largest range, or the first call grows them.  The count is the call's own rule, l2_range_count -- asked generously:
     // every slot of the plan at an ordinary window's full size where the call halves the longest window's, against fresh memory alone,

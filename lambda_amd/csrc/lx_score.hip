@@ -385,53 +385,10 @@ static hipError_t launch_score_cfg(ScoreParams const & p, bool multi, hipStream_
     return hipGetLastError();
 }
 
-// Kernel geometries (G lanes per extension x C columns per lane).  G = 8 geometries put 8 extensions in a
-// wavefront and are only used with one shared profile per wavefront (LX_OPT_QUERY_RUN / host-side binning).
-struct ScoreCfg
-{
-    int g, c;
-};
-static constexpr ScoreCfg kScoreCfgs[] = {
-    {16, 10}, // 0: 160 columns
-    {8, 8},   // 1:  64
-    {32, 10}, // 2: 320
-    {64, 10}, // 3: 640 (and the multi-panel workhorse for longer queries)
-    {8, 13},  // 4: 104
-    {8, 16},  // 5: 128
-    {8, 19},  // 6: 152
-    {16, 13}, // 7: 208
-    {16, 16}, // 8: 256
-};
-constexpr int kNumScoreCfgs = sizeof(kScoreCfgs) / sizeof(ScoreCfg);
-
 // multi: the batch may hold queries wider than the panel (enables the carry-workspace code path)
-hipError_t launch_score(int cfg, ScoreParams const & p, bool multi, hipStream_t stream)
+hipError_t launch_score(Geo geo, ScoreParams const & p, bool multi, hipStream_t stream)
 {
-    switch (cfg)
-    {
-        case 0: return launch_score_cfg<16, 10>(p, multi, stream);
-        case 1: return launch_score_cfg<8, 8>(p, multi, stream);
-        case 2: return launch_score_cfg<32, 10>(p, multi, stream);
-        case 3: return launch_score_cfg<64, 10>(p, multi, stream);
-        case 4: return launch_score_cfg<8, 13>(p, multi, stream);
-        case 5: return launch_score_cfg<8, 16>(p, multi, stream);
-        case 6: return launch_score_cfg<8, 19>(p, multi, stream);
-        case 7: return launch_score_cfg<16, 13>(p, multi, stream);
-        case 8: return launch_score_cfg<16, 16>(p, multi, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-int score_cfg_count() { return kNumScoreCfgs; }
-
-int score_cfg_panel(int cfg)
-{
-    return (cfg >= 0 && cfg < kNumScoreCfgs) ? kScoreCfgs[cfg].g * kScoreCfgs[cfg].c : 0;
-}
-
-int score_cfg_groups(int cfg)
-{
-    return (cfg >= 0 && cfg < kNumScoreCfgs) ? 64 / kScoreCfgs[cfg].g : 0;
+    return geo_dispatch(ScoreGeos{}, geo, hipErrorInvalidValue, [&](auto t) { return launch_score_cfg<t.g, t.c>(p, multi, stream); }); // (lx_device.h: ScoreGeos)
 }
 
 } // namespace lx

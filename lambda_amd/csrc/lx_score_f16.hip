@@ -634,79 +634,28 @@ static hipError_t launch_pair_cfg(ScoreParams const & p, hipStream_t stream)
     return hipGetLastError();
 }
 
-// pair geometries: 0 = (8,19) 152 columns, 1 = (8,13) 104, 2 = (8,16) 128, 3 = (8,8) 64, 4 = (8,24) 192, 5 = (16,13) 208,
-// 6 = (16,10) 160 [8 extensions per wavefront: for query runs that are a multiple of 8 but not of 16], 7 = (8,25) 200
-// [200-residue queries without a padded column: 7.7 against 6.7 TCUPS for (16,13) in pass 1]
-hipError_t launch_score_pair(int cfg, ScoreParams const & p, hipStream_t stream)
+// The single sweep: the geometries lx_ckpt.hip's layout is instantiated for -- (8,13) for short queries, (8,25) for 153 - 200 columns.
+// Pass 1: ScorePairGeos (lx_device.h) -- (16,10) and (16,13) hold 8 extensions per wavefront, for query runs that are a multiple of 8
+// but not of 16; (8,25) takes 200-residue queries without a padded column: 7.7 against 6.7 TCUPS for (16,13).
+using HalfSweepGeos = GeoList<GeoT<8, 19>, GeoT<16, 13>, GeoT<8, 13>, GeoT<8, 25>>;
+
+hipError_t launch_score_pair(Geo geo, ScoreParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
-    if (p.ckpt) // single sweep: the geometries lx_ckpt.hip's layout is instantiated for
+    if (p.ckpt)
     {
         if (!p.ends || p.steps_cap % 16 != 0)
             return hipErrorInvalidValue;
-        return cfg == 0   ? launch_pair_cfg<8, 19, true>(p, stream)
-               : cfg == 5 ? launch_pair_cfg<16, 13, true>(p, stream)
-               : cfg == 1 ? launch_pair_cfg<8, 13, true>(p, stream) // short queries: 104 columns
-               : cfg == 7 ? launch_pair_cfg<8, 25, true>(p, stream) // 153 - 200 columns
-                          : hipErrorInvalidValue;
+        return geo_dispatch(HalfSweepGeos{}, geo, hipErrorInvalidValue, [&](auto t) { return launch_pair_cfg<t.g, t.c, true>(p, stream); });
     }
-    switch (cfg)
-    {
-        case 0: return launch_pair_cfg<8, 19>(p, stream);
-        case 1: return launch_pair_cfg<8, 13>(p, stream);
-        case 2: return launch_pair_cfg<8, 16>(p, stream);
-        case 3: return launch_pair_cfg<8, 8>(p, stream);
-        case 4: return launch_pair_cfg<8, 24>(p, stream);
-        case 5: return launch_pair_cfg<16, 13>(p, stream);
-        case 6: return launch_pair_cfg<16, 10>(p, stream);
-        case 7: return launch_pair_cfg<8, 25>(p, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return geo_dispatch(ScorePairGeos{}, geo, hipErrorInvalidValue, [&](auto t) { return launch_pair_cfg<t.g, t.c>(p, stream); });
 }
-
-int score_pair_cfg_for(uint32_t max_qlen)
-{
-    if (max_qlen <= 64)
-        return 3;
-    if (max_qlen <= 104)
-        return 1;
-    if (max_qlen <= 128)
-        return 2;
-    if (max_qlen <= 152)
-        return 0;
-    if (max_qlen <= 192)
-        return 4;
-    if (max_qlen <= 200)
-        return 7;
-    if (max_qlen <= 208)
-        return 5;
-    return -1;
-}
-
-// geometries with 16-lane groups (8 extensions per wavefront)
-int score_pair_cfg_for_runs_of_8(uint32_t max_qlen)
-{
-    if (max_qlen <= 160)
-        return 6;
-    if (max_qlen <= 208)
-        return 5;
-    return -1;
-}
-
-int score_pair_cfg_cols(int cfg)
-{
-    static int const c[8] = {19, 13, 16, 8, 24, 13, 10, 25};
-    return (cfg >= 0 && cfg < 8) ? c[cfg] : 0;
-}
-
-int score_pair_cfg_group(int cfg) { return (cfg == 5 || cfg == 6) ? 16 : 8; }
 
 // LDS bytes of one profile (the kernel's occupancy allows about 13 KB per wavefront)
-size_t score_pair_profile_bytes(int cfg, int nrows)
+size_t score_pair_profile_bytes(Geo geo, int nrows)
 {
-    int const G = score_pair_cfg_group(cfg), C = score_pair_cfg_cols(cfg);
-    return (size_t)nrows * (size_t)((((C + 1) / 2 + 3) & ~3) * G) * sizeof(uint32_t);
+    return (size_t)nrows * (size_t)((((geo.c + 1) / 2 + 3) & ~3) * geo.g) * sizeof(uint32_t);
 }
 
 } // namespace lx

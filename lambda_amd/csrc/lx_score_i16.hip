@@ -710,7 +710,10 @@ static hipError_t launch_sweep16_compact_cfg(ScoreParams const & p, hipStream_t 
     hipLaunchKernelGGL((sweep_pair16_kernel<G, C, false, true, true>), dim3((unsigned)blocks), dim3(64), lds, stream, p);
     return hipGetLastError();
 }
-hipError_t launch_sweep_pair16_compact(int trace_cfg, ScoreParams const & p, hipStream_t stream)
+// (8,19): 16 extensions of one query per wavefront; (16,13): 8
+using Sweep16Geos = GeoList<GeoT<8, 19>, GeoT<16, 13>>;
+
+hipError_t launch_sweep_pair16_compact(Geo geo, ScoreParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
@@ -718,21 +721,20 @@ hipError_t launch_sweep_pair16_compact(int trace_cfg, ScoreParams const & p, hip
     {
         using Geo = Pair16Geo<8, 19>;
         uint64_t const blocks = (p.n + 2ull * Geo::kGroups - 1) / (2ull * Geo::kGroups);
-        if (trace_cfg != 1 || blocks > 0x7fffffffull || !p.ckpt || !p.ends || p.steps_cap % 16 != 0)
+        if (geo != kGeo8x19 || blocks > 0x7fffffffull || !p.ckpt || !p.ends || p.steps_cap % 16 != 0)
             return hipErrorInvalidValue;
         size_t const lds = ((size_t)p.nrows * Geo::kRowDw + 64 * 8) * sizeof(uint32_t);
         hipLaunchKernelGGL((sweep_pair16_kernel<8, 19, true, true, true>), dim3((unsigned)blocks), dim3(64), lds, stream, p);
         return hipGetLastError();
     }
-    return trace_cfg == 1 ? launch_sweep16_compact_cfg<8, 19>(p, stream) : trace_cfg == 2 ? launch_sweep16_compact_cfg<16, 13>(p, stream) : hipErrorInvalidValue;
+    return geo_dispatch(Sweep16Geos{}, geo, hipErrorInvalidValue, [&](auto t) { return launch_sweep16_compact_cfg<t.g, t.c>(p, stream); });
 }
 
-// trace cfg 1 = (8,19): 16 extensions of one query per wavefront; 2 = (16,13): 8
-hipError_t launch_sweep_pair16(int trace_cfg, ScoreParams const & p, hipStream_t stream)
+hipError_t launch_sweep_pair16(Geo geo, ScoreParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
-    return trace_cfg == 1 ? launch_sweep16_cfg<8, 19>(p, stream) : trace_cfg == 2 ? launch_sweep16_cfg<16, 13>(p, stream) : hipErrorInvalidValue;
+    return geo_dispatch(Sweep16Geos{}, geo, hipErrorInvalidValue, [&](auto t) { return launch_sweep16_cfg<t.g, t.c>(p, stream); });
 }
 
 } // namespace lx

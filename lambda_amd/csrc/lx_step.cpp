@@ -112,25 +112,25 @@ int lxi::launch_score_list(lx_handle * h, int slot, void const * d_q, void const
         p.shared_profile = pl.narrow ? 1 : 0;
         LX_HIP(h, lx::launch_score(pl.launch_cfg(), p, true, stream));
     }
-    else if (pl.pair_cfg == kPair16)
+    else if (pl.pair16)
     {
         // queries wider than the packed-half geometries: packed 16-bit integers (lx_score_i16.hip), panel by panel; what
         // fails its range test is left to the int32 kernel, which starts with an empty carry workspace
         LX_HIP(h, lx::launch_score_pair16(p, stream));
         LX_HIP(h, reset_carry(h, stream));
         p.fixup = 1;
-        LX_HIP(h, lx::launch_score(pl.cfg, p, pl.multi, stream));
+        LX_HIP(h, lx::launch_score(pl.geo, p, pl.multi, stream));
     }
-    else if (pl.pair_cfg >= 0)
+    else if (pl.pair_geo.chosen())
     {
         // packed-half kernel first (two extensions per lane group); wavefronts whose score bound does not fit half
         // precision leave the sentinel -1, which the int32 kernel then resolves in fix-up mode
-        LX_HIP(h, lx::launch_score_pair(pl.pair_cfg, p, stream));
+        LX_HIP(h, lx::launch_score_pair(pl.pair_geo, p, stream));
         p.fixup = 1;
-        LX_HIP(h, lx::launch_score(pl.cfg, p, pl.multi, stream));
+        LX_HIP(h, lx::launch_score(pl.geo, p, pl.multi, stream));
     }
     else
-        LX_HIP(h, lx::launch_score(pl.cfg, p, pl.multi, stream));
+        LX_HIP(h, lx::launch_score(pl.geo, p, pl.multi, stream));
     char buf[128];
     describe_score(pl, buf, sizeof(buf));
     h->last_kernel = buf;
@@ -213,7 +213,7 @@ int lxi::align_dev_impl(lx_handle * h, int slot, void const * d_q, void const * 
         p.band           = (int32_t)h->opt_band;
         p.band_diag      = lim.band_diag ? (d_src ? lim.band_diag : lim.band_diag + c0) : nullptr; // indexed like the caller's list
         p.shared_profile = pl.shared_profile;
-        p.cfg            = pl.cfg;
+        p.geo            = pl.geo;
         if (pl.panels_cap > 1) // each chunk starts with an empty carry workspace
             LX_HIP(h, reset_carry(h, stream));
         PhaseTimer ptf(h, stream, 2);
@@ -272,7 +272,7 @@ int plan_for_call(StepCtx & x)
     StepOptions so{};
     so.max_qlen = c.lim.max_qlen, so.max_slen = c.lim.max_slen, so.query_run = c.lim.query_run, so.pass2 = h->opt_pass2;
     so.mq = h->opt_mq, so.f16 = h->opt_f16, so.band = h->opt_band, so.trace_bytes = h->opt_trace_bytes, so.n = c.n;
-    so.mq_cfg = c.mq_cfg, so.adapt = h->opt_adapt, so.mq_wide = c.mq_wide, so.surv_frac = h->surv_frac;
+    so.mq_geo = c.mq_geo, so.adapt = h->opt_adapt, so.mq_wide = c.mq_wide, so.surv_frac = h->surv_frac;
     if (x.tab_on)
     {
         so.n   = 1;
@@ -292,7 +292,7 @@ int plan_for_call(StepCtx & x)
     // sweep of one-panel queries interleaves the compact slots of a wavefront's windows -- ScoreParams::wave_slots --, so that what
     // one store instruction writes is one contiguous piece: headline sweep 11.87 -> 11.6 ms)
     // (slots by wavefront: [the wavefronts before slot n0][overflow slots][the wavefronts from n0 on])
-    uint64_t const wave_w = 128 / (uint64_t)lx::trace_cfg_group(plan.cfg); // windows of a packed-half wavefront
+    uint64_t const wave_w = plan.family == kHalfSweep ? 128 / (uint64_t)plan.geo.g : 1; // windows of a packed-half wavefront
     x.tab_ovf_dw          = x.tab_on ? plan.ovf_cap * plan.stride32 : 0;
     x.batch_dw            = x.tab_on                     ? tab.dw0
                             : plan.family == kHalfSweep ? (c.n + wave_w - 1) / wave_w * wave_w * plan.stride
@@ -342,8 +342,8 @@ int sweep_stage(StepCtx & x, bool & first_part_only)
     p.panels_cap      = plan.panels;
     p.score_out       = static_cast<int32_t *>(c.d_out_score);
     // every wavefront holds one query (the multi-query sweep: every run; the solo packing: every window its own)
-    p.shared_profile  = plan.family == kMqSweep ? (plan.share < 0 ? 1 : std::min(2 * plan.share, 8)) : 64 / lx::trace_cfg_group(plan.cfg);
-    p.cfg             = plan.cfg;
+    p.shared_profile  = plan.family == kMqSweep ? (plan.share < 0 ? 1 : std::min(2 * plan.share, 8)) : plan.geo.groups();
+    p.geo             = plan.geo;
     if (plan.packed)
     {
         p.ovf        = p.trace + x.batch_dw;
@@ -375,7 +375,7 @@ int sweep_stage(StepCtx & x, bool & first_part_only)
                 sp.nrows = x.facts.alph + 1;
             }
             sp.narrow = 1;
-            LX_HIP(h, lx::launch_sweep_mq(plan.cfg, sp, stream));
+            LX_HIP(h, lx::launch_sweep_mq(plan.geo, sp, stream));
             if (x.tab_on && tab.part == 1)
             {
                 pt0.close();
@@ -391,7 +391,7 @@ int sweep_stage(StepCtx & x, bool & first_part_only)
         {
             lx::ScoreParams sp = sweep_params(p, true);
             sp.pair_share      = std::max(plan.share, 0);
-            LX_HIP(h, lx::launch_sweep_pair16_compact(plan.cfg, sp, stream));
+            LX_HIP(h, lx::launch_sweep_pair16_compact(plan.geo, sp, stream));
             LX_HIP(h, reset_carry(h, stream)); // (the fix-up launch carries)
             p.fixup = 1;
             break;
@@ -401,12 +401,12 @@ int sweep_stage(StepCtx & x, bool & first_part_only)
             lx::ScoreParams sp = sweep_params(p, false); // (always one panel)
             sp.pair_share      = std::max(plan.share, 0);
             sp.wave_slots      = 1;
-            LX_HIP(h, lx::launch_score_pair(pair_cfg_of(plan.cfg), sp, stream));
+            LX_HIP(h, lx::launch_score_pair(plan.geo, sp, stream));
             p.fixup = 1;
             break;
         }
         case kI16Pairs:
-            LX_HIP(h, lx::launch_sweep_pair16(plan.cfg, sweep_params(p, true), stream));
+            LX_HIP(h, lx::launch_sweep_pair16(plan.geo, sweep_params(p, true), stream));
             if (plan.panels > 1) // (the fix-up launch carries)
                 LX_HIP(h, reset_carry(h, stream));
             p.fixup = 1;
@@ -528,7 +528,7 @@ int backtrace_stage(StepCtx & x)
     p.src         = static_cast<uint32_t const *>(h->d_sel_src.ptr);
     p.count_ptr   = static_cast<uint64_t const *>(c.d_out_count);
     p.chunk_start = 0;
-    p.cfg         = plan.cfg;
+    p.geo         = plan.geo;
     p.slot_by_src = 1;
     p.out_by_pos  = c.by_pos ? 1 : 0;
     if (plan.packed)

@@ -66,11 +66,6 @@ uint32_t panels_for(uint64_t max_qlen, int panel)
     return (uint32_t)std::max<uint64_t>(1, (max_qlen + panel - 1) / panel);
 }
 
-int pair_cfg_of(int trace_cfg)
-{
-    return trace_cfg == 1 ? 0 : trace_cfg == 3 ? 1 : trace_cfg == 4 ? 7 : 5;
-}
-
 uint64_t carry_pairs(uint64_t n, uint64_t max_slen)
 {
     return n * ((max_slen + 3) & ~3ull);
@@ -86,107 +81,138 @@ size_t pair_lds_limit()
 }
 
 // what two profiles of a packed-half geometry and the kernel's staging take of a wavefront's LDS
-static size_t two_profiles_bytes(int pair_cfg, int nrows)
+static size_t two_profiles_bytes(Geo geo, int nrows)
 {
-    return 2 * lx::score_pair_profile_bytes(pair_cfg, nrows) + 64 * 8 * 4;
+    return 2 * lx::score_pair_profile_bytes(geo, nrows) + 64 * 8 * 4;
 }
 
 // Smallest panel that holds the query; 8-lane geometries need one shared profile per wavefront (8 profile slots
 // per wavefront would not fit the LDS budget), so without sharing only the 16/32/64-lane geometries are used.
-int pick_cfg(uint32_t qlen, bool shared)
+Geo pick_cfg(uint32_t qlen, bool shared)
 {
     if (shared)
     {
         if (qlen <= 64)
-            return 1;
+            return Geo{8, 8};
         if (qlen <= 104)
-            return 4;
+            return Geo{8, 13};
         if (qlen <= 128)
-            return 5;
+            return Geo{8, 16};
         if (qlen <= 152)
-            return 6;
+            return Geo{8, 19};
     }
     if (qlen <= 64 && !shared)
-        return 1; // 64 columns: 8 slots of a 64-column profile are small enough
+        return Geo{8, 8}; // 64 columns: 8 slots of a 64-column profile are small enough
     if (qlen <= 160)
-        return 0;
+        return Geo{16, 10};
     if (qlen <= 208)
-        return 7;
+        return Geo{16, 13};
     if (qlen <= 256)
-        return 8;
+        return Geo{16, 16};
     // Longer queries: several panels of a 16-lane geometry beat one wide panel of the 32- / 64-lane ones (400 aa x 442:
     // (16,13) x 2 panels 4.4 TCUPS, (16,16) x 2 3.8, (16,10) x 3 3.8, (32,10) x 2 2.6, (64,10) 2.3 -- the wide groups pay
     // for their long skew and cross-row shifts).  Pick the geometry with the least padded work, weighted by the time
     // each took per padded column in that measurement.
     struct Cand
     {
-        int    cfg, panel;
+        Geo    geo;
         double cost;
     };
-    static constexpr Cand cands[] = {{8, 256, 0.0581}, {7, 208, 0.0619}, {0, 160, 0.0621}};
-    int    best      = 8;
+    static constexpr Cand cands[] = {{{16, 16}, 0.0581}, {{16, 13}, 0.0619}, {{16, 10}, 0.0621}};
+    Geo    best      = cands[0].geo;
     double best_cost = 1e30;
     for (Cand const & c : cands)
     {
-        double const cost = (double)((qlen + c.panel - 1) / c.panel * c.panel) * c.cost;
+        uint32_t const panel = (uint32_t)c.geo.panel();
+        double const   cost  = (double)((qlen + panel - 1) / panel * panel) * c.cost;
         if (cost < best_cost)
         {
             best_cost = cost;
-            best      = c.cfg;
+            best      = c.geo;
         }
     }
     return best;
 }
 
-// Checkpoint geometry (trace cfg 1 = (8,19), 2 = (16,13)) for a query of max_q columns: one panel if it fits, else the
+// Checkpoint geometry, (8,19) or (16,13), for a query of max_q columns: one panel if it fits, else the
 // panel count x width x measured time per padded column that is least (int32 kernels: 0.070 vs 0.062 per column;
 // packed16 = the sweep of lx_score_i16.hip will run).
-int ckpt_cfg_for(uint64_t max_q, bool packed16)
+Geo ckpt_cfg_for(uint64_t max_q, bool packed16)
 {
-    uint64_t const p1 = (uint64_t)lx::trace_cfg_panel(1), p2 = (uint64_t)lx::trace_cfg_panel(2);
+    uint64_t const p1 = (uint64_t)lx::kGeo8x19.panel(), p2 = (uint64_t)lx::kGeo16x13.panel();
     if (max_q <= p1)
-        return 1;
+        return lx::kGeo8x19;
     if (max_q <= p2)
-        return 2;
+        return lx::kGeo16x13;
     // (the packed 16-bit sweep is bound by its checkpoint bytes: the 19-column strips of (8,19) store fewer boundary
     // columns -- 400 aa: 0.0134 ms per padded column against 0.0156 for (16,13) with int16-pair slots; with compact codes,
     // which only the (8,19) panels have, 0.0108)
     double const f1 = packed16 ? 0.0108 : 0.070, f2 = packed16 ? 0.0156 : 0.062;
     double const c1 = (double)((max_q + p1 - 1) / p1 * p1) * f1, c2 = (double)((max_q + p2 - 1) / p2 * p2) * f2;
-    return c1 < c2 ? 1 : 2;
+    return c1 < c2 ? lx::kGeo8x19 : lx::kGeo16x13;
 }
 
-// Multi-query sweep (lx_sweep_mq.hip): checkpoint geometry for queries of up to max_q columns -- trace cfg 3 = (8,13),
-// 5 = (8,11), 1 = (8,19), as many panels as the query needs: the one with the least padded work (columns swept x instructions
+// Multi-query sweep (lx_sweep_mq.hip): checkpoint geometry for queries of up to max_q columns -- (8,19), (8,11) or
+// (8,13), as many panels as the query needs: the one with the least padded work (columns swept x instructions
 // per column: 3.75 per cell of the recurrence + ~12 per step and lane spread over the strip's columns).  lx_host_plan.cpp deals
 // ragged lists to classes with the same function, so a chunk's geometry is the one its class was formed for.
-int mq_cfg_for(uint64_t max_q)
+Geo mq_cfg_for(uint64_t max_q)
 {
-    int    best = 1;
+    Geo    best = lx::kGeo8x19;
     double best_cost = 1e30;
-    for (int cfg : {1, 5, 3})
+    for (Geo geo : {Geo{8, 19}, Geo{8, 11}, Geo{8, 13}})
     {
-        uint64_t const panel = (uint64_t)lx::trace_cfg_panel(cfg);
+        uint64_t const panel = (uint64_t)geo.panel();
         double const   C     = (double)panel / 8.0;
         double const   cost  =(double)((std::max<uint64_t>(max_q, 1) + panel - 1) / panel * panel) * (3.75 * C + 12.0) / C;
         if (cost < best_cost - 1e-9)
         {
             best_cost = cost;
-            best      = cfg;
+            best      = geo;
         }
     }
     return best;
 }
 
+// The packed-half geometry of pass 1 for queries of up to max_qlen columns ({}: none is wide enough)
+Geo score_pair_cfg_for(uint32_t max_qlen)
+{
+    if (max_qlen <= 64)
+        return Geo{8, 8};
+    if (max_qlen <= 104)
+        return Geo{8, 13};
+    if (max_qlen <= 128)
+        return Geo{8, 16};
+    if (max_qlen <= 152)
+        return Geo{8, 19};
+    if (max_qlen <= 192)
+        return Geo{8, 24};
+    if (max_qlen <= 200)
+        return Geo{8, 25};
+    if (max_qlen <= 208)
+        return Geo{16, 13};
+    return Geo{};
+}
+
+// geometries with 16-lane groups (8 extensions per wavefront)
+Geo score_pair_cfg_for_runs_of_8(uint32_t max_qlen)
+{
+    if (max_qlen <= 160)
+        return Geo{16, 10};
+    if (max_qlen <= 208)
+        return Geo{16, 13};
+    return Geo{};
+}
+
 // ---- pass 1 ---------------------------------------------------------------------------------------------------------------
 
-ScorePlan plan_score_cfg(int cfg, bool multi, bool shared, uint64_t band, int pair_cfg, int pair_share)
+ScorePlan plan_score_cfg(Geo geo, bool multi, bool shared, uint64_t band, Geo pair_geo, bool pair16)
 {
     ScorePlan pl{};
-    pl.cfg = cfg, pl.multi = multi, pl.shared = shared, pl.pair_cfg = pair_cfg, pl.pair_share = pair_share, pl.band = band;
+    pl.geo = geo, pl.multi = multi, pl.shared = shared, pl.pair_geo = pair_geo, pl.pair16 = pair16, pl.band = band;
     // band mode: the int32 kernel of the generic geometry, any query width (the packed kernels carry no band code) -- or, for query
     // runs of a multiple of 8 whose queries fit 152 columns, (8,19) with one LDS profile per wavefront
-    pl.narrow = band && shared && cfg == 6 && !multi;
+    pl.narrow = band && shared && geo == lx::kGeo8x19 && !multi;
     return pl;
 }
 
@@ -195,50 +221,53 @@ ScorePlan plan_score(SchemeFacts const & sc, ListLimits const & lim, ScoreOption
     uint32_t const q32 = (uint32_t)std::min<uint64_t>(lim.max_qlen, 0xffffffffu);
     // geometry from the caller's hints
     bool const want_shared = lim.query_run != 0 && lim.query_run % 8 == 0;
-    int const  cfg         = lim.max_qlen ? pick_cfg(q32, want_shared) : 0;
-    bool const multi       = lim.max_qlen == 0 || lim.max_qlen > (uint64_t)lx::score_cfg_panel(cfg);
-    bool const shared      = lim.query_run != 0 && (lim.query_run % (uint64_t)lx::score_cfg_groups(cfg)) == 0;
+    Geo const  geo         = lim.max_qlen ? pick_cfg(q32, want_shared) : lx::kGeo16x10;
+    bool const multi       = lim.max_qlen == 0 || lim.max_qlen > (uint64_t)geo.panel();
+    bool const shared      = lim.query_run != 0 && (lim.query_run % (uint64_t)geo.groups()) == 0;
     // packed-half path: the extensions of a wavefront (or, where two LDS profiles fit, of each half of it) must
     // share their query and the query must fit one panel
-    int pair_cfg = -1, pair_share = 0;
+    Geo  pair_geo;
+    int  pair_share = 0;
+    bool pair16     = false;
     if (o.f16 && shared && lim.max_qlen != 0)
     {
-        int const pc = lx::score_pair_cfg_for(q32);
-        if (pc >= 0)
+        Geo const pc = score_pair_cfg_for(q32);
+        if (pc.chosen())
         {
-            int const      groups   = 64 / lx::score_pair_cfg_group(pc);
+            int const      groups   = pc.groups();
             uint64_t const per_wave = 2ull * groups;
             if (lim.query_run % per_wave == 0)
-                pair_cfg = pc;
+                pair_geo = pc;
             else if (groups >= 2 && lim.query_run % (per_wave / 2) == 0 && 2 * lx::score_pair_profile_bytes(pc, sc.nrows()) <= pair_lds_limit())
             {
-                pair_cfg   = pc;
+                pair_geo   = pc;
                 pair_share = groups / 2;
             }
             else if (lim.query_run % 8 == 0) // two profiles do not fit: a 16-lane geometry holds 8 extensions per wavefront
-                pair_cfg = lx::score_pair_cfg_for_runs_of_8(q32);
+                pair_geo = score_pair_cfg_for_runs_of_8(q32);
         }
         else if (lim.query_run % 16 == 0 && lim.max_slen != 0) // wider than any packed-half geometry
-            pair_cfg = kPair16;
+            pair16 = true;
     }
-    ScorePlan pl = plan_score_cfg(cfg, multi, shared, o.band, pair_cfg, pair_share);
-    pl.max_slen  = lim.max_slen;
+    ScorePlan pl  = plan_score_cfg(geo, multi, shared, o.band, pair_geo, pair16);
+    pl.pair_share = pair_share;
+    pl.max_slen   = lim.max_slen;
     // carry pairs: where the launch's own panel does not hold the widest query (the packed 16-bit kernel sweeps wide queries in
     // (8,19) panels even where the int32 geometry is a single one)
-    pl.carry = o.band ? (lim.max_qlen == 0 || lim.max_qlen > (uint64_t)lx::score_cfg_panel(pl.launch_cfg())) : (multi || pair_cfg == kPair16);
+    pl.carry = o.band ? (lim.max_qlen == 0 || lim.max_qlen > (uint64_t)pl.launch_cfg().panel()) : (multi || pair16);
     return pl;
 }
 
 void describe_score(ScorePlan const & pl, char * buf, size_t len)
 {
-    int const G = 64 / std::max(1, lx::score_cfg_groups(pl.cfg)), C = lx::score_cfg_panel(pl.cfg) * lx::score_cfg_groups(pl.cfg) / 64;
+    int const G = pl.geo.g, C = pl.geo.c;
     if (pl.band)
         snprintf(buf, len, "lx::score_kernel<%s,band> (band mode, +-%d diagonals)", pl.narrow ? "8,19,false" : "16,10,true", (int32_t)pl.band);
-    else if (pl.pair_cfg == kPair16)
+    else if (pl.pair16)
         snprintf(buf, len, "lx::sweep_pair16_kernel<8,19,true,false> (+ int32 fix-up lx::score_kernel<%d,%d,%s>)", G, C, pl.multi ? "true" : "false");
-    else if (pl.pair_cfg >= 0)
-        snprintf(buf, len, "lx::score_pair_kernel<%d,%d> (+ int32 fix-up lx::score_kernel<%d,%d,%s>)", lx::score_pair_cfg_group(pl.pair_cfg),
-                 lx::score_pair_cfg_cols(pl.pair_cfg), G, C, pl.multi ? "true" : "false");
+    else if (pl.pair_geo.chosen())
+        snprintf(buf, len, "lx::score_pair_kernel<%d,%d> (+ int32 fix-up lx::score_kernel<%d,%d,%s>)", pl.pair_geo.g, pl.pair_geo.c, G, C,
+                 pl.multi ? "true" : "false");
     else
         snprintf(buf, len, "lx::score_kernel<%d,%d,%s>%s", G, C, pl.multi ? "true" : "false", pl.shared ? " shared-profile" : "");
 }
@@ -248,40 +277,41 @@ void describe_score(ScorePlan const & pl, char * buf, size_t len)
 TracePlan plan_trace(SchemeFacts const & sc, ListLimits const & lim, int share_slots, TraceOptions const & o)
 {
     uint64_t const max_q = lim.max_qlen, max_s = lim.max_slen;
-    uint64_t const p1 = (uint64_t)lx::trace_cfg_panel(1), p2 = (uint64_t)lx::trace_cfg_panel(2);
+    Geo const      generic = lx::kGeo16x10, g8 = lx::kGeo8x19, g16 = lx::kGeo16x13;
+    uint64_t const p1 = (uint64_t)g8.panel(), p2 = (uint64_t)g16.panel();
     TracePlan      pl{};
     // checkpoint mode (lx_ckpt.hip): shared-profile geometries (8,19) / (16,13), scores that fit int16; queries wider
     // than 208 columns take several (16,13) panels
     pl.ckpt = !o.band && o.pass2 >= 1 && share_slots >= 2 && fits_int16(sc, max_q, max_s);
     // Direction bits beyond one panel: the 16-lane geometry that pads the query less ((16,13) needs the shared profile).
-    auto padded = [&](int c) { return (max_q + lx::trace_cfg_panel(c) - 1) / lx::trace_cfg_panel(c) * lx::trace_cfg_panel(c); };
-    pl.cfg = (o.band && !(share_slots >= 4 && max_q <= p1)) ? 0 // (band mode: (8,19) or generic)
-             : (share_slots >= 2 && max_q <= p1)            ? 1
-             : (share_slots >= 2 && max_q <= p2)            ? 2
-             : pl.ckpt                                      ? ckpt_cfg_for(max_q)
-             : (share_slots >= 4 && padded(2) < padded(0))  ? 2
-                                                            : 0;
-    int const G = lx::trace_cfg_group(pl.cfg), W = lx::trace_cfg_words(pl.cfg);
-    pl.panels_cap     = panels_for(max_q, lx::trace_cfg_panel(pl.cfg));
+    auto padded = [&](Geo g) { return (max_q + g.panel() - 1) / g.panel() * g.panel(); };
+    pl.geo = (o.band && !(share_slots >= 4 && max_q <= p1))      ? generic // (band mode: (8,19) or generic)
+             : (share_slots >= 2 && max_q <= p1)                 ? g8
+             : (share_slots >= 2 && max_q <= p2)                 ? g16
+             : pl.ckpt                                           ? ckpt_cfg_for(max_q)
+             : (share_slots >= 4 && padded(g16) < padded(generic)) ? g16
+                                                                 : generic;
+    int const G = pl.geo.g, W = lx::trace_cfg_words(pl.geo);
+    pl.panels_cap     = panels_for(max_q, pl.geo.panel());
     pl.steps_cap      = steps_for(max_s, G);
-    pl.stride         = pl.ckpt ? (uint64_t)pl.panels_cap * lx::ckpt_slot_dwords(pl.cfg, pl.steps_cap) : (uint64_t)pl.panels_cap * pl.steps_cap * G * W;
+    pl.stride         = pl.ckpt ? (uint64_t)pl.panels_cap * lx::ckpt_slot_dwords(pl.geo, pl.steps_cap) : (uint64_t)pl.panels_cap * pl.steps_cap * G * W;
     pl.per_ext        = pl.stride * 4;
     pl.budget_ext     = std::max<uint64_t>(1, o.trace_bytes / std::max<uint64_t>(pl.per_ext, 1));
-    pl.shared_profile = (o.band && pl.cfg == 0) ? 0 : share_slots;
+    pl.shared_profile = (o.band && pl.geo == generic) ? 0 : share_slots;
     // The forward kernel finds the end cell cheaply when it knows each extension's best score; a stand-alone traceback call
     // computes them first (a fraction of the traceback's cost), one profile per lane group
-    int const scfg = pick_cfg((uint32_t)std::min<uint64_t>(max_q, 0xffffffffu), false);
-    pl.score       = plan_score_cfg(scfg, max_q > (uint64_t)lx::score_cfg_panel(scfg), false, o.band);
+    Geo const sgeo = pick_cfg((uint32_t)std::min<uint64_t>(max_q, 0xffffffffu), false);
+    pl.score       = plan_score_cfg(sgeo, max_q > (uint64_t)sgeo.panel(), false, o.band);
     pl.max_slen    = max_s;
     // (the panels of pass 2 are never wider than those of its pass 1: several panels there mean several here)
-    pl.carry = pl.panels_cap > 1 || pl.score.multi || (o.band && max_q > (uint64_t)lx::score_cfg_panel(0));
+    pl.carry = pl.panels_cap > 1 || pl.score.multi || (o.band && max_q > (uint64_t)generic.panel());
     pl.score.carry = pl.carry, pl.score.max_slen = max_s;
     return pl;
 }
 
 void describe_trace(TracePlan const & pl, char * buf, size_t len)
 {
-    int const G = lx::trace_cfg_group(pl.cfg), C = lx::trace_cfg_panel(pl.cfg) / G;
+    int const G = pl.geo.g, C = pl.geo.c;
     if (pl.ckpt)
         snprintf(buf, len, "lx::ckpt_forward_kernel<%d,%d>", G, C);
     else
@@ -299,7 +329,8 @@ namespace
 struct SweepCand
 {
     bool     runs = false;
-    int      cfg = 0, share = 0;
+    Geo      geo;
+    int      share = 0;
     uint32_t steps = 0, panels = 1;
     uint64_t stride = 0;   // uint32 per slot of the batch
     uint64_t stride32 = 0; // ... of an int16-pair slot (the whole batch's, or the overflow area's)
@@ -327,14 +358,14 @@ bool mq_wanted(SchemeFacts const & sc, StepOptions const & o)
     uint64_t const run = o.query_run;
     // (runs of 8: the packed-half sweep with one profile per half wavefront keeps its occupancy while both profiles fit
     // ~13 KB -- the small alphabets: configs[2] 29.1 against 31.8 ms, configs[4] 7.4 against 8.1 -- and loses it beyond)
-    bool const half8_cheap = two_profiles_bytes(0, sc.nrows()) <= 13 * 1024;
+    bool const half8_cheap = two_profiles_bytes(lx::kGeo8x19, sc.nrows()) <= 13 * 1024;
     // (... and for queries beyond 208 columns a run that is a multiple of 8 but not of 16 has no packed sweep with compact
     // codes of its own: the multi-query one serves it)
     bool const odd8 = run % 8 == 0 && run % 16 != 0 && run != 0;
     // (run 2 = the free packing: pairs of one query, at most four queries per wavefront -- only this sweep serves it;
     // run 1 = the solo packing: no promise, a byte profile per window, where 16 of them fit a wavefront's LDS share: the
     // alphabets of at most 6 rows -- nucleotides, bisulfite)
-    bool const solo_fits = lx::sweep_mq_lds_bytes(1, sc.alph + 1, -1) <= 20 * 1024;
+    bool const solo_fits = lx::sweep_mq_lds_bytes(lx::kGeo8x19, sc.alph + 1, -1) <= 20 * 1024;
     bool const wanted    = run == 1     ? (o.mq >= 1 && solo_fits)
                            : run == 2   ? o.mq >= 1
                            : o.mq == 2  ? (run != 0 && run % 4 == 0)
@@ -348,16 +379,16 @@ SweepCand mq_candidate(SchemeFacts const & sc, StepOptions const & o)
     SweepCand c{};
     if (!mq_wanted(sc, o))
         return c;
-    c.cfg    = o.mq_cfg ? o.mq_cfg : mq_cfg_for(o.max_qlen);
-    c.panels = panels_for(o.max_qlen, lx::trace_cfg_panel(c.cfg));
+    c.geo    = o.mq_geo.chosen() ? o.mq_geo : mq_cfg_for(o.max_qlen);
+    c.panels = panels_for(o.max_qlen, c.geo.panel());
     if (!fits_int16(sc, o.max_qlen, o.max_slen))
         return c;
     int const G = 8;
     c.steps     = steps_for(o.max_slen, G);
-    c.stride32  = (uint64_t)c.panels * lx::ckpt_slot_dwords(c.cfg, c.steps);
+    c.stride32  = (uint64_t)c.panels * lx::ckpt_slot_dwords(c.geo, c.steps);
     // (mq_wide: int16-pair slots from the sweep itself -- lists whose windows score beyond the compact codes, lx_xb_wf.cpp)
-    c.mq_wide   = o.mq_wide && c.cfg == 1;
-    c.stride    = c.mq_wide ? c.stride32 : (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.cfg, c.steps);
+    c.mq_wide   = o.mq_wide && c.geo == lx::kGeo8x19;
+    c.stride    = c.mq_wide ? c.stride32 : (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.geo, c.steps);
     // lane groups per query: a wavefront's 16 slots hold 16 / 8 / 4 windows of one query, whatever divides the run
     // (1 = the free packing: a lane group's pair shares a query, up to four queries per wavefront in any split; -1: solo)
     c.share     = o.query_run == 1 ? -1 : o.query_run == 2 ? 1 : (o.query_run % 16 == 0 ? 16 : o.query_run % 8 == 0 ? 8 : 4) / 2;
@@ -378,34 +409,33 @@ SweepCand one_query_candidate(SchemeFacts const & sc, StepOptions const & o, Swe
 {
     bool const run16 = o.query_run % 16 == 0;
     int const  nrows = sc.nrows();
-    c.cfg = ckpt_cfg_for(o.max_qlen, o.f16 && run16);
+    c.geo = ckpt_cfg_for(o.max_qlen, o.f16 && run16);
     // short queries (<= 104 columns, e.g. 100-residue reads): the (8,13) geometry where the packed-half sweep applies --
     // a third fewer padded columns than (8,19)
     bool const half_ok = o.f16 && compact_gaps_ok(sc);
-    if (c.cfg == 1 && half_ok && o.max_qlen <= (uint64_t)lx::trace_cfg_panel(3) && (run16 || two_profiles_bytes(1, nrows) <= pair_lds_limit()))
-        c.cfg = 3;
+    if (c.geo == lx::kGeo8x19 && half_ok && o.max_qlen <= (uint64_t)Geo{8, 13}.panel() && (run16 || two_profiles_bytes(Geo{8, 13}, nrows) <= pair_lds_limit()))
+        c.geo = Geo{8, 13};
     // 153 - 200 columns: 25-column strips of 8-lane groups (16 extensions of one query per wavefront, 7 steps of skew
     // instead of 15, no padded column at 200) where the packed-half sweep applies
-    if (c.cfg == 2 && half_ok && o.max_qlen <= (uint64_t)lx::trace_cfg_panel(4) && run16)
-        c.cfg = 4;
-    c.panels = panels_for(o.max_qlen, lx::trace_cfg_panel(c.cfg));
-    if (c.cfg == 0 || !fits_int16(sc, o.max_qlen, o.max_slen))
+    if (c.geo == lx::kGeo16x13 && half_ok && o.max_qlen <= (uint64_t)Geo{8, 25}.panel() && run16)
+        c.geo = Geo{8, 25};
+    c.panels = panels_for(o.max_qlen, c.geo.panel());
+    if (!fits_int16(sc, o.max_qlen, o.max_slen))
         return c;
-    int const G = lx::trace_cfg_group(c.cfg);
+    int const G = c.geo.g;
     c.steps     = steps_for(o.max_slen, G);
-    c.stride32  = (uint64_t)c.panels * lx::ckpt_slot_dwords(c.cfg, c.steps);
+    c.stride32  = (uint64_t)c.panels * lx::ckpt_slot_dwords(c.geo, c.steps);
     // Packed half precision where its geometry matches the checkpoint layout ((8,19): 16 extensions of one query per
     // wavefront, or runs of 8 with one query per half wavefront where two LDS profiles fit, i.e. for the small
     // alphabets; (16,13): 8 extensions) and a gap's first character costs at most 31 (the compact checkpoint codes
     // of Ckpt16Layout).  Wavefronts it declines leave the sentinel -1; the int32 kernel fills those in.
-    bool const g8 = c.cfg == 1 || c.cfg == 3 || c.cfg == 4;
-    c.packed      = half_ok && c.panels == 1 && ((g8 && run16) || c.cfg == 2);
+    c.packed      = half_ok && c.panels == 1 && ((G == 8 && run16) || c.geo == lx::kGeo16x13);
     // Queries wider than a panel: compact codes as well, one part per (8,19) panel, written by the packed int16 kernel
     // (the half-precision one has no carry between panels); what scores beyond the codes goes to the int32 launch
-    c.wide_compact = half_ok && c.panels > 1 && c.cfg == 1 && run16;
+    c.wide_compact = half_ok && c.panels > 1 && c.geo == lx::kGeo8x19 && run16;
     c.packed       = c.packed || c.wide_compact;
-    if (half_ok && c.panels == 1 && (c.cfg == 1 || c.cfg == 3) && !c.packed && o.query_run % 8 == 0 &&
-        two_profiles_bytes(pair_cfg_of(c.cfg), nrows) <= pair_lds_limit())
+    if (half_ok && c.panels == 1 && (c.geo == lx::kGeo8x19 || c.geo == Geo{8, 13}) && !c.packed && o.query_run % 8 == 0 &&
+        two_profiles_bytes(c.geo, nrows) <= pair_lds_limit())
     {
         c.packed = true;
         c.share  = 4;
@@ -413,7 +443,7 @@ SweepCand one_query_candidate(SchemeFacts const & sc, StepOptions const & o, Swe
     if (c.packed)
     {
         // (the packed-half sweep keeps a pair of windows in one dword: CkptPairLayout, never larger than two Ckpt16Layout slots)
-        c.stride = c.wide_compact ? (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.cfg, c.steps) : lx::ckpt_pair_slot_dwords(c.cfg, c.steps);
+        c.stride = c.wide_compact ? (uint64_t)c.panels * lx::ckpt16_slot_dwords(c.geo, c.steps) : lx::ckpt_pair_slot_dwords(c.geo, c.steps);
         c.runs   = packed_fits(o, c.stride);
         // (the packed kernel cannot decline when even the worst query passes its test)
         // (the packed-half kernel computes in a frame raised by half_frame_bias and tests with it in; the int16 one has no bias)
@@ -445,7 +475,7 @@ StepPlan plan_step(SchemeFacts const & sc, StepOptions const & o)
     // No packed-half sweep (queries wider than a panel, gap costs beyond the compact codes, ...): the packed int16 kernel
     // writes the int16-pair slots of the int32 kernel, two extensions per lane group; what fails its range test is left to
     // the int32 launch.  16 extensions of one query per wavefront at (8,19), 8 at (16,13).
-    bool const i16_sweep = c.runs && !c.packed && o.f16 && o.query_run % (c.cfg == 1 ? 16 : 8) == 0 && c.cfg != 3 && c.cfg != 4;
+    bool const i16_sweep = c.runs && !c.packed && o.f16 && o.query_run % (c.geo == lx::kGeo8x19 ? 16 : 8) == 0 && c.geo != Geo{8, 13} && c.geo != Geo{8, 25};
     // Adaptive choice (the one-query-per-wavefront sweep; lx_extend_batch's multi-query plan keeps its sweep): few survivors
     // last time -> plain pass 1, checkpoints for the survivors only (mode 1).
     bool const adapted = c.runs && !mq && o.adapt != 0 && o.surv_frac >= 0.0 && o.surv_frac * 1000.0 < (double)o.adapt;
@@ -454,7 +484,7 @@ StepPlan plan_step(SchemeFacts const & sc, StepOptions const & o)
     pl.sweep       = c.runs && !adapted;
     pl.adapted     = adapted;
     pl.family      = !pl.sweep ? kNoSweep : mq ? kMqSweep : c.wide_compact ? kI16CompactWide : c.packed ? kHalfSweep : i16_sweep ? kI16Pairs : kInt32Sweep;
-    pl.cfg         = c.cfg;
+    pl.geo         = c.geo;
     pl.steps       = c.steps;
     pl.panels      = c.panels;
     pl.stride      = c.stride;
@@ -471,7 +501,7 @@ StepPlan plan_step(SchemeFacts const & sc, StepOptions const & o)
 // the sweep a plan names, as the launch sequence fused_impl issues for it (what lx_last_trace_kernel_name reports)
 void describe_plan(StepPlan const & pl, char * buf, size_t len)
 {
-    int const nameG = lx::trace_cfg_group(pl.cfg), nameC = lx::trace_cfg_panel(pl.cfg) / std::max(1, lx::trace_cfg_group(pl.cfg));
+    int const nameG = pl.geo.g, nameC = pl.geo.c;
     switch (pl.family)
     {
         case kMqSweep:

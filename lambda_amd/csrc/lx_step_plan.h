@@ -1,34 +1,28 @@
 // lx_step_plan.h -- every decision about HOW a step runs: kernel family, geometry, panel count, slot layout, queries per wavefront,
 // carry workspace.  Pure functions of a scheme's facts, the list's limits and the options: no handle, no HIP call.  The launchers
-// (lx_step.cpp) follow these plans; lx_plan_step() shows plan_step to tests/test_plan.py.  The geometry tables the plans read stay
-// with their kernels (the .hip files); only their declarations are here.
+// (lx_step.cpp) follow these plans; lx_plan_step() shows plan_step to tests/test_plan.py.  A geometry is a Geo (lx_geo.h); what stays
+// with the kernels (the .hip files) and is only declared here are the sizes of their slot layouts and of their LDS use.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/lambda_ext.h"
+#include "lx_geo.h"
 
 namespace lx
 {
-int      score_cfg_panel(int cfg);
-int      score_cfg_groups(int cfg);
-int      score_cfg_count();
-int      score_pair_cfg_for(uint32_t max_qlen);
-int      score_pair_cfg_cols(int cfg);
-int      score_pair_cfg_for_runs_of_8(uint32_t max_qlen);
-int      score_pair_cfg_group(int cfg);
-size_t   score_pair_profile_bytes(int cfg, int nrows);
-int      trace_cfg_panel(int cfg);
-int      trace_cfg_group(int cfg);
-int      trace_cfg_words(int cfg);
-uint64_t ckpt_slot_dwords(int cfg, uint32_t steps_cap);
-uint64_t ckpt16_slot_dwords(int cfg, uint32_t steps_cap);
-uint64_t ckpt_pair_slot_dwords(int cfg, uint32_t steps_cap);
-size_t   sweep_mq_lds_bytes(int trace_cfg, int nrows, int share);
+size_t   score_pair_profile_bytes(Geo geo, int nrows);
+// (these four: 0 for a geometry the kernels are not instantiated for)
+int      trace_cfg_words(Geo geo);
+uint64_t ckpt_slot_dwords(Geo geo, uint32_t steps_cap);
+uint64_t ckpt16_slot_dwords(Geo geo, uint32_t steps_cap);
+uint64_t ckpt_pair_slot_dwords(Geo geo, uint32_t steps_cap);
+size_t   sweep_mq_lds_bytes(Geo geo, int nrows, int share);
 } // namespace lx
 
 namespace lxi
 {
+using lx::Geo;
 
 // what lx_set_scoring derives from a scheme besides the tables (one per scoring slot; the plans decide by them): pass 2 applies
 // (every matrix - gap_extend in [-31, 31]), byte profiles apply (0 <= matrix - gap_open <= 255), the largest entry
@@ -66,20 +60,18 @@ int64_t  half_frame_bias(SchemeFacts const & sc, int G);
 uint32_t steps_for(uint64_t max_slen, int G);
 // panels of `panel` columns that hold the query (at least one)
 uint32_t panels_for(uint64_t max_qlen, int panel);
-// the packed-half (pair) geometry with the same (G, C) as a checkpoint (trace) geometry: (8,19) / (8,13) / (8,25) / (16,13)
-int      pair_cfg_of(int trace_cfg);
 // carry pairs (8 bytes each) of n extensions wider than a panel: one per subject row
 uint64_t carry_pairs(uint64_t n, uint64_t max_slen);
 
 // ---- the geometry pickers
 size_t pair_lds_limit();
-int    pick_cfg(uint32_t qlen, bool shared);
-int    ckpt_cfg_for(uint64_t max_q, bool packed16 = false);
-int    mq_cfg_for(uint64_t max_q);
+Geo    pick_cfg(uint32_t qlen, bool shared);
+Geo    ckpt_cfg_for(uint64_t max_q, bool packed16 = false);
+Geo    mq_cfg_for(uint64_t max_q);
+Geo    score_pair_cfg_for(uint32_t max_qlen);           // the packed-half geometry of pass 1 ({}: wider than any)
+Geo    score_pair_cfg_for_runs_of_8(uint32_t max_qlen); // ... with 16-lane groups (8 extensions per wavefront)
 
 // ---- pass 1 over a device list
-constexpr int kPair16    = 100; // ScorePlan::pair_cfg: the packed 16-bit integer kernel, any query width
-constexpr int kPair16Bin = 8;   // its bin among the packed geometries of lx_score_batch
 struct ScoreOptions
 {
     bool     f16  = true;
@@ -87,19 +79,21 @@ struct ScoreOptions
 };
 struct ScorePlan
 {
-    int      cfg = 0;                      // int32 geometry (score cfg); any geometry is correct for any query length (multi-panel path)
+    Geo      geo = lx::kGeo16x10;          // int32 geometry; any geometry is correct for any query length (multi-panel path)
     bool     multi = false, shared = false;
-    int      pair_cfg = -1, pair_share = 0; // packed kernel in front of the int32 one (-1: none; kPair16), lane groups per LDS profile
+    Geo      pair_geo;                     // packed-half kernel in front of the int32 one ({}: none)
+    bool     pair16 = false;               // ... or the packed 16-bit integer kernel, any query width
+    int      pair_share = 0;               // lane groups per LDS profile of the packed-half kernel
     bool     narrow = false;               // band mode: (8,19) with one LDS profile per wavefront instead of the generic geometry
     uint64_t band = 0;
     bool     carry = false;                // a launch of the plan may use the carry workspace
     uint64_t max_slen = 0;
-    int      launch_cfg() const { return band ? (narrow ? 6 : 0) : cfg; }
+    Geo      launch_cfg() const { return band ? (narrow ? lx::kGeo8x19 : lx::kGeo16x10) : geo; }
     uint64_t carry_pairs(uint64_t n) const { return carry ? lxi::carry_pairs(n, max_slen) : 0; } // prepare_workspace's hint
 };
 ScorePlan plan_score(SchemeFacts const & sc, ListLimits const & lim, ScoreOptions const & o);
 // the int32 geometry of a list without query runs (lx_score_batch's bins, pass 2's own pass 1)
-ScorePlan plan_score_cfg(int cfg, bool multi, bool shared, uint64_t band, int pair_cfg = -1, int pair_share = 0);
+ScorePlan plan_score_cfg(Geo geo, bool multi, bool shared, uint64_t band, Geo pair_geo = {}, bool pair16 = false);
 void      describe_score(ScorePlan const & pl, char * buf, size_t len); // what lx_last_kernel_name reports
 
 // ---- pass 2 over a device list.  share_slots = every aligned block of that many slots holds one query (0: no such guarantee); the
@@ -111,7 +105,8 @@ struct TraceOptions
 struct TracePlan
 {
     bool      ckpt = false;               // checkpoints (lx_ckpt.hip) instead of direction bits (lx_trace.hip)
-    int       cfg = 0, shared_profile = 0;
+    Geo       geo = lx::kGeo16x10;
+    int       shared_profile = 0;
     uint32_t  panels_cap = 1, steps_cap = 0;
     uint64_t  stride = 0, per_ext = 0;    // uint32 / bytes of an extension's slot
     uint64_t  budget_ext = 1;             // slots the trace budget holds (the launcher sizes its chunks from this and the buffer it has)
@@ -127,7 +122,7 @@ void      describe_trace(TracePlan const & pl, char * buf, size_t len); // what 
 struct StepOptions
 {
     uint64_t max_qlen = 0, max_slen = 0, query_run = 0, pass2 = 2, mq = 1, f16 = 1, band = 0, trace_bytes = 0, n = 0, adapt = 0;
-    int      mq_cfg = 0;
+    Geo      mq_geo;              // the strip geometry of the multi-query sweep ({}: mq_cfg_for picks)
     bool     mq_wide     = false; // the multi-query sweep writes int16-pair slots (lx_sweep_mq.hip: WIDE)
     double   surv_frac   = -1.0;
 };
@@ -146,7 +141,8 @@ struct StepPlan
     bool        packed = false; // a packed sweep's launch structure: a spare slot behind the batch's, an overflow area for what it declines
     bool        wide   = false; // the multi-query sweep with int16-pair slots
     SweepFamily family = kNoSweep;
-    int         cfg = 0, share = 0;
+    Geo         geo;            // ({}: no candidate got as far as a geometry -- never a sweep)
+    int         share = 0;
     uint32_t    steps = 0, panels = 1;
     uint64_t    stride = 0, stride32 = 0, ovf_cap = 0;
 };

@@ -965,24 +965,25 @@ static hipError_t launch_sweep_mq_cfg(ScoreParams const & p, hipStream_t stream)
     return hipGetLastError();
 }
 
-// trace cfg 5 = (8,11), 3 = (8,13), 1 = (8,19): strips whose byte profiles leave room for four queries per wavefront at two
+// (8,19), (8,13), (8,11): strips whose byte profiles leave room for four queries per wavefront at two
 // wavefronts per SIMD (<= 20 bytes per lane and letter; 25-column strips were measured and lose a fifth to their occupancy).
 // p.pair_share = lane groups per query (1, 2, 4; 0 or 8 = one query per wavefront); the slots are the compact codes of
 // Ckpt16Layout<8, C>, p.panels_cap parts each.
-hipError_t launch_sweep_mq(int trace_cfg, ScoreParams const & p, hipStream_t stream)
+using SweepMqGeos = GeoList<GeoT<8, 19>, GeoT<8, 13>, GeoT<8, 11>>;
+
+hipError_t launch_sweep_mq(Geo geo, ScoreParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
-    return trace_cfg == 1 ? launch_sweep_mq_cfg<19>(p, stream) : trace_cfg == 3 ? launch_sweep_mq_cfg<13>(p, stream) : trace_cfg == 5 ? launch_sweep_mq_cfg<11>(p, stream) : hipErrorInvalidValue;
+    return geo_dispatch(SweepMqGeos{}, geo, hipErrorInvalidValue, [&](auto t) { return launch_sweep_mq_cfg<t.c>(p, stream); });
 }
 
 // LDS bytes of one wavefront (profiles + staging)
-size_t sweep_mq_lds_bytes(int trace_cfg, int nrows, int share)
+size_t sweep_mq_lds_bytes(Geo geo, int nrows, int share)
 {
-    int const C = trace_cfg == 1 ? 19 : trace_cfg == 3 ? 13 : 11;
     int const s = (share > 0 && share < 8) ? share : 8;
     // (share -1: the solo packing, a profile per window)
-    return ((size_t)(share < 0 ? 16 : share == 1 ? 4 : 8 / s) * (size_t)nrows * (size_t)((C + 3) / 4 * 8) + 64 * 8) * sizeof(uint32_t);
+    return ((size_t)(share < 0 ? 16 : share == 1 ? 4 : 8 / s) * (size_t)nrows * (size_t)((geo.c + 3) / 4 * geo.g) + 64 * 8) * sizeof(uint32_t);
 }
 
 } // namespace lx

@@ -695,14 +695,15 @@ __global__ void max_lens_kernel(Extension const * ext, uint64_t n, MaxLens * out
 
 // ---- host-visible launchers ---------------------------------------------------------------------------
 
-// trace geometries: cfg 0 = (16,10) [any query length, multi-panel], cfg 1 = (8,19) [<= 152 columns, shared profile]
-// (cfg 2 = (16,13) [<= 208 columns, shared profile])
-// (cfg 3 = (8,13) [<= 104 columns, shared profile]: checkpoint / single-sweep kernels only, for short queries)
-// (cfg 3 = (8,13) and cfg 4 = (8,25) exist for the checkpoint kernels of lx_ckpt.hip only)
-// trace cfg: 0 = (16,10), 1 = (8,19), 2 = (16,13), 3 = (8,13), 4 = (8,25), 5 = (8,11) [checkpoint kernels only: the multi-query sweep]
-int trace_cfg_panel(int cfg) { return cfg == 1 ? 8 * 19 : cfg == 2 ? 16 * 13 : cfg == 3 ? 8 * 13 : cfg == 4 ? 8 * 25 : cfg == 5 ? 8 * 11 : 16 * 10; }
-int trace_cfg_group(int cfg) { return (cfg == 1 || cfg == 3 || cfg == 4 || cfg == 5) ? 8 : 16; }
-int trace_cfg_words(int cfg) { return cfg == 1 ? TraceWords<19>::kWords : (cfg == 2 || cfg == 3) ? TraceWords<13>::kWords : cfg == 4 ? TraceWords<25>::kWords : cfg == 5 ? TraceWords<11>::kWords : TraceWords<10>::kWords; }
+// Direction-bit geometries: (16,10) [any query length, multi-panel], (8,19) [<= 152 columns, shared profile], (16,13) [<= 208 columns,
+// shared profile]
+using TraceGeos = GeoList<GeoT<16, 10>, GeoT<8, 19>, GeoT<16, 13>>;
+
+// uint32 of direction bits per lane and step (0: no such kernel)
+int trace_cfg_words(Geo geo)
+{
+    return geo_dispatch(TraceGeos{}, geo, 0, [](auto t) { return (int)TraceWords<t.c>::kWords; });
+}
 
 template <int G, int C>
 static hipError_t launch_trace_forward_cfg(TraceParams const & p, hipStream_t stream)
@@ -747,18 +748,14 @@ hipError_t launch_trace_forward(TraceParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
-    return p.cfg == 1   ? launch_trace_forward_cfg<8, 19>(p, stream)
-           : p.cfg == 2 ? launch_trace_forward_cfg<16, 13>(p, stream)
-                        : launch_trace_forward_cfg<16, 10>(p, stream);
+    return geo_dispatch(TraceGeos{}, p.geo, hipErrorInvalidValue, [&](auto t) { return launch_trace_forward_cfg<t.g, t.c>(p, stream); });
 }
 
 hipError_t launch_backtrace(TraceParams const & p, hipStream_t stream)
 {
     if (p.n == 0)
         return hipSuccess;
-    return p.cfg == 1   ? launch_backtrace_cfg<8, 19>(p, stream)
-           : p.cfg == 2 ? launch_backtrace_cfg<16, 13>(p, stream)
-                        : launch_backtrace_cfg<16, 10>(p, stream);
+    return geo_dispatch(TraceGeos{}, p.geo, hipErrorInvalidValue, [&](auto t) { return launch_backtrace_cfg<t.g, t.c>(p, stream); });
 }
 
 hipError_t launch_max_lens(Extension const * ext, uint64_t n, MaxLens * out, hipStream_t stream)

@@ -86,7 +86,7 @@ int Xb::run_fused(int L, uint64_t slots, uint64_t stride, uint64_t max_q, uint64
     sc.fx.d_rle_len  = static_cast<uint32_t *>(ln.d_len.ptr);
     sc.lim           = ListLimits{max_q, max_s, run, h->band_dev, bs_rule};
     sc.tab           = tab;
-    sc.mq_cfg        = p.use_mq ? p.mq_cfg : 0;
+    sc.mq_geo        = p.use_mq ? p.mq_geo : lx::Geo{};
     sc.mq_wide       = wide;
     sc.keep_events   = true; // (the call's phase list holds every chunk's events)
     return fused_impl(h, slot, sc);

@@ -43,7 +43,7 @@ struct WfDriver
     bool     mq_wide = false; // the chunks' sweep writes int16-pair slots (decided chunk by chunk, with hysteresis: choose_wide)
 
     bool by_range() const { return x.sink.where == XbSink::kDeviceByRange; }
-    bool wide_ok() const { return p.mq_cfg == 1 && !lx::dev_aids().mq_no_wide; }
+    bool wide_ok() const { return p.mq_geo == lx::kGeo8x19 && !lx::dev_aids().mq_no_wide; }
     bool maybe_wide() const { return wide_ok() && h->mq_decl_frac > 0.01; }
 
     // Compact codes hold scores up to 2046; a window beyond them is redone by the int32 launch, one profile per pair, at a tenth
@@ -219,7 +219,7 @@ struct WfDriver
     // query, offsets from 0; returns the dwords they take
     uint64_t fill_table(lx::WfSlots * tab, uint64_t wlo, uint64_t whi, bool wide) const
     {
-        uint64_t const pc  = (uint64_t)lx::trace_cfg_panel(p.mq_cfg) / 8;
+        uint64_t const pc  = (uint64_t)p.mq_geo.c;
         uint64_t       off = 0, per_panel = 0;
         uint32_t       last_steps = 0; // (a sorted plan repeats its step counts: the slot size is asked for once per run of them)
         for (uint64_t w = wlo; w < whi; ++w)
@@ -228,7 +228,7 @@ struct WfDriver
             uint32_t const panels = (uint32_t)std::max<uint64_t>(1, ((uint64_t)p.wf_pan[w] + pc - 1) / pc);
             if (steps != last_steps)
             {
-                per_panel  = slot_dwords(p.mq_cfg, 1, p.wf_maxs[w], wide);
+                per_panel  = slot_dwords(p.mq_geo, 1, p.wf_maxs[w], wide);
                 last_steps = steps;
             }
             tab[w - wlo] = lx::WfSlots{off, steps, panels};
@@ -328,7 +328,7 @@ struct WfDriver
         auto const          t0 = now();
         lx_handle::XbLane & ln = h->xb[L];
         XbPrep &            pr = x.prep[L];
-        uint64_t const      slots = (w1 - w0) * kWave, nw = w1 - w0, panel = (uint64_t)lx::trace_cfg_panel(p.mq_cfg);
+        uint64_t const      slots = (w1 - w0) * kWave, nw = w1 - w0, panel = (uint64_t)p.mq_geo.panel();
         pr.k0 = w0, pr.k1 = w1, pr.slots = slots, pr.cap_sel = (slots + 7) / 8 * 8 + 8;
         int rc2;
         if ((!x.preplanned && (rc2 = ensure_pinned(h, ln.p_orig, slots * sizeof(uint32_t), kRoom))) || (rc2 = ensure_pinned(h, ln.p_wft, nw * sizeof(lx::WfSlots), kRoom)))
@@ -361,7 +361,7 @@ struct WfDriver
         auto const          t0    = now();
         lx_handle::XbLane & ln    = h->xb[L];
         XbPrep &            pr    = x.prep[L];
-        uint64_t const      panel = (uint64_t)lx::trace_cfg_panel(p.mq_cfg), slots1 = w1 * kWave;
+        uint64_t const      panel = (uint64_t)p.mq_geo.panel(), slots1 = w1 * kWave;
         pr.k0 = 0, pr.k1 = w1, pr.slots = slots1, pr.cap_sel = (cap_slots + 7) / 8 * 8 + 8, pr.max_s = cap_s, pr.max_pan = cap_pan;
         int rc2;
         if ((rc2 = ensure_pinned(h, ln.p_orig, cap_slots * sizeof(uint32_t), kRoom)) || (rc2 = ensure_pinned(h, ln.p_wft, (cap_slots / kWave + 1) * sizeof(lx::WfSlots), kRoom)))
@@ -382,7 +382,7 @@ struct WfDriver
         if ((rc2 = x.size_lane(L, cap_slots, two.stride, true, true)) || (rc2 = ensure(h, ln.d_wft, (cap_slots / kWave + 1) * sizeof(lx::WfSlots))))
             return rc2;
         // (overflow slots have the size of the chunk's widest query and longest window: an eighth of the slots, within 16 GiB)
-        uint64_t const s32 = slot_dwords(p.mq_cfg, cap_pan, two.max_s, true);
+        uint64_t const s32 = slot_dwords(p.mq_geo, cap_pan, two.max_s, true);
         two.ovf_cap        = std::min<uint64_t>(std::min<uint64_t>(cap_slots, cap_slots / 8 + 64), std::max<uint64_t>(1024, (4ull << 30) / std::max<uint64_t>(s32, 1)));
         two.ovf_dw         = two.ovf_cap * s32;
         // (reserved now: the pool's slots, the overflow slots, what the caller expects the second call's slots to take -- within the budget)

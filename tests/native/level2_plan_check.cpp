@@ -6,7 +6,7 @@
 //   cuts N Q_FRAMES P target from upto (P times) RUNS count q (RUNS times)  -> the ranges' bounds
 //        (the list's windows are given as runs of `count` windows of frame-expanded query id q; the probes' windows are copied out of
 //        it into a block of kL2ProbeWindows per probe, exactly as large as the driver's: what l2_cuts reads beyond it, the sanitizer sees)
-//   cfg C19 C13 C11                                            -> trace cfg
+//   cfg C19 C13 C11                                            -> columns per lane of the strips chosen
 //   consts                                                     -> kFpMaxRanges kL2ProbeWindows
 #include <cstdio>
 #include <iostream>
